@@ -18,7 +18,19 @@ triples of all ranks / max time over ranks.
 runs the collectives around the data path over gloo, ranks sharing the visible GPUs (rank r on device r mod
 count) — how a 1-GPU box exercises every multi-rank branch of this file (tests/test_gpu_bench_ranks.py).
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with
+A plain run (`--gpus N --steps K --warmup W`) does only what the headline needs: set-up, warm-up, the K timed steps,
+the outputs of the last step if --dump-outputs is given, and ONE JSON line on rank 0 (metric, value, unit, ms_per_step,
+config, and the roofline with the kernel classes as the timed region's own HIP-event brackets saw them).  `--full` adds
+everything else below: the launches timed again with the GPU to themselves, the verification against the oracle, the
+side legs and the CPU baseline.
+
+--dump-outputs DIR writes what the timed path's last step computed, as its caller reads it: DIR/z.npy, float64
+[triples][vec_size], the decrypted products z_i of every execute() call of that step in call order.  Clear inputs
+(seeded by rank) and key pairs (seeded) are the same from run to run; encrypt() draws fresh randomness per call, as
+the product does, so the ciphertext words differ between runs by design and the decrypted values only by the scheme's
+noise.
+
+With --full the line also carries
   roofline     — SURVEY.md section 8(d) algorithmic bytes of the op-triple x value over the 8 TB/s HBM peak
                  (`frac` = `hbm_frac`), the VALU-issue fraction from the committed SQ-counter pass (`valu_frac`; the
                  path is integer-issue bound, `bound` says so), the compulsory bytes of one launch set with the key
@@ -737,7 +749,7 @@ def main():
     ap.add_argument("--dag-batch", type=int, default=256, help="--shard dag / the dag_batch leg: independent Sobel DAGs in the batch")
     ap.add_argument("--harris-batch", type=int, default=64, help="the dag_harris_batch leg: independent Harris DAGs (N=2^15, L=8) in the batch")
     ap.add_argument("--harris-chunk", type=int, default=0, help="instances per batched device handle of the dag_harris_batch leg (0: the leg's default)")
-    ap.add_argument("--legs-first", action="store_true", help="run the DAG legs before the headline (EVA_BENCH_LEGS_FIRST=1)")
+    ap.add_argument("--legs-first", action="store_true", help="--full: run the DAG legs before the headline (EVA_BENCH_LEGS_FIRST=1)")
     ap.add_argument("--only-leg", default="", help="run only this leg (dag | dag_batch | dag_harris_batch | dag_configs) and print its dict")
     ap.add_argument("--shard", choices=["ciphertexts", "limb", "subdag", "dag"], default="ciphertexts",
                     help="ciphertexts: independent triples per GPU, no collective (default, weak scaling); "
@@ -751,6 +763,11 @@ def main():
                     help="run only the raw C-ABI leg (uploaded operands, no encrypt / decrypt kernels in the trace) and print its "
                          "dict: what scripts/collect_profiles.sh runs under the rocprofv3 counter passes — the launches per "
                          "group are the ones execute() issues")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-launch profile, verification against the oracle, side legs, CPU baseline "
+                         "(a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the last timed step's outputs (decrypted, float64) as DIR/z.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -801,7 +818,7 @@ def main():
     # --legs-first / EVA_BENCH_LEGS_FIRST=1: the DAG legs before the headline's state exists (each leg builds and frees its
     # own key pair and valuations; the order of the legs inside one process is not part of any number's definition)
     dag_legs_first = None
-    if (args.legs_first or os.environ.get("EVA_BENCH_LEGS_FIRST") == "1") and world == 1 and not args.no_legs:
+    if args.full and (args.legs_first or os.environ.get("EVA_BENCH_LEGS_FIRST") == "1") and world == 1 and not args.no_legs:
         hold = None
         if os.environ.get("EVA_BENCH_HOLD_GB"):  # experiment: other allocations of the process alive during the legs
             hold = [torch.empty(1 << 28, dtype=torch.uint8, device=f"cuda:{dev}") for _ in range(4 * int(os.environ["EVA_BENCH_HOLD_GB"]))]
@@ -844,7 +861,9 @@ def main():
     for _ in range(max(args.warmup, 2)):       # device context / key upload / pools of both issue queues
         outs = step()
     barrier()
-    pub.profile(True)                          # HIP-event brackets around every launch of the timed region
+    # HIP-event brackets around every launch of the timed region, in plain runs too: the headline has always been timed
+    # with them (in an A/B on MI355X a step without them measured ~1 % slower)
+    pub.profile(True)
     pub.profile_reset()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -859,47 +878,56 @@ def main():
     triples = args.steps * batch * world
     value = triples / dt
 
-    # The calls alternate between two issue queues whose launches overlap, so a launch's HIP-event duration in the
-    # timed region is the time it SHARED the GPU for.  Outside the timed region: calls separated by a synchronize,
-    # every launch bracketed, for the duration a kernel takes with the GPU to itself (what a rocprofv3 PMC pass,
-    # which serialises the kernels, reports as well).
-    pub.profile_reset()
-    for _ in range(2):
-        for v in vals:
-            outs_alone = pub.execute(compiled, v)
-            pub.synchronize()
-    prof_excl = {c: v for c, v in pub.profile_get().items() if v[0]}
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        z = np.array([sec.decrypt(out, sig)[f'z{i}'] for out in outs for i in range(G)], dtype=np.float64)
+        np.save(os.path.join(args.dump_outputs, "z.npy"), z)
+
+    prof_excl = {}
+    if args.full:
+        # The calls alternate between two issue queues whose launches overlap, so a launch's HIP-event duration in the
+        # timed region is the time it SHARED the GPU for.  Outside the timed region: calls separated by a synchronize,
+        # every launch bracketed, for the duration a kernel takes with the GPU to itself (what a rocprofv3 PMC pass,
+        # which serialises the kernels, reports as well).
+        pub.profile_reset()
+        for _ in range(2):
+            for v in vals:
+                outs_alone = pub.execute(compiled, v)
+                pub.synchronize()
+        prof_excl = {c: v for c, v in pub.profile_get().items() if v[0]}
+        del outs_alone
     pub.profile(False)
-    del outs_alone
 
-    # ---- outside the timed region: the first and last product of every group of the LAST timed step are downloaded and
-    # compared with the CPU oracle's op-triple of the same encrypted operands and key; the same outputs are decrypted
+    # ---- outside the timed region (--full): the first and last product of every group of the LAST timed step are
+    # downloaded and compared with the CPU oracle's op-triple of the same encrypted operands and key; the same outputs
+    # are decrypted
     verified, host_ops = None, []
-    from oracle import pyoracle as po  # checker only
-    o = po.Oracle(N, primes)
-    ok, checked, max_err = True, 0, 0.0
-    key_host = pub.relin_key()
-    for ci, (v, out) in enumerate(zip(vals, outs)):
-        dec = sec.decrypt(out, sig)
-        for i in sorted({0, G - 1}):
-            a, b = v.get(f'x{i}')[4], v.get(f'y{i}')[4]
-            if len(host_ops) < 4:
-                host_ops.append((a, b))
-            ok = ok and bool(np.array_equal(out.get(f'z{i}')[4], o.op_triple(a, b, key_host)))
-            want = np.asarray(clear[ci][f'x{i}']) * np.asarray(clear[ci][f'y{i}'])
-            max_err = max(max_err, float(np.max(np.abs(np.asarray(dec[f'z{i}']) - want))))
-            checked += 1
-    bad = dist.sum_over_ranks(0.0 if ok and max_err < 1e-3 else 1.0)
-    if bad > 0:
-        raise SystemExit("bench.py: the timed path's output differs from the CPU oracle (or does not decrypt to x * y) — number withheld")
-    verified = {"triples_checked": checked, "bit_exact_vs_oracle": True, "decrypt_max_abs_err_vs_x_times_y": max_err,
-                "what": "outputs of the last timed step's execute() calls vs oracle multiply+relinearize+rescale of the same ciphertexts and key"}
+    if args.full:
+        from oracle import pyoracle as po  # checker only
+        o = po.Oracle(N, primes)
+        ok, checked, max_err = True, 0, 0.0
+        key_host = pub.relin_key()
+        for ci, (v, out) in enumerate(zip(vals, outs)):
+            dec = sec.decrypt(out, sig)
+            for i in sorted({0, G - 1}):
+                a, b = v.get(f'x{i}')[4], v.get(f'y{i}')[4]
+                if len(host_ops) < 4:
+                    host_ops.append((a, b))
+                ok = ok and bool(np.array_equal(out.get(f'z{i}')[4], o.op_triple(a, b, key_host)))
+                want = np.asarray(clear[ci][f'x{i}']) * np.asarray(clear[ci][f'y{i}'])
+                max_err = max(max_err, float(np.max(np.abs(np.asarray(dec[f'z{i}']) - want))))
+                checked += 1
+        bad = dist.sum_over_ranks(0.0 if ok and max_err < 1e-3 else 1.0)
+        if bad > 0:
+            raise SystemExit("bench.py: the timed path's output differs from the CPU oracle (or does not decrypt to x * y) — number withheld")
+        verified = {"triples_checked": checked, "bit_exact_vs_oracle": True, "decrypt_max_abs_err_vs_x_times_y": max_err,
+                    "what": "outputs of the last timed step's execute() calls vs oracle multiply+relinearize+rescale of the same ciphertexts and key"}
 
-    # N > 1: BASELINE config 4's scaling leg rides along — every rank runs its share (instance b on rank b mod
-    # world) of the 256 Sobel DAGs, so a multi-GPU run of the default command reports DAGs/s and the achieved-HBM
-    # fraction per GPU count as well (all ranks take part: the timing is barrier-bracketed)
+    # N > 1 (--full): BASELINE config 4's scaling leg rides along — every rank runs its share (instance b on rank b mod
+    # world) of the 256 Sobel DAGs, so a multi-GPU run reports DAGs/s and the achieved-HBM fraction per GPU count as
+    # well (all ranks take part: the timing is barrier-bracketed)
     dag_batch_multi = None
-    if world > 1 and not args.no_legs:
+    if args.full and world > 1 and not args.no_legs:
         dag_batch_multi = dag_batch_leg(args.dag_batch, 5, dist)
 
     if rank == 0:
@@ -979,7 +1007,7 @@ def main():
                 pass
 
         legs = {}
-        if world == 1 and not args.no_legs:
+        if args.full and world == 1 and not args.no_legs:
             try:
                 legs["raw_cabi"] = raw_cabi_leg(args, N, l, primes, dev, max(5, min(args.steps, 20)), 3)
             except Exception as e:  # noqa: BLE001 — a leg must not cost the headline line
@@ -1009,7 +1037,7 @@ def main():
             legs["dag_batch"] = dag_batch_multi
 
         cpu = None
-        if not args.no_cpu_baseline and world == 1:  # reported baseline: rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # reported baseline: rank 0 at N=1 only
             hp = host_ops
             a, b = hp[0]
             t1 = time.perf_counter()

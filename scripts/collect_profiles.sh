@@ -12,8 +12,8 @@ OUT=$R/gpurun_out/prof_bench
 rm -rf $OUT; mkdir -p $OUT
 export PYTHONPATH=$R
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 20 --warmup 3 --no-legs"
-timeout 600 python $R/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/${TAG}_bench_line.json 2> $OUT/bench.err
+ARGS="--full --steps 20 --warmup 3 --no-legs"
+timeout 600 python $R/bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/${TAG}_bench_line.json 2> $OUT/bench.err
 tail -c 400 $OUT/${TAG}_bench_line.json
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python $R/bench.py $ARGS --no-cpu-baseline > $OUT/trace.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python $R/bench.py --raw-only --steps 2 --warmup 1 > $OUT/pmc_fetch.log 2>&1

@@ -29,8 +29,9 @@ def _bench(*flags, timeout=420):
 
 
 def test_two_ranks_default_command():
-    """the driver's multi-GPU command at N = 2: op-triples through execute() on two ranks + the rank-sharded Sobel batch"""
-    j = _bench("--gpus", "2", "--steps", "2", "--warmup", "1", "--dag-batch", "64", "--no-cpu-baseline")
+    """the driver's multi-GPU command at N = 2 with --full: op-triples through execute() on two ranks, verified, + the
+    rank-sharded Sobel batch"""
+    j = _bench("--gpus", "2", "--steps", "2", "--warmup", "1", "--dag-batch", "64", "--no-cpu-baseline", "--full")
     assert j["n_gpus"] == 2 and j["steps"] == 2 and j["warmup"] == 1 and j["scaling"] == "weak"
     assert j["metric"].startswith("homomorphic ops/sec (mul+rescale+relin) at N=2^16, L=10")
     cfg = j["config"]
