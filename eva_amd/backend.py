@@ -97,6 +97,7 @@ _SIGS = {
     "evah_rescale": [_vp, _vp, C.c_uint32, _vpp],
     "evah_mod_switch": [_vp, _vp, _vpp],
     "evah_test_ntt": [_vp, C.c_uint32, C.c_int, _u64p],
+    "evah_test_devmath": [_vp, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, _u64p, _u64p, _u64p, _u64p],
     "evah_profile_enable": [_vp, C.c_int],
     "evah_profile_reset": [_vp],
     "evah_profile_get": [_vp, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_double)],
@@ -131,6 +132,13 @@ _VOID = {
 EXPORTED_SYMBOLS = sorted(list(_SIGS) + list(_VOID) + ["evah_host_alloc", "evah_host_free", "evah_buf_ptr", "evah_buf_words"] + [
     "evah_last_error", "evah_abi_version", "evah_profile_classes", "evah_profile_class_name"])
 
+
+
+# evah_test_devmath op codes (include/eva_hip.h EVAH_DM_*); bfly_fwd<REDUCE, MAD, TB> as "bfly_fwd_<R><M><T>" (0 / 1 each)
+DEVMATH_OPS = {name: i for i, name in enumerate([
+    "mul_shoup_lazy", "mul_shoup", "barrett64", "mul_tw_lazy5", "mul_tw_lazy5_add", "mul_tw_lazy5_add_mad", "barrett128",
+    "reduce128_lazy", "acc128", "acc128c", "addmod", "submod", "negmod", "topbit", "mac3", "ks128", "bfly_inv"])}
+DEVMATH_OPS.update({f"bfly_fwd_{r}{m}{t}": len(DEVMATH_OPS) + r + 2 * m + 4 * t for r in (0, 1) for m in (0, 1) for t in (0, 1)})
 
 
 class EvahVal(C.Structure):
@@ -805,3 +813,16 @@ class Context:
         y = np.ascontiguousarray(x, dtype=np.uint64).copy()
         _chk(_lib.evah_test_ntt(self.h, int(prime_idx), 1 if inverse else 0, _p(y)))
         return y
+
+    def test_devmath(self, prime_idx, op, a, b=None, c=None):
+        """One kernel primitive per lane (include/eva_hip.h evah_test_devmath): `op` is a name of DEVMATH_OPS, a and b
+        are (n,) or, for the sequence ops, (n, m) words, c is (n, 2) words.  Returns the (n, 2) output words."""
+        a = np.ascontiguousarray(a, dtype=np.uint64)
+        if a.ndim == 1:
+            a = a.reshape(-1, 1)
+        n, m = a.shape
+        b = np.zeros_like(a) if b is None else np.ascontiguousarray(np.asarray(b, dtype=np.uint64).reshape(n, m))
+        c = np.zeros((n, 2), dtype=np.uint64) if c is None else np.ascontiguousarray(np.asarray(c, dtype=np.uint64).reshape(n, 2))
+        out = np.zeros((n, 2), dtype=np.uint64)
+        _chk(_lib.evah_test_devmath(self.h, int(prime_idx), DEVMATH_OPS[op], n, m, _p(a), _p(b), _p(c), _p(out)))
+        return out

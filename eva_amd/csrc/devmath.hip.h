@@ -74,9 +74,10 @@ __device__ __forceinline__ void acc128(u128_t &acc, u64 a, u64 b) {
   acc.hi = (u64)(s >> 64);
 }
 
-// acc += a*b for CANONICAL operands (a, b < q <= 2^60: runtime.hip refuses larger primes) and sums of fewer than 2^7 terms —
-// the shape of the hoisted key inner products.  With both high words below 2^28 the cross terms a0 b1 + a1 b0 (+ the high
-// word of a0 b0 + lo) fit ONE 64-bit multiply-add chain, and a1 b1 + hi (< 2^56 + 2^63) cannot carry out, so the only carry
+// acc += a*b for CANONICAL operands (a, b < q <= 2^60: runtime.hip refuses larger primes) while the sum stays below 2^128 —
+// up to 256 products of such operands (each < 2^120); the hoisted key inner products take fewer than 64.  With both high
+// words below 2^28 the cross terms a0 b1 + a1 b0 (+ the high word of a0 b0 + lo) fit ONE 64-bit multiply-add chain, and
+// a1 b1 + hi (< 2^56 + hi, at most the high word of the new sum) cannot carry out, so the only carry
 // of the whole update is the one out of the first v_mad_u64_u32 (its scalar destination), added where the cross terms' high
 // word is added: 4 v_mad_u64_u32 + 2 v_addc_co_u32 + 2 moves, against the ~15 instructions the unsigned __int128 form
 // compiles to (r6: k_hoist_mac<4,2> 2 567 -> 1 700 VALU instructions per wave).  The result is the same 128-bit sum.
@@ -90,7 +91,7 @@ __device__ __forceinline__ void acc128c(u128_t &acc, u64 a, u64 b) {
   asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(t), "=s"(c1) : "v"(a0), "v"(b0), "v"(acc.lo));
   u64 m = (u64)a0 * b1 + (t >> 32);       // < 2^60 + 2^32
   m = (u64)a1 * b0 + m;                   // < 2^61 + 2^32
-  const u64 x = (u64)a1 * b1 + acc.hi;    // < 2^56 + acc.hi: no carry while the sum stays below 2^127
+  const u64 x = (u64)a1 * b1 + acc.hi;    // < 2^56 + acc.hi <= the new sum's high word: no carry while it is below 2^128
   uint32_t x0, x1;
   asm("v_addc_co_u32 %0, %1, %2, %3, %4" : "=v"(x0), "=s"(c2) : "v"((uint32_t)x), "v"((uint32_t)(m >> 32)), "s"(c1));
   asm("v_addc_co_u32 %0, %1, %2, 0, %3" : "=v"(x1), "=s"(c3) : "v"((uint32_t)(x >> 32)), "s"(c2));

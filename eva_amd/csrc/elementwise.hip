@@ -271,6 +271,95 @@ void key_split_launch(evah_ctx *c, const u64 *src, u64 *dst, size_t words) {
   hipLaunchKernelGGL(k_key_split, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, c->stream, src, dst, words);
   HIPCHK(hipGetLastError());
 }
+
+// evah_test_devmath: one arithmetic primitive per lane on the caller's words (DevmathOp, include/eva_hip.h).  Lane i reads
+// a[i m + j], b[i m + j] (j < m: the terms of a sequence op, m = 1 otherwise) and c[2 i], c[2 i + 1], and writes out[2 i],
+// out[2 i + 1].  The primitives are the ones the kernels call, never copies of them.
+__global__ void __launch_bounds__(256)
+k_test_devmath(DevCtx cx, uint32_t prime_idx, int op, uint32_t n, uint32_t m, const u64 *a, const u64 *b, const u64 *c,
+               u64 *out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const DevPrime pm = cx.primes[prime_idx];
+  const u64 *ai = a + (size_t)i * m, *bi = b + (size_t)i * m;
+  const u64 x = ai[0], y = bi[0], c0 = c[2 * i], c1 = c[2 * i + 1];
+  u64 r0 = 0, r1 = 0;
+  switch (op) {
+  case EVAH_DM_MUL_SHOUP_LAZY: r0 = mul_shoup_lazy(x, y, c0, pm.q); break;
+  case EVAH_DM_MUL_SHOUP: r0 = mul_shoup(x, y, c0, pm.q); break;
+  case EVAH_DM_BARRETT64: r0 = barrett64(x, pm.q, pm.brt); break;
+  case EVAH_DM_MUL_TW_LAZY5: r0 = mul_tw_lazy5(x, y, c0, pm.nq); break;
+  case EVAH_DM_MUL_TW_LAZY5_ADD: r0 = mul_tw_lazy5_add(x, y, c0, pm.nq, c1); break;
+  case EVAH_DM_MUL_TW_LAZY5_ADD_MAD: r0 = mul_tw_lazy5_add_mad(x, y, c0, pm.nq, c1); break;
+  case EVAH_DM_BARRETT128: r0 = barrett128(u128_t{x, y}, pm); break;
+  case EVAH_DM_REDUCE128_LAZY: r0 = reduce128_lazy(u128_t{x, y}, pm); break;
+  case EVAH_DM_ACC128:
+  case EVAH_DM_ACC128C: {
+    u128_t acc{c0, c1};
+    for (uint32_t j = 0; j < m; j++) {
+      if (op == EVAH_DM_ACC128) acc128(acc, ai[j], bi[j]);
+      else acc128c(acc, ai[j], bi[j]);
+    }
+    r0 = acc.lo;
+    r1 = acc.hi;
+    break;
+  }
+  case EVAH_DM_ADDMOD: r0 = addmod(x, y, pm.q); break;
+  case EVAH_DM_SUBMOD: r0 = submod(x, y, pm.q); break;
+  case EVAH_DM_NEGMOD: r0 = negmod(x, pm.q); break;
+  case EVAH_DM_TOPBIT: r0 = mac3_digit(x, pm); break;
+  case EVAH_DM_MAC3: { // ks_inner_kernel<MAC3>'s digit loop for one key polynomial; c0 != 0 overrides the fold period
+    const uint32_t period = c0 ? (uint32_t)c0 : MAC3_FOLD_DIGITS;
+    u64 s0 = 0, s1 = 0, s2 = 0;
+    uint32_t since_fold = 0;
+    for (uint32_t j = 0; j < m; j++) {
+      const u64 v = mac3_digit(ai[j], pm);
+      mac3_acc(s0, s1, s2, (uint32_t)v & 0x3fffffffu, (uint32_t)(v >> 30), bi[j]);
+      if (++since_fold == period && j + 1 < m) {
+        since_fold = 0;
+        mac3_fold(s0, s1, s2);
+      }
+    }
+    const u128_t r = mac3_recombine(s0, s1, s2);
+    r0 = r.lo;
+    r1 = r.hi;
+    break;
+  }
+  case EVAH_DM_KS128: { // the 128-bit digit loop (lazy digit x key word, folded every KS128_FOLD_DIGITS), then three c0 c1 terms
+    u128_t acc{0, 0};
+    uint32_t since_fold = 0;
+    for (uint32_t j = 0; j < m; j++) {
+      acc128(acc, ai[j], bi[j]);
+      if (++since_fold == KS128_FOLD_DIGITS && j + 1 < m) {
+        since_fold = 0;
+        ks128_fold(acc, pm);
+      }
+    }
+    for (int t = 0; t < 3; t++) acc128(acc, c0, c1);
+    r0 = acc.lo;
+    r1 = acc.hi;
+    break;
+  }
+  case EVAH_DM_BFLY_INV: r0 = x; r1 = y; bfly_inv(r0, r1, make_ulonglong2(c0, c1), pm.nq, pm.q5, pm.nq5); break;
+  default: { // EVAH_DM_BFLY_FWD + (REDUCE | MAD << 1 | TB << 2)
+    r0 = x;
+    r1 = y;
+    const ulonglong2 w = make_ulonglong2(c0, c1);
+#define EVAH_DM_FWD(R, M, T)                                                                                              \
+  case EVAH_DM_BFLY_FWD + (R) + 2 * (M) + 4 * (T):                                                                        \
+    bfly_fwd<R, M, T>(r0, r1, w, pm.nq, pm.q4, pm.q8, pm.nq8, pm.tb_c, pm.tb_sh, pm.tb_mask);                             \
+    break;
+    switch (op) {
+      EVAH_DM_FWD(false, false, false) EVAH_DM_FWD(true, false, false) EVAH_DM_FWD(false, true, false)
+      EVAH_DM_FWD(true, true, false) EVAH_DM_FWD(false, false, true) EVAH_DM_FWD(true, false, true)
+      EVAH_DM_FWD(false, true, true) EVAH_DM_FWD(true, true, true)
+    }
+#undef EVAH_DM_FWD
+  }
+  }
+  out[2 * i] = r0;
+  out[2 * i + 1] = r1;
+}
 } // namespace evah
 
 extern "C" {
@@ -612,6 +701,31 @@ int evah_test_ntt(evah_ctx *c, uint32_t prime_idx, int inverse, uint64_t *host) 
   if (inverse) ntt_inverse<OpPlain>(c, p, 1);
   else ntt_forward<OpPlain>(c, p, 1);
   HIPCHK(hipMemcpyAsync(host, s.d, sizeof(u64) * c->N, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  API_END
+}
+
+
+int evah_test_devmath(evah_ctx *c, uint32_t prime_idx, int op, uint32_t n, uint32_t m, const uint64_t *a, const uint64_t *b,
+                      const uint64_t *cw, uint64_t *out) {
+  API_BEGIN
+  use(c);
+  if (c->capturing) throw std::logic_error("this call synchronises with the host and cannot be captured into a graph");
+  if (prime_idx >= c->k) throw std::invalid_argument("prime index out of range");
+  if (op < 0 || op >= EVAH_DM_COUNT) throw std::invalid_argument("unknown devmath op");
+  const bool seq = op == EVAH_DM_ACC128 || op == EVAH_DM_ACC128C || op == EVAH_DM_MAC3 || op == EVAH_DM_KS128;
+  if (n < 1 || n > (1u << 20) || m < 1 || m > 1024 || (!seq && m != 1)) throw std::invalid_argument("devmath: bad n / m");
+  // the radix-2^30 sums are only ever used on a context whose every prime has the top-bit shape or lies below 2^54
+  if (op == EVAH_DM_MAC3 && !c->all_tb) throw std::invalid_argument("devmath: MAC3 does not apply to this context's primes");
+  const size_t nm = (size_t)n * m;
+  Scratch sa(c, nm), sb(c, nm), sc(c, 2 * (size_t)n), so(c, 2 * (size_t)n);
+  HIPCHK(hipMemcpyAsync(sa.d, a, sizeof(u64) * nm, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(sb.d, b, sizeof(u64) * nm, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(sc.d, cw, sizeof(u64) * 2 * n, hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(k_test_devmath, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->dev, prime_idx, op, n, m, sa.d, sb.d,
+                     sc.d, so.d);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, so.d, sizeof(u64) * 2 * n, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   API_END
 }

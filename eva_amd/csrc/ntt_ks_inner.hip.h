@@ -82,6 +82,43 @@ template <> struct KsArgs<KS_FOLDADD> { using Mul = NoMul; using Add = PtrTab; }
 template <int MODE> using KsMulArg = typename KsArgs<MODE>::Mul;
 template <int MODE> using KsAddArg = typename KsArgs<MODE>::Add;
 
+// The arithmetic of the inner product's accumulators, shared by ks_inner_kernel and evah_test_devmath (elementwise.hip),
+// so that the test exercises the code the kernel runs.
+// KS128_FOLD_DIGITS: the 128-bit accumulators take 15 lazy products (each < 16q * q), then fold to one word
+// (ks128_fold) — leaving room for that word and the three P * d_K terms of the fold modes (< 12 q^2 together).
+constexpr uint32_t KS128_FOLD_DIGITS = 15;
+__device__ __forceinline__ void ks128_fold(u128_t &acc, const DevPrime &pm) { acc = {barrett128(acc, pm), 0}; }
+// MAC3_FOLD_DIGITS: the middle radix-2^30 sum takes 14 products < 2^60.1 (7 digits) before mac3_fold carries the sums'
+// upper bits up.  MAC3 is only selected for l <= 15 (keyswitch.hip), because the top sum is never folded.
+constexpr uint32_t MAC3_FOLD_DIGITS = 7;
+// the top-bit reduction of a lazy digit: < 2^60 + 2^36 for a prime of the top-bit shape and any 64-bit x; the identity
+// for another prime (DevPrime (tb_c, tb_sh, tb_mask) = (0, 0, ~0))
+__device__ __forceinline__ u64 mac3_digit(u64 x, const DevPrime &pm) {
+  const uint32_t hi = (uint32_t)(x >> 32);
+  return mad64(hi >> pm.tb_sh, pm.tb_c, ((u64)(hi & pm.tb_mask) << 32) | (uint32_t)x);
+}
+// the four partial products of the digit (v0 + v1 2^30) and the split key word (kw = k0 | k1 << 32, k0, k1 < 2^30)
+__device__ __forceinline__ void mac3_acc(u64 &s0, u64 &s1, u64 &s2, uint32_t v0, uint32_t v1, u64 kw) {
+  s0 = mad64(v0, (uint32_t)kw, s0);
+  s1 = mad64(v0, (uint32_t)(kw >> 32), s1);
+  s1 = mad64(v1, (uint32_t)kw, s1);
+  s2 = mad64(v1, (uint32_t)(kw >> 32), s2);
+}
+// carry words up: s0, s1 < 2^30 afterwards, s0 + s1 2^30 + s2 2^60 unchanged
+__device__ __forceinline__ void mac3_fold(u64 &s0, u64 &s1, u64 &s2) {
+  s1 += s0 >> 30;
+  s0 &= 0x3fffffffull;
+  s2 += s1 >> 30;
+  s1 &= 0x3fffffffull;
+}
+// S = s0 + s1 2^30 + s2 2^60 (< 2^125 for l <= 15) as a 128-bit accumulator
+__device__ __forceinline__ u128_t mac3_recombine(u64 s0, u64 s1, u64 s2) {
+  unsigned __int128 a = s0;
+  a += (unsigned __int128)s1 << 30;
+  a += (unsigned __int128)s2 << 60;
+  return {(u64)a, (u64)(a >> 64)};
+}
+
 // INVSP (latency-bound launches): the workgroups of the special-prime row (I == l) go straight on
 // with the contiguous pass of that row's inverse transform — the first step of the mod-down that
 // always follows — on the tile they hold, and store its lazy intermediate to r_out[2 inst + K]
@@ -292,30 +329,18 @@ ks_inner_kernel(DevCtx cx, const u64 *__restrict__ target_b, size_t target_bs, c
     if constexpr (MAC3) {
 #pragma unroll
       for (int i = 0; i < NTT_R; i++) {
-        const uint32_t hi = (uint32_t)(val[i] >> 32);
-        const u64 v = mad64(hi >> pm.tb_sh, pm.tb_c, ((u64)(hi & pm.tb_mask) << 32) | (uint32_t)val[i]); // < 2^60 + 2^36
+        const u64 v = mac3_digit(val[i], pm);
         const uint32_t v0 = (uint32_t)v & 0x3fffffffu, v1 = (uint32_t)(v >> 30);
         const u64 kw0 = (i & 1) ? k0r[i >> 1].y : k0r[i >> 1].x, kw1 = (i & 1) ? k1r[i >> 1].y : k1r[i >> 1].x;
-        s0[0][i] = mad64(v0, (uint32_t)kw0, s0[0][i]);
-        s1[0][i] = mad64(v0, (uint32_t)(kw0 >> 32), s1[0][i]);
-        s1[0][i] = mad64(v1, (uint32_t)kw0, s1[0][i]);
-        s2[0][i] = mad64(v1, (uint32_t)(kw0 >> 32), s2[0][i]);
-        s0[1][i] = mad64(v0, (uint32_t)kw1, s0[1][i]);
-        s1[1][i] = mad64(v0, (uint32_t)(kw1 >> 32), s1[1][i]);
-        s1[1][i] = mad64(v1, (uint32_t)kw1, s1[1][i]);
-        s2[1][i] = mad64(v1, (uint32_t)(kw1 >> 32), s2[1][i]);
+        mac3_acc(s0[0][i], s1[0][i], s2[0][i], v0, v1, kw0);
+        mac3_acc(s0[1][i], s1[1][i], s2[1][i], v0, v1, kw1);
       }
-      if (++since_fold == 7u && J + 1 < l) { // block-uniform: carry words up, 7 more digits fit
+      if (++since_fold == MAC3_FOLD_DIGITS && J + 1 < l) { // block-uniform: carry words up, MAC3_FOLD_DIGITS more digits fit
         since_fold = 0;
 #pragma unroll
         for (int K = 0; K < 2; K++)
 #pragma unroll
-          for (int i = 0; i < NTT_R; i++) {
-            s1[K][i] += s0[K][i] >> 30;
-            s0[K][i] &= 0x3fffffffull;
-            s2[K][i] += s1[K][i] >> 30;
-            s1[K][i] &= 0x3fffffffull;
-          }
+          for (int i = 0; i < NTT_R; i++) mac3_fold(s0[K][i], s1[K][i], s2[K][i]);
       }
       continue;
     }
@@ -329,25 +354,20 @@ ks_inner_kernel(DevCtx cx, const u64 *__restrict__ target_b, size_t target_bs, c
     // 16 lazy products (each < 16q * q < 2^124) fill the 128-bit accumulators, 15 of them and a folded word leave
     // room for the P * d_K terms added after the loop (< 12 q^2 together): with more digits than that, fold the
     // accumulators back to one word every 15 (block-uniform, only ever taken when l > 15)
-    if (++since_fold == 15u && J + 1 < l) {
+    if (++since_fold == KS128_FOLD_DIGITS && J + 1 < l) {
       since_fold = 0;
 #pragma unroll
       for (int i = 0; i < NTT_R; i++) {
-        acc0[i] = {barrett128(acc0[i], pm), 0};
-        acc1[i] = {barrett128(acc1[i], pm), 0};
+        ks128_fold(acc0[i], pm);
+        ks128_fold(acc1[i], pm);
       }
     }
   }
   if constexpr (MAC3) { // S = s0 + s1 2^30 + s2 2^60 < 2^125: the 128-bit accumulators of the epilogue
 #pragma unroll
     for (int i = 0; i < NTT_R; i++) {
-      unsigned __int128 a = s0[0][i], b = s0[1][i];
-      a += (unsigned __int128)s1[0][i] << 30;
-      a += (unsigned __int128)s2[0][i] << 60;
-      b += (unsigned __int128)s1[1][i] << 30;
-      b += (unsigned __int128)s2[1][i] << 60;
-      acc0[i] = {(u64)a, (u64)(a >> 64)};
-      acc1[i] = {(u64)b, (u64)(b >> 64)};
+      acc0[i] = mac3_recombine(s0[0][i], s1[0][i], s2[0][i]);
+      acc1[i] = mac3_recombine(s0[1][i], s1[1][i], s2[1][i]);
     }
   }
   if constexpr (MODE == KS_FOLDMUL || MODE == KS_FOLDADD) {

@@ -407,6 +407,27 @@ void evah_graph_free(evah_graph *g);
 /* ---- test / measurement hooks -------------------------------------------------------------- */
 /* in-place negacyclic NTT (inverse=0) or INTT (inverse=1) of one host polynomial mod primes[i] */
 int evah_test_ntt(evah_ctx *ctx, uint32_t prime_idx, int inverse, uint64_t *host_inout);
+/* One arithmetic primitive of the kernels (devmath.hip.h, the butterflies of ntt.hip.h, the key-switch accumulators of
+ * ntt_ks_inner.hip.h) applied by a small kernel to n lanes of host words, with the DevPrime of primes[prime_idx].
+ * Lane i reads a[i*m + j], b[i*m + j] for j < m (m > 1 only for the sequence ops ACC128, ACC128C, MAC3, KS128) and
+ * c[2i], c[2i+1]; it writes out[2i], out[2i+1] (a single result in out[2i], a 128-bit one as (lo, hi), a butterfly as
+ * (X, Y)).  Operands by op:
+ *   MUL_SHOUP_LAZY, MUL_SHOUP, MUL_TW_LAZY5   x = a, w = b, w' = c[2i]
+ *   MUL_TW_LAZY5_ADD(_MAD)                  the same, addend c[2i+1]
+ *   BARRETT64 a;  BARRETT128, REDUCE128_LAZY  (lo, hi) = (a, b);  ADDMOD, SUBMOD a, b;  NEGMOD a;  TOPBIT a
+ *   ACC128, ACC128C                         (c[2i], c[2i+1]) + sum_j a_j b_j
+ *   MAC3                                    digits a_j, split key words b_j (k0 | k1 << 32); c[2i] != 0 overrides the
+ *                                           fold period; refused unless the context's key switches may use MAC3
+ *   KS128                                   lazy digits a_j, key words b_j, then three terms c[2i] c[2i+1]
+ *   BFLY_FWD + (REDUCE | MAD << 1 | TB << 2), BFLY_INV   (X, Y) = (a, b), twiddle (w, w') = (c[2i], c[2i+1]) */
+enum {
+  EVAH_DM_MUL_SHOUP_LAZY = 0, EVAH_DM_MUL_SHOUP, EVAH_DM_BARRETT64, EVAH_DM_MUL_TW_LAZY5, EVAH_DM_MUL_TW_LAZY5_ADD,
+  EVAH_DM_MUL_TW_LAZY5_ADD_MAD, EVAH_DM_BARRETT128, EVAH_DM_REDUCE128_LAZY, EVAH_DM_ACC128, EVAH_DM_ACC128C,
+  EVAH_DM_ADDMOD, EVAH_DM_SUBMOD, EVAH_DM_NEGMOD, EVAH_DM_TOPBIT, EVAH_DM_MAC3, EVAH_DM_KS128, EVAH_DM_BFLY_INV,
+  EVAH_DM_BFLY_FWD, EVAH_DM_COUNT = EVAH_DM_BFLY_FWD + 8
+};
+int evah_test_devmath(evah_ctx *ctx, uint32_t prime_idx, int op, uint32_t n, uint32_t m, const uint64_t *a,
+                      const uint64_t *b, const uint64_t *c, uint64_t *out);
 /* Per-launch HIP-event profile by kernel class (events are recorded on the launch stream around
  * every kernel launch while enabled); used by bench.py for the roofline of the dominant kernel. */
 int evah_profile_enable(evah_ctx *ctx, int on);

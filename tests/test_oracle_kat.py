@@ -314,3 +314,92 @@ def test_encode_decodes_through_canonical_embedding():
         ev = sum(co[j] * z ** j for j in range(N))
         assert abs(ev.real / scale - vals[i]) < 1e-6 and abs(ev.imag / scale) < 1e-6
         pos = pos * 3 % (2 * N)
+
+
+# ---- worst-case words (tests/test_gpu_extremes.py compares the HIP kernels with the oracle on these inputs)
+
+def _worst_target(o, primes, lv, N, form):
+    """'delta': every limb the constant x = min(primes) - 1 in NTT form (x * delta in coefficient form), so every digit
+    of every limb is x; 'dense': every coefficient x; 'qm1': q - 1 in every word"""
+    x = min(primes) - 1
+    if form == "delta":
+        return np.stack([np.full(N, x % primes[i], dtype=np.uint64) for i in range(lv)])
+    if form == "dense":
+        return np.stack([o.ntt(i, np.full(N, x % primes[i], dtype=np.uint64)) for i in range(lv)])
+    return np.stack([np.full(N, primes[i] - 1, dtype=np.uint64) for i in range(lv)])
+
+
+@pytest.mark.parametrize("N,l", [(1024, 7), (1024, 8), (1024, 15), (1024, 16), (1024, 31), (2048, 7), (2048, 16)])
+@pytest.mark.parametrize("form", ["delta", "dense", "qm1"])
+def test_switch_key_worst_case_words(N, l, form):
+    """switch_key with key words of q - 1 and digits near their maximum at 7, 8, 15, 16 and 31 digits: the oracle's
+    128-bit accumulation of l products and its mod-down against Python integers.  The inner products are formed in the
+    NTT domain with the transforms test_ntt_matches_definition pins; the mod-down's rounding in coefficient form."""
+    primes = po.coeff_modulus_create(N, [60] * (l + 1))
+    o = po.Oracle(N, primes)
+    k = l + 1
+    P = primes[-1]
+    key = np.stack([np.full((l, 2, N), primes[i] - 1, dtype=np.uint64) for i in range(k)], axis=2)
+    target = _worst_target(o, primes, l, N, form)
+    ct = _worst_target(o, primes, l, N, "qm1")
+    ct = np.stack([ct, ct])
+    out = o.switch_key(ct, target, key)
+    t = [np.array([int(v) for v in o.intt(J, target[J])], dtype=object) for J in range(l)]
+    mods, kidx = primes[:l] + [P], list(range(l)) + [k - 1]
+    prod = []
+    for I in range(l + 1):
+        q = mods[I]
+        acc = np.zeros(N, dtype=object)
+        for J in range(l):
+            tj = np.array([int(v) for v in o.ntt(kidx[I], (t[J] % q).astype(np.uint64))], dtype=object)
+            acc = acc + tj * (q - 1)  # exact: the oracle reduces once per digit or once at the end, Python never
+        acc = acc % q
+        prod.append(np.array([int(v) for v in o.intt(kidx[I], acc.astype(np.uint64))], dtype=object))
+    rr = (prod[l] + (P >> 1)) % P
+    for K in range(2):  # both key polynomials are q - 1: prod is the same for K = 0, 1
+        for J in range(l):
+            q = primes[J]
+            base = np.array([int(v) for v in o.intt(J, ct[K, J])], dtype=object)
+            u = (rr % q - (P >> 1) % q) % q
+            exp = (base + (prod[J] - u) * pow(P, -1, q)) % q
+            got = np.array([int(v) for v in o.intt(J, out[K, J])], dtype=object)
+            assert np.array_equal(got, exp), (form, l, K, J)
+
+
+@pytest.mark.parametrize("N,bits", [(1024, [60, 60, 60, 60]), (1024, [60, 40, 30, 60]), (2048, [50, 20, 60])])
+def test_rescale_on_rounding_ties(N, bits):
+    """rescale == divide_round after CRT when the dropped limb's coefficients are 0, (q_last - 1) / 2, (q_last + 1) / 2
+    and q_last - 1 — the ties of its rounding — and the other limbs hold random residues or q - 1"""
+    o, primes = _ctx(N, bits)
+    l = len(primes) - 1
+    ql = primes[l - 1]
+    rng = random.Random(13)
+    pat = [0, (ql - 1) // 2, (ql + 1) // 2, ql - 1]
+    coeff = [[rng.randrange(primes[i]) if j % 8 < 4 else primes[i] - 1 for j in range(N)] for i in range(l - 1)]
+    coeff.append([pat[j % 4] for j in range(N)])
+    ct = np.stack([np.stack([o.ntt(i, np.array(coeff[i], dtype=np.uint64)) for i in range(l)])] * 2)
+    out = o.rescale(ct)
+    got = [[int(v) for v in o.intt(i, out[0, i])] for i in range(l - 1)]
+    for j in range(N):
+        X, _ = pyref.crt([coeff[i][j] for i in range(l)], primes[:l])
+        Y = pyref.divide_round(X, ql)
+        for i in range(l - 1):
+            assert got[i][j] == Y % primes[i], (j, i)
+
+
+@pytest.mark.parametrize("form", ["delta", "dense", "qm1"])
+def test_multiply_worst_case_words(form):
+    """multiply on words of q - 1 / the delta and dense forms: the dyadic products against Python integers"""
+    N = 1024
+    primes = po.coeff_modulus_create(N, [60, 60, 60, 60])
+    o = po.Oracle(N, primes)
+    l = 3
+    a = _worst_target(o, primes, l, N, form)
+    b = _worst_target(o, primes, l, N, "qm1")
+    a2, b2 = np.stack([a, b]), np.stack([b, a])
+    d = o.multiply(a2, b2)
+    q = np.array(primes[:l], dtype=object).reshape(l, 1)
+    A, B = a2.astype(object), b2.astype(object)
+    assert np.array_equal(d[0].astype(object), A[0] * B[0] % q)
+    assert np.array_equal(d[1].astype(object), (A[0] * B[1] + A[1] * B[0]) % q)
+    assert np.array_equal(d[2].astype(object), A[1] * B[1] % q)
