@@ -106,6 +106,12 @@ _SIGS = {
     "evah_client_key_upload": [_vp, C.c_int, _u64p],
     "evah_encrypt": [_vp, _vp, C.POINTER(C.c_int8), _vpp],
     "evah_decrypt_decode": [_vp, _vp, C.c_uint32, C.POINTER(C.c_double)],
+    # seeded symmetric ciphertexts
+    "evah_encrypt_symmetric": [_vp, _vp, C.POINTER(C.c_int8), C.POINTER(C.c_uint8), _vpp],
+    "evah_ct_upload_seeded_instances": [_vp, C.c_uint32, C.c_uint32, C.c_double, C.POINTER(_u64p), C.POINTER(C.POINTER(C.c_uint8)),
+                                        C.c_int, _vpp],
+    "evah_ct_write_seeded": [_vp, _vp, _u64p, C.POINTER(C.c_uint8)],
+    "evah_ct_download_poly": [_vp, _vp, C.c_uint32, _u64p],
     # limb-sharded execution
     "evah_ctx_set_shard": [_vp, C.c_uint32, C.c_uint32],
     "evah_ctx_shard_info": [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
@@ -244,6 +250,13 @@ class Ciphertext:
         out = np.empty((b, s, l, self.ctx.N), dtype=np.uint64)
         _chk(_lib.evah_ct_download(self.ctx.h, self.h, _p(out)))
         return out if b > 1 else out[0]
+
+    def download_poly(self, poly):
+        """polynomial `poly` of a single ciphertext as [limbs][N]"""
+        _, l, _ = self.info()
+        out = np.empty((l, self.ctx.N), dtype=np.uint64)
+        _chk(_lib.evah_ct_download_poly(self.ctx.h, self.h, int(poly), _p(out)))
+        return out
 
     def write(self, data):
         """overwrite the device words of this handle (same shape): refill of a captured graph's input"""
@@ -446,6 +459,32 @@ class Context:
         small = np.ascontiguousarray(small, dtype=np.int8)
         h = C.c_void_p()
         _chk(_lib.evah_encrypt(self.h, pt.h, small.ctypes.data_as(C.POINTER(C.c_int8)), C.byref(h)))
+        return Ciphertext(self, h)
+
+    def encrypt_symmetric(self, pt, e, seed):
+        """pt: Plaintext (NTT form); e: int8 [N] error polynomial; seed: 32 bytes -> (c0, c1 = a(seed))"""
+        e = np.ascontiguousarray(e, dtype=np.int8)
+        sd = np.frombuffer(bytes(seed), dtype=np.uint8)
+        assert e.shape == (self.N,) and sd.shape == (32,)
+        h = C.c_void_p()
+        _chk(_lib.evah_encrypt_symmetric(self.h, pt.h, e.ctypes.data_as(C.POINTER(C.c_int8)),
+                                         sd.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(h)))
+        return Ciphertext(self, h)
+
+    def upload_ct_seeded(self, c0s, seeds, scale):
+        """c0s: [batch][limbs][N] (or [limbs][N]); seeds: one 32-byte string per instance -> one (batched) size-2
+        handle whose c1 is expanded from the seeds on the device"""
+        c0s = np.ascontiguousarray(c0s, dtype=np.uint64)
+        if c0s.ndim == 2:
+            c0s = c0s[None]
+        batch, limbs, n = c0s.shape
+        assert n == self.N and len(seeds) == batch
+        sds = [np.frombuffer(bytes(s), dtype=np.uint8).copy() for s in seeds]
+        assert all(s.shape == (32,) for s in sds)
+        ptrs = (_u64p * batch)(*[_p(c0s[b]) for b in range(batch)])
+        sptrs = (C.POINTER(C.c_uint8) * batch)(*[s.ctypes.data_as(C.POINTER(C.c_uint8)) for s in sds])
+        h = C.c_void_p()
+        _chk(_lib.evah_ct_upload_seeded_instances(self.h, batch, limbs, 1.0 * scale, ptrs, sptrs, 0, C.byref(h)))
         return Ciphertext(self, h)
 
     def decrypt_decode(self, ct, n_out):

@@ -5,6 +5,7 @@
 // travel as int8 arrays (3 N bytes per encryption); everything of size N log N or l N runs here.
 //   encrypt  : c = (pk0 u + e0, pk1 u + e1) at l+1 limbs, divided-and-rounded by the extra prime
 //              (same rule as rescale A.5), plus the plaintext on c0
+//   encrypt_symmetric : c1 = a expanded from a 32-byte seed (seeded.hip.h), c0 = pt - (a s + NTT(e)) at pt's limbs
 //   decrypt  : m = c0 + c1 s (+ c2 s^2) per limb, inverse transform, exact recomposition to base-2^64
 //              words (mixed-radix digits first), the words to one double in SEAL 3.6's order with
 //              1/scale folded in and the sign taken against (Q+1)/2, forward special FFT
@@ -13,6 +14,7 @@
 //              decoder, bit for bit (tests/test_decode_parity.py)
 
 #include "launch.hip.h"
+#include "seeded.hip.h"
 
 namespace evah {
 
@@ -35,6 +37,29 @@ k_encrypt_zero(DevCtx cx, const u64 *pk, const u64 *small, uint32_t up, u64 *c) 
   const u64 p = pk[((size_t)K * cx.k + i) * cx.N + n];
   c[((size_t)K * up + i) * cx.N + n] = addmod(mulmod(p, u, pm), e, pm.q);
 }
+// c1 = a, c0 = m - (a s + en) for l limbs; m (NTT plaintext) [l][N], en (NTT error) [l][N], sk [k][N] by prime
+__global__ void __launch_bounds__(256)
+k_encrypt_symmetric(DevCtx cx, Seeds8 seed, const u64 *m, const u64 *en, const u64 *sk, uint32_t l, u64 *c0, u64 *c1) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
+  if (t >= cx.N / 4 || i >= l) return;
+  const uint32_t prime = cx.prime_of(i);
+  const DevPrime pm = cx.primes[prime];
+  u64 a[4];
+  seeded_block(seed.w[0], prime, t, pm, a);
+  const size_t off = (size_t)i * cx.N + 4 * (size_t)t;
+  const u64 *s = sk + (size_t)prime * cx.N + 4 * (size_t)t;
+  const ulonglong2 m01 = ld2(m + off), m23 = ld2(m + off + 2), e01 = ld2(en + off), e23 = ld2(en + off + 2);
+  const ulonglong2 s01 = ld2(s), s23 = ld2(s + 2);
+  const u64 mv[4] = {m01.x, m01.y, m23.x, m23.y}, ev[4] = {e01.x, e01.y, e23.x, e23.y}, sv[4] = {s01.x, s01.y, s23.x, s23.y};
+  u64 b[4];
+#pragma unroll
+  for (int r = 0; r < 4; r++) b[r] = submod(mv[r], addmod(mulmod(a[r], sv[r], pm), ev[r], pm.q), pm.q);
+  st2(c1 + off, make_ulonglong2(a[0], a[1]));
+  st2(c1 + off + 2, make_ulonglong2(a[2], a[3]));
+  st2(c0 + off, make_ulonglong2(b[0], b[1]));
+  st2(c0 + off + 2, make_ulonglong2(b[2], b[3]));
+}
+
 // m[i] = c0 + c1 s + c2 s^2 (size 2 or 3; a size-1 value is its own message)
 __global__ void __launch_bounds__(256)
 k_decrypt_dot(DevCtx cx, const u64 *ct, size_t ps, uint32_t size, const u64 *sk, u64 *m) {
@@ -180,6 +205,41 @@ int evah_encrypt(evah_ctx *c, const evah_pt *pt, const int8_t *small, evah_ct **
     OpModDown::Params mp{r.d, N, ct.d, (size_t)up * N, pt->d, 0, 1, o->d, o->ps, l, l};
     ntt_forward<OpModDown>(c, mp, 2 * l);
     HIPCHK(hipStreamSynchronize(c->stream)); // `small` is pageable host memory
+  } catch (...) {
+    evah_ct_free(c, o);
+    throw;
+  }
+  *out = o;
+  API_END
+}
+
+// Encryptor::encrypt_symmetric of an NTT-form plaintext: e = one error polynomial as int8 [N] (the caller's
+// sampler), a from seed32; c1 = a, c0 = pt - (a s + NTT(e)) at pt's limbs
+int evah_encrypt_symmetric(evah_ctx *c, const evah_pt *pt, const int8_t *e, const uint8_t *seed32, evah_ct **out) {
+  API_BEGIN
+  use(c);
+  if (c->capturing) throw std::logic_error("this call synchronises with the host and cannot be captured into a graph");
+  if (!c->sh->sk.d) throw std::invalid_argument("secret key not present");
+  if (!e || !seed32) throw std::invalid_argument("error polynomial and seed are required");
+  if (c->N % 256) throw std::invalid_argument("encryption needs N divisible by 256");
+  const uint32_t l = pt->limbs;
+  if (l < 1 || l > c->k - 1) throw std::invalid_argument("plaintext level is not valid for encryption"); // no special prime
+  acquire(c, pt->buf);
+  const size_t N = c->N;
+  Scratch e8(c, (N + 7) / 8), en(c, (size_t)l * N);
+  HIPCHK(hipMemcpyAsync(e8.d, e, N, hipMemcpyHostToDevice, c->stream));
+  EW_LAUNCH(k_small_to_residues, dim3(c->N / 256, l, 1), dim3(256), 0, c->stream, c->dev, reinterpret_cast<const int8_t *>(e8.d), 1u, l, en.d);
+  OpPlain::Params fp{en.d, en.d, (size_t)l * N, (size_t)l * N, l, 0, 0, {}};
+  ntt_forward<OpPlain>(c, fp, l);
+  evah_ct *o = ct_new(c, 2, l, pt->scale);
+  try {
+    const Seeds8 s = seeds_of(&seed32, 0, 1);
+    EW_LAUNCH(k_encrypt_symmetric, seeded_grid(c, l, 1), dim3(256), 0, c->stream, c->dev, s, pt->d, en.d, c->sh->sk.d, l, o->d, o->d + o->ps);
+    HIPCHK(hipGetLastError());
+    // the error does not stay behind in pool memory the next call reuses
+    HIPCHK(hipMemsetAsync(en.d, 0, sizeof(u64) * (size_t)l * N, c->stream));
+    HIPCHK(hipMemsetAsync(e8.d, 0, N, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream)); // `e` is pageable host memory
   } catch (...) {
     evah_ct_free(c, o);
     throw;

@@ -1,0 +1,58 @@
+// seeded.hip.h — the expansion of a seeded polynomial, shared by seeded.hip (uploads of c0 + seed)
+// and client.hip (evah_encrypt_symmetric): limb i (chain prime index), coefficient j = (hi 2^64 + lo) mod q_i with
+// (lo, hi) = the words 2 (j % 4) and 2 (j % 4) + 1 (as little-endian u64) of the ChaCha20 block of key = seed, block
+// counter = j / 4 (state words 12-13), nonce = 0x6331000000000000 | i (words 14-15).  The result is limb i of c1 in NTT
+// form as stored; a limb depends only on (seed, i).  Host twin: eva_amd/host/csprng.h seeded_limb.
+#pragma once
+#include "internal.hip.h"
+
+namespace evah {
+
+// up to 8 seeds as launch arguments (256 bytes): no host buffer has to outlive the call, and a launch needs no copy
+struct Seeds8 {
+  uint32_t w[8][8];
+};
+constexpr uint32_t SEEDS_PER_LAUNCH = 8;
+constexpr uint32_t SEED_NONCE_HI = 0x63310000u;
+
+__device__ __forceinline__ uint32_t rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
+#define CHACHA_QR(a, b, c, d)                      \
+  a += b; d = rotl32(d ^ a, 16);                   \
+  c += d; b = rotl32(b ^ c, 12);                   \
+  a += b; d = rotl32(d ^ a, 8);                    \
+  c += d; b = rotl32(b ^ c, 7);
+
+// the four coefficients of block `blk` of limb `prime` (the chain index) as canonical residues
+__device__ __forceinline__ void seeded_block(const uint32_t *key, uint32_t prime, uint64_t blk, const DevPrime &pm, u64 out[4]) {
+  const uint32_t s0 = 0x61707865u, s1 = 0x3320646eu, s2 = 0x79622d32u, s3 = 0x6b206574u;
+  const uint32_t k0 = key[0], k1 = key[1], k2 = key[2], k3 = key[3], k4 = key[4], k5 = key[5], k6 = key[6], k7 = key[7];
+  const uint32_t c0 = (uint32_t)blk, c1 = (uint32_t)(blk >> 32), n0 = prime, n1 = SEED_NONCE_HI;
+  uint32_t x0 = s0, x1 = s1, x2 = s2, x3 = s3, x4 = k0, x5 = k1, x6 = k2, x7 = k3;
+  uint32_t x8 = k4, x9 = k5, x10 = k6, x11 = k7, x12 = c0, x13 = c1, x14 = n0, x15 = n1;
+#pragma unroll
+  for (int r = 0; r < 10; r++) {
+    CHACHA_QR(x0, x4, x8, x12) CHACHA_QR(x1, x5, x9, x13) CHACHA_QR(x2, x6, x10, x14) CHACHA_QR(x3, x7, x11, x15)
+    CHACHA_QR(x0, x5, x10, x15) CHACHA_QR(x1, x6, x11, x12) CHACHA_QR(x2, x7, x8, x13) CHACHA_QR(x3, x4, x9, x14)
+  }
+  x0 += s0; x1 += s1; x2 += s2; x3 += s3; x4 += k0; x5 += k1; x6 += k2; x7 += k3;
+  x8 += k4; x9 += k5; x10 += k6; x11 += k7; x12 += c0; x13 += c1; x14 += n0; x15 += n1;
+  auto w64 = [](uint32_t lo, uint32_t hi) { return (u64)lo | ((u64)hi << 32); };
+  out[0] = barrett128(u128_t{w64(x0, x1), w64(x2, x3)}, pm);
+  out[1] = barrett128(u128_t{w64(x4, x5), w64(x6, x7)}, pm);
+  out[2] = barrett128(u128_t{w64(x8, x9), w64(x10, x11)}, pm);
+  out[3] = barrett128(u128_t{w64(x12, x13), w64(x14, x15)}, pm);
+}
+#undef CHACHA_QR
+
+inline Seeds8 seeds_of(const uint8_t *const *seeds, uint32_t first, uint32_t n) {
+  Seeds8 s;
+  std::memset(&s, 0, sizeof s);
+  for (uint32_t z = 0; z < n; z++) {
+    if (!seeds[first + z]) throw std::invalid_argument("seed pointer is null");
+    std::memcpy(s.w[z], seeds[first + z], 32); // little-endian key words, as the host generator reads its key
+  }
+  return s;
+}
+inline dim3 seeded_grid(const evah_ctx *c, uint32_t limbs, uint32_t z) { return dim3((c->N / 4 + 255) / 256, limbs, z); }
+
+} // namespace evah

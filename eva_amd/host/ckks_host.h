@@ -7,6 +7,7 @@
 // Algebra follows SURVEY.md Appendix A.9/A.10 (restating SEAL 3.6 CKKSEncoder / KeyGenerator /
 // Encryptor / Decryptor).  Randomness is not SEAL's stream; only the algebraic relations matter.
 #pragma once
+#include <array>
 #include <cmath>
 #include <complex>
 #include <cstdint>
@@ -524,12 +525,21 @@ using CipherWords = std::vector<u64, HostAlloc<u64>>;
 // ciphertext over PCIe.  The host words are filled on demand (words(): a download) — by get(),
 // save(), a context on another device, or the host-only code paths.
 struct DeviceResident;
+// A symmetric ciphertext sent as c0 plus the seed of c1 = a: c1's words follow from (seed, limb)
+// alone (seeded_limb, csprng.h), so the value costs half the words of a full ciphertext on the wire and over PCIe
+struct SeededForm {
+  std::array<uint8_t, 32> seed{};
+  CipherWords c0;          // [limbs][N]; empty when the value is device-resident (the handle holds c0)
+  std::vector<u64> primes; // the chain c1 is reduced by (limb i -> primes[i]), so words() needs no context
+  uint32_t N = 0;
+};
 struct HostCipher {
   uint32_t size = 0, limbs = 0;
   double scale = 1.0;
-  mutable CipherWords data; // [size][limbs][N]; empty while the value lives only on the device
+  mutable CipherWords data; // [size][limbs][N]; empty while the value lives only on the device or in its seeded form
   std::shared_ptr<DeviceResident> dev;
   mutable bool words_checked = false; // every word < its prime: verified (values from files / Python) or by construction
+  std::shared_ptr<const SeededForm> seeded; // set by HipSecret::encrypt (and load()); never by execute()
 };
 struct HostPlain {
   uint32_t limbs = 0;
@@ -537,6 +547,45 @@ struct HostPlain {
   std::vector<u64> data; // [limbs][N], NTT form
   mutable bool words_checked = false;
 };
+
+// Secret-key encryption of an NTT-form plaintext at its limbs: c1 = a expanded from `seed`,
+// c0 = m - (a s + NTT(e)) — the sign convention of KeyGenerator::encrypt_zero_symmetric; no special prime, no
+// mod-down.  The value is returned in its seeded form (c0 + seed); words() materialises c1.
+inline HostCipher encrypt_symmetric(const HostContext &cx, const SecretKey &sk, const HostPlain &pt, const std::vector<int8_t> &e,
+                                    const std::array<uint8_t, 32> &seed) {
+  const uint32_t N = cx.N, l = pt.limbs;
+  if (l < 1 || l > cx.k - 1) throw std::invalid_argument("plaintext level is not valid for encryption");
+  auto sf = std::make_shared<SeededForm>();
+  sf->seed = seed;
+  sf->N = N;
+  sf->primes.assign(cx.primes.begin(), cx.primes.begin() + l);
+  sf->c0.resize((size_t)l * N);
+  std::vector<u64> a(N), en(N);
+  for (uint32_t i = 0; i < l; i++) {
+    const u64 q = cx.primes[i];
+    seeded_limb(seed.data(), i, q, N, (uint64_t *)a.data());
+    cx.small_to_ntt(e, i, en.data());
+    const u64 *m = pt.data.data() + (size_t)i * N, *s = sk.s_ntt.data() + (size_t)i * N;
+    u64 *c0 = sf->c0.data() + (size_t)i * N;
+    for (uint32_t j = 0; j < N; j++) c0[j] = evah::submod(m[j], evah::addmod(cx.mulm(a[j], s[j], i), en[j], q), q);
+  }
+  std::fill(en.begin(), en.end(), 0);
+  HostCipher out;
+  out.size = 2;
+  out.limbs = l;
+  out.scale = pt.scale;
+  out.words_checked = true;
+  out.seeded = std::move(sf);
+  return out;
+}
+// the full words [2][l][N] of a seeded value from its host form
+inline void materialise_seeded(const SeededForm &sf, uint32_t limbs, CipherWords &out) {
+  const size_t each = (size_t)limbs * sf.N;
+  if (sf.c0.size() != each || sf.primes.size() < limbs) throw std::runtime_error("seeded ciphertext: c0 or its primes do not match the shape");
+  out.resize(2 * each);
+  std::copy(sf.c0.begin(), sf.c0.end(), out.begin());
+  for (uint32_t i = 0; i < limbs; i++) seeded_limb(sf.seed.data(), i, sf.primes[i], sf.N, (uint64_t *)(out.data() + each + (size_t)i * sf.N));
+}
 
 // Public-key encryption of an NTT-form plaintext at `limbs` data limbs (A.10): encrypt zero one
 // level up (limbs+1 primes), divide-and-round by that extra prime, add the plaintext to c0.

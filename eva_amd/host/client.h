@@ -65,8 +65,8 @@ inline bool HipPublic::client_on_device() {
 }
 
 // same bound as HipExecutor::device_encodable: every rounded coefficient below 2^62 and inside the modulus
-inline bool HipPublic::device_encodable(const std::vector<double> &in, double scale, uint32_t limbs) const {
-  const size_t slots = host->N / 2;
+inline bool device_encodable(const HostContext &hc, const std::vector<double> &in, double scale, uint32_t limbs) {
+  const size_t slots = hc.N / 2;
   if (std::getenv("EVA_DEVICE_ENCODE") && !std::atoi(std::getenv("EVA_DEVICE_ENCODE"))) return false;
   if (in.empty() || in.size() > slots || slots % in.size()) return false;
   double sum = 0;
@@ -74,9 +74,12 @@ inline bool HipPublic::device_encodable(const std::vector<double> &in, double sc
     if (!std::isfinite(x)) return false;
     sum += std::fabs(x);
   }
-  const double bound = 2.0 * sum * (double)(slots / in.size()) * scale / (double)host->N;
+  const double bound = 2.0 * sum * (double)(slots / in.size()) * scale / (double)hc.N;
   const int bits = (int)std::ceil(std::log2(std::max(bound, 1.0))) + 1;
-  return bits < 62 && bits < host->total_bits[limbs];
+  return bits < 62 && bits < hc.total_bits[limbs];
+}
+inline bool HipPublic::device_encodable(const std::vector<double> &in, double scale, uint32_t limbs) const {
+  return evahost::device_encodable(*host, in, scale, limbs);
 }
 
 // coeff_pt: the host encoder's coefficient-form plaintext, or (null) values: the slot values for the device encoder
@@ -141,6 +144,109 @@ public:
   int state = -1;
   std::shared_ptr<DeviceHolder> holder = std::make_shared<DeviceHolder>();
   std::shared_ptr<DeviceCtx> dev;
+  // encrypt() leaves its ciphertexts in HBM (the key pair's device state) unless EVA_RESIDENT=0
+  bool resident = std::getenv("EVA_RESIDENT") ? std::atoi(std::getenv("EVA_RESIDENT")) != 0 : true;
+
+  // Encryptor::encrypt_symmetric + a seeded save: every encrypted input is c0 plus the 32-byte
+  // seed of c1 = a, half the words of HipPublic::encrypt's ciphertexts.  Same input checks and Plain / Raw handling
+  // as HipPublic::encrypt.  Two streams, as in the keygen: seeds (public) and errors (secret) never share one.
+  // seed != 0 is the reproducible test hook (streams (seed, 4) and (seed, 3)) and is NOT secret-grade.
+  HipValuation encrypt(const Valuation &inputs, const CKKSSignature &sig, uint64_t seed = 0) {
+    const size_t slots = host->N / 2;
+    if (sig.vec_size <= 0) throw std::runtime_error("Signature vector size must be positive");
+    if (slots < (size_t)sig.vec_size) throw std::runtime_error("Vector size cannot be larger than slot count");
+    if (slots % sig.vec_size) throw std::runtime_error("Vector size must exactly divide the slot count");
+    std::unique_ptr<SecureRng> seeds = seed ? std::make_unique<SecureRng>(seed, 4) : std::make_unique<SecureRng>();
+    std::unique_ptr<SecureRng> errors = seed ? std::make_unique<SecureRng>(seed, 3) : std::make_unique<SecureRng>();
+    std::vector<std::string> names; // name order: the same seed gives the same valuation whatever the map's order
+    for (auto &kv : inputs) names.push_back(kv.first);
+    std::sort(names.begin(), names.end());
+    HipValuation out;
+    for (const std::string &name : names) {
+      const auto &v = inputs.at(name);
+      if (v.size() != (size_t)sig.vec_size) throw std::runtime_error("Input size does not match program vector size");
+      auto it = sig.inputs.find(name);
+      if (it == sig.inputs.end()) throw std::out_of_range("No input named " + name + " in the signature");
+      const CKKSEncodingInfo &info = it->second;
+      if (info.input_type != Type::Cipher && info.input_type != Type::Plain) {
+        out.values[name] = v;
+        continue;
+      }
+      if ((uint32_t)info.level >= host->k - 1) throw std::runtime_error("Input level exceeds the modulus chain");
+      const uint32_t limbs = host->k - 1 - (uint32_t)info.level;
+      const double scale = std::pow(2.0, (double)info.scale);
+      if (info.input_type == Type::Plain) {
+        HostPlain pt = encode_host(v, scale, limbs);
+        for (uint32_t i = 0; i < limbs; i++) host->ntt(i, pt.data.data() + (size_t)i * host->N);
+        out.values[name] = std::move(pt);
+        continue;
+      }
+      std::array<uint8_t, 32> sd;
+      for (int w = 0; w < 4; w++) {
+        const uint64_t x = (*seeds)();
+        std::memcpy(sd.data() + 8 * w, &x, 8);
+      }
+      std::vector<int8_t> e;
+      host->sample_error(*errors, e);
+      if (on_device()) {
+        out.values[name] = encrypt_on_device(v, scale, limbs, e, sd);
+      } else {
+        HostPlain pt = encode_host(v, scale, limbs);
+        for (uint32_t i = 0; i < limbs; i++) host->ntt(i, pt.data.data() + (size_t)i * host->N);
+        out.values[name] = encrypt_symmetric(*host, sk, pt, e, sd);
+      }
+      std::fill(e.begin(), e.end(), 0);
+    }
+    return out;
+  }
+  // the host encoder's coefficient-form plaintext of v repeated over the slots
+  HostPlain encode_host(const std::vector<double> &v, double scale, uint32_t limbs) const {
+    const size_t slots = host->N / 2;
+    HostPlain pt;
+    pt.limbs = limbs;
+    pt.scale = scale;
+    pt.data.resize((size_t)limbs * host->N);
+    std::vector<double> vec(slots);
+    for (size_t r = 0; r < slots / v.size(); r++) std::copy(v.begin(), v.end(), vec.begin() + r * v.size());
+    host->encode_coeff(vec.data(), scale, limbs, pt.data.data());
+    return pt;
+  }
+  // evah_pt_encode (or the host encoder + evah_pt_upload_coeff) -> evah_encrypt_symmetric; the same words as the
+  // host path bit for bit (same plaintext, exact modular arithmetic)
+  HostCipher encrypt_on_device(const std::vector<double> &v, double scale, uint32_t limbs, const std::vector<int8_t> &e,
+                               const std::array<uint8_t, 32> &sd) {
+    const uint32_t N = host->N;
+    evah_pt *p = nullptr;
+    if (device_encodable(*host, v, scale, limbs)) {
+      chk(evah_pt_encode(dev->h, v.data(), (uint32_t)v.size(), limbs, scale, &p));
+    } else {
+      HostPlain pt = encode_host(v, scale, limbs);
+      chk(evah_pt_upload_coeff(dev->h, limbs, scale, (const uint64_t *)pt.data.data(), &p));
+    }
+    evah_ct *c = nullptr;
+    int rc = evah_encrypt_symmetric(dev->h, p, e.data(), sd.data(), &c);
+    evah_pt_free(dev->h, p);
+    chk(rc);
+    auto handle = std::make_shared<CtHandle>(dev->h, c);
+    auto sf = std::make_shared<SeededForm>();
+    sf->seed = sd;
+    sf->N = N;
+    sf->primes.assign(host->primes.begin(), host->primes.begin() + limbs);
+    HostCipher out;
+    out.size = 2;
+    out.limbs = limbs;
+    out.scale = scale;
+    out.words_checked = true;
+    if (resident) { // stays in HBM; the seed stays with it, so that save() can still write the value compressed
+      out.dev = std::make_shared<DeviceResident>(DeviceResident{dev, nullptr, handle, N});
+      out.seeded = std::move(sf);
+      return out;
+    }
+    sf->c0.resize((size_t)limbs * N); // only c0 crosses PCIe: c1 is the seed's (host words on demand, words())
+    chk(evah_ct_download_poly(dev->h, c, 0, (uint64_t *)sf->c0.data()));
+    out.seeded = std::move(sf);
+    return out;
+  }
   // SEALSecret::decrypt (seal.cpp:124-146)
   Valuation decrypt(const HipValuation &enc, const CKKSSignature &sig) {
     Valuation out;
@@ -149,7 +255,7 @@ public:
       if (auto *c = std::get_if<HostCipher>(&kv.second)) {
         if (on_device()) { // dot product with s, inverse transforms, recomposition and the special FFT on the GPU
           if (c->size < 1 || c->size > 3 || c->limbs < 1 || c->limbs > host->k - 1 ||
-              (!resident_only(*c) && c->data.size() != (size_t)c->size * c->limbs * host->N) || (c->dev && c->dev->N != host->N))
+              (!resident_only(*c) && words(*c).size() != (size_t)c->size * c->limbs * host->N) || (c->dev && c->dev->N != host->N))
             throw std::runtime_error("output " + kv.first + ": ciphertext shape does not match its data or the encryption parameters");
           v.resize((size_t)sig.vec_size);
           if (c->dev && c->dev->root == dev) { // resident on this key pair's device state: read in place

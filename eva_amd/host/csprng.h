@@ -14,6 +14,47 @@
 
 namespace evahost {
 
+// RFC 8439 section 2.3 block function: out = the 16 words of the block for the state `in`
+inline void chacha20_block(const uint32_t in[16], uint32_t out[16]) {
+  auto rotl = [](uint32_t x, int r) { return (x << r) | (x >> (32 - r)); };
+  auto quarter = [&](uint32_t *s, int a, int b, int c, int d) {
+    s[a] += s[b]; s[d] = rotl(s[d] ^ s[a], 16);
+    s[c] += s[d]; s[b] = rotl(s[b] ^ s[c], 12);
+    s[a] += s[b]; s[d] = rotl(s[d] ^ s[a], 8);
+    s[c] += s[d]; s[b] = rotl(s[b] ^ s[c], 7);
+  };
+  std::memcpy(out, in, 64);
+  for (int r = 0; r < 10; r++) {
+    quarter(out, 0, 4, 8, 12); quarter(out, 1, 5, 9, 13); quarter(out, 2, 6, 10, 14); quarter(out, 3, 7, 11, 15);
+    quarter(out, 0, 5, 10, 15); quarter(out, 1, 6, 11, 12); quarter(out, 2, 7, 8, 13); quarter(out, 3, 4, 9, 14);
+  }
+  for (int i = 0; i < 16; i++) out[i] += in[i];
+}
+
+// Limb `prime` (the chain index) of the uniform polynomial a of a seeded symmetric ciphertext, in NTT
+// form as stored: coefficient j = (hi 2^64 + lo) mod q with (lo, hi) = u64 words 2 (j % 4), 2 (j % 4) + 1 of the
+// ChaCha20 block with key = seed, block counter j / 4 (state words 12-13), nonce 0x6331000000000000 | prime (words
+// 14-15).  No rejection: the bias is below q / 2^128.  The device twin is csrc/seeded.hip.
+inline void seeded_limb(const uint8_t seed[32], uint32_t prime, uint64_t q, uint32_t N, uint64_t *out) {
+  static const uint32_t sigma[4] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u};
+  uint32_t st[16], w[16];
+  std::memcpy(st, sigma, 16);
+  std::memcpy(st + 4, seed, 32);
+  const uint64_t nonce = 0x6331000000000000ull | prime;
+  st[14] = (uint32_t)nonce;
+  st[15] = (uint32_t)(nonce >> 32);
+  for (uint32_t j0 = 0; j0 < N; j0 += 4) {
+    const uint64_t blk = j0 / 4;
+    st[12] = (uint32_t)blk;
+    st[13] = (uint32_t)(blk >> 32);
+    chacha20_block(st, w);
+    for (uint32_t r = 0; r < 4 && j0 + r < N; r++) {
+      const uint64_t lo = (uint64_t)w[4 * r] | ((uint64_t)w[4 * r + 1] << 32), hi = (uint64_t)w[4 * r + 2] | ((uint64_t)w[4 * r + 3] << 32);
+      out[j0 + r] = (uint64_t)((((unsigned __int128)hi << 64) | lo) % q);
+    }
+  }
+}
+
 class SecureRng {
 public:
   using result_type = uint64_t;
@@ -56,13 +97,6 @@ private:
     volatile unsigned char *v = static_cast<volatile unsigned char *>(p);
     while (n--) *v++ = 0;
   }
-  static uint32_t rotl(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
-  static void quarter(uint32_t *s, int a, int b, int c, int d) {
-    s[a] += s[b]; s[d] = rotl(s[d] ^ s[a], 16);
-    s[c] += s[d]; s[b] = rotl(s[b] ^ s[c], 12);
-    s[a] += s[b]; s[d] = rotl(s[d] ^ s[a], 8);
-    s[c] += s[d]; s[b] = rotl(s[b] ^ s[c], 7);
-  }
   void init(const unsigned char *key, const unsigned char *nonce8) {
     static const uint32_t sigma[4] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u};
     std::memcpy(state_, sigma, 16);
@@ -72,12 +106,7 @@ private:
   }
   void refill() {
     uint32_t w[16];
-    std::memcpy(w, state_, sizeof w);
-    for (int r = 0; r < 10; r++) {
-      quarter(w, 0, 4, 8, 12); quarter(w, 1, 5, 9, 13); quarter(w, 2, 6, 10, 14); quarter(w, 3, 7, 11, 15);
-      quarter(w, 0, 5, 10, 15); quarter(w, 1, 6, 11, 12); quarter(w, 2, 7, 8, 13); quarter(w, 3, 4, 9, 14);
-    }
-    for (int i = 0; i < 16; i++) w[i] += state_[i];
+    chacha20_block(state_, w);
     std::memcpy(block_, w, sizeof block_);
     wipe(w, sizeof w);
     if (++state_[12] == 0) ++state_[13];

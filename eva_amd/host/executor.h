@@ -54,8 +54,15 @@ public:
   // values may come from files or from Python (_set_cipher): before any upload the declared shape
   // has to agree with the data length and the context, or the copy would read past the host buffer
   void check_shape(const std::string &name, const HostCipher &c) const {
+    // a seeded value of other parameters (another prime chain) travels as its full words
+    if (seeded_on_host(c) && !resident_only(c) && !seeded_upload_ok(c, host) && c.seeded->primes.size() >= c.limbs) (void)words(c);
+    const bool seeded = c.data.empty() && !c.dev && seeded_upload_ok(c, host);
+    if (seeded && !c.words_checked) { // c1 is reduced by construction; c0 may come from a file
+      check_words(name, c.seeded->c0.data(), 1, c.limbs);
+      c.words_checked = true;
+    }
     if (c.size < 1 || c.size > 3 || c.limbs < 1 || c.limbs > host.k - 1 ||
-        (!resident_only(c) && c.data.size() != (size_t)c.size * c.limbs * host.N) ||
+        (!resident_only(c) && !seeded && c.data.size() != (size_t)c.size * c.limbs * host.N) ||
         (c.dev && c.dev->N != host.N)) // a resident value of another key pair: its download would have the wrong length
       throw std::runtime_error("input " + name + ": ciphertext shape does not match its data or the encryption parameters");
     if (!c.words_checked && !c.data.empty()) { // once per value: files and Python arrays are untrusted
@@ -106,8 +113,15 @@ public:
           resident_inputs.push_back(c->dev);
           continue;
         }
-        const CipherWords &w = words(*c); // a value of another device state comes through the host
         evah_ct *h = nullptr;
+        if (seeded_upload_ok(*c, host)) { // c0 + 32 bytes over PCIe, c1 expanded on the device
+          const uint64_t *c0 = (const uint64_t *)c->seeded->c0.data();
+          const uint8_t *sd = c->seeded->seed.data();
+          chk(evah_ct_upload_seeded_instances(ctx, 1, c->limbs, c->scale, &c0, &sd, 0, &h));
+          objects[t] = std::make_shared<CtHandle>(ctx, h);
+          continue;
+        }
+        const CipherWords &w = words(*c); // a value of another device state comes through the host
         chk(evah_ct_upload(ctx, c->size, c->limbs, c->scale, (const uint64_t *)w.data(), &h));
         objects[t] = std::make_shared<CtHandle>(ctx, h);
       } else if (auto *p = std::get_if<HostPlain>(&kv.second)) {
@@ -160,6 +174,15 @@ public:
           for (uint32_t b = 0; b < B; b++) hs[b] = rh[b]->h;
           chk(evah_ct_stack(ctx, hs.data(), B, &h));
           batch_inputs_resident = true;
+        } else if (std::all_of(batch.begin(), batch.end(), [&](const HipValuation *v) { return seeded_upload_ok(std::get<HostCipher>(v->values.at(kv.first)), host); })) {
+          // every instance seeded on the host: c0 words + 32 bytes each, c1 expanded on this queue
+          std::vector<const uint8_t *> seeds(B);
+          for (uint32_t b = 0; b < B; b++) {
+            const SeededForm &sf = *std::get<HostCipher>(batch[b]->values.at(kv.first)).seeded;
+            ptrs[b] = (const uint64_t *)sf.c0.data();
+            seeds[b] = sf.seed.data();
+          }
+          chk(evah_ct_upload_seeded_instances(ctx, B, c0->limbs, c0->scale, ptrs.data(), seeds.data(), async ? 1 : 0, &h));
         } else {
           for (uint32_t b = 0; b < B; b++) ptrs[b] = (const uint64_t *)words(std::get<HostCipher>(batch[b]->values.at(kv.first))).data();
           chk((async ? evah_ct_upload_instances_async : evah_ct_upload_instances)(ctx, B, c0->size, c0->limbs, c0->scale, ptrs.data(), &h));

@@ -295,8 +295,15 @@ PYBIND11_MODULE(_eva, m) {
         auto it = v.values.find(name);
         if (it == v.values.end()) throw std::out_of_range("No value named " + name);
         auto *c = std::get_if<HostCipher>(&it->second);
-        return !c || !c->data.empty();
-      }, py::arg("name"), "True when host words of the value exist (always, for plaintexts and raw vectors)")
+        return !c || !c->data.empty() || seeded_on_host(*c);
+      }, py::arg("name"), "True when host words of the value exist (always, for plaintexts and raw vectors; c0 + seed for a seeded ciphertext)")
+      .def("seed", [](const HipValuation &v, const std::string &name) -> py::object {
+        auto it = v.values.find(name);
+        if (it == v.values.end()) throw std::out_of_range("No value named " + name);
+        auto *c = std::get_if<HostCipher>(&it->second);
+        if (!c || !c->seeded) return py::none();
+        return py::bytes(reinterpret_cast<const char *>(c->seeded->seed.data()), 32);
+      }, py::arg("name"), "The 32-byte seed of c1 of a ciphertext from SEALSecret.encrypt (DESIGN.md 1.3), else None")
       .def("to_host", [](HipValuation &v, bool drop_device) {
         for (auto &kv : v.values)
           if (auto *c = std::get_if<HostCipher>(&kv.second)) {
@@ -421,6 +428,13 @@ PYBIND11_MODULE(_eva, m) {
         return d;
       });
   py::class_<HipSecret, std::shared_ptr<HipSecret>>(mseal, "SEALSecret", "Secret context: decryption. Holds the secret key.")
+      .def("encrypt", [](HipSecret &s, const Valuation &inputs, const CKKSSignature &sig, uint64_t seed) {
+        HipValuation v = s.encrypt(inputs, sig, seed);
+        v.params = s.host;
+        return v;
+      }, py::arg("inputs"), py::arg("signature"), py::arg("seed") = 0,
+         "Secret-key encryption: every ciphertext is c0 plus the 32-byte seed of c1 (half the bytes of SEALPublic.encrypt). "
+         "seed != 0: reproducible test streams, not secret-grade")
       .def("decrypt", &HipSecret::decrypt, py::arg("enc_outputs"), py::arg("signature"))
       .def_readwrite("device", &HipSecret::device, "device of the secret half's state when it is not shared with a public context")
       // test hook (as relin_key() on the public side): the secret key under every key prime, NTT form [k][N]

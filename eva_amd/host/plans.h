@@ -25,7 +25,11 @@ inline std::unique_ptr<HipPublic::GraphPlan> HipPublic::build_plan(Program &prog
       ex.check_shape(kv.first, *c);
       evah_ct *h = nullptr;
       if (c->dev && c->dev->root == dev) chk(evah_ct_copy(q0, c->dev->h->h, &h)); // the slot is the graph's own buffer
-      else chk(evah_ct_upload(q0, c->size, c->limbs, c->scale, (const uint64_t *)words(*c).data(), &h));
+      else if (seeded_upload_ok(*c, *host)) {
+        const uint64_t *c0 = (const uint64_t *)c->seeded->c0.data();
+        const uint8_t *sd = c->seeded->seed.data();
+        chk(evah_ct_upload_seeded_instances(q0, 1, c->limbs, c->scale, &c0, &sd, 0, &h));
+      } else chk(evah_ct_upload(q0, c->size, c->limbs, c->scale, (const uint64_t *)words(*c).data(), &h));
       auto sp = std::make_shared<CtHandle>(q0, h);
       plan->in_ct[kv.first] = sp;
       ex.set_value(t, sp);
@@ -74,6 +78,10 @@ inline HipValuation HipPublic::run_plan(HipPublic::GraphPlan &plan, const HipVal
     if (auto *c = std::get_if<HostCipher>(&kv.second)) {
       if (c->dev && c->dev->root == dev) { // resident: refill the slot device to device
         chk(evah_ct_assign(q0, plan.in_ct.at(kv.first)->h, c->dev->h->h));
+        continue;
+      }
+      if (seeded_upload_ok(*c, *host)) { // c0 + 32 bytes; c1 expanded into the slot on the plan's queue
+        chk(evah_ct_write_seeded(q0, plan.in_ct.at(kv.first)->h, (const uint64_t *)c->seeded->c0.data(), c->seeded->seed.data()));
         continue;
       }
       const CipherWords &w = words(*c);

@@ -183,6 +183,21 @@ inline void write(Writer &w, const HipValuation &v) {
   for (auto &kv : v.values) {
     w.str(kv.first);
     if (auto *c = std::get_if<HostCipher>(&kv.second)) {
+      if (c->seeded && c->size == 2) {
+        // kind 4, a seeded symmetric ciphertext: limbs, scale, N, the primes of its limbs, the
+        // seed, c0 — about half the bytes of kind 1; c1 is expanded again when somebody needs its words
+        const SeededForm &sf = *c->seeded;
+        const size_t each = (size_t)c->limbs * sf.N;
+        const u64 *c0 = sf.c0.empty() ? words(*c).data() : sf.c0.data(); // a resident value: c0 downloaded for the file
+        if (sf.primes.size() < c->limbs || (sf.c0.empty() ? c->data.size() < each : sf.c0.size() != each))
+          throw std::runtime_error("seeded ciphertext " + kv.first + ": c0 does not match its shape");
+        w.pod<uint32_t>(4); w.pod(c->limbs); w.pod(c->scale); w.pod(sf.N);
+        w.vec(std::vector<u64>(sf.primes.begin(), sf.primes.begin() + c->limbs));
+        w.pod(sf.seed);
+        w.pod<uint64_t>(each);
+        w.buf.insert(w.buf.end(), reinterpret_cast<const char *>(c0), reinterpret_cast<const char *>(c0 + each));
+        continue;
+      }
       w.pod<uint32_t>(1); w.pod(c->size); w.pod(c->limbs); w.pod(c->scale);
       w.vec(words(*c)); // a device-resident value is downloaded for the file
     }
@@ -216,6 +231,21 @@ inline HipValuation read_valuation(Reader &r) {
       v.values[name] = std::move(p);
     }
     else if (kind == 3) v.values[name] = r.vec<double>();
+    else if (kind == 4) {
+      HostCipher c; c.size = 2; c.limbs = r.pod<uint32_t>(); c.scale = r.pod<double>();
+      auto sf = std::make_shared<SeededForm>();
+      sf->N = r.pod<uint32_t>();
+      sf->primes = r.vec<u64>();
+      sf->seed = r.pod<std::array<uint8_t, 32>>();
+      { auto w = r.vec<u64>(); sf->c0.assign(w.begin(), w.end()); }
+      if (c.limbs < 1 || c.limbs > 61 || sf->primes.size() != c.limbs || sf->N < 1024 || sf->N > 131072 || (sf->N & (sf->N - 1)) ||
+          sf->c0.size() != (size_t)c.limbs * sf->N)
+        throw std::runtime_error("Could not parse message: seeded ciphertext shape does not match its data");
+      for (u64 q : sf->primes)
+        if (q < 2 || q >> 61) throw std::runtime_error("Could not parse message: seeded ciphertext prime out of range");
+      c.seeded = std::move(sf);
+      v.values[name] = std::move(c);
+    }
     else throw std::runtime_error("Could not parse message: unknown value kind");
   }
   return v;

@@ -152,16 +152,33 @@ struct DeviceResident {
   uint32_t N = 0;                  // poly_modulus_degree: words per limb
   evah_ctx *ctx() const { return queue ? queue->h : root->h; }
 };
-// host words of a ciphertext value, downloaded on first use (waits for the value to be computed)
+// host words of a ciphertext value, downloaded on first use (waits for the value to be computed) or expanded
+// from its seeded form (c0 + seed)
 inline const CipherWords &words(const HostCipher &c) {
   if (c.data.empty() && c.dev) {
     CipherWords w((size_t)c.size * c.limbs * c.dev->N);
     chk(evah_ct_download(c.dev->ctx(), c.dev->h->h, (uint64_t *)w.data()));
     c.data = std::move(w);
     c.words_checked = true; // the device's own residues
+  } else if (c.data.empty() && c.seeded && !c.seeded->c0.empty()) {
+    if (c.size != 2) throw std::runtime_error("a seeded ciphertext has two polynomials");
+    CipherWords w;
+    materialise_seeded(*c.seeded, c.limbs, w);
+    c.data = std::move(w);
   }
   return c.data;
 }
 inline bool resident_only(const HostCipher &c) { return c.data.empty() && c.dev; }
+// c0 + seed on the host: the value can be uploaded seeded (its full words may have been materialised as well)
+inline bool seeded_on_host(const HostCipher &c) { return c.seeded && !c.seeded->c0.empty() && c.size == 2; }
+// ... and the device of `host` expands the same c1: same degree, same primes under the value's limbs
+inline bool seeded_upload_ok(const HostCipher &c, const HostContext &host) {
+  if (!seeded_on_host(c) || c.seeded->N != host.N || c.seeded->primes.size() < c.limbs || c.limbs > host.k - 1 ||
+      c.seeded->c0.size() != (size_t)c.limbs * host.N)
+    return false;
+  for (uint32_t i = 0; i < c.limbs; i++)
+    if (c.seeded->primes[i] != host.primes[i]) return false;
+  return true;
+}
 
 } // namespace evahost

@@ -289,6 +289,24 @@ int evah_encrypt(evah_ctx *ctx, const evah_pt *pt, const int8_t *small, evah_ct 
  * values, the same doubles as the host decoder and the CPU oracle produce */
 int evah_decrypt_decode(evah_ctx *ctx, const evah_ct *ct, uint32_t n_out, double *out);
 
+/* ---- seeded symmetric ciphertexts (Encryptor::encrypt_symmetric + a seeded save) ---------
+ * c1 = a is uniform and travels as a 32-byte seed: limb i, coefficient j is (hi 2^64 + lo) mod q_i with
+ * (lo, hi) = u64 words 2 (j % 4), 2 (j % 4) + 1 of the ChaCha20 block with key = seed, block counter j / 4 and
+ * nonce 0x6331000000000000 | i.  A ciphertext at a lower level is the prefix of the same expansion.
+ * Seeded uploads count in evah_ctx_transfer_stats as c0's words plus 32 bytes per ciphertext. */
+/* c1 = a (from seed32), c0 = pt - (a s + NTT(e)) at pt's limbs; e = one error polynomial as int8 [N]; needs
+ * EVAH_KEY_SECRET */
+int evah_encrypt_symmetric(evah_ctx *ctx, const evah_pt *pt, const int8_t *e, const uint8_t *seed32, evah_ct **out);
+/* `batch` size-2 ciphertexts from c0[b] ([limbs][N] each) and seeds[b] (32 bytes each) as one handle; c1 is
+ * expanded on ctx's queue.  async = 0: returns when the words have landed; async != 0: stream-ordered like
+ * evah_ct_upload_instances_async (c0 arrays stay valid until evah_ctx_sync; the seeds are read at the call) */
+int evah_ct_upload_seeded_instances(evah_ctx *ctx, uint32_t batch, uint32_t limbs, double scale, const uint64_t *const *c0,
+                                    const uint8_t *const *seeds, int async, evah_ct **out);
+/* overwrite a single size-2 handle from c0 [limbs][N] and a seed (the input slot of a captured execute()) */
+int evah_ct_write_seeded(evah_ctx *ctx, evah_ct *ct, const uint64_t *c0, const uint8_t *seed32);
+/* polynomial `poly` of a single ciphertext -> out [limbs][N] (c0 of a seeded value: its c1 is the seed's) */
+int evah_ct_download_poly(evah_ctx *ctx, const evah_ct *ct, uint32_t poly, uint64_t *out);
+
 /* ---- whole-DAG submit: a topologically sorted flat op list over a value table.
  * One call replaces the per-node loop ProgramTraversal::forwardPass + SEALExecutor::operator()
  * (program_traversal.h:36-93, seal_executor.h:279-404) for the encrypted part of a program.
