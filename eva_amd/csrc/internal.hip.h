@@ -319,6 +319,11 @@ struct Tunables {
   // a handle become entries of the fused call's launch set); 0 = the three batched calls
   bool chain_step = true, chain_batched = true;
   uint32_t chain_fuse_blocks = 256;
+  // EVAH_MODUP (1): a key switch too large for the fused small-launch form, in one output-limb slice (EVAH_KS_GROUPS 1),
+  // runs the digits' strided inverse pass and their conversion + first forward pass under every output prime as ONE
+  // launch, a workgroup per digit tile (ntt_modup_kernel, ntt_modup.hip.h); 0 = the strided inverse pass storing the
+  // canonical digits, then the OpKsDigit strided pass reading each digit tile once per output prime
+  bool modup = true;
   // EVAH_LDS_EXTRA (0): bytes of dynamic LDS added to every ntt_pass_kernel launch — an occupancy probe for the
   // tuning notes (fewer workgroups per CU), never set in production
   uint32_t lds_extra = 0;
@@ -358,6 +363,7 @@ struct Tunables {
     flag("EVAH_CHAIN_STEP", t.chain_step);
     flag("EVAH_CHAIN_BATCHED", t.chain_batched);
     count("EVAH_CHAIN_FUSE_BLOCKS", t.chain_fuse_blocks);
+    flag("EVAH_MODUP", t.modup);
     count("EVAH_HOIST_V", t.hoist_v);
     if (const char *e = std::getenv("EVAH_KS_GROUPS")) t.ks_groups = std::max(1, std::atoi(e));
     if (const char *e = std::getenv("EVAH_KS_THREADS")) {

@@ -145,14 +145,17 @@ bool switch_key_products(evah_ctx *c, uint32_t l, const u64 *target, size_t targ
   // a small key switch is latency-bound: the digits' strided inverse pass and the first pass of the
   // digit conversion then run as one launch
   const bool small = c->tun.fuse_mac && std::max(1, c->tun.ks_groups) == 1 && fuse_small_launch(c, n * (l + 1) * l);
+  // a throughput-sized one: the strided inverse pass of each digit tile runs once, in the workgroup that converts it for
+  // every output prime (ntt_modup_kernel) — t is then the contiguous pass's intermediate, never the canonical digits
+  const bool modup = !small && c->tun.modup && c->tun.fuse_mac && std::max(1, c->tun.ks_groups) == 1 && modup_fits(c);
   if (mul) { // the target is the product's d2, formed on load
     OpMulIntt::Params ip{*mul, t.d, (size_t)l * N, l, fold ? d2.d : nullptr};
-    if (small) launch_pass_p<false, true, OpMulIntt>(c, c->logN / 2, ip, n * l);
+    if (small || modup) launch_pass_p<false, true, OpMulIntt>(c, c->logN / 2, ip, n * l);
     else ntt_inverse<OpMulIntt>(c, ip, n * l);
   } else {
     OpPlain::Params ip{target, t.d, target_bs, (size_t)l * N, l, 0, 0, {}};
     if (target_tab) ip.src_tab = *target_tab;
-    if (small) launch_pass_p<false, true, OpPlain>(c, c->logN / 2, ip, n * l);
+    if (small || modup) launch_pass_p<false, true, OpPlain>(c, c->logN / 2, ip, n * l);
     else ntt_inverse<OpPlain>(c, ip, n * l);
   }
   if (small) {
@@ -179,8 +182,10 @@ bool switch_key_products(evah_ctx *c, uint32_t l, const u64 *target, size_t targ
       if (i1 == i0) continue;
       dp.i0 = kb.i0 = i0;
       dp.ni = kb.ni = i1 - i0;
-      // 2a. base-convert + first (strided) NTT pass of every digit under the slice's output primes
-      launch_pass_p<true, false, OpKsDigit>(c, a, dp, n * (i1 - i0) * l);
+      // 2a. base-convert + first (strided) NTT pass of every digit under the slice's output primes (modup: with the
+      // digits' strided inverse pass in front, all output primes in one slice)
+      if (modup) launch_modup<OpKsDigit>(c, dp, n);
+      else launch_pass_p<true, false, OpKsDigit>(c, a, dp, n * (i1 - i0) * l);
       // 2b. second (contiguous) pass fused with the inner product with the key
       launch_ks_inner(c, b, target, sc.d, kb, prod_d, l);
     }

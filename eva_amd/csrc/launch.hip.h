@@ -189,6 +189,30 @@ template <class Op> static void launch_inv_fwd(evah_ctx *c, const typename Op::P
   default: throw std::runtime_error("unsupported poly_modulus_degree for the fused inverse/forward pass");
   }
 }
+// ---- the key switch's mod-up at throughput size: strided inverse pass of each digit, then its conversion and forward
+// strided pass under every output prime of prm (i0 = 0, istep = 1), one workgroup per (column tile, digit, instance) —
+// ntt_modup_kernel (ntt_modup.hip.h).  n = instances; the digits' contiguous inverse pass left its intermediate in prm.t
+static inline bool modup_fits(evah_ctx *c) { return c->N >= ((uint32_t)NTT_THREADS << 3) && (c->logN + 1) / 2 <= 9; }
+template <int P, class Op> static void launch_modup_p(evah_ctx *c, const typename Op::Params &prm, uint32_t n) {
+  ProfScope ps(c, OpClass<Op>::fwd_a);
+  constexpr int LR = 3;
+  const uint32_t tile = (uint32_t)NTT_THREADS << LR, n_tiles = c->N / tile;
+  const int logC = (int)ilog2(tile) - P;
+  const size_t lds = ((((size_t)1 << logC) * lds_sub_stride<P>() + 1) & ~(size_t)1) * sizeof(u64) + ((size_t)1 << P) * sizeof(ulonglong2);
+  hipLaunchKernelGGL((ntt_modup_kernel<P, LR, Op>), dim3(n_tiles * prm.l, 1, n), dim3(NTT_THREADS), lds, c->stream, c->dev, prm,
+                     (int)ilog2(n_tiles));
+  HIPCHK(hipGetLastError());
+}
+template <class Op> static void launch_modup(evah_ctx *c, const typename Op::Params &prm, uint32_t n) {
+  if (!modup_fits(c) || prm.i0 != 0 || prm.istep != 1) throw std::logic_error("mod-up kernel outside its shapes");
+  switch ((c->logN + 1) / 2) {
+  case 6: launch_modup_p<6, Op>(c, prm, n); break;
+  case 7: launch_modup_p<7, Op>(c, prm, n); break;
+  case 8: launch_modup_p<8, Op>(c, prm, n); break;
+  case 9: launch_modup_p<9, Op>(c, prm, n); break;
+  default: throw std::runtime_error("unsupported poly_modulus_degree for the mod-up kernel");
+  }
+}
 // two strided inverse passes + combine (+ strided forward pass): ntt_inv2_kernel (ntt_chain.hip.h)
 template <int P, class Op, bool FWD, int LR> static void launch_inv2_plr(evah_ctx *c, const typename Op::Params &prm, uint32_t jobs) {
   ProfScope ps(c, OpClass<Op>::fwd_a);

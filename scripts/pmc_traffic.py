@@ -20,6 +20,8 @@ def classify(name):
         if m.group(1) == "true":
             return "intt_pass1"
         return f"{base or 'ntt'}_pass2"
+    if "ntt_modup_kernel" in name:  # the digits' strided inverse pass + their first forward pass: attributed to the latter
+        return f"{base or 'ntt'}_pass1"
     if "ntt_pass_kernel" in name:
         import re
         m = re.search(r"ntt_pass_kernel<\d+, \d+, (true|false), (true|false)", name)
