@@ -6,7 +6,15 @@ on (MAC3's fold every 7 digits and its l <= 15 gate, the 128-bit path's fold eve
   delta  each c1 / target limb is the constant x = min(primes) - 1 in NTT form (x * delta in coefficient form), so every
          digit of every limb is x, and the transforms see zero y inputs, which push their lazy values up;
   dense  every coefficient is x (no zero coefficients: the hoisted rotations stay on their MAC kernel);
-  qm1    q - 1 in every word.
+  qm1    q - 1 in every word;
+  dense_max  limb J has every COEFFICIENT at q_J - 1, so every digit sits at its own prime's maximum (x above is the
+         smallest prime's, which in a mixed chain leaves the larger primes' digits far below theirs).
+At N = 4096 a single key switch of l <= 31 takes the fused small-launch form, so the cases above hardly reach the mod-up
+kernel of throughput-sized key switches (ntt_modup_kernel).  test_key_switch_forms_on_the_mod_up_kernel and
+test_other_prime_shapes_on_the_mod_up_kernel run the same words with EVAH_FUSE_SMALL=0 (l = 1, 7, 8, 15, 16, 17; the chains
+with primes of no top-bit shape), and check by launch counts that the kernel is what ran.
+test_digit_conversion_at_the_lazy_flag_boundary has primes on both sides of the digit conversion's rule "q_J <= 8 q_kappa:
+the digit enters the forward rounds unreduced" by the narrowest margin there is (BOUNDARY below), in both launch forms.
 Rounding ties (coefficients (q_last +- 1) / 2 of the dropped limb) go through rescale, the fused forms and the chain step."""
 import os
 
@@ -40,13 +48,22 @@ def _ntt_prime_below(bound, N):
     return q
 
 
+def _ntt_prime_above(bound, N):
+    """the smallest prime q > bound with q = 1 (mod 2N)"""
+    q = bound - (bound % (2 * N)) + 1
+    while q <= bound or not po.lib.evo_is_prime(q):
+        q += 2 * N
+    return q
+
+
 def _forms(o, primes, nl, N):
-    """(name, poly of nl limbs in NTT form) for the three worst-case shapes"""
+    """(name, poly of nl limbs in NTT form) for the four worst-case shapes"""
     x = min(primes) - 1
     delta = np.stack([np.full(N, x % primes[i], dtype=np.uint64) for i in range(nl)])
     dense = np.stack([o.ntt(i, np.full(N, x % primes[i], dtype=np.uint64)) for i in range(nl)])
     qm1 = np.stack([np.full(N, primes[i] - 1, dtype=np.uint64) for i in range(nl)])
-    return [("delta", delta), ("dense", dense), ("qm1", qm1)]
+    dense_max = np.stack([o.ntt(i, np.full(N, primes[i] - 1, dtype=np.uint64)) for i in range(nl)])
+    return [("delta", delta), ("dense", dense), ("qm1", qm1), ("dense_max", dense_max)]
 
 
 def _keys(primes, l, N, rng, kind):
@@ -67,7 +84,27 @@ def _ties(o, primes, nl, N):
     return np.stack([o.ntt(i, (coeff % primes[i]).astype(np.uint64)) for i in range(nl)])
 
 
-def _check_key_switches(g, o, primes, rng, key_kind, forms=None):
+# one relinearize of a stored size-3 ciphertext when its key switch runs on ntt_modup_kernel (switch_key_products +
+# switch_key's mod-down, nothing in the small-launch form): the digits' strided inverse pass is inside the ksdigit_pass1
+# launch, so the only intt_pass2 launch is the special rows'.  The two-launch form (EVAH_MODUP=0) has two, the small-launch
+# form none (test_gpu_modup_forms.py compares the three)
+MODUP_LAUNCHES = {"elementwise": 0, "intt_pass1": 2, "intt_pass2": 1, "ksdigit_pass1": 1, "ksdigit_pass2": 0, "ks_mac": 1,
+                  "moddown_pass1": 1, "moddown_pass2": 1, "ntt_pass1": 0, "ntt_pass2": 0}
+
+
+def _relinearize_launches(g, A3):
+    g.profile(True)
+    g.profile_reset()
+    out = g.relinearize(A3)
+    g.sync()
+    prof = g.profile_get()
+    g.profile(False)
+    del out
+    return {name: n for name, (n, _) in prof.items()}
+
+
+def _check_key_switches(g, o, primes, rng, key_kind, forms=None, launches=None):
+    """launches: the launch counts one relinearize must show (None: not checked)"""
     N, k = o.N, len(primes)
     l = k - 1
     rk = _keys(primes, l, N, rng, key_kind)
@@ -85,6 +122,8 @@ def _check_key_switches(g, o, primes, rng, key_kind, forms=None):
         A3 = g.upload_ct(a3, 2.0 ** 20)
         want = o.relinearize(a3, rk)
         assert np.array_equal(g.relinearize(A3).download(), want), f"relinearize {name} l={l}"
+        if launches is not None and name == F[0][0]:
+            assert _relinearize_launches(g, A3) == launches
         if l >= 2:
             assert np.array_equal(g.relinearize_rescale(A3, div).download(), o.rescale(want)), f"relinearize_rescale {name}"
             for got in g.relinearize_rescale_many([A3, A3], div):
@@ -154,6 +193,22 @@ def test_key_switch_forms_on_worst_case_words(name, N, bits, knobs):
     g.close()
 
 
+# the same words on ntt_modup_kernel: EVAH_FUSE_SMALL=0 sends every key switch past the small-launch form.  l = 1 (one digit,
+# whose only job is the special row), both sides of MAC3's first fold (7 | 8) and of its gate (15 | 16), the 128-bit path's
+# first fold (15 | 16 | 17); l = 30 and 31 are not repeated, the n = 2 calls of the cases above reach the kernel already
+MODUP_CHAINS = [c for c in CHAINS if len(c[2]) - 1 in (1, 7, 8, 15, 16, 17)]
+
+
+@pytest.mark.parametrize("name,N,bits,knobs", MODUP_CHAINS, ids=[c[0] for c in MODUP_CHAINS])
+def test_key_switch_forms_on_the_mod_up_kernel(name, N, bits, knobs):
+    primes = po.coeff_modulus_create(N, bits)
+    o = po.Oracle(N, primes)
+    g = _ctx(N, primes, dict(knobs, EVAH_FUSE_SMALL=0))
+    rng = np.random.default_rng(len(bits))
+    _check_key_switches(g, o, primes, rng, "qm1", launches=MODUP_LAUNCHES)
+    g.close()
+
+
 def _special_chains():
     N = 4096
     c60 = po.coeff_modulus_create(N, [60] * 5)
@@ -176,6 +231,56 @@ def test_key_switch_forms_on_other_prime_shapes(name, N, primes, key_kind):
     for knobs in ({}, {"EVAH_MAC3": 0}):
         g = _ctx(N, primes, knobs)
         _check_key_switches(g, o, primes, np.random.default_rng(5), key_kind)
+        g.close()
+
+
+@pytest.mark.parametrize("name,N,primes", SPECIAL, ids=[s[0] for s in SPECIAL])
+@pytest.mark.parametrize("key_kind", ["qm1", "mixed"])
+def test_other_prime_shapes_on_the_mod_up_kernel(name, N, primes, key_kind):
+    """compare-and-subtract butterflies and MAC3's unreduced rows behind the mod-up kernel's conversion"""
+    o = po.Oracle(N, primes)
+    for knobs in ({}, {"EVAH_MAC3": 0}):
+        g = _ctx(N, primes, dict(knobs, EVAH_FUSE_SMALL=0))
+        _check_key_switches(g, o, primes, np.random.default_rng(5), key_kind, launches=MODUP_LAUNCHES)
+        g.close()
+
+
+def boundary_chains(N=4096):
+    """Chains around the digit conversion's rule (OpKsDigit::setup): digit t_J < q_J enters the forward rounds under q_kappa
+    unreduced when q_J <= 8 q_kappa, through a Barrett reduction otherwise.  p is a 57-bit prime, qA the largest NTT prime
+    <= 8 p (lazy under p, by the narrowest margin: with the dense_max and qm1 words its digits are qA - 1, about 8 p, the
+    largest value the rule ever lets into the rounds), qB the smallest one > 8 p (reduced under p, by the narrowest
+    margin).  None of p, qA, qB has the top-bit shape and all are above 2^54, so these chains take the compare-and-subtract
+    butterflies and the 128-bit inner products whatever EVAH_MAC3 says.  Rows (output prime: lazy digits | reduced digits):
+      [qA, p, qB, special]       qA: p qB |  -      p: qA | qB      qB: qA p | -      special: qA p qB | -
+      [p, qA, p2, qB, special]   p: qA p2 | qB      qA: p p2 qB | -      p2: p | qA qB      qB: p qA p2 | -
+                                 special: all | -
+    so the workgroup of digit qA (and of digit qB) switches between the two conversions from row to row.
+    -> {name: primes}, and (p, p2, qA, qB, special)"""
+    p = _ntt_prime_below(3 << 55, N)
+    qA = _ntt_prime_below(8 * p + 1, N)
+    qB = _ntt_prime_above(8 * p, N)
+    p2 = _ntt_prime_below(p, N)
+    special = next(q for q in po.coeff_modulus_create(N, [60] * 3) if q not in (p, p2, qA, qB))
+    return {"qA_p_qB": [qA, p, qB, special], "p_qA_p2_qB": [p, qA, p2, qB, special]}, (p, p2, qA, qB, special)
+
+
+BOUNDARY = boundary_chains()[0]
+
+
+@pytest.mark.parametrize("chain", sorted(BOUNDARY))
+@pytest.mark.parametrize("form", ["small", "modup"])
+def test_digit_conversion_at_the_lazy_flag_boundary(chain, form):
+    """every key-switch form on the BOUNDARY chains, keys at q - 1, in the small-launch form (ntt_inv_fwd_kernel) and on the
+    mod-up kernel, EVAH_MAC3 at its default and 0 (the same kernels here, see boundary_chains: kept because the issue of
+    this test asks for both)"""
+    N, primes = 4096, BOUNDARY[chain]
+    o = po.Oracle(N, primes)
+    for knobs in ({}, {"EVAH_MAC3": 0}):
+        if form == "modup":
+            knobs = dict(knobs, EVAH_FUSE_SMALL=0)
+        g = _ctx(N, primes, knobs)
+        _check_key_switches(g, o, primes, np.random.default_rng(7), "qm1", launches=MODUP_LAUNCHES if form == "modup" else None)
         g.close()
 
 

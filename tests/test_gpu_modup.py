@@ -4,7 +4,12 @@ the same lazy intermediates as the two-launch form, so every result is the oracl
 context with EVAH_MODUP=0 returns.  Shapes: the headline's (N = 2^16, l = 10, 1 / 32 / 64 fused op-triples), stored
 products through relinearize / relinearize + rescale, chains with primes not of the top-bit shape (compare-and-subtract
 butterflies; with and without the radix-2^30 inner product), more than 16 digits, N = 2^12 and 2^15, a batched handle.  Small shapes are
-pushed past the fused small-launch form with EVAH_FUSE_SMALL=0 so that they take the mod-up kernel too."""
+pushed past the fused small-launch form with EVAH_FUSE_SMALL=0 so that they take the mod-up kernel too; among them the
+two ends of the kernel's P dispatch: N = 2^11 (P = 6 with ONE column tile per digit, so the digit index is the whole of
+blockIdx.x) and N = 2^17 (P = 9, at l = 2 to keep the oracle quick).  Every shape of test_other_shapes also counts
+launches (_Pair.ran_on_modup): the EVAH_MODUP=1 context must have run the digits' strided inverse pass inside the
+ksdigit_pass1 launch, or the comparison covers nothing.  The other callers of the key switch, the launch counts
+themselves and the gate are in test_gpu_modup_forms.py; worst-case words on this kernel in test_gpu_extremes.py."""
 import os
 
 import numpy as np
@@ -55,6 +60,26 @@ class _Pair:
         for x, y in zip(got[1], got[0]):
             assert np.array_equal(x, y), "EVAH_MODUP=1 and EVAH_MODUP=0 differ"
         return got[1]
+
+    def launches(self, fn):
+        """{EVAH_MODUP setting: {kernel class: launches}} of fn(context)"""
+        out = {}
+        for m, g in self.ctx.items():
+            g.profile(True)
+            g.profile_reset()
+            keep = fn(g)  # results stay alive until the launches have run
+            g.sync()
+            del keep
+            out[m] = {name: n for name, (n, _) in g.profile_get().items()}
+            g.profile(False)
+        return out
+
+    def ran_on_modup(self, fn, calls=1):
+        """fn(context) holds `calls` key switches: under EVAH_MODUP=1 each one's stand-alone strided inverse pass of the
+        digits (an intt_pass2 launch) is gone, into the ksdigit_pass1 launch it had anyway; no other count moves"""
+        n = self.launches(fn)
+        assert n[0]["intt_pass2"] >= calls and n[0]["ksdigit_pass1"] >= calls, n
+        assert n[1] == dict(n[0], intt_pass2=n[0]["intt_pass2"] - calls), n
 
     def close(self):
         for g in self.ctx.values():
@@ -125,25 +150,30 @@ def _shapes():
     c60 = po.coeff_modulus_create(1 << 13, [60] * 5)
     nontb = _ntt_prime_below((1 << 55) - (1 << 40), 1 << 13)  # 2^55 - c with c >= 2^32, above 2^54: no top-bit shape
     return [
-        ("N4096", 1 << 12, po.coeff_modulus_create(1 << 12, [60] * 11), {}),       # P = 6
-        ("N32768", 1 << 15, po.coeff_modulus_create(1 << 15, [60] * 11), {}),      # P = 8 over 7-bit contiguous sub-transforms
-        ("l17", 1 << 14, po.coeff_modulus_create(1 << 14, [60] * 18), {}),         # more than 16 digits (128-bit inner products)
+        ("N4096", 1 << 12, po.coeff_modulus_create(1 << 12, [60] * 11), {}, 4),       # P = 6
+        ("N32768", 1 << 15, po.coeff_modulus_create(1 << 15, [60] * 11), {}, 4),      # P = 8 over 7-bit contiguous sub-transforms
+        ("l17", 1 << 14, po.coeff_modulus_create(1 << 14, [60] * 18), {}, 4),         # more than 16 digits (128-bit inner products)
         # compare-and-subtract butterflies under a 30-bit prime (the radix-2^30 inner products still apply) / under a
         # 55-bit prime of no top-bit shape (128-bit inner products)
-        ("bits30", 1 << 13, po.coeff_modulus_create(1 << 13, [60, 30, 60, 60, 60]), {}),
-        ("nontb55", 1 << 13, [c60[0], nontb, c60[1], c60[2], c60[4]], {}),
+        ("bits30", 1 << 13, po.coeff_modulus_create(1 << 13, [60, 30, 60, 60, 60]), {}, 4),
+        ("nontb55", 1 << 13, [c60[0], nontb, c60[1], c60[2], c60[4]], {}, 4),
+        # the ends of the P dispatch: P = 6 with one column tile per digit (log_tiles = 0) / P = 9
+        ("N2048", 1 << 11, po.coeff_modulus_create(1 << 11, [50, 50, 50, 51]), {}, 2),
+        ("N131072", 1 << 17, po.coeff_modulus_create(1 << 17, [60] * 3), {}, 2),
     ]
 
 
 SHAPES = _shapes()
 
 
-@pytest.mark.parametrize("name,N,primes,knobs", SHAPES, ids=[s[0] for s in SHAPES])
-def test_other_shapes(name, N, primes, knobs):
+@pytest.mark.parametrize("name,N,primes,knobs,triples", SHAPES, ids=[s[0] for s in SHAPES])
+def test_other_shapes(name, N, primes, knobs, triples):
     """small shapes pushed past the fused small-launch form (EVAH_FUSE_SMALL=0) so that they take the mod-up kernel"""
     p = _Pair(N, primes, extra=dict(knobs, EVAH_FUSE_SMALL=0), seed=N + len(primes))
     try:
-        _triples(p, 4, distinct=2)
+        _triples(p, triples, distinct=2)
         _stored(p)
+        m = p.rand((3,), p.l)
+        p.ran_on_modup(lambda g: g.relinearize(g.upload_ct(m, 2.0 ** 60)))
     finally:
         p.close()
