@@ -112,6 +112,9 @@ _SIGS = {
                                         C.c_int, _vpp],
     "evah_ct_write_seeded": [_vp, _vp, _u64p, C.POINTER(C.c_uint8)],
     "evah_ct_download_poly": [_vp, _vp, C.c_uint32, _u64p],
+    # seed-compressed evaluation keys
+    "evah_key_upload_seeded": [_vp, C.c_int, C.c_uint32, C.c_uint32, _u64p, C.POINTER(C.c_uint8)],
+    "evah_test_key_words": [_vp, C.c_int, C.c_uint32, C.c_int, _u64p],
     # limb-sharded execution
     "evah_ctx_set_shard": [_vp, C.c_uint32, C.c_uint32],
     "evah_ctx_shard_info": [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
@@ -572,6 +575,31 @@ class Context:
         key = np.ascontiguousarray(key, dtype=np.uint64)
         assert key.shape[1:] == (2, self.k, self.N)
         _chk(_lib.evah_key_upload(self.h, KEY_GALOIS, int(elt), key.shape[0], _p(key)))
+
+    def _upload_key_seeded(self, kind, elt, c0, seeds):
+        c0 = np.ascontiguousarray(c0, dtype=np.uint64)
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint8)
+        assert c0.shape[1:] == (self.k, self.N) and seeds.shape == (c0.shape[0], 32)
+        _chk(_lib.evah_key_upload_seeded(self.h, kind, int(elt), c0.shape[0], _p(c0), seeds.ctypes.data_as(C.POINTER(C.c_uint8))))
+
+    def upload_relin_key_seeded(self, c0, seeds):
+        """c0: [digits][k][N], seeds: [digits][32] uint8 — c1 of every digit is expanded on the device"""
+        self._upload_key_seeded(KEY_RELIN, 0, c0, seeds)
+
+    def upload_galois_key_seeded(self, elt, c0, seeds):
+        self._upload_key_seeded(KEY_GALOIS, elt, c0, seeds)
+
+    def key_words(self, kind, elt=0, which=0, digits=None):
+        """test hook (evah_test_key_words): the device words of an installed key as [digits][2][rows][N] — rows = k, or
+        the rows a limb shard keeps; which=1: its split copy.  digits: the digit count the key was uploaded with (k - 1
+        unless given)"""
+        s, G = C.c_uint32(), C.c_uint32()
+        _chk(_lib.evah_ctx_shard_info(self.h, C.byref(s), C.byref(G)))
+        s, G = s.value, G.value
+        rows = self.k if G <= 1 else (max(0, self.k - 1 - s + G - 1) // G if self.k - 1 > s else 0) + 1
+        out = np.empty((self.k - 1 if digits is None else int(digits), 2, rows, self.N), dtype=np.uint64)
+        _chk(_lib.evah_test_key_words(self.h, int(kind), int(elt), int(which), _p(out)))
+        return out
 
     def galois_elt_from_step(self, steps):
         e = C.c_uint32()

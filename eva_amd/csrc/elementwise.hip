@@ -239,8 +239,7 @@ namespace evah {
 __global__ void __launch_bounds__(256) k_key_split(const u64 *__restrict__ src, u64 *__restrict__ dst, size_t words) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < words) {
-    const u64 k = src[i];
-    dst[i] = (k & 0x3fffffffull) | ((k >> 30) << 32);
+    dst[i] = split30(src[i]);
   }
 }
 // evah_ct_stack: n single ciphertexts (separate allocations, possibly views with their own polynomial stride) -> the

@@ -595,6 +595,12 @@ inline evah_pt *pt_new(evah_ctx *c, uint32_t limbs, double scale) {
 // (the scheduler groups sibling rotations for it only when it does)
 bool hoist_wanted(const evah_ctx *c, uint32_t l, uint32_t n, uint32_t B);
 
+// runtime.hip: what evah_key_upload and evah_key_upload_seeded (seeded.hip) share — the argument checks and the shape
+// of the rows this context keeps, the row copies of a limb shard, and the hand-over of the uploaded key to the device state
+KeyDev key_shape(evah_ctx *c, uint32_t n_digits);
+hipError_t key_rows_h2d(evah_ctx *c, const KeyDev &kd, const u64 *src, uint32_t blocks, uint32_t first, uint32_t step);
+void key_install(evah_ctx *c, int kind, uint32_t galois_elt, const KeyDev &kd);
+
 struct Scratch { // pool-backed temporary, returned on scope exit (stream-ordered reuse)
   evah_ctx *c;
   u64 *d;

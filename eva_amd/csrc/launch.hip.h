@@ -18,6 +18,8 @@ namespace evah {
 
 __device__ __forceinline__ ulonglong2 ld2(const u64 *p) { return *reinterpret_cast<const ulonglong2 *>(p); }
 __device__ __forceinline__ void st2(u64 *p, ulonglong2 v) { *reinterpret_cast<ulonglong2 *>(p) = v; }
+// a key word cut at bit 30 (KeyDev::d_split): the operand form of the radix-2^30 inner product
+__device__ __forceinline__ u64 split30(u64 k) { return (k & 0x3fffffffull) | ((k >> 30) << 32); }
 
 // ---- NTT launch plumbing
 template <class Op> struct OpClass;

@@ -273,9 +273,13 @@ int evah_galois_elt_from_step(evah_ctx *c, int32_t steps, uint32_t *elt) {
   API_END
 }
 
-int evah_key_upload(evah_ctx *c, int kind, uint32_t galois_elt, uint32_t n_digits, const uint64_t *data) {
-  API_BEGIN
-  use(c);
+} // extern "C"
+
+namespace evah {
+
+// The argument checks and the shape every key upload shares: the digit count, the shard map the device state's keys
+// were uploaded under, and the prime rows this context keeps of a key.
+KeyDev key_shape(evah_ctx *c, uint32_t n_digits) {
   if (c->capturing) throw std::logic_error("this call synchronises with the host and cannot be captured into a graph");
   if (n_digits == 0 || n_digits > c->k - 1) throw std::invalid_argument("invalid key digit count");
   KeyDev kd;
@@ -289,37 +293,30 @@ int evah_key_upload(evah_ctx *c, int kind, uint32_t galois_elt, uint32_t n_digit
     throw std::logic_error("the keys of this device state were uploaded under a different shard map");
   kd.rows = local_rows ? (c->k - 1 > s ? (c->k - 1 - s + G - 1) / G : 0) + 1 : c->k;
   kd.bytes = sizeof(u64) * (size_t)n_digits * 2 * kd.rows * c->N;
-  HIPCHK(hipMalloc(&kd.d, kd.bytes));
-  if (!local_rows) {
-    h2d_now(c, kd.d, data, kd.bytes);
-  } else {
-    const size_t row = sizeof(u64) * c->N;
-    hipError_t e = hipSuccess;
-    for (uint32_t dk = 0; dk < 2 * n_digits && e == hipSuccess; dk++) {
-      // rows s, s + G, ... of this (digit, polynomial): one strided copy; then the special prime's row
-      const u64 *src = (const u64 *)data + (size_t)dk * c->k * c->N;
-      u64 *dst = kd.d + (size_t)dk * kd.rows * c->N;
-      for (uint32_t r = 0; r + 1 < kd.rows && e == hipSuccess; r++) // (linear copies: see evah_ct_download on 2-D copies and pageable memory)
-        e = hipMemcpyAsync(dst + (size_t)r * c->N, src + (size_t)(s + r * G) * c->N, row, hipMemcpyHostToDevice, c->stream);
-      if (e == hipSuccess) e = hipMemcpyAsync(dst + (size_t)(kd.rows - 1) * c->N, src + (size_t)(c->k - 1) * c->N, row, hipMemcpyHostToDevice, c->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream); // complete before any queue reads the rows (h2d_now)
-    if (e != hipSuccess) {
-      (void)hipFree(kd.d);
-      HIPCHK(e);
-    }
+  return kd;
+}
+
+// the [digit][poly] blocks `first`, `first + step`, ... of a key, host -> device on the calling queue: the rows s, s + G, ...
+// of each block and then the special prime's.  src: block b at src + b * k * N; dst block b at kd.d + (first + b * step) * rows * N
+hipError_t key_rows_h2d(evah_ctx *c, const KeyDev &kd, const u64 *src, uint32_t blocks, uint32_t first, uint32_t step) {
+  const uint32_t s = c->dev.p0, G = c->dev.pstep;
+  const size_t row = sizeof(u64) * c->N;
+  hipError_t e = hipSuccess;
+  for (uint32_t b = 0; b < blocks && e == hipSuccess; b++) {
+    const u64 *from = src + (size_t)b * c->k * c->N;
+    u64 *dst = kd.d + (size_t)(first + b * step) * kd.rows * c->N;
+    for (uint32_t r = 0; r + 1 < kd.rows && e == hipSuccess; r++) // (linear copies: see evah_ct_download on 2-D copies and pageable memory)
+      e = hipMemcpyAsync(dst + (size_t)r * c->N, from + (size_t)(s + r * G) * c->N, row, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dst + (size_t)(kd.rows - 1) * c->N, from + (size_t)(c->k - 1) * c->N, row, hipMemcpyHostToDevice, c->stream);
   }
-  if (!local_rows && c->all_tb && c->tun.mac3) { // the split copy ks_inner_kernel<MAC3> multiplies with
-    if (hipMalloc(&kd.d_split, kd.bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      kd.d_split = nullptr; // no memory for the second copy: the 128-bit accumulation is used
-    } else {
-      key_split_launch(c, kd.d, kd.d_split, kd.bytes / sizeof(u64));
-      HIPCHK(hipStreamSynchronize(c->stream));
-    }
-  }
-  c->sh->key_rows = local_rows ? 2 : 1;
-  c->sh->key_shard = s;
+  return e;
+}
+
+// An uploaded key becomes the device state's: the key it replaces is freed with the tables derived from it.  Owns kd's
+// allocations from here on (they are freed when the kind or the element is refused).
+void key_install(evah_ctx *c, int kind, uint32_t galois_elt, const KeyDev &kd) {
+  c->sh->key_rows = c->dev.pstep > 1 ? 2 : 1;
+  c->sh->key_shard = c->dev.p0;
   if (kind == EVAH_KEY_RELIN) {
     if (c->sh->relin.d) (void)hipFree(c->sh->relin.d);
     if (c->sh->relin.d_split) (void)hipFree(c->sh->relin.d_split);
@@ -351,6 +348,62 @@ int evah_key_upload(evah_ctx *c, int kind, uint32_t galois_elt, uint32_t n_digit
     if (kd.d_split) (void)hipFree(kd.d_split);
     throw std::invalid_argument("unknown key kind");
   }
+}
+
+} // namespace evah
+
+extern "C" {
+
+int evah_key_upload(evah_ctx *c, int kind, uint32_t galois_elt, uint32_t n_digits, const uint64_t *data) {
+  API_BEGIN
+  use(c);
+  KeyDev kd = key_shape(c, n_digits);
+  const bool local_rows = c->dev.pstep > 1;
+  HIPCHK(hipMalloc(&kd.d, kd.bytes));
+  if (!local_rows) {
+    h2d_now(c, kd.d, data, kd.bytes);
+  } else {
+    hipError_t e = key_rows_h2d(c, kd, (const u64 *)data, 2 * n_digits, 0, 1);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream); // complete before any queue reads the rows (h2d_now)
+    if (e != hipSuccess) {
+      (void)hipFree(kd.d);
+      HIPCHK(e);
+    }
+  }
+  if (!local_rows && c->all_tb && c->tun.mac3) { // the split copy ks_inner_kernel<MAC3> multiplies with
+    if (hipMalloc(&kd.d_split, kd.bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      kd.d_split = nullptr; // no memory for the second copy: the 128-bit accumulation is used
+    } else {
+      key_split_launch(c, kd.d, kd.d_split, kd.bytes / sizeof(u64));
+      HIPCHK(hipStreamSynchronize(c->stream));
+    }
+  }
+  key_install(c, kind, galois_elt, kd);
+  API_END
+}
+
+// test hook: the device words of an installed key, as the kernels read them
+int evah_test_key_words(evah_ctx *c, int kind, uint32_t galois_elt, int which, uint64_t *out) {
+  API_BEGIN
+  use(c);
+  if (c->capturing) throw std::logic_error("this call synchronises with the host and cannot be captured into a graph");
+  if (!out) throw std::invalid_argument("output pointer is null");
+  const KeyDev *kd = nullptr;
+  if (kind == EVAH_KEY_RELIN) {
+    kd = &c->sh->relin;
+  } else if (kind == EVAH_KEY_GALOIS) {
+    auto it = c->sh->galois.find(galois_elt);
+    if (it != c->sh->galois.end()) kd = &it->second;
+  } else {
+    throw std::invalid_argument("unknown key kind");
+  }
+  if (!kd || !kd->d) throw std::invalid_argument("no such key has been uploaded");
+  if (which != 0 && which != 1) throw std::invalid_argument("which must be 0 (key words) or 1 (split copy)");
+  const u64 *src = which ? kd->d_split : kd->d;
+  if (!src) throw std::invalid_argument("this key has no split copy");
+  HIPCHK(hipMemcpyAsync(out, src, kd->bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
   API_END
 }
 

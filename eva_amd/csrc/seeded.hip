@@ -1,7 +1,8 @@
 // seeded.hip — ciphertexts whose second polynomial travels as a 32-byte seed (SEAL's Encryptor::encrypt_symmetric
 // followed by a seeded save): uploads of c0 + seed with c1 expanded on the queue (the expansion rule:
 // seeded.hip.h), slot refills of captured graphs, and the download of c0 alone.  The fused symmetric encryption
-// (evah_encrypt_symmetric) lives in client.hip beside evah_encrypt.
+// (evah_encrypt_symmetric) lives in client.hip beside evah_encrypt.  Evaluation keys travel the same way:
+// evah_key_upload_seeded takes c0 and one seed per digit and expands every c1 row — and the split copy — in one launch.
 
 #include "launch.hip.h"
 #include "seeded.hip.h"
@@ -34,9 +35,92 @@ static void expand_c1(evah_ctx *c, evah_ct *ct, const uint8_t *const *seeds) {
   HIPCHK(hipGetLastError());
 }
 
+// The c1 half of a seed-compressed evaluation key in the device layout d = [digit][2][rows][N]: row r of
+// digit J is seeded_block(seed_J, prime of r, .) — every chain prime of a whole key; the data limbs s, s + G, ... and then
+// the special prime on a limb shard.  When the key has a split copy (KeyDev::d_split) the same launch writes both of its
+// halves: split(c1) from the registers and split(c0) from the words the upload's copies left in d[J][0][r], so no pass
+// reads the whole key again.  One thread per ChaCha block (4 coefficients); grid = (ceil(N / 4 / 256), rows, digits).
+// Seeds: launch arguments for up to 8 digits, else seed_buf ([digits][8] words, uploaded on the same queue).
+__global__ void __launch_bounds__(256)
+k_key_expand(DevCtx cx, Seeds8 seeds, const uint32_t *__restrict__ seed_buf, uint32_t rows, u64 *__restrict__ d, u64 *__restrict__ d_split) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y, J = blockIdx.z;
+  if (t >= cx.N / 4 || r >= rows) return;
+  const uint32_t prime = cx.pstep > 1 && r + 1 == rows ? cx.k - 1 : cx.prime_of(r);
+  const DevPrime pm = cx.primes[prime];
+  uint32_t key[8];
+  if (seed_buf) {
+#pragma unroll
+    for (int i = 0; i < 8; i++) key[i] = seed_buf[8 * J + i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 8; i++) key[i] = seeds.w[J][i];
+  }
+  u64 a[4];
+  seeded_block(key, prime, t, pm, a);
+  const size_t at0 = ((size_t)2 * J * rows + r) * cx.N + 4 * (size_t)t, at1 = at0 + (size_t)rows * cx.N;
+  st2(d + at1, make_ulonglong2(a[0], a[1]));
+  st2(d + at1 + 2, make_ulonglong2(a[2], a[3]));
+  if (d_split) {
+    st2(d_split + at1, make_ulonglong2(split30(a[0]), split30(a[1])));
+    st2(d_split + at1 + 2, make_ulonglong2(split30(a[2]), split30(a[3])));
+    const ulonglong2 b0 = ld2(d + at0), b1 = ld2(d + at0 + 2);
+    st2(d_split + at0, make_ulonglong2(split30(b0.x), split30(b0.y)));
+    st2(d_split + at0 + 2, make_ulonglong2(split30(b1.x), split30(b1.y)));
+  }
+}
+
 } // namespace evah
 
 extern "C" {
+
+// A relinearization or Galois key from c0 [n_digits][k][N] and one 32-byte seed per digit: what
+// evah_key_upload installs for the materialised key, with half the words crossing PCIe
+int evah_key_upload_seeded(evah_ctx *c, int kind, uint32_t galois_elt, uint32_t n_digits, const uint64_t *c0, const uint8_t *seeds) {
+  API_BEGIN
+  use(c);
+  KeyDev kd = key_shape(c, n_digits);
+  if (kind != EVAH_KEY_RELIN && kind != EVAH_KEY_GALOIS) throw std::invalid_argument("unknown key kind");
+  if (kind == EVAH_KEY_GALOIS && (!(galois_elt & 1) || galois_elt >= 2 * c->N)) throw std::invalid_argument("Galois element is not valid");
+  if (!c0) throw std::invalid_argument("key pointer is null");
+  if (!seeds) throw std::invalid_argument("seed pointer is null");
+  const bool local_rows = c->dev.pstep > 1;
+  Seeds8 s8;
+  std::memset(&s8, 0, sizeof s8);
+  std::unique_ptr<Scratch> seed_dev; // more than 8 digits: the seeds as a device buffer, returned to the pool after the drain
+  HIPCHK(hipMalloc(&kd.d, kd.bytes));
+  if (!local_rows && c->all_tb && c->tun.mac3 && hipMalloc(&kd.d_split, kd.bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    kd.d_split = nullptr; // no memory for the second copy: the 128-bit accumulation is used
+  }
+  try {
+    const size_t poly = (size_t)c->k * c->N;
+    hipError_t e = hipSuccess;
+    if (!local_rows) // c0 of digit J into d[J][0]: one copy per digit
+      for (uint32_t J = 0; J < n_digits && e == hipSuccess; J++)
+        e = hipMemcpyAsync(kd.d + (size_t)J * 2 * poly, (const u64 *)c0 + (size_t)J * poly, sizeof(u64) * poly, hipMemcpyHostToDevice, c->stream);
+    else
+      e = key_rows_h2d(c, kd, (const u64 *)c0, n_digits, 0, 2);
+    HIPCHK(e);
+    const uint32_t *seed_buf = nullptr;
+    if (n_digits <= SEEDS_PER_LAUNCH) {
+      std::memcpy(s8.w, seeds, (size_t)32 * n_digits); // little-endian key words, as the host generator reads its key
+    } else {
+      seed_dev = std::make_unique<Scratch>(c, (size_t)4 * n_digits);
+      HIPCHK(hipMemcpyAsync(seed_dev->d, seeds, (size_t)32 * n_digits, hipMemcpyHostToDevice, c->stream));
+      seed_buf = reinterpret_cast<const uint32_t *>(seed_dev->d);
+    }
+    EW_LAUNCH(k_key_expand, seeded_grid(c, kd.rows, n_digits), dim3(256), 0, c->stream, c->dev, s8, seed_buf, kd.rows, kd.d, kd.d_split);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream)); // complete before any queue reads the rows (h2d_now)
+  } catch (...) {
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(kd.d);
+    if (kd.d_split) (void)hipFree(kd.d_split);
+    throw;
+  }
+  key_install(c, kind, galois_elt, kd);
+  API_END
+}
 
 // `batch` symmetric ciphertexts from c0[b] ([limbs][N] each) and seeds[b] (32 bytes each) as one handle [batch][2][limbs][N]
 int evah_ct_upload_seeded_instances(evah_ctx *c, uint32_t batch, uint32_t limbs, double scale, const uint64_t *const *c0,

@@ -393,7 +393,25 @@ private:
 // Key material in the layout libeva_hip.so expects.
 struct SwitchKey {
   uint32_t n_digits = 0;
-  std::vector<u64> data; // [digit][2][k][N], NTT form
+  std::vector<u64> data; // [digit][2][k][N], NTT form; empty while the key is kept in its compressed form
+  // the compressed form: c1 of digit J is public and uniform, so it is kept as the 32-byte seed it is
+  // expanded from — row i = seeded_limb(seed_J, i, q_i, N) — beside c0.  Half the words in memory, in files and over PCIe.
+  std::vector<u64> c0;        // [digit][k][N]
+  std::vector<uint8_t> seeds; // [digit][32]
+  bool compressed() const { return !seeds.empty(); }
+  // the full words [digit][2][k][N]: `data`, or materialised into `tmp` (never stored back: a compressed key stays compressed)
+  const std::vector<u64> &words(const HostContext &cx, std::vector<u64> &tmp) const {
+    if (!compressed()) return data;
+    const size_t poly = (size_t)cx.k * cx.N;
+    if (c0.size() != n_digits * poly || seeds.size() != (size_t)32 * n_digits) throw std::runtime_error("compressed key: c0 or its seeds do not match the shape");
+    tmp.resize((size_t)n_digits * 2 * poly);
+    for (uint32_t J = 0; J < n_digits; J++) {
+      u64 *d = tmp.data() + (size_t)J * 2 * poly;
+      std::copy(c0.begin() + (size_t)J * poly, c0.begin() + (size_t)(J + 1) * poly, d);
+      for (uint32_t i = 0; i < cx.k; i++) seeded_limb(seeds.data() + (size_t)32 * J, i, cx.primes[i], cx.N, (uint64_t *)(d + poly + (size_t)i * cx.N));
+    }
+    return tmp;
+  }
 };
 
 struct SecretKey {
@@ -431,16 +449,39 @@ public:
     encrypt_zero_symmetric(pk.data.data(), pk.data.data() + (size_t)cx.k * cx.N);
     return pk;
   }
-  // key-switch key from s' (NTT form over all k primes) to s: digit J carries P * s' in limb J
-  SwitchKey switch_key(const std::vector<u64> &sprime_ntt) {
+  // key-switch key from s' (NTT form over all k primes) to s: digit J carries P * s' in limb J.
+  // seeded: c1 of every digit is the expansion of a 32-byte seed — 4 words of the public stream in place
+  // of its k N rejection-sampled draws — and the key is returned as c0 + seeds
+  SwitchKey switch_key(const std::vector<u64> &sprime_ntt, bool seeded = false) {
     const uint32_t N = cx.N, k = cx.k, D = k - 1;
     SwitchKey key;
     key.n_digits = D;
-    key.data.resize((size_t)D * 2 * k * N);
+    if (seeded) {
+      key.c0.resize((size_t)D * k * N);
+      key.seeds.resize((size_t)32 * D);
+    } else {
+      key.data.resize((size_t)D * 2 * k * N);
+    }
     const u64 P = cx.primes[k - 1];
+    std::vector<u64> a;
     for (uint32_t J = 0; J < D; J++) {
-      u64 *c0 = key.data.data() + (size_t)J * 2 * k * N, *c1 = c0 + (size_t)k * N;
-      encrypt_zero_symmetric(c0, c1);
+      u64 *c0, *c1;
+      if (seeded) {
+        uint8_t *seed = key.seeds.data() + (size_t)32 * J;
+        for (int w = 0; w < 4; w++) {
+          const u64 r = (*pub)();
+          std::memcpy(seed + 8 * w, &r, 8);
+        }
+        a.resize((size_t)k * N);
+        for (uint32_t i = 0; i < k; i++) seeded_limb(seed, i, cx.primes[i], N, (uint64_t *)(a.data() + (size_t)i * N));
+        c0 = key.c0.data() + (size_t)J * k * N;
+        c1 = a.data();
+        encrypt_zero_symmetric(c0, c1, false);
+      } else {
+        c0 = key.data.data() + (size_t)J * 2 * k * N;
+        c1 = c0 + (size_t)k * N;
+        encrypt_zero_symmetric(c0, c1);
+      }
       const u64 q = cx.primes[J], f = P % q;
       u64 *dst = c0 + (size_t)J * N;
       const u64 *sp = sprime_ntt.data() + (size_t)J * N;
@@ -448,16 +489,16 @@ public:
     }
     return key;
   }
-  SwitchKey relin_key() {
+  SwitchKey relin_key(bool seeded = false) {
     std::vector<u64> s2((size_t)cx.k * cx.N);
     for (uint32_t i = 0; i < cx.k; i++)
       for (uint32_t j = 0; j < cx.N; j++) {
         u64 v = sk.s_ntt[(size_t)i * cx.N + j];
         s2[(size_t)i * cx.N + j] = cx.mulm(v, v, i);
       }
-    return switch_key(s2);
+    return switch_key(s2, seeded);
   }
-  SwitchKey galois_key(uint32_t elt) {
+  SwitchKey galois_key(uint32_t elt, bool seeded = false) {
     // s(X^elt) in NTT form = permutation of s_ntt (same table as the device uses)
     std::vector<u64> sp((size_t)cx.k * cx.N);
     for (uint32_t j = 0; j < cx.N; j++) {
@@ -466,12 +507,12 @@ public:
       uint32_t src = evah::bitrev((uint32_t)raw, cx.logN);
       for (uint32_t i = 0; i < cx.k; i++) sp[(size_t)i * cx.N + j] = sk.s_ntt[(size_t)i * cx.N + src];
     }
-    return switch_key(sp);
+    return switch_key(sp, seeded);
   }
 
 private:
-  // (c0, c1) = (-(a s + e), a) over all k primes, NTT form
-  void encrypt_zero_symmetric(u64 *c0, u64 *c1) {
+  // (c0, c1) = (-(a s + e), a) over all k primes, NTT form; draw_a = false: a is given in c1 (expanded from a seed)
+  void encrypt_zero_symmetric(u64 *c0, u64 *c1, bool draw_a = true) {
     const uint32_t N = cx.N;
     std::vector<int8_t> e;
     cx.sample_error(*secret, e);
@@ -479,7 +520,7 @@ private:
     for (uint32_t i = 0; i < cx.k; i++) {
       const u64 q = cx.primes[i];
       u64 *a = c1 + (size_t)i * N, *b = c0 + (size_t)i * N;
-      cx.sample_uniform(*pub, i, a);
+      if (draw_a) cx.sample_uniform(*pub, i, a);
       cx.small_to_ntt(e, i, en.data());
       const u64 *s = sk.s_ntt.data() + (size_t)i * N;
       for (uint32_t j = 0; j < N; j++) b[j] = evah::negmod(evah::addmod(cx.mulm(a[j], s[j], i), en[j], q), q);

@@ -288,9 +288,11 @@ public:
 };
 
 // generateKeys (seal.cpp:174-203): prime chain from bit sizes, secret/public key, one Galois key
-// per exact rotation step, relinearization key.
+// per exact rotation step, relinearization key.  compress_keys: the relinearization and Galois keys are
+// generated, kept, saved and uploaded as c0 plus a 32-byte seed per digit; the secret and the public key are drawn
+// before any of them, so they are the same with and without the option for one test seed.
 inline std::pair<std::shared_ptr<HipPublic>, std::shared_ptr<HipSecret>>
-generate_keys(const CKKSParameters &params, uint64_t seed = 0) {
+generate_keys(const CKKSParameters &params, uint64_t seed = 0, bool compress_keys = false) {
   std::vector<int> bits(params.prime_bits.begin(), params.prime_bits.end());
   if (bits.size() < 2) throw std::invalid_argument("need at least two primes (data + special)");
   auto primes = evah::coeff_modulus_create(params.poly_modulus_degree, bits);
@@ -301,7 +303,7 @@ generate_keys(const CKKSParameters &params, uint64_t seed = 0) {
   sec->holder = pub->holder; // one device state for the pair: results stay resident from encrypt to decrypt
   pub->host = host;
   pub->pk = kg.public_key();
-  pub->relin = kg.relin_key();
+  pub->relin = kg.relin_key(compress_keys);
   const uint32_t N = host->N, m = 2 * N;
   for (int step : params.rotations) {
     uint32_t elt;
@@ -313,7 +315,7 @@ generate_keys(const CKKSParameters &params, uint64_t seed = 0) {
       elt = 1;
       for (uint32_t i = 0; i < s; i++) elt = (elt * 3u) & (m - 1);
     }
-    if (!pub->galois.count(elt)) pub->galois.emplace(elt, kg.galois_key(elt));
+    if (!pub->galois.count(elt)) pub->galois.emplace(elt, kg.galois_key(elt, compress_keys));
   }
   sec->host = host;
   sec->sk = kg.sk;

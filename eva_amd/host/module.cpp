@@ -250,8 +250,9 @@ PYBIND11_MODULE(_eva, m) {
   // devices / shard: several GPUs behind one execute() (eva_amd/host/multi_device.h); the defaults come from
   // EVA_NUM_GPUS / EVA_DEVICES / EVA_SHARD.  set_num_threads(n) — the reference's size of the parallel
   // traversal (wrapper.cpp:128-137) — is the number of issue queues independent DAG nodes are spread over.
-  mseal.def("generate_keys", [](const CKKSParameters &p, uint64_t seed, py::object devices, py::object shard) {
-    auto kp = generate_keys(p, seed);
+  // compress_keys: the evaluation keys as c0 + a 32-byte seed per digit, expanded on the GPU at upload
+  mseal.def("generate_keys", [](const CKKSParameters &p, uint64_t seed, py::object devices, py::object shard, bool compress_keys) {
+    auto kp = generate_keys(p, seed, compress_keys);
     if (!devices.is_none()) {
       kp.first->devices = devices.cast<std::vector<int>>();
       // the key pair's own device state (inputs, constants, outputs; the secret half decrypts there) is member 0
@@ -260,7 +261,8 @@ PYBIND11_MODULE(_eva, m) {
     if (!shard.is_none()) kp.first->shard_mode = shard.cast<std::string>();
     if (g_num_threads > 1) kp.first->num_queues = std::min(g_num_threads, 8);
     return kp;
-  }, py::arg("abstract_params"), py::arg("seed") = 0, py::arg("devices") = py::none(), py::arg("shard") = py::none());
+  }, py::arg("abstract_params"), py::arg("seed") = 0, py::arg("devices") = py::none(), py::arg("shard") = py::none(),
+     py::arg("compress_keys") = false);
   py::class_<HipValuation>(mseal, "SEALValuation", "Inputs or outputs of execute(): ciphertexts, plaintexts or raw vectors")
       .def(py::init<>())
       .def("_set_cipher", [](HipValuation &v, const std::string &name, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> data, double scale) {
@@ -417,14 +419,30 @@ PYBIND11_MODULE(_eva, m) {
         for (uint32_t i = 0; i < limbs; i++) h.ntt(i, out.data() + (size_t)i * h.N);
         return to_numpy(out, {(py::ssize_t)limbs, (py::ssize_t)h.N});
       }, py::arg("values"), py::arg("scale_bits"), py::arg("level"))
+      // the full words of a key, materialised for the caller when the context keeps it compressed (which it goes on doing)
       .def("relin_key", [](const HipPublic &p) {
-        return to_numpy(p.relin.data, {(py::ssize_t)p.relin.n_digits, 2, (py::ssize_t)p.host->k, (py::ssize_t)p.host->N});
+        std::vector<u64> tmp;
+        return to_numpy(p.relin.words(*p.host, tmp), {(py::ssize_t)p.relin.n_digits, 2, (py::ssize_t)p.host->k, (py::ssize_t)p.host->N});
       })
+      .def_property_readonly("keys_compressed", &HipPublic::keys_compressed, "the evaluation keys are kept, saved and uploaded as c0 + a 32-byte seed per digit (generate_keys(..., compress_keys=True))")
+      .def("key_seeds", [](const HipPublic &p) -> py::object {
+        if (!p.keys_compressed()) return py::none();
+        auto seeds_of = [](const SwitchKey &k) {
+          py::array_t<uint8_t> a({(py::ssize_t)k.n_digits, (py::ssize_t)32});
+          std::memcpy(a.mutable_data(), k.seeds.data(), k.seeds.size());
+          return a;
+        };
+        py::dict d;
+        d[py::int_(0)] = seeds_of(p.relin);
+        for (auto &kv : p.galois) d[py::int_(kv.first)] = seeds_of(kv.second);
+        return d;
+      }, "{0: the relinearization key's seeds [digits][32], Galois element: that key's} of a compressed context (DESIGN.md 1.4), else None")
       .def("public_key", [](const HipPublic &p) { return to_numpy(p.pk.data, {2, (py::ssize_t)p.host->k, (py::ssize_t)p.host->N}); })
       .def("galois_keys", [](const HipPublic &p) {
         py::dict d;
+        std::vector<u64> tmp;
         for (auto &kv : p.galois)
-          d[py::int_(kv.first)] = to_numpy(kv.second.data, {(py::ssize_t)kv.second.n_digits, 2, (py::ssize_t)p.host->k, (py::ssize_t)p.host->N});
+          d[py::int_(kv.first)] = to_numpy(kv.second.words(*p.host, tmp), {(py::ssize_t)kv.second.n_digits, 2, (py::ssize_t)p.host->k, (py::ssize_t)p.host->N});
         return d;
       });
   py::class_<HipSecret, std::shared_ptr<HipSecret>>(mseal, "SEALSecret", "Secret context: decryption. Holds the secret key.")

@@ -21,6 +21,8 @@ public:
   PublicKey pk;
   SwitchKey relin;
   std::map<uint32_t, SwitchKey> galois; // by Galois element
+  // the evaluation keys are kept as c0 + one seed per digit (generate_keys(..., compress_keys))
+  bool keys_compressed() const { return relin.compressed(); }
   int device = 0;
   bool free_eagerly = true;
   std::array<double, 3> last_timing{0, 0, 0}; // ms: input upload, DAG enqueue (host), drain + output download
@@ -339,10 +341,15 @@ private:
   std::vector<int> limb_ids;
   struct LimbConst { uint64_t hash = 0; std::unordered_map<TermId, ShardedValue> plain; };
   std::unordered_map<const Program *, LimbConst> limb_const; // encoded plaintexts of a program, dealt over the shards
+  // every mode's key upload (the single device, sub-DAG members, limb shards): a compressed key crosses as c0 + seeds
+  // and is expanded on the device (evah_key_upload_seeded)
   void upload_eval_keys(evah_ctx *c) {
-    chk(evah_key_upload(c, EVAH_KEY_RELIN, 0, relin.n_digits, (const uint64_t *)relin.data.data()));
-    for (auto &kv : galois)
-      chk(evah_key_upload(c, EVAH_KEY_GALOIS, kv.first, kv.second.n_digits, (const uint64_t *)kv.second.data.data()));
+    auto up = [&](int kind, uint32_t elt, const SwitchKey &k) {
+      if (k.compressed()) chk(evah_key_upload_seeded(c, kind, elt, k.n_digits, (const uint64_t *)k.c0.data(), k.seeds.data()));
+      else chk(evah_key_upload(c, kind, elt, k.n_digits, (const uint64_t *)k.data.data()));
+    };
+    up(EVAH_KEY_RELIN, 0, relin);
+    for (auto &kv : galois) up(EVAH_KEY_GALOIS, kv.first, kv.second);
   }
   void check_devices() const {
     int n = 0;

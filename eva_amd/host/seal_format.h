@@ -299,7 +299,9 @@ inline std::string kswitch_obj(const HostContext &h, uint64_t dim1, const std::m
       const SwitchKey &k = *it->second;
       put<uint64_t>(m, k.n_digits);
       const size_t each = (size_t)2 * h.k * h.N;
-      for (uint32_t j = 0; j < k.n_digits; j++) m += public_key_obj(h, k.data.data() + j * each, None);
+      std::vector<u64> tmp; // a compressed key is written expanded: SEAL's seeded form names SEAL's own generator
+      const std::vector<u64> &kw = k.words(h, tmp);
+      for (uint32_t j = 0; j < k.n_digits; j++) m += public_key_obj(h, kw.data() + j * each, None);
       ++it;
     } else {
       put<uint64_t>(m, 0);

@@ -261,12 +261,33 @@ inline std::shared_ptr<HostContext> read_ctx(Reader &r) {
       throw std::runtime_error("Could not parse message: invalid coefficient modulus");
   return std::make_shared<HostContext>(N, primes);
 }
+// A switch key: its digit count and words.  A compressed key sets the top bit of the digit count and
+// carries its seeds (32 bytes per digit) and c0 instead; a reader from before that form sees a digit count no context
+// has and refuses the file.
+constexpr uint32_t SWITCH_KEY_SEEDED = 0x80000000u;
+inline void write(Writer &w, const SwitchKey &k) {
+  if (k.compressed()) { w.pod<uint32_t>(k.n_digits | SWITCH_KEY_SEEDED); w.vec(k.seeds); w.vec(k.c0); }
+  else { w.pod(k.n_digits); w.vec(k.data); }
+}
+inline SwitchKey read_switch_key(Reader &r) {
+  SwitchKey k;
+  k.n_digits = r.pod<uint32_t>();
+  if (k.n_digits & SWITCH_KEY_SEEDED) {
+    k.n_digits &= ~SWITCH_KEY_SEEDED;
+    k.seeds = r.vec<uint8_t>();
+    k.c0 = r.vec<u64>();
+    if (k.seeds.empty()) throw std::runtime_error("Could not parse message: compressed key without seeds");
+  } else {
+    k.data = r.vec<u64>();
+  }
+  return k;
+}
 inline void write(Writer &w, const HipPublic &p) {
   write_ctx(w, *p.host);
   w.vec(p.pk.data);
-  w.pod(p.relin.n_digits); w.vec(p.relin.data);
+  write(w, p.relin);
   w.pod<uint64_t>(p.galois.size());
-  for (auto &kv : p.galois) { w.pod(kv.first); w.pod(kv.second.n_digits); w.vec(kv.second.data); }
+  for (auto &kv : p.galois) { w.pod(kv.first); write(w, kv.second); }
 }
 // every word of a key-level object ([...][k][N]) must be a canonical residue of its prime: the kernels'
 // lazy-reduction bounds assume it, so an out-of-range word would give silently wrong results
@@ -280,6 +301,13 @@ template <class Vec> inline void check_residues(const Vec &words, const HostCont
   }
 }
 inline void check_switch_key(const SwitchKey &k, const HostContext &h, const char *what) {
+  if (k.compressed()) { // c1 is reduced by construction; c0 and the seeds come from the file
+    if (k.n_digits == 0 || k.n_digits > h.k - 1 || k.seeds.size() != (size_t)32 * k.n_digits || k.c0.size() != (size_t)k.n_digits * h.k * h.N ||
+        !k.data.empty())
+      throw std::runtime_error(std::string("Could not parse message: ") + what + " has the wrong size for its context");
+    check_residues(k.c0, h, what);
+    return;
+  }
   if (k.n_digits == 0 || k.n_digits > h.k - 1 || k.data.size() != (size_t)k.n_digits * 2 * h.k * h.N)
     throw std::runtime_error(std::string("Could not parse message: ") + what + " has the wrong size for its context");
   check_residues(k.data, h, what);
@@ -290,12 +318,12 @@ inline std::shared_ptr<HipPublic> read_public(Reader &r) {
   p->pk.data = r.vec<u64>();
   if (p->pk.data.size() != (size_t)2 * p->host->k * p->host->N) throw std::runtime_error("Could not parse message: public key has the wrong size for its context");
   check_residues(p->pk.data, *p->host, "public key");
-  p->relin.n_digits = r.pod<uint32_t>(); p->relin.data = r.vec<u64>();
+  p->relin = read_switch_key(r);
   check_switch_key(p->relin, *p->host, "relinearization key");
   uint64_t n = r.pod<uint64_t>();
   for (uint64_t i = 0; i < n; i++) {
     uint32_t elt = r.pod<uint32_t>();
-    SwitchKey k; k.n_digits = r.pod<uint32_t>(); k.data = r.vec<u64>();
+    SwitchKey k = read_switch_key(r);
     if (!(elt & 1) || elt >= 2 * p->host->N) throw std::runtime_error("Could not parse message: Galois element is not valid");
     check_switch_key(k, *p->host, "Galois key");
     p->galois.emplace(elt, std::move(k));

@@ -73,6 +73,13 @@ int evah_ctx_mem_info(evah_ctx *ctx, size_t *in_use, size_t *cached);
 #define EVAH_KEY_SECRET 3
 int evah_key_upload(evah_ctx *ctx, int kind, uint32_t galois_elt, uint32_t n_digits,
                     const uint64_t *data);
+/* The same key from its seed-compressed form (what SEAL's KeyGenerator::create_relin_keys /
+ * create_galois_keys hand out as Serializable<RelinKeys / GaloisKeys> objects that are saved seeded): c0 of every digit and
+ * the 32-byte seed its c1 is expanded from on ctx's queue — row i of digit J is the expansion rule of the seeded
+ * ciphertexts under chain prime i with seed J.  Installs exactly the words evah_key_upload installs for the materialised
+ * key (the split copy included), with half of them crossing PCIe; a limb shard copies and expands its own rows only. */
+int evah_key_upload_seeded(evah_ctx *ctx, int kind, uint32_t galois_elt, uint32_t n_digits,
+                           const uint64_t *c0 /* [n_digits][k][N] */, const uint8_t *seeds /* [n_digits][32] */);
 /* Galois element used by evah_rotate for `steps` (SEAL GaloisTool::get_elt_from_step). */
 int evah_galois_elt_from_step(evah_ctx *ctx, int32_t steps, uint32_t *elt);
 
@@ -425,6 +432,10 @@ void evah_graph_free(evah_graph *g);
 /* ---- test / measurement hooks -------------------------------------------------------------- */
 /* in-place negacyclic NTT (inverse=0) or INTT (inverse=1) of one host polynomial mod primes[i] */
 int evah_test_ntt(evah_ctx *ctx, uint32_t prime_idx, int inverse, uint64_t *host_inout);
+/* the device words of an installed relinearization / Galois key -> out: which = 0 the key as the kernels read it
+ * ([n_digits][2][rows][N]; rows = k, or a limb shard's own rows), which = 1 its radix-2^30 split copy — an error when the
+ * key has none (primes of another shape, EVAH_MAC3=0, a limb shard) */
+int evah_test_key_words(evah_ctx *ctx, int kind, uint32_t galois_elt, int which, uint64_t *out);
 /* One arithmetic primitive of the kernels (devmath.hip.h, the butterflies of ntt.hip.h, the key-switch accumulators of
  * ntt_ks_inner.hip.h) applied by a small kernel to n lanes of host words, with the DevPrime of primes[prime_idx].
  * Lane i reads a[i*m + j], b[i*m + j] for j < m (m > 1 only for the sequence ops ACC128, ACC128C, MAC3, KS128) and
