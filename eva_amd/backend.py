@@ -44,6 +44,7 @@ _SIGS = {
     "evah_ctx_transfer_stats": [_vp, _u64p],
     "evah_ctx_key_bytes": [_vp, _u64p],
     "evah_ctx_key_bytes_detail": [_vp, _u64p],
+    "evah_ctx_key_upload_stats": [_vp, _u64p],
     "evah_pt_copy": [_vp, _vp, _vpp],
     "evah_pt_write": [_vp, _vp, _u64p],
     "evah_capture_begin": [_vp, _vpp, C.c_uint32],
@@ -114,6 +115,7 @@ _SIGS = {
     "evah_ct_download_poly": [_vp, _vp, C.c_uint32, _u64p],
     # seed-compressed evaluation keys
     "evah_key_upload_seeded": [_vp, C.c_int, C.c_uint32, C.c_uint32, _u64p, C.POINTER(C.c_uint8)],
+    "evah_keygen_switch": [_vp, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_int8), C.POINTER(C.c_uint8), C.c_int, _u64p],
     "evah_test_key_words": [_vp, C.c_int, C.c_uint32, C.c_int, _u64p],
     # limb-sharded execution
     "evah_ctx_set_shard": [_vp, C.c_uint32, C.c_uint32],
@@ -537,6 +539,12 @@ class Context:
         _chk(_lib.evah_ctx_key_bytes_detail(self.h, out))
         return tuple(int(x) for x in out)
 
+    def key_upload_stats(self):
+        """(evaluation-key uploads installed from the host, bytes they sent); a key generated in place counts in neither"""
+        out = (C.c_uint64 * 2)()
+        _chk(_lib.evah_ctx_key_upload_stats(self.h, out))
+        return tuple(int(x) for x in out)
+
     def mem_info(self):
         a, b = C.c_size_t(), C.c_size_t()
         _chk(_lib.evah_ctx_mem_info(self.h, C.byref(a), C.byref(b)))
@@ -588,6 +596,17 @@ class Context:
 
     def upload_galois_key_seeded(self, elt, c0, seeds):
         self._upload_key_seeded(KEY_GALOIS, elt, c0, seeds)
+
+    def keygen_switch(self, kind, elt, errors, seeds, install=True):
+        """evah_keygen_switch: the relinearization (KEY_RELIN) or Galois key of `elt` under the uploaded
+        secret key from errors [digits][N] int8 and seeds [digits][32] uint8; returns c0 [digits][k][N]"""
+        errors = np.ascontiguousarray(errors, dtype=np.int8)
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint8)
+        assert errors.ndim == 2 and errors.shape[1] == self.N and seeds.shape == (errors.shape[0], 32)
+        c0 = np.empty((errors.shape[0], self.k, self.N), dtype=np.uint64)
+        _chk(_lib.evah_keygen_switch(self.h, int(kind), int(elt), errors.shape[0], errors.ctypes.data_as(C.POINTER(C.c_int8)),
+                                     seeds.ctypes.data_as(C.POINTER(C.c_uint8)), int(bool(install)), _p(c0)))
+        return c0
 
     def key_words(self, kind, elt=0, which=0, digits=None):
         """test hook (evah_test_key_words): the device words of an installed key as [digits][2][rows][N] — rows = k, or

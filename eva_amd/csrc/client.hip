@@ -27,6 +27,13 @@ k_small_to_residues(DevCtx cx, const int8_t *small, uint32_t n_polys, uint32_t l
   const u64 q = cx.primes[cx.prime_of(i)].q;
   out[((size_t)p * limbs + i) * cx.N + n] = v < 0 ? q - (u64)(-v) : (u64)v;
 }
+// NTT forms [n_polys][limbs][N] of n_polys small polynomials (int8 [n_polys][N] on the device) under the chain primes
+// 0 .. limbs - 1, on the calling queue: what evah_encrypt_symmetric and evah_keygen_switch (seeded.hip) make of their errors
+void small_to_ntt(evah_ctx *c, const u64 *small8, uint32_t n_polys, uint32_t limbs, u64 *out) {
+  EW_LAUNCH(k_small_to_residues, dim3(c->N / 256, limbs, n_polys), dim3(256), 0, c->stream, c->dev, reinterpret_cast<const int8_t *>(small8), n_polys, limbs, out);
+  OpPlain::Params fp{out, out, (size_t)limbs * c->N, (size_t)limbs * c->N, limbs, 0, 0, {}};
+  ntt_forward<OpPlain>(c, fp, n_polys * limbs);
+}
 // c[K][i] = pk[K][i] * u[i] + e_K[i]; small = NTT forms [3][up][N] of (u, e0, e1); pk [2][k][N]
 __global__ void __launch_bounds__(256)
 k_encrypt_zero(DevCtx cx, const u64 *pk, const u64 *small, uint32_t up, u64 *c) {
@@ -228,9 +235,7 @@ int evah_encrypt_symmetric(evah_ctx *c, const evah_pt *pt, const int8_t *e, cons
   const size_t N = c->N;
   Scratch e8(c, (N + 7) / 8), en(c, (size_t)l * N);
   HIPCHK(hipMemcpyAsync(e8.d, e, N, hipMemcpyHostToDevice, c->stream));
-  EW_LAUNCH(k_small_to_residues, dim3(c->N / 256, l, 1), dim3(256), 0, c->stream, c->dev, reinterpret_cast<const int8_t *>(e8.d), 1u, l, en.d);
-  OpPlain::Params fp{en.d, en.d, (size_t)l * N, (size_t)l * N, l, 0, 0, {}};
-  ntt_forward<OpPlain>(c, fp, l);
+  small_to_ntt(c, e8.d, 1, l, en.d);
   evah_ct *o = ct_new(c, 2, l, pt->scale);
   try {
     const Seeds8 s = seeds_of(&seed32, 0, 1);

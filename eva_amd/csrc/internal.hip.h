@@ -202,6 +202,7 @@ struct SharedDev {
   uint32_t *enc_slot_map = nullptr; // slot i (and its conjugate, at slots + i) -> FFT input index
   uint32_t key_rows = 0, key_shard = 0; // evaluation keys: 0 none yet, 1 whole, 2 the prime rows of limb shard `key_shard`
   uint64_t xfer[6] = {0, 0, 0, 0, 0, 0}; // evah_ctx_transfer_stats: ct up / down, pt up / down, bytes up / down
+  uint64_t key_up[2] = {0, 0}; // evah_ctx_key_upload_stats: evaluation keys uploaded from the host (calls, bytes sent)
   ~SharedDev() {
     (void)hipSetDevice(device);
     if (enc_roots) (void)hipFree(enc_roots);

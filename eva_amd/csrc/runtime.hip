@@ -380,6 +380,8 @@ int evah_key_upload(evah_ctx *c, int kind, uint32_t galois_elt, uint32_t n_digit
     }
   }
   key_install(c, kind, galois_elt, kd);
+  c->sh->key_up[0]++;
+  c->sh->key_up[1] += kd.bytes;
   API_END
 }
 
@@ -667,6 +669,15 @@ int evah_ctx_key_bytes(evah_ctx *c, uint64_t *bytes) {
   uint64_t b = c->sh->relin.d ? c->sh->relin.bytes : 0;
   for (auto &kv : c->sh->galois) b += kv.second.bytes;
   *bytes = b;
+  API_END
+}
+
+// evaluation keys that crossed the host boundary into this device state: installed uploads (evah_key_upload,
+// evah_key_upload_seeded) and the bytes they sent.  A key generated in place (evah_keygen_switch) is no upload.
+int evah_ctx_key_upload_stats(evah_ctx *c, uint64_t out[2]) {
+  API_BEGIN
+  out[0] = c->sh->key_up[0];
+  out[1] = c->sh->key_up[1];
   API_END
 }
 

@@ -3,6 +3,8 @@
 // seeded.hip.h), slot refills of captured graphs, and the download of c0 alone.  The fused symmetric encryption
 // (evah_encrypt_symmetric) lives in client.hip beside evah_encrypt.  Evaluation keys travel the same way:
 // evah_key_upload_seeded takes c0 and one seed per digit and expands every c1 row — and the split copy — in one launch.
+// evah_keygen_switch makes the whole key here: c0 as well, from the resident secret key and N int8 error
+// draws per digit.
 
 #include "launch.hip.h"
 #include "seeded.hip.h"
@@ -69,6 +71,60 @@ k_key_expand(DevCtx cx, Seeds8 seeds, const uint32_t *__restrict__ seed_buf, uin
   }
 }
 
+// A whole key-switching key from the secret key and seeds, in the device layout d = [digit][2][k][N]: for
+// digit J and chain prime i, a = seeded_block(seed_J, i, .), c0 = -(a s + NTT(e_J)) and, on the row i == J (uniform over
+// the block), + (P mod q_J) s'.  s' is never stored: s * s for the relinearization key (perm == nullptr), s read through
+// the Galois element's permutation table otherwise (the table rotations use: s'[n] = s[perm[n]]).  en = NTT(e)
+// [digit][k][N], sk [k][N].  The split copy, when the key has one, leaves from the same registers.  One thread per
+// ChaCha block (4 coefficients); grid = (ceil(N / 4 / 256), k, digits).  Seeds as in k_key_expand.
+__global__ void __launch_bounds__(256)
+k_keygen_switch(DevCtx cx, Seeds8 seeds, const uint32_t *__restrict__ seed_buf, const u64 *__restrict__ en, const u64 *__restrict__ sk,
+                const uint32_t *__restrict__ perm, u64 *__restrict__ d, u64 *__restrict__ d_split) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y, J = blockIdx.z;
+  if (t >= cx.N / 4 || i >= cx.k) return;
+  const DevPrime pm = cx.primes[i];
+  uint32_t key[8];
+  if (seed_buf) {
+#pragma unroll
+    for (int w = 0; w < 8; w++) key[w] = seed_buf[8 * J + w];
+  } else {
+#pragma unroll
+    for (int w = 0; w < 8; w++) key[w] = seeds.w[J][w];
+  }
+  u64 a[4], b[4];
+  seeded_block(key, i, t, pm, a);
+  const size_t n0 = 4 * (size_t)t;
+  const u64 *s = sk + (size_t)i * cx.N, *e = en + ((size_t)J * cx.k + i) * cx.N + n0;
+  const ulonglong2 s01 = ld2(s + n0), s23 = ld2(s + n0 + 2), e01 = ld2(e), e23 = ld2(e + 2);
+  const u64 sv[4] = {s01.x, s01.y, s23.x, s23.y}, ev[4] = {e01.x, e01.y, e23.x, e23.y};
+#pragma unroll
+  for (int r = 0; r < 4; r++) b[r] = negmod(addmod(mulmod(a[r], sv[r], pm), ev[r], pm.q), pm.q);
+  if (i == J) {
+    const u64 pmod = cx.modq[(size_t)(cx.k - 1) * cx.k + J].x; // P mod q_J
+    u64 sp[4];
+    if (perm) {
+      const uint4 pi = *reinterpret_cast<const uint4 *>(perm + n0);
+      sp[0] = s[pi.x]; sp[1] = s[pi.y]; sp[2] = s[pi.z]; sp[3] = s[pi.w];
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; r++) sp[r] = mulmod(sv[r], sv[r], pm);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; r++) b[r] = addmod(b[r], mulmod(sp[r], pmod, pm), pm.q);
+  }
+  const size_t at0 = ((size_t)2 * J * cx.k + i) * cx.N + n0, at1 = at0 + (size_t)cx.k * cx.N;
+  st2(d + at0, make_ulonglong2(b[0], b[1]));
+  st2(d + at0 + 2, make_ulonglong2(b[2], b[3]));
+  st2(d + at1, make_ulonglong2(a[0], a[1]));
+  st2(d + at1 + 2, make_ulonglong2(a[2], a[3]));
+  if (d_split) {
+    st2(d_split + at0, make_ulonglong2(split30(b[0]), split30(b[1])));
+    st2(d_split + at0 + 2, make_ulonglong2(split30(b[2]), split30(b[3])));
+    st2(d_split + at1, make_ulonglong2(split30(a[0]), split30(a[1])));
+    st2(d_split + at1 + 2, make_ulonglong2(split30(a[2]), split30(a[3])));
+  }
+}
+
 } // namespace evah
 
 extern "C" {
@@ -119,6 +175,79 @@ int evah_key_upload_seeded(evah_ctx *c, int kind, uint32_t galois_elt, uint32_t 
     throw;
   }
   key_install(c, kind, galois_elt, kd);
+  c->sh->key_up[0]++;
+  c->sh->key_up[1] += kd.bytes / 2 + (size_t)32 * n_digits; // c0 of the rows kept + the seeds
+  API_END
+}
+
+// A relinearization or Galois key generated on the device: the caller supplies what is random — one int8
+// error polynomial and one 32-byte seed per digit — and the context's secret key does the rest; the key is installed like
+// an uploaded one and / or its c0 handed back, word for word the host generator's compressed key for the same draws
+int evah_keygen_switch(evah_ctx *c, int kind, uint32_t galois_elt, uint32_t n_digits, const int8_t *errors, const uint8_t *seeds,
+                       int install, uint64_t *c0_out) {
+  API_BEGIN
+  use(c);
+  if (c->dev.pstep > 1) throw std::invalid_argument("a limb shard holds no whole secret key");
+  KeyDev kd = key_shape(c, n_digits);
+  if (kind != EVAH_KEY_RELIN && kind != EVAH_KEY_GALOIS) throw std::invalid_argument("unknown key kind");
+  if (kind == EVAH_KEY_GALOIS && (!(galois_elt & 1) || galois_elt >= 2 * c->N)) throw std::invalid_argument("Galois element is not valid");
+  if (!errors) throw std::invalid_argument("error pointer is null");
+  if (!seeds) throw std::invalid_argument("seed pointer is null");
+  if (!install && !c0_out) throw std::invalid_argument("the key is neither installed nor returned");
+  if (c->N % 256) throw std::invalid_argument("key generation needs N divisible by 256");
+  if (!c->sh->sk.d) throw std::invalid_argument("secret key not present");
+  const uint32_t *perm = kind == EVAH_KEY_GALOIS ? perm_table(c, galois_elt) : nullptr;
+  const size_t N = c->N, poly = (size_t)c->k * N, e_bytes = (size_t)n_digits * N;
+  Seeds8 s8;
+  std::memset(&s8, 0, sizeof s8);
+  std::unique_ptr<Scratch> seed_dev; // more than 8 digits: the seeds as a device buffer, returned to the pool after the drain
+  HIPCHK(hipMalloc(&kd.d, kd.bytes));
+  if (c->all_tb && c->tun.mac3 && hipMalloc(&kd.d_split, kd.bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    kd.d_split = nullptr; // no memory for the second copy: the 128-bit accumulation is used
+  }
+  try {
+    Scratch e8(c, (e_bytes + 7) / 8), en(c, (size_t)n_digits * poly);
+    try {
+      HIPCHK(hipMemcpyAsync(e8.d, errors, e_bytes, hipMemcpyHostToDevice, c->stream));
+      small_to_ntt(c, e8.d, n_digits, c->k, en.d);
+      const uint32_t *seed_buf = nullptr;
+      if (n_digits <= SEEDS_PER_LAUNCH) {
+        std::memcpy(s8.w, seeds, (size_t)32 * n_digits); // little-endian key words, as the host generator reads its key
+      } else {
+        seed_dev = std::make_unique<Scratch>(c, (size_t)4 * n_digits);
+        HIPCHK(hipMemcpyAsync(seed_dev->d, seeds, (size_t)32 * n_digits, hipMemcpyHostToDevice, c->stream));
+        seed_buf = reinterpret_cast<const uint32_t *>(seed_dev->d);
+      }
+      EW_LAUNCH(k_keygen_switch, seeded_grid(c, c->k, n_digits), dim3(256), 0, c->stream, c->dev, s8, seed_buf, en.d, c->sh->sk.d, perm, kd.d,
+                kd.d_split);
+      HIPCHK(hipGetLastError());
+      if (c0_out) // c0 of digit J from d[J][0]: one linear copy per digit (evah_ct_download on 2-D copies and pageable memory)
+        for (uint32_t J = 0; J < n_digits; J++)
+          HIPCHK(hipMemcpyAsync(c0_out + (size_t)J * poly, kd.d + (size_t)J * 2 * poly, sizeof(u64) * poly, hipMemcpyDeviceToHost, c->stream));
+    } catch (...) {
+      (void)hipMemsetAsync(en.d, 0, sizeof(u64) * (size_t)n_digits * poly, c->stream);
+      (void)hipMemsetAsync(e8.d, 0, e_bytes, c->stream);
+      throw;
+    }
+    // the errors do not stay behind in pool memory the next call reuses
+    HIPCHK(hipMemsetAsync(en.d, 0, sizeof(u64) * (size_t)n_digits * poly, c->stream));
+    HIPCHK(hipMemsetAsync(e8.d, 0, e_bytes, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream)); // `errors` and c0_out are pageable; complete before any queue reads the key
+  } catch (...) {
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(kd.d);
+    if (kd.d_split) (void)hipFree(kd.d_split);
+    throw;
+  }
+  c->sh->xfer[4] += e_bytes + (size_t)32 * n_digits;
+  if (c0_out) c->sh->xfer[5] += sizeof(u64) * (size_t)n_digits * poly;
+  if (install) {
+    key_install(c, kind, galois_elt, kd);
+  } else {
+    (void)hipFree(kd.d);
+    if (kd.d_split) (void)hipFree(kd.d_split);
+  }
   API_END
 }
 

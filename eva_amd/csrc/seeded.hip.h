@@ -53,6 +53,8 @@ inline Seeds8 seeds_of(const uint8_t *const *seeds, uint32_t first, uint32_t n) 
   }
   return s;
 }
+// client.hip: small polynomials (int8 on the device) to their NTT forms under the first `limbs` chain primes
+void small_to_ntt(evah_ctx *c, const u64 *small8, uint32_t n_polys, uint32_t limbs, u64 *out);
 inline dim3 seeded_grid(const evah_ctx *c, uint32_t limbs, uint32_t z) { return dim3((c->N / 4 + 255) / 256, limbs, z); }
 
 } // namespace evah

@@ -390,6 +390,13 @@ private:
   }
 };
 
+// Zeroes secret-stream draws (error polynomials) once they are used.  The stores go through a volatile pointer: the
+// vectors are destroyed right afterwards, and a plain std::fill would be a dead store the compiler may remove.
+inline void wipe(std::vector<int8_t> &v) {
+  volatile int8_t *p = v.data();
+  for (size_t i = 0, n = v.size(); i < n; i++) p[i] = 0;
+}
+
 // Key material in the layout libeva_hip.so expects.
 struct SwitchKey {
   uint32_t n_digits = 0;
@@ -449,6 +456,16 @@ public:
     encrypt_zero_symmetric(pk.data.data(), pk.data.data() + (size_t)cx.k * cx.N);
     return pk;
   }
+  // What one digit of a seed-compressed key draws, and in which order — the one place that says so, for the host
+  // generator below and for the device's (client.h generate_keys(..., device_keygen)): 4 words of the
+  // public stream, which are the 32-byte seed of c1, then one error polynomial of the secret stream
+  void draw_seeded_digit(uint8_t *seed32, std::vector<int8_t> &e) {
+    for (int w = 0; w < 4; w++) {
+      const u64 r = (*pub)();
+      std::memcpy(seed32 + 8 * w, &r, 8);
+    }
+    cx.sample_error(*secret, e);
+  }
   // key-switch key from s' (NTT form over all k primes) to s: digit J carries P * s' in limb J.
   // seeded: c1 of every digit is the expansion of a 32-byte seed — 4 words of the public stream in place
   // of its k N rejection-sampled draws — and the key is returned as c0 + seeds
@@ -464,19 +481,18 @@ public:
     }
     const u64 P = cx.primes[k - 1];
     std::vector<u64> a;
+    std::vector<int8_t> e;
     for (uint32_t J = 0; J < D; J++) {
       u64 *c0, *c1;
       if (seeded) {
         uint8_t *seed = key.seeds.data() + (size_t)32 * J;
-        for (int w = 0; w < 4; w++) {
-          const u64 r = (*pub)();
-          std::memcpy(seed + 8 * w, &r, 8);
-        }
+        draw_seeded_digit(seed, e);
         a.resize((size_t)k * N);
         for (uint32_t i = 0; i < k; i++) seeded_limb(seed, i, cx.primes[i], N, (uint64_t *)(a.data() + (size_t)i * N));
         c0 = key.c0.data() + (size_t)J * k * N;
         c1 = a.data();
-        encrypt_zero_symmetric(c0, c1, false);
+        zero_symmetric(c0, c1, e);
+        wipe(e);
       } else {
         c0 = key.data.data() + (size_t)J * 2 * k * N;
         c1 = c0 + (size_t)k * N;
@@ -511,16 +527,21 @@ public:
   }
 
 private:
-  // (c0, c1) = (-(a s + e), a) over all k primes, NTT form; draw_a = false: a is given in c1 (expanded from a seed)
-  void encrypt_zero_symmetric(u64 *c0, u64 *c1, bool draw_a = true) {
-    const uint32_t N = cx.N;
+  // (c0, c1) = (-(a s + e), a) over all k primes, NTT form, with fresh e (secret stream) and a (public stream)
+  void encrypt_zero_symmetric(u64 *c0, u64 *c1) {
     std::vector<int8_t> e;
     cx.sample_error(*secret, e);
+    for (uint32_t i = 0; i < cx.k; i++) cx.sample_uniform(*pub, i, c1 + (size_t)i * cx.N);
+    zero_symmetric(c0, c1, e);
+  }
+  // c0 = -(a s + e) for a given in c1 and e given
+  void zero_symmetric(u64 *c0, const u64 *c1, const std::vector<int8_t> &e) {
+    const uint32_t N = cx.N;
     std::vector<u64> en(N);
     for (uint32_t i = 0; i < cx.k; i++) {
       const u64 q = cx.primes[i];
-      u64 *a = c1 + (size_t)i * N, *b = c0 + (size_t)i * N;
-      if (draw_a) cx.sample_uniform(*pub, i, a);
+      const u64 *a = c1 + (size_t)i * N;
+      u64 *b = c0 + (size_t)i * N;
       cx.small_to_ntt(e, i, en.data());
       const u64 *s = sk.s_ntt.data() + (size_t)i * N;
       for (uint32_t j = 0; j < N; j++) b[j] = evah::negmod(evah::addmod(cx.mulm(a[j], s[j], i), en[j], q), q);

@@ -195,7 +195,7 @@ public:
         for (uint32_t i = 0; i < limbs; i++) host->ntt(i, pt.data.data() + (size_t)i * host->N);
         out.values[name] = encrypt_symmetric(*host, sk, pt, e, sd);
       }
-      std::fill(e.begin(), e.end(), 0);
+      wipe(e);
     }
     return out;
   }
@@ -291,8 +291,13 @@ public:
 // per exact rotation step, relinearization key.  compress_keys: the relinearization and Galois keys are
 // generated, kept, saved and uploaded as c0 plus a 32-byte seed per digit; the secret and the public key are drawn
 // before any of them, so they are the same with and without the option for one test seed.
+// device_keygen: the same compressed keys, word for word, with c0 computed by evah_keygen_switch on the
+// key pair's device state from the host's draws (KeyGenerator::draw_seeded_digit).  devices / shard (null: the
+// environment's defaults) are set before any key is made, so that the device state is created on the right device; in the
+// default single-device mode the keys stay installed there and the first execute() uploads none.
 inline std::pair<std::shared_ptr<HipPublic>, std::shared_ptr<HipSecret>>
-generate_keys(const CKKSParameters &params, uint64_t seed = 0, bool compress_keys = false) {
+generate_keys(const CKKSParameters &params, uint64_t seed = 0, bool compress_keys = false, bool device_keygen = false,
+              const std::vector<int> *devices = nullptr, const std::string *shard = nullptr) {
   std::vector<int> bits(params.prime_bits.begin(), params.prime_bits.end());
   if (bits.size() < 2) throw std::invalid_argument("need at least two primes (data + special)");
   auto primes = evah::coeff_modulus_create(params.poly_modulus_degree, bits);
@@ -301,10 +306,43 @@ generate_keys(const CKKSParameters &params, uint64_t seed = 0, bool compress_key
   auto pub = std::make_shared<HipPublic>();
   auto sec = std::make_shared<HipSecret>();
   sec->holder = pub->holder; // one device state for the pair: results stay resident from encrypt to decrypt
+  if (devices) {
+    pub->devices = *devices;
+    // the key pair's own device state (inputs, constants, outputs; the secret half decrypts there) is member 0
+    if (!pub->devices.empty()) pub->device = sec->device = physical_device(pub->devices[0]);
+  }
+  if (shard) pub->shard_mode = *shard;
   pub->host = host;
+  sec->host = host;
+  sec->sk = kg.sk;
   pub->pk = kg.public_key();
-  pub->relin = kg.relin_key(compress_keys);
-  const uint32_t N = host->N, m = 2 * N;
+  const uint32_t N = host->N, m = 2 * N, D = host->k - 1;
+  const bool install = pub->devices.empty() && pub->shard_mode.empty(); // every other mode uploads from the host's c0 + seeds
+  if (device_keygen) {
+    // the key pair's device state is created here, not by the first execute(): a one-member `devices` list names its
+    // device wherever the list came from (the argument above or EVA_DEVICES / EVA_NUM_GPUS), as ensure_device rules
+    if (pub->devices.size() == 1) pub->device = sec->device = physical_device(pub->devices[0]);
+  }
+  if (device_keygen && !sec->on_device())
+    throw std::runtime_error("device_keygen needs a HIP device: none is visible, or EVA_DEVICE_CLIENT=0 keeps the client on the host");
+  // one key on the device: the draws of switch_key(., seeded) in its order, then evah_keygen_switch
+  auto device_key = [&](int kind, uint32_t elt) {
+    SwitchKey key;
+    key.n_digits = D;
+    key.seeds.resize((size_t)32 * D);
+    key.c0.resize((size_t)D * host->k * N);
+    std::vector<int8_t> errors((size_t)D * N), e;
+    for (uint32_t J = 0; J < D; J++) {
+      kg.draw_seeded_digit(key.seeds.data() + (size_t)32 * J, e);
+      std::copy(e.begin(), e.end(), errors.begin() + (size_t)J * N);
+    }
+    wipe(e);
+    const int rc = evah_keygen_switch(sec->dev->h, kind, elt, D, errors.data(), key.seeds.data(), install ? 1 : 0, (uint64_t *)key.c0.data());
+    wipe(errors);
+    chk(rc);
+    return key;
+  };
+  pub->relin = device_keygen ? device_key(EVAH_KEY_RELIN, 0) : kg.relin_key(compress_keys);
   for (int step : params.rotations) {
     uint32_t elt;
     if (step == 0) elt = m - 1;
@@ -315,10 +353,9 @@ generate_keys(const CKKSParameters &params, uint64_t seed = 0, bool compress_key
       elt = 1;
       for (uint32_t i = 0; i < s; i++) elt = (elt * 3u) & (m - 1);
     }
-    if (!pub->galois.count(elt)) pub->galois.emplace(elt, kg.galois_key(elt, compress_keys));
+    if (!pub->galois.count(elt)) pub->galois.emplace(elt, device_keygen ? device_key(EVAH_KEY_GALOIS, elt) : kg.galois_key(elt, compress_keys));
   }
-  sec->host = host;
-  sec->sk = kg.sk;
+  if (device_keygen && install) pub->eval_keys_installed();
   return {pub, sec};
 }
 

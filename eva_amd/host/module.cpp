@@ -251,18 +251,18 @@ PYBIND11_MODULE(_eva, m) {
   // EVA_NUM_GPUS / EVA_DEVICES / EVA_SHARD.  set_num_threads(n) — the reference's size of the parallel
   // traversal (wrapper.cpp:128-137) — is the number of issue queues independent DAG nodes are spread over.
   // compress_keys: the evaluation keys as c0 + a 32-byte seed per digit, expanded on the GPU at upload
-  mseal.def("generate_keys", [](const CKKSParameters &p, uint64_t seed, py::object devices, py::object shard, bool compress_keys) {
-    auto kp = generate_keys(p, seed, compress_keys);
-    if (!devices.is_none()) {
-      kp.first->devices = devices.cast<std::vector<int>>();
-      // the key pair's own device state (inputs, constants, outputs; the secret half decrypts there) is member 0
-      if (!kp.first->devices.empty()) kp.first->device = kp.second->device = evahost::physical_device(kp.first->devices[0]);
-    }
-    if (!shard.is_none()) kp.first->shard_mode = shard.cast<std::string>();
+  // device_keygen: the same compressed keys, generated on the GPU from the secret key and the host's draws
+  mseal.def("generate_keys", [](const CKKSParameters &p, uint64_t seed, py::object devices, py::object shard, bool compress_keys, bool device_keygen) {
+    // devices / shard reach generate_keys before any key is made: device key generation runs on member 0's device
+    std::vector<int> dv;
+    std::string sh;
+    if (!devices.is_none()) dv = devices.cast<std::vector<int>>();
+    if (!shard.is_none()) sh = shard.cast<std::string>();
+    auto kp = generate_keys(p, seed, compress_keys, device_keygen, devices.is_none() ? nullptr : &dv, shard.is_none() ? nullptr : &sh);
     if (g_num_threads > 1) kp.first->num_queues = std::min(g_num_threads, 8);
     return kp;
   }, py::arg("abstract_params"), py::arg("seed") = 0, py::arg("devices") = py::none(), py::arg("shard") = py::none(),
-     py::arg("compress_keys") = false);
+     py::arg("compress_keys") = false, py::arg("device_keygen") = false);
   py::class_<HipValuation>(mseal, "SEALValuation", "Inputs or outputs of execute(): ciphertexts, plaintexts or raw vectors")
       .def(py::init<>())
       .def("_set_cipher", [](HipValuation &v, const std::string &name, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> data, double scale) {
@@ -363,6 +363,12 @@ PYBIND11_MODULE(_eva, m) {
       .def_readwrite("devices", &HipPublic::devices, "device index per member of the multi-GPU modes (a repeated index = several contexts on one GPU)")
       .def_readwrite("shard_mode", &HipPublic::shard_mode, "'' (one device) | 'subdag' | 'limb' | 'dag' — how execute() / execute_batch() use `devices`")
       .def_readonly("last_subdag_plan", &HipPublic::last_subdag_plan, "(member, ops) per piece of the last sub-DAG split: prefix, components..., suffix")
+      .def("key_upload_stats", [](HipPublic &p) {
+        auto st = p.key_upload_stats();
+        py::dict d;
+        d["uploads"] = st[0]; d["bytes"] = st[1];
+        return d;
+      }, "evaluation keys uploaded from the host to the context's own device so far: calls and bytes sent (keys generated on the device count in neither)")
       .def("key_bytes", &HipPublic::key_bytes, "HBM bytes of evaluation keys: one entry per limb shard (when limb-sharded), then the whole keys on the context's own device (0 if never uploaded)")
       .def("set_limb_dist", [](HipPublic &p, uint32_t rank, uint32_t world, py::object all_gather, py::object broadcast, py::object sum_host,
                                uintptr_t stream) {

@@ -75,6 +75,13 @@ public:
   // nodes are large enough to be GPU-bound.
   int num_queues = 1;
 
+  // generate_keys(..., device_keygen) in the single-device mode: evah_keygen_switch installed every evaluation key on the
+  // key pair's device state as it made it, so this context adopts that state and execute() uploads no key
+  void eval_keys_installed() {
+    dev = holder->dev;
+    eval_keys_uploaded = true;
+  }
+
   // SEALPublic::encrypt (seal.cpp:24-102)
   HipValuation encrypt(const Valuation &inputs, const CKKSSignature &sig);
 
@@ -249,6 +256,14 @@ public:
   std::array<uint64_t, 6> transfer_stats() {
     std::array<uint64_t, 6> st{0, 0, 0, 0, 0, 0};
     if (dev) chk(evah_ctx_transfer_stats(dev->h, st.data()));
+    return st;
+  }
+
+  // evaluation keys this context's own device state received from the host: (uploads, bytes sent) — (0, 0) while none
+  // was uploaded, which is where generate_keys(..., device_keygen) leaves a single-device context for good
+  std::array<uint64_t, 2> key_upload_stats() {
+    std::array<uint64_t, 2> st{0, 0};
+    if (dev) chk(evah_ctx_key_upload_stats(dev->h, st.data()));
     return st;
   }
 

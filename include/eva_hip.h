@@ -80,6 +80,16 @@ int evah_key_upload(evah_ctx *ctx, int kind, uint32_t galois_elt, uint32_t n_dig
  * key (the split copy included), with half of them crossing PCIe; a limb shard copies and expands its own rows only. */
 int evah_key_upload_seeded(evah_ctx *ctx, int kind, uint32_t galois_elt, uint32_t n_digits,
                            const uint64_t *c0 /* [n_digits][k][N] */, const uint8_t *seeds /* [n_digits][32] */);
+/* The same key generated on the device (KeyGenerator::create_relin_keys / create_galois_keys as the
+ * reference calls them in generateKeys, /root/reference/eva/seal/seal.cpp:174-203): the secret key is the one
+ * evah_client_key_upload(EVAH_KEY_SECRET) left on ctx, the caller draws what is random — one error polynomial (int8) and
+ * one 32-byte seed per digit — and c0 = -(a s + NTT(e)) + [row J] (P mod q_J) s' is formed on ctx's queue with
+ * a = the seed's expansion; s' = s^2 (relinearization) or s(X^galois_elt) (Galois) is never stored.  install != 0: the key
+ * becomes ctx's, as after evah_key_upload_seeded of the same c0 and seeds.  c0_out != NULL: c0 is copied back, word for
+ * word the host generator's compressed key for the same draws.  Not on a limb shard, which holds no whole secret key. */
+int evah_keygen_switch(evah_ctx *ctx, int kind, uint32_t galois_elt, uint32_t n_digits,
+                       const int8_t *errors /* [n_digits][N] */, const uint8_t *seeds /* [n_digits][32] */,
+                       int install, uint64_t *c0_out /* [n_digits][k][N] or NULL */);
 /* Galois element used by evah_rotate for `steps` (SEAL GaloisTool::get_elt_from_step). */
 int evah_galois_elt_from_step(evah_ctx *ctx, int32_t steps, uint32_t *elt);
 
@@ -151,6 +161,10 @@ int evah_ctx_key_bytes(evah_ctx *ctx, uint64_t *bytes);
  * keys that hoisted rotation sets have used so far.  Up to 3x out[0]; a copy that does not fit the device is simply
  * not made (the affected launches take the form that does not need it). */
 int evah_ctx_key_bytes_detail(evah_ctx *ctx, uint64_t out[3]);
+/* Evaluation keys uploaded from the host into ctx's device state so far (the reference uploads nothing: its keys live
+ * where SEALPublic lives, seal.h:58-66): out[0] = installed uploads (evah_key_upload, evah_key_upload_seeded), out[1] =
+ * the bytes they sent.  A key generated in place (evah_keygen_switch) is not an upload and counts in neither. */
+int evah_ctx_key_upload_stats(evah_ctx *ctx, uint64_t out[2]);
 int evah_ct_info(const evah_ct *ct, uint32_t *size, uint32_t *limbs, double *scale);
 int evah_ct_download(evah_ctx *ctx, const evah_ct *ct, uint64_t *out /* [size][limbs][N] */);
 void evah_ct_free(evah_ctx *ctx, evah_ct *ct);
