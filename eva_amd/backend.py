@@ -113,6 +113,11 @@ _SIGS = {
                                         C.c_int, _vpp],
     "evah_ct_write_seeded": [_vp, _vp, _u64p, C.POINTER(C.c_uint8)],
     "evah_ct_download_poly": [_vp, _vp, C.c_uint32, _u64p],
+    # the client calls for a batch per call
+    "evah_encode_encrypt_many": [_vp, C.c_uint32, C.POINTER(C.c_double), C.c_uint32, C.c_uint32, C.c_double, C.POINTER(C.c_int8), _vpp],
+    "evah_encode_encrypt_symmetric_many": [_vp, C.c_uint32, C.POINTER(C.c_double), C.c_uint32, C.c_uint32, C.c_double,
+                                           C.POINTER(C.c_int8), C.POINTER(C.c_uint8), _vpp],
+    "evah_decrypt_decode_many": [_vp, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.POINTER(C.c_double)],
     # seed-compressed evaluation keys
     "evah_key_upload_seeded": [_vp, C.c_int, C.c_uint32, C.c_uint32, _u64p, C.POINTER(C.c_uint8)],
     "evah_keygen_switch": [_vp, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_int8), C.POINTER(C.c_uint8), C.c_int, _u64p],
@@ -495,6 +500,39 @@ class Context:
     def decrypt_decode(self, ct, n_out):
         out = np.empty(n_out, dtype=np.float64)
         _chk(_lib.evah_decrypt_decode(self.h, ct.h, int(n_out), out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def encode_encrypt_many(self, values, limbs, scale, small):
+        """values: [batch][n_values] reals; small: int8 [batch][3][N] = (u, e0, e1) per instance -> one batched handle whose
+        instance b is encode_pt(values[b]) -> encrypt(small[b]) word for word"""
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        small = np.ascontiguousarray(small, dtype=np.int8)
+        assert v.ndim == 2 and small.shape == (v.shape[0], 3, self.N)
+        h = C.c_void_p()
+        _chk(_lib.evah_encode_encrypt_many(self.h, v.shape[0], v.ctypes.data_as(C.POINTER(C.c_double)), v.shape[1], int(limbs),
+                                           float(scale), small.ctypes.data_as(C.POINTER(C.c_int8)), C.byref(h)))
+        return Ciphertext(self, h)
+
+    def encode_encrypt_symmetric_many(self, values, limbs, scale, e, seeds):
+        """values: [batch][n_values] reals; e: int8 [batch][N]; seeds: one 32-byte string per instance -> one batched
+        handle whose instance b is encode_pt(values[b]) -> encrypt_symmetric(e[b], seeds[b]) word for word"""
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        e = np.ascontiguousarray(e, dtype=np.int8)
+        sd = np.frombuffer(b"".join(bytes(s) for s in seeds), dtype=np.uint8).copy()
+        assert v.ndim == 2 and e.shape == (v.shape[0], self.N) and sd.shape == (32 * v.shape[0],)
+        h = C.c_void_p()
+        _chk(_lib.evah_encode_encrypt_symmetric_many(self.h, v.shape[0], v.ctypes.data_as(C.POINTER(C.c_double)), v.shape[1],
+                                                     int(limbs), float(scale), e.ctypes.data_as(C.POINTER(C.c_int8)),
+                                                     sd.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(h)))
+        return Ciphertext(self, h)
+
+    def decrypt_decode_many(self, cts, n_out):
+        """the first n_out slot values of every single ciphertext of `cts` (one size, limb count and scale; views are read in
+        place) -> float64 [len(cts)][n_out], the doubles of decrypt_decode per ciphertext"""
+        n = len(cts)
+        out = np.empty((n, int(n_out)), dtype=np.float64)
+        ptrs = (C.c_void_p * max(n, 1))(*[ct.h for ct in cts])
+        _chk(_lib.evah_decrypt_decode_many(self.h, ptrs, n, int(n_out), out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
 
     def copy_here(self, value):

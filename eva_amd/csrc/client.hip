@@ -14,6 +14,7 @@
 //              decoder, bit for bit (tests/test_decode_parity.py)
 
 #include "launch.hip.h"
+#include "client.hip.h"
 #include "seeded.hip.h"
 
 namespace evah {
@@ -82,64 +83,11 @@ k_decrypt_dot(DevCtx cx, const u64 *ct, size_t ps, uint32_t size, const u64 *sk,
   }
   m[off] = acc;
 }
-// Garner tables of a level: inv_prefix[i] = (q_0..q_{i-1})^-1 mod q_i, pre_mod[i][t] = q_0..q_{t-1} mod q_i,
-// prefix[i][w] = word w of q_0..q_{i-1} (base 2^64, l words), qwords[w] / half[w] = word w of Q / of floor(Q/2)
-struct CrtTab {
-  const u64 *inv_prefix, *pre_mod, *prefix, *qwords, *half;
-};
-__device__ __forceinline__ void garner(const DevCtx &cx, const CrtTab &t, uint32_t l, const u64 *r, u64 *v) {
-  for (uint32_t i = 0; i < l; i++) {
-    const DevPrime pm = cx.primes[i];
-    u128_t acc = {0, 0};
-    for (uint32_t j = 0; j < i; j++) acc128(acc, v[j] >= pm.q ? barrett64(v[j], pm.q, pm.brt) : v[j], t.pre_mod[i * l + j]);
-    const u64 a = barrett128(acc, pm);
-    v[i] = i ? mulmod(submod(r[i], a, pm.q), t.inv_prefix[i], pm) : r[0];
-  }
-}
-// SEAL 3.6 CKKSEncoder::decode_internal between the inverse NTTs and the FFT: the composed coefficient
-// x in [0, Q) as l base-2^64 words (here from the mixed-radix digits: x = sum_i v_i q_0..q_{i-1}, exact),
-// then ONE double from the words, least significant first, with inv_scale folded into the running power
-// of 2^64; x >= (Q + 1) / 2 is negative and accumulates the signed per-word differences against Q's
-// words.  Same operations in the same order as the oracle's evo_decode and the host decoder: same doubles.
+// one double per decrypted coefficient (crt_to_double, client.hip.h), as the real part of the FFT's input
 __global__ void __launch_bounds__(256)
 k_crt_to_double(DevCtx cx, CrtTab t, uint32_t l, const u64 *coeff, double inv_scale, double2 *out) {
-#pragma clang fp contract(off)
   const size_t n = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  u64 r[62], v[62], x[63];
-  for (uint32_t i = 0; i < l; i++) r[i] = coeff[(size_t)i * cx.N + n];
-  garner(cx, t, l, r, v);
-  for (uint32_t w = 0; w <= l; w++) x[w] = 0;
-  for (uint32_t i = 0; i < l; i++) { // x += v_i * prefix_i (prefix_i has at most i words; the sum stays below Q)
-    u64 carry = 0;
-    const u64 *pf = t.prefix + (size_t)i * l;
-    for (uint32_t w = 0; w < l; w++) {
-      u128_t p = mul128(pf[w], v[i]);
-      const u64 lo = p.lo + carry;
-      u64 hi = p.hi + (lo < carry);
-      const u64 sum = x[w] + lo;
-      hi += (sum < lo);
-      x[w] = sum;
-      carry = hi;
-    }
-  }
-  bool negative = false; // x > floor(Q/2), compared from the most significant word
-  for (int w = (int)l - 1; w >= 0; w--)
-    if (x[w] != t.half[w]) { negative = x[w] > t.half[w]; break; }
-  const double two_pow_64 = 18446744073709551616.0;
-  double acc = 0.0, scaled = inv_scale;
-  for (uint32_t w = 0; w < l; w++, scaled *= two_pow_64) {
-    const u64 xw = x[w], qw = t.qwords[w];
-    if (!negative) {
-      acc += xw ? (double)xw * scaled : 0.0;
-    } else if (xw > qw) {
-      const u64 diff = xw - qw;
-      acc += diff ? (double)diff * scaled : 0.0;
-    } else {
-      const u64 diff = qw - xw;
-      acc -= diff ? (double)diff * scaled : 0.0;
-    }
-  }
-  out[n] = make_double2(acc, 0.0);
+  out[n] = make_double2(crt_to_double(cx, t, l, coeff, n, inv_scale), 0.0);
 }
 // forward special FFT stage (Cooley-Tukey): group g of `groups` uses roots[groups + g]
 // (DWTHandler::transform_to_rev of SEAL 3.6: x = u + v r, y = u - v r; the complex product as four rounded
@@ -266,41 +214,14 @@ int evah_decrypt_decode(evah_ctx *c, const evah_ct *ct, uint32_t n_out, double *
   if (l > 61) throw std::invalid_argument("too many limbs");
   check_scale(c, ct->scale, l); // decode_internal: "scale out of bounds"
   enc_tables(c);
-  if (!c->sh->dec_roots) { // forward roots zeta^br(j) (hostmath.h), once per context family
-    const CkksRoots cr = ckks_roots(N);
-    std::vector<double> roots(2 * (size_t)N);
-    for (uint32_t j = 0; j < N; j++) { roots[2 * j] = cr.fwd[j].real(); roots[2 * j + 1] = cr.fwd[j].imag(); }
-    HIPCHK(hipMalloc(&c->sh->dec_roots, sizeof(double2) * N));
-    h2d_now(c, c->sh->dec_roots, roots.data(), sizeof(double2) * N);
-  }
-  // Garner tables of this level: [inv_prefix l][pre_mod l*l][prefix l*l][Q l][floor(Q/2) l]
-  std::vector<u64> tab((size_t)2 * l * l + 3 * l, 0);
-  {
-    u64 *inv_prefix = tab.data(), *pre_mod = inv_prefix + l, *prefix = pre_mod + (size_t)l * l,
-        *qwords = prefix + (size_t)l * l, *half = qwords + l;
-    std::vector<u64> w{1}; // q_0..q_{i-1}, little-endian words
-    for (uint32_t i = 0; i < l; i++) {
-      const u64 qi = c->primes[i];
-      u64 acc = 1 % qi;
-      for (uint32_t j = 0; j < i; j++) {
-        pre_mod[i * l + j] = acc;
-        acc = mulmod(acc, c->primes[j] % qi, qi);
-      }
-      inv_prefix[i] = invmod(acc, qi);
-      for (size_t t = 0; t < w.size() && t < l; t++) prefix[(size_t)i * l + t] = w[t];
-      u64 carry = 0;
-      for (auto &x : w) { u128 t = (u128)x * qi + carry; x = (u64)t; carry = (u64)(t >> 64); }
-      if (carry) w.push_back(carry);
-    }
-    for (size_t t = 0; t < w.size() && t < l; t++) qwords[t] = w[t];
-    for (size_t t = 0; t < w.size() && t < l; t++) half[t] = (w[t] >> 1) | (t + 1 < w.size() ? w[t + 1] << 63 : 0);
-  }
+  dec_tables(c);
+  const std::vector<u64> tab = crt_tab_build(c, l); // Garner tables of this level
   Scratch m(c, (size_t)l * N), tabd(c, tab.size()), cbuf(c, 2 * (size_t)N), outd(c, n_out);
   HIPCHK(hipMemcpyAsync(tabd.d, tab.data(), sizeof(u64) * tab.size(), hipMemcpyHostToDevice, c->stream));
   EW_LAUNCH(k_decrypt_dot, dim3(N / 256, l), dim3(256), 0, c->stream, c->dev, ct->d, ct->ps, ct->size, c->sh->sk.d, m.d);
   OpPlain::Params ip{m.d, m.d, 0, 0, l, 0, 0, {}};
   ntt_inverse<OpPlain>(c, ip, l);
-  CrtTab t{tabd.d, tabd.d + l, tabd.d + l + (size_t)l * l, tabd.d + l + (size_t)2 * l * l, tabd.d + 2 * l + (size_t)2 * l * l};
+  const CrtTab t = crt_tab_at(tabd.d, l);
   double2 *cd = reinterpret_cast<double2 *>(cbuf.d);
   EW_LAUNCH(k_crt_to_double, dim3(N / 256), dim3(256), 0, c->stream, c->dev, t, l, m.d, 1.0 / ct->scale, cd);
   // the decrypted message and its FP image do not stay behind in pool memory the next call reuses

@@ -1,0 +1,411 @@
+// client_batch.hip — the client calls of client.hip for a batch per call: encode + encrypt of up to 64
+// value vectors into one batched handle (public key, or secret key with one seed per instance) and decrypt + decode of up
+// to 64 single ciphertexts read in place.  Instance b is word for word (double for double) what evah_pt_encode ->
+// evah_encrypt / evah_encrypt_symmetric and evah_decrypt_decode give for it: the modular kernels are the single ones with
+// an instance index, and the FP64 special FFT runs the single path's butterflies — same operands, same roots, same
+// rounded operations, no FMA — in another order among independent butterflies only.  No launch count depends on the batch.
+//
+// The FFT (k_fft_tile): a workgroup keeps 2048 complex points in LDS and runs every stage whose butterflies stay inside
+// the tile before it writes.  2048 double2 are 32 KiB: twice that is the whole 64 KiB a kernel may declare statically (no
+// room left for the layout below, one workgroup per 64 KiB), while 2048 points already cover every supported N
+// (2^10 .. 2^17) in two launches — 11 stages in the contiguous pass, the remaining logN - 11 <= 6 in the strided one —
+// and leave room for several workgroups per CU, which a transform of 16 .. 64 tiles per instance needs more than depth.
+//   contiguous pass: tile = 2048 consecutive points, the stages with gap 1 .. 1024
+//   strided pass   : tile = R = N / 2048 rows (row stride 2048 points) by C = 2048 / R consecutive columns, the stages
+//                    with gap 2048 .. N / 2; a row piece is C >= 32 consecutive double2 (512 B), so the accesses coalesce
+// The encoder (Gentleman-Sande, gaps ascending) runs contiguous then strided, the decoder (Cooley-Tukey, gaps descending)
+// strided then contiguous; N <= 2048 is the contiguous pass alone.
+// LDS layout: a double2 fills one of the 16 slots of 16 bytes of a 256-byte bank row, and a ds_read_b128 is served in
+// groups of 16 lanes.  Lane bf of a stage with gap 2^s reads element a = bf with a zero bit inserted at position s, so
+// for s >= 4 the 16 lanes of a group read 16 consecutive elements, which the linear layout already spreads over the 16
+// slots; it is the stages with gap 1 .. 8 that are 2-way in the linear layout, where a and a + 16 fall on one slot.
+// Element e lives at e ^ (e >> 4 & 15) ^ (e >> 8): the slot index is the XOR of the three nibbles of e, which moves
+// a + 16 to another slot and, being a permutation within each aligned run of 16 elements, keeps the stages with s >= 4
+// and the tile's consecutive loads and stores conflict-free.  The XOR stays inside a 256-byte row, so the tile keeps its
+// 32 KiB (the padding of DESIGN.md 4 "LDS layout" without its extra words).  This is counted from the access pattern;
+// the layout has not been timed against the linear one.
+
+#include "launch.hip.h"
+#include "client.hip.h"
+#include "seeded.hip.h"
+
+namespace evah {
+
+constexpr uint32_t FFT_LOG_TILE = 11, FFT_TILE = 1u << FFT_LOG_TILE, FFT_THREADS = 256;
+
+__device__ __forceinline__ uint32_t fft_lds_at(uint32_t e) { return e ^ ((e >> 4) & 15u) ^ (e >> 8); }
+
+// c [batch][N] complex points, instance = blockIdx.y, tile = blockIdx.x; the stages with global gap 2^L for
+// L = L0 .. L0 + n_stages - 1, ascending (ENC) or descending (decoder).  lt = log2 points per tile (logN below one tile).
+// ENC : k_enc_fft_stage's butterfly with root inv_seq[N - 2 (N >> L + 1) + 1 + g]; the stage L = logN - 1 is
+//       k_enc_fft_last's (sum times fix, difference times the pre-scaled root)
+// !ENC: k_dec_fft_stage's butterfly with root roots[(N >> L + 1) + g]
+// g = the butterfly's group in the whole transform = its upper index >> (L + 1).
+template <bool ENC, bool STRIDED>
+__global__ void __launch_bounds__(FFT_THREADS)
+k_fft_tile(double2 *c, const double2 *__restrict__ roots, uint32_t logN, uint32_t lt, uint32_t L0, uint32_t n_stages, double2 scaled_root,
+           double fix) {
+#pragma clang fp contract(off)
+  __shared__ double2 tile[FFT_TILE];
+  const uint32_t N = 1u << logN, T = 1u << lt, tid = threadIdx.x;
+  double2 *x = c + (size_t)blockIdx.y * N;
+  const uint32_t logC = STRIDED ? 2 * FFT_LOG_TILE - logN : 0; // columns per strided tile: 2048 / (N / 2048)
+  auto global_of = [&](uint32_t e) -> uint32_t {
+    if (STRIDED) return ((e >> logC) << FFT_LOG_TILE) + (blockIdx.x << logC) + (e & ((1u << logC) - 1));
+    return (blockIdx.x << lt) + e;
+  };
+  for (uint32_t e = tid; e < T; e += FFT_THREADS) tile[fft_lds_at(e)] = x[global_of(e)];
+  __syncthreads();
+  for (uint32_t s = 0; s < n_stages; s++) {
+    const uint32_t L = ENC ? L0 + s : L0 + n_stages - 1 - s;
+    const uint32_t ll = STRIDED ? L - FFT_LOG_TILE + logC : L, gap = 1u << ll; // the gap inside the tile
+    const uint32_t groups = N >> (L + 1);
+    for (uint32_t bf = tid; bf < (T >> 1); bf += FFT_THREADS) {
+      const uint32_t a = ((bf >> ll) << (ll + 1)) + (bf & (gap - 1)), b = a + gap;
+      const uint32_t g = global_of(a) >> (L + 1);
+      const uint32_t ia = fft_lds_at(a), ib = fft_lds_at(b);
+      const double2 u = tile[ia], v = tile[ib];
+      if (ENC) {
+        if (L + 1 == logN) { // k_enc_fft_last
+          tile[ia] = make_double2((u.x + v.x) * fix, (u.y + v.y) * fix);
+          const double dx = u.x - v.x, dy = u.y - v.y;
+          const double p = dx * scaled_root.x, q = dy * scaled_root.y, sx = dx * scaled_root.y, t = dy * scaled_root.x;
+          tile[ib] = make_double2(p - q, sx + t);
+        } else { // k_enc_fft_stage
+          const double2 r = roots[N - 2 * groups + 1 + g];
+          tile[ia] = make_double2(u.x + v.x, u.y + v.y);
+          const double dx = u.x - v.x, dy = u.y - v.y;
+          const double p = dx * r.x, q = dy * r.y, sx = dx * r.y, t = dy * r.x;
+          tile[ib] = make_double2(p - q, sx + t);
+        }
+      } else { // k_dec_fft_stage
+        const double2 w = roots[groups + g];
+        const double ac = v.x * w.x, bd = v.y * w.y, ad = v.x * w.y, bc = v.y * w.x;
+        const double tx = ac - bd, ty = ad + bc;
+        tile[ia] = make_double2(u.x + tx, u.y + ty);
+        tile[ib] = make_double2(u.x - tx, u.y - ty);
+      }
+    }
+    __syncthreads();
+  }
+  for (uint32_t e = tid; e < T; e += FFT_THREADS) x[global_of(e)] = tile[fft_lds_at(e)];
+}
+
+// the special FFT of `batch` instances in c [batch][N]: one launch for N <= 2048, two above
+template <bool ENC> static void fft_batched(evah_ctx *c, double2 *cd, const double2 *roots, uint32_t batch, double2 scaled_root, double fix) {
+  const uint32_t logN = c->logN;
+  if (logN < 10 || logN > 2 * FFT_LOG_TILE - 5) throw std::invalid_argument("the batched client calls need N from 2^10 to 2^17");
+  const uint32_t lt = std::min(logN, FFT_LOG_TILE), low = lt, high = logN - lt;
+  const dim3 grid(c->N >> lt, batch), block(FFT_THREADS);
+  ProfScope ps(c, KC_EW);
+  if (ENC || !high) hipLaunchKernelGGL((k_fft_tile<ENC, false>), grid, block, 0, c->stream, cd, roots, logN, lt, 0u, low, scaled_root, fix);
+  if (high) hipLaunchKernelGGL((k_fft_tile<ENC, true>), grid, block, 0, c->stream, cd, roots, logN, lt, FFT_LOG_TILE, high, scaled_root, fix);
+  if (!ENC && high) hipLaunchKernelGGL((k_fft_tile<ENC, false>), grid, block, 0, c->stream, cd, roots, logN, lt, 0u, low, scaled_root, fix);
+  HIPCHK(hipGetLastError());
+}
+
+// ---- the encoder's small kernels with an instance index (grid.y)
+__global__ void __launch_bounds__(256)
+k_enc_scatter_b(const double *vals, uint32_t n_vals, const uint32_t *slot_map, double2 *c, uint32_t slots) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= slots) return;
+  const double v = vals[(size_t)blockIdx.y * n_vals + i % n_vals];
+  c += (size_t)blockIdx.y * 2 * slots;
+  c[slot_map[i]] = make_double2(v, 0.0);
+  c[slot_map[slots + i]] = make_double2(v, -0.0); // conjugate of a real value
+}
+__global__ void __launch_bounds__(256)
+k_enc_round_b(DevCtx cx, const double2 *c, uint32_t limbs, u64 *out) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= cx.N) return;
+  const double t = c[(size_t)blockIdx.y * cx.N + j].x;
+  const double x = fabs(t) < 4503599627370496.0 ? round(t) : t; // >= 2^52: already an integer
+  const bool neg = signbit(x);
+  const u64 mant = (u64)fabs(x); // |x| < 2^63 is guaranteed by the caller's bound
+  out += (size_t)blockIdx.y * limbs * cx.N;
+  for (uint32_t i = 0; i < limbs; i++) {
+    const DevPrime pm = cx.primes[cx.prime_of(i)];
+    const u64 r = barrett64(mant, pm.q, pm.brt);
+    out[(size_t)i * cx.N + j] = (neg && r) ? pm.q - r : r;
+  }
+}
+// k_encrypt_zero per instance: grid.z = 2 instance + K; small [batch][3][up][N], c [batch][2][up][N]
+__global__ void __launch_bounds__(256)
+k_encrypt_zero_b(DevCtx cx, const u64 *pk, const u64 *small, uint32_t up, u64 *c) {
+  const size_t n = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t i = blockIdx.y, inst = blockIdx.z >> 1, K = blockIdx.z & 1u;
+  const DevPrime pm = cx.primes[i];
+  small += (size_t)inst * 3 * up * cx.N;
+  const u64 u = small[(size_t)i * cx.N + n], e = small[((size_t)(1 + K) * up + i) * cx.N + n];
+  const u64 p = pk[((size_t)K * cx.k + i) * cx.N + n];
+  c[(((size_t)2 * inst + K) * up + i) * cx.N + n] = addmod(mulmod(p, u, pm), e, pm.q);
+}
+// k_encrypt_symmetric per instance (grid.z): m, en [batch][l][N], ct [batch][2][l][N]; seeds as k_key_expand takes them
+__global__ void __launch_bounds__(256)
+k_encrypt_symmetric_b(DevCtx cx, Seeds8 seeds, const uint32_t *__restrict__ seed_buf, const u64 *m, const u64 *en, const u64 *sk, uint32_t l,
+                      u64 *ct) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y, z = blockIdx.z;
+  if (t >= cx.N / 4 || i >= l) return;
+  const uint32_t prime = cx.prime_of(i);
+  const DevPrime pm = cx.primes[prime];
+  uint32_t key[8];
+  if (seed_buf) {
+#pragma unroll
+    for (int w = 0; w < 8; w++) key[w] = seed_buf[8 * z + w];
+  } else {
+#pragma unroll
+    for (int w = 0; w < 8; w++) key[w] = seeds.w[z][w];
+  }
+  u64 a[4];
+  seeded_block(key, prime, t, pm, a);
+  const size_t row = (size_t)l * cx.N, off = (size_t)i * cx.N + 4 * (size_t)t, in = z * row + off;
+  const u64 *s = sk + (size_t)prime * cx.N + 4 * (size_t)t;
+  const ulonglong2 m01 = ld2(m + in), m23 = ld2(m + in + 2), e01 = ld2(en + in), e23 = ld2(en + in + 2);
+  const ulonglong2 s01 = ld2(s), s23 = ld2(s + 2);
+  const u64 mv[4] = {m01.x, m01.y, m23.x, m23.y}, ev[4] = {e01.x, e01.y, e23.x, e23.y}, sv[4] = {s01.x, s01.y, s23.x, s23.y};
+  u64 b[4];
+#pragma unroll
+  for (int r = 0; r < 4; r++) b[r] = submod(mv[r], addmod(mulmod(a[r], sv[r], pm), ev[r], pm.q), pm.q);
+  u64 *c0 = ct + (size_t)2 * z * row + off, *c1 = c0 + row;
+  st2(c1, make_ulonglong2(a[0], a[1]));
+  st2(c1 + 2, make_ulonglong2(a[2], a[3]));
+  st2(c0, make_ulonglong2(b[0], b[1]));
+  st2(c0 + 2, make_ulonglong2(b[2], b[3]));
+}
+
+// ---- the decryptor's small kernels with an instance index
+// the ciphertexts of a call: separate allocations, possibly views with a polynomial stride of their own
+struct DotTab {
+  const u64 *ct[KS_BATCH_MAX];
+  uint32_t ct_ps[KS_BATCH_MAX]; // poly strides in units of N coefficients
+};
+// m[inst][i] = c0 + c1 s (+ c2 s^2) of ciphertext inst (grid.z)
+__global__ void __launch_bounds__(256)
+k_decrypt_dot_b(DevCtx cx, DotTab tab, uint32_t size, uint32_t l, const u64 *sk, u64 *m) {
+  const size_t n = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t i = blockIdx.y, inst = blockIdx.z;
+  const DevPrime pm = cx.primes[i];
+  const size_t off = (size_t)i * cx.N + n, ps = (size_t)tab.ct_ps[inst] * cx.N;
+  const u64 *ct = tab.ct[inst];
+  const u64 s = sk[off];
+  u64 acc = ct[off], sp = s;
+  for (uint32_t p = 1; p < size; p++) {
+    acc = addmod(acc, mulmod(ct[p * ps + off], sp, pm), pm.q);
+    sp = mulmod(sp, s, pm);
+  }
+  m[(size_t)inst * l * cx.N + off] = acc;
+}
+__global__ void __launch_bounds__(256)
+k_crt_to_double_b(DevCtx cx, CrtTab t, uint32_t l, const u64 *coeff, double inv_scale, double2 *out) {
+  const size_t n = (size_t)blockIdx.x * blockDim.x + threadIdx.x, inst = blockIdx.y;
+  out[inst * cx.N + n] = make_double2(crt_to_double(cx, t, l, coeff + inst * l * cx.N, n, inv_scale), 0.0);
+}
+__global__ void __launch_bounds__(256)
+k_dec_gather_b(const double2 *c, const uint32_t *slot_map, uint32_t n_out, uint32_t N, double *out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n_out) out[(size_t)blockIdx.y * n_out + i] = c[(size_t)blockIdx.y * N + slot_map[i]].x;
+}
+
+// the Garner tables of level l on the device, built once per context family (freed with it)
+static CrtTab crt_tab_cached(evah_ctx *c, uint32_t l) {
+  auto it = c->sh->crt_tabs.find(l);
+  if (it == c->sh->crt_tabs.end()) {
+    const std::vector<u64> tab = crt_tab_build(c, l);
+    u64 *d = nullptr;
+    HIPCHK(hipMalloc(&d, sizeof(u64) * tab.size()));
+    try {
+      h2d_now(c, d, tab.data(), sizeof(u64) * tab.size());
+    } catch (...) {
+      (void)hipFree(d);
+      throw;
+    }
+    it = c->sh->crt_tabs.emplace(l, d).first;
+  }
+  return crt_tab_at(it->second, l);
+}
+
+// queue-ordered zeroing of a pool temporary that held something secret, also when the call fails
+struct Wipe {
+  evah_ctx *c;
+  void *d;
+  size_t bytes;
+  bool done = false;
+  void now() { // the success path: a wipe that fails is an error, as in the single calls
+    done = true;
+    HIPCHK(hipMemsetAsync(d, 0, bytes, c->stream));
+  }
+  ~Wipe() {
+    if (!done) (void)hipMemsetAsync(d, 0, bytes, c->stream);
+  }
+};
+
+// the checks both encryption calls share, in the order evah_pt_encode and the encryptors make them
+static void encode_many_checks(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, evah_ct **out) {
+  if (c->capturing) throw std::logic_error("this call synchronises with the host and cannot be captured into a graph");
+  if (batch < 1 || batch > (uint32_t)KS_BATCH_MAX) throw std::invalid_argument("batch must be 1..64");
+  if (!values) throw std::invalid_argument("value pointer is null");
+  if (!out) throw std::invalid_argument("output pointer is null");
+  if (limbs < 1 || limbs > c->k - 1) throw std::invalid_argument("invalid limb count for this context");
+  const uint32_t slots = c->N >> 1;
+  if (n_values < 1 || n_values > slots || slots % n_values) throw std::invalid_argument("value count must divide the slot count");
+  if (c->N % 256) throw std::invalid_argument("encryption needs N divisible by 256");
+}
+// values [batch][n_values] (host) -> NTT-form plaintexts pt [batch][limbs][N] on the queue; vals, cbuf: the call's scratch
+static void encode_many(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale, u64 *vals,
+                        double2 *cd, u64 *pt) {
+  const uint32_t N = c->N, slots = N >> 1;
+  enc_tables(c);
+  HIPCHK(hipMemcpyAsync(vals, values, sizeof(double) * (size_t)batch * n_values, hipMemcpyHostToDevice, c->stream));
+  EW_LAUNCH(k_enc_scatter_b, dim3((slots + 255) / 256, batch), dim3(256), 0, c->stream, reinterpret_cast<const double *>(vals), n_values,
+            c->sh->enc_slot_map, cd, slots);
+  const double fix = scale / (double)N;
+  fft_batched<true>(c, cd, c->sh->enc_roots, batch, make_double2(c->sh->enc_last_root[0] * fix, c->sh->enc_last_root[1] * fix), fix);
+  EW_LAUNCH(k_enc_round_b, dim3((N + 255) / 256, batch), dim3(256), 0, c->stream, c->dev, cd, limbs, pt);
+  HIPCHK(hipGetLastError());
+  OpPlain::Params p{pt, pt, (size_t)limbs * N, (size_t)limbs * N, limbs, 0, 0, {}};
+  ntt_forward<OpPlain>(c, p, batch * limbs);
+}
+
+} // namespace evah
+
+extern "C" {
+
+int evah_encode_encrypt_many(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale,
+                             const int8_t *small, evah_ct **out) {
+  API_BEGIN
+  use(c);
+  encode_many_checks(c, batch, values, n_values, limbs, out);
+  if (!small) throw std::invalid_argument("randomness pointer is null");
+  if (!c->sh->pk.d) throw std::invalid_argument("public key not present");
+  const uint32_t l = limbs, up = l + 1;
+  if (up > c->k) throw std::invalid_argument("plaintext level is not valid for encryption");
+  const size_t N = c->N, B = batch;
+  Scratch vals(c, B * n_values), cbuf(c, B * 2 * N), pt(c, B * l * N), sm8(c, (3 * B * N + 7) / 8), sm(c, 3 * B * up * N),
+      ct(c, 2 * B * up * N), r(c, 2 * B * N);
+  evah_ct *o = ct_new(c, 2, l, scale, batch);
+  try {
+    encode_many(c, batch, values, n_values, l, scale, vals.d, reinterpret_cast<double2 *>(cbuf.d), pt.d);
+    HIPCHK(hipMemcpyAsync(sm8.d, small, 3 * B * N, hipMemcpyHostToDevice, c->stream));
+    small_to_ntt(c, sm8.d, 3 * batch, up, sm.d);
+    EW_LAUNCH(k_encrypt_zero_b, dim3(c->N / 256, up, 2 * batch), dim3(256), 0, c->stream, c->dev, c->sh->pk.d, sm.d, up, ct.d);
+    HIPCHK(hipGetLastError());
+    // divide and round by prime `l` (the last of the up primes), then add instance b's plaintext to its c0
+    OpPlain::Params ip{ct.d + (size_t)l * N, r.d, (size_t)up * N, N, 1, l, 1, {}};
+    ntt_inverse<OpPlain>(c, ip, 2 * batch);
+    OpModDown::Params mp{r.d, N, ct.d, (size_t)up * N, nullptr, 0, 0, o->d, o->ps, l, l};
+    mp.use_add_tab = true;
+    for (uint32_t b = 0; b < batch; b++) mp.add_tab.p[2 * b] = pt.d + b * l * N;
+    ntt_forward<OpModDown>(c, mp, 2 * batch * l);
+    HIPCHK(hipStreamSynchronize(c->stream)); // `values` and `small` are pageable host memory
+  } catch (...) {
+    (void)hipStreamSynchronize(c->stream);
+    evah_ct_free(c, o);
+    throw;
+  }
+  *out = o;
+  API_END
+}
+
+int evah_encode_encrypt_symmetric_many(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale,
+                                       const int8_t *e, const uint8_t *seeds, evah_ct **out) {
+  API_BEGIN
+  use(c);
+  encode_many_checks(c, batch, values, n_values, limbs, out);
+  if (!c->sh->sk.d) throw std::invalid_argument("secret key not present");
+  if (!e || !seeds) throw std::invalid_argument("error polynomial and seed are required");
+  const uint32_t l = limbs;
+  const size_t N = c->N, B = batch;
+  Scratch vals(c, B * n_values), cbuf(c, B * 2 * N), pt(c, B * l * N), e8(c, (B * N + 7) / 8), en(c, B * l * N);
+  std::unique_ptr<Scratch> seed_dev; // more than 8 instances: the seeds as a device buffer, returned to the pool after the drain
+  evah_ct *o = ct_new(c, 2, l, scale, batch);
+  try {
+    // the errors do not stay behind in pool memory the next call reuses
+    Wipe w_en{c, en.d, sizeof(u64) * B * l * N}, w_e8{c, e8.d, B * N};
+    encode_many(c, batch, values, n_values, l, scale, vals.d, reinterpret_cast<double2 *>(cbuf.d), pt.d);
+    HIPCHK(hipMemcpyAsync(e8.d, e, B * N, hipMemcpyHostToDevice, c->stream));
+    small_to_ntt(c, e8.d, batch, l, en.d);
+    Seeds8 s8;
+    std::memset(&s8, 0, sizeof s8);
+    const uint32_t *seed_buf = nullptr;
+    if (batch <= SEEDS_PER_LAUNCH) {
+      std::memcpy(s8.w, seeds, (size_t)32 * batch); // little-endian key words, as the host generator reads its key
+    } else {
+      seed_dev = std::make_unique<Scratch>(c, (size_t)4 * batch);
+      HIPCHK(hipMemcpyAsync(seed_dev->d, seeds, (size_t)32 * batch, hipMemcpyHostToDevice, c->stream));
+      seed_buf = reinterpret_cast<const uint32_t *>(seed_dev->d);
+    }
+    EW_LAUNCH(k_encrypt_symmetric_b, seeded_grid(c, l, batch), dim3(256), 0, c->stream, c->dev, s8, seed_buf, pt.d, en.d, c->sh->sk.d, l, o->d);
+    HIPCHK(hipGetLastError());
+    w_en.now();
+    w_e8.now();
+  } catch (...) {
+    (void)hipStreamSynchronize(c->stream);
+    evah_ct_free(c, o);
+    throw;
+  }
+  try {
+    HIPCHK(hipStreamSynchronize(c->stream)); // `values`, `e` and `seeds` are pageable host memory
+  } catch (...) {
+    evah_ct_free(c, o);
+    throw;
+  }
+  *out = o;
+  API_END
+}
+
+int evah_decrypt_decode_many(evah_ctx *c, const evah_ct *const *cts, uint32_t n, uint32_t n_out, double *out) {
+  API_BEGIN
+  use(c);
+  if (c->capturing) throw std::logic_error("this call synchronises with the host and cannot be captured into a graph");
+  if (!c->sh->sk.d) throw std::invalid_argument("secret key not present");
+  if (n < 1 || n > (uint32_t)KS_BATCH_MAX) throw std::invalid_argument("batch must be 1..64");
+  if (!cts || !out) throw std::invalid_argument("ciphertext list and output are required");
+  const uint32_t N = c->N, slots = N >> 1;
+  for (uint32_t i = 0; i < n; i++) {
+    const std::string at = "ciphertext " + std::to_string(i);
+    if (!cts[i]) throw std::invalid_argument(at + " is null");
+    if (cts[i]->batch != 1) throw std::invalid_argument(at + ": decrypt takes a single ciphertext");
+    if (cts[i]->size != cts[0]->size) throw std::invalid_argument(at + ": size differs from ciphertext 0");
+    if (cts[i]->limbs != cts[0]->limbs) throw std::invalid_argument(at + ": limb count differs from ciphertext 0");
+    if (cts[i]->scale != cts[0]->scale) throw std::invalid_argument(at + ": scale differs from ciphertext 0");
+  }
+  const uint32_t l = cts[0]->limbs, size = cts[0]->size;
+  if (size < 1 || size > 3) throw std::invalid_argument("ciphertext size out of range");
+  if (n_out < 1 || n_out > slots) throw std::invalid_argument("slot count out of range");
+  if (l > 61) throw std::invalid_argument("too many limbs");
+  if (N % 256) throw std::invalid_argument("decryption needs N divisible by 256");
+  check_scale(c, cts[0]->scale, l); // decode_internal: "scale out of bounds"
+  enc_tables(c);
+  dec_tables(c);
+  const CrtTab t = crt_tab_cached(c, l);
+  DotTab tab{};
+  for (uint32_t i = 0; i < n; i++) {
+    acquire(c, cts[i]->buf);
+    tab.ct[i] = cts[i]->d;
+    tab.ct_ps[i] = (uint32_t)(cts[i]->ps / N);
+  }
+  const size_t B = n;
+  Scratch m(c, B * l * N), cbuf(c, B * 2 * N), outd(c, B * n_out);
+  {
+    // the decrypted messages, their FP images and the slot values do not stay behind in pool memory the next call reuses
+    Wipe w_m{c, m.d, sizeof(u64) * B * l * N}, w_c{c, cbuf.d, sizeof(double2) * B * N}, w_o{c, outd.d, sizeof(double) * B * n_out};
+    EW_LAUNCH(k_decrypt_dot_b, dim3(N / 256, l, n), dim3(256), 0, c->stream, c->dev, tab, size, l, c->sh->sk.d, m.d);
+    OpPlain::Params ip{m.d, m.d, (size_t)l * N, (size_t)l * N, l, 0, 0, {}};
+    ntt_inverse<OpPlain>(c, ip, n * l);
+    double2 *cd = reinterpret_cast<double2 *>(cbuf.d);
+    EW_LAUNCH(k_crt_to_double_b, dim3(N / 256, n), dim3(256), 0, c->stream, c->dev, t, l, m.d, 1.0 / cts[0]->scale, cd);
+    HIPCHK(hipGetLastError());
+    fft_batched<false>(c, cd, c->sh->dec_roots, n, make_double2(0.0, 0.0), 0.0);
+    EW_LAUNCH(k_dec_gather_b, dim3((n_out + 255) / 256, n), dim3(256), 0, c->stream, cd, c->sh->enc_slot_map, n_out, N,
+              reinterpret_cast<double *>(outd.d));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, outd.d, sizeof(double) * B * n_out, hipMemcpyDeviceToHost, c->stream));
+    w_m.now();
+    w_c.now();
+    w_o.now();
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  API_END
+}
+
+} // extern "C"

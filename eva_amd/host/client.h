@@ -5,6 +5,21 @@
 
 namespace evahost {
 
+// instances per batched client call (KS_BATCH_MAX of the library)
+constexpr size_t CLIENT_BATCH_MAX = 64;
+// the sorted input names of a batch: every instance must name exactly the inputs of instance 0
+inline std::vector<std::string> batch_input_names(const std::vector<Valuation> &inputs) {
+  std::vector<std::string> names;
+  for (auto &kv : inputs[0]) names.push_back(kv.first);
+  std::sort(names.begin(), names.end());
+  for (size_t b = 1; b < inputs.size(); b++) {
+    bool same = inputs[b].size() == names.size();
+    for (size_t i = 0; same && i < names.size(); i++) same = inputs[b].count(names[i]) != 0;
+    if (!same) throw std::runtime_error("instance " + std::to_string(b) + ": input names differ from those of instance 0");
+  }
+  return names;
+}
+
 // SEALPublic::encrypt (seal.cpp:24-102)
 inline HipValuation HipPublic::encrypt(const Valuation &inputs, const CKKSSignature &sig) {
   const size_t slots = host->N / 2;
@@ -116,6 +131,99 @@ inline HostCipher HipPublic::encrypt_on_device(const HostPlain *coeff_pt, const 
   out.data.resize((size_t)2 * out.limbs * N);
   out.words_checked = true;
   chk(evah_ct_download(dev->h, c, (uint64_t *)out.data.data()));
+  return out;
+}
+
+// encrypt() for a list of input valuations of one signature.  Per input name the instances leave in
+// groups of <= 64 as ONE evah_encode_encrypt_many each — a launch set whose length does not depend on the group — and
+// come back as views of the group's handle (evah_ct_unstack).  A name with an instance the device encoder cannot take,
+// plain and raw inputs, and every input without a device take encrypt()'s path per instance.
+inline std::vector<HipValuation> HipPublic::encrypt_batch(const std::vector<Valuation> &inputs, const CKKSSignature &sig) {
+  const size_t slots = host->N / 2;
+  if (sig.vec_size <= 0) throw std::runtime_error("Signature vector size must be positive");
+  if (slots < (size_t)sig.vec_size) throw std::runtime_error("Vector size cannot be larger than slot count");
+  if (slots % sig.vec_size) throw std::runtime_error("Vector size must exactly divide the slot count");
+  std::vector<HipValuation> out(inputs.size());
+  if (inputs.empty()) return out;
+  const std::vector<std::string> names = batch_input_names(inputs);
+  SecureRng rng; // one fresh ChaCha20 stream keyed from the OS for the whole call
+  for (const std::string &name : names) {
+    auto it = sig.inputs.find(name);
+    if (it == sig.inputs.end()) throw std::out_of_range("No input named " + name + " in the signature");
+    const CKKSEncodingInfo &info = it->second;
+    bool grouped = info.input_type == Type::Cipher && client_on_device();
+    uint32_t limbs = 0;
+    double scale = 0;
+    if (grouped) {
+      if ((uint32_t)info.level >= host->k - 1) throw std::runtime_error("Input level exceeds the modulus chain");
+      limbs = host->k - 1 - (uint32_t)info.level;
+      scale = std::pow(2.0, (double)info.scale);
+    }
+    for (size_t b = 0; b < inputs.size(); b++) {
+      const auto &v = inputs[b].at(name);
+      if (v.size() != (size_t)sig.vec_size) throw std::runtime_error("Input size does not match program vector size");
+      if (grouped && !device_encodable(v, scale, limbs)) grouped = false;
+    }
+    if (!grouped) { // encrypt()'s path, instance by instance
+      for (size_t b = 0; b < inputs.size(); b++) {
+        HipValuation one = encrypt(Valuation{{name, inputs[b].at(name)}}, sig);
+        out[b].values[name] = std::move(one.values.at(name));
+      }
+      continue;
+    }
+    for (size_t b0 = 0; b0 < inputs.size(); b0 += CLIENT_BATCH_MAX) {
+      const size_t n = std::min<size_t>(CLIENT_BATCH_MAX, inputs.size() - b0);
+      std::vector<const std::vector<double> *> vals(n);
+      for (size_t b = 0; b < n; b++) vals[b] = &inputs[b0 + b].at(name);
+      std::vector<HostCipher> cts = encrypt_group_on_device(vals, scale, limbs, rng);
+      for (size_t b = 0; b < n; b++) out[b0 + b].values[name] = std::move(cts[b]);
+    }
+  }
+  return out;
+}
+
+// one group of encrypt_batch: the sampler calls of encrypt_on_device per instance, in list order, then one device call
+inline std::vector<HostCipher> HipPublic::encrypt_group_on_device(const std::vector<const std::vector<double> *> &vals, double scale,
+                                                                  uint32_t limbs, SecureRng &rng) {
+  ensure_device(false);
+  if (!pk_uploaded) {
+    chk(evah_client_key_upload(dev->h, EVAH_KEY_PUBLIC, (const uint64_t *)pk.data.data()));
+    pk_uploaded = true;
+  }
+  const uint32_t N = host->N;
+  const size_t B = vals.size(), nv = vals[0]->size();
+  std::vector<double> flat(B * nv);
+  std::vector<int8_t> u, e0, e1, small(B * 3 * N);
+  for (size_t b = 0; b < B; b++) {
+    std::copy(vals[b]->begin(), vals[b]->end(), flat.begin() + b * nv);
+    host->sample_ternary(rng, u);
+    host->sample_error(rng, e0);
+    host->sample_error(rng, e1);
+    std::copy(u.begin(), u.end(), small.begin() + (3 * b) * N);
+    std::copy(e0.begin(), e0.end(), small.begin() + (3 * b + 1) * N);
+    std::copy(e1.begin(), e1.end(), small.begin() + (3 * b + 2) * N);
+  }
+  evah_ct *c = nullptr;
+  const int rc = evah_encode_encrypt_many(dev->h, (uint32_t)B, flat.data(), (uint32_t)nv, limbs, scale, small.data(), &c);
+  wipe(u); wipe(e0); wipe(e1); wipe(small);
+  chk(rc);
+  CtHandle group(dev->h, c); // the instances share its allocation, which lives until the last view is freed
+  std::vector<HostCipher> out(B);
+  for (size_t b = 0; b < B; b++) {
+    evah_ct *view = nullptr;
+    chk(evah_ct_unstack(dev->h, c, (uint32_t)b, &view));
+    auto handle = std::make_shared<CtHandle>(dev->h, view);
+    out[b].size = 2;
+    out[b].limbs = limbs;
+    out[b].scale = scale;
+    if (resident) { // stays in HBM; host words on demand
+      out[b].dev = std::make_shared<DeviceResident>(DeviceResident{dev, nullptr, handle, host->N});
+      continue;
+    }
+    out[b].data.resize((size_t)2 * limbs * N);
+    out[b].words_checked = true;
+    chk(evah_ct_download(dev->h, view, (uint64_t *)out[b].data.data()));
+  }
   return out;
 }
 
@@ -247,41 +355,226 @@ public:
     out.seeded = std::move(sf);
     return out;
   }
+  // encrypt() for a list of input valuations of one signature.  ONE pair of streams for the call;
+  // instances are visited in list order, the names sorted within an instance, and every encrypted input takes 4 seed words
+  // and one sample_error — so instance 0 of a seeded call is encrypt() of that instance word for word and no two values
+  // share a seed.  The draws made, each name's instances leave in groups of <= 64 as one
+  // evah_encode_encrypt_symmetric_many (views of the group's handle come back); a name with an instance the device
+  // encoder cannot take, and every input without a device, takes encrypt()'s path per instance with the same draws.
+  std::vector<HipValuation> encrypt_batch(const std::vector<Valuation> &inputs, const CKKSSignature &sig, uint64_t seed = 0) {
+    const size_t slots = host->N / 2;
+    if (sig.vec_size <= 0) throw std::runtime_error("Signature vector size must be positive");
+    if (slots < (size_t)sig.vec_size) throw std::runtime_error("Vector size cannot be larger than slot count");
+    if (slots % sig.vec_size) throw std::runtime_error("Vector size must exactly divide the slot count");
+    std::vector<HipValuation> out(inputs.size());
+    if (inputs.empty()) return out;
+    const std::vector<std::string> names = batch_input_names(inputs);
+    std::unique_ptr<SecureRng> seeds = seed ? std::make_unique<SecureRng>(seed, 4) : std::make_unique<SecureRng>();
+    std::unique_ptr<SecureRng> errors = seed ? std::make_unique<SecureRng>(seed, 3) : std::make_unique<SecureRng>();
+    struct Drawn {
+      std::vector<std::vector<int8_t>> e;          // per instance
+      std::vector<std::array<uint8_t, 32>> sd;
+      uint32_t limbs = 0;
+      double scale = 0;
+    };
+    std::vector<Drawn> drawn(names.size());
+    struct WipeAll {
+      std::vector<Drawn> &d;
+      ~WipeAll() { for (auto &x : d) for (auto &e : x.e) wipe(e); }
+    } wipe_all{drawn};
+    for (size_t b = 0; b < inputs.size(); b++) {
+      for (size_t i = 0; i < names.size(); i++) {
+        const std::string &name = names[i];
+        const auto &v = inputs[b].at(name);
+        if (v.size() != (size_t)sig.vec_size) throw std::runtime_error("Input size does not match program vector size");
+        auto it = sig.inputs.find(name);
+        if (it == sig.inputs.end()) throw std::out_of_range("No input named " + name + " in the signature");
+        const CKKSEncodingInfo &info = it->second;
+        if (info.input_type != Type::Cipher && info.input_type != Type::Plain) {
+          out[b].values[name] = v;
+          continue;
+        }
+        if ((uint32_t)info.level >= host->k - 1) throw std::runtime_error("Input level exceeds the modulus chain");
+        const uint32_t limbs = host->k - 1 - (uint32_t)info.level;
+        const double scale = std::pow(2.0, (double)info.scale);
+        if (info.input_type == Type::Plain) {
+          HostPlain pt = encode_host(v, scale, limbs);
+          for (uint32_t j = 0; j < limbs; j++) host->ntt(j, pt.data.data() + (size_t)j * host->N);
+          out[b].values[name] = std::move(pt);
+          continue;
+        }
+        Drawn &d = drawn[i];
+        d.limbs = limbs;
+        d.scale = scale;
+        d.sd.emplace_back();
+        for (int w = 0; w < 4; w++) {
+          const uint64_t x = (*seeds)();
+          std::memcpy(d.sd.back().data() + 8 * w, &x, 8);
+        }
+        d.e.emplace_back();
+        host->sample_error(*errors, d.e.back());
+      }
+    }
+    for (size_t i = 0; i < names.size(); i++) {
+      const std::string &name = names[i];
+      const Drawn &d = drawn[i];
+      if (d.e.empty()) continue; // a plain or raw input: done above
+      bool grouped = on_device();
+      for (size_t b = 0; grouped && b < inputs.size(); b++) grouped = device_encodable(*host, inputs[b].at(name), d.scale, d.limbs);
+      if (!grouped) { // encrypt()'s path, instance by instance
+        for (size_t b = 0; b < inputs.size(); b++) {
+          const auto &v = inputs[b].at(name);
+          if (on_device()) {
+            out[b].values[name] = encrypt_on_device(v, d.scale, d.limbs, d.e[b], d.sd[b]);
+          } else {
+            HostPlain pt = encode_host(v, d.scale, d.limbs);
+            for (uint32_t j = 0; j < d.limbs; j++) host->ntt(j, pt.data.data() + (size_t)j * host->N);
+            out[b].values[name] = encrypt_symmetric(*host, sk, pt, d.e[b], d.sd[b]);
+          }
+        }
+        continue;
+      }
+      for (size_t b0 = 0; b0 < inputs.size(); b0 += CLIENT_BATCH_MAX) {
+        const size_t n = std::min<size_t>(CLIENT_BATCH_MAX, inputs.size() - b0);
+        std::vector<const std::vector<double> *> vals(n);
+        for (size_t b = 0; b < n; b++) vals[b] = &inputs[b0 + b].at(name);
+        std::vector<HostCipher> cts = encrypt_group_on_device(vals, d.scale, d.limbs, d.e.data() + b0, d.sd.data() + b0);
+        for (size_t b = 0; b < n; b++) out[b0 + b].values[name] = std::move(cts[b]);
+      }
+    }
+    return out;
+  }
+  // one group of encrypt_batch on the device: instance b from (vals[b], e[b], sd[b]); the values encrypt_on_device returns
+  std::vector<HostCipher> encrypt_group_on_device(const std::vector<const std::vector<double> *> &vals, double scale, uint32_t limbs,
+                                                  const std::vector<int8_t> *e, const std::array<uint8_t, 32> *sd) {
+    const uint32_t N = host->N;
+    const size_t B = vals.size(), nv = vals[0]->size();
+    std::vector<double> flat(B * nv);
+    std::vector<int8_t> errs(B * N);
+    std::vector<uint8_t> seeds(B * 32);
+    for (size_t b = 0; b < B; b++) {
+      std::copy(vals[b]->begin(), vals[b]->end(), flat.begin() + b * nv);
+      std::copy(e[b].begin(), e[b].end(), errs.begin() + b * N);
+      std::copy(sd[b].begin(), sd[b].end(), seeds.begin() + b * 32);
+    }
+    evah_ct *c = nullptr;
+    const int rc = evah_encode_encrypt_symmetric_many(dev->h, (uint32_t)B, flat.data(), (uint32_t)nv, limbs, scale, errs.data(), seeds.data(), &c);
+    wipe(errs);
+    chk(rc);
+    CtHandle group(dev->h, c); // the instances share its allocation, which lives until the last view is freed
+    std::vector<HostCipher> out(B);
+    for (size_t b = 0; b < B; b++) {
+      evah_ct *view = nullptr;
+      chk(evah_ct_unstack(dev->h, c, (uint32_t)b, &view));
+      auto handle = std::make_shared<CtHandle>(dev->h, view);
+      auto sf = std::make_shared<SeededForm>();
+      sf->seed = sd[b];
+      sf->N = N;
+      sf->primes.assign(host->primes.begin(), host->primes.begin() + limbs);
+      out[b].size = 2;
+      out[b].limbs = limbs;
+      out[b].scale = scale;
+      out[b].words_checked = true;
+      if (resident) { // stays in HBM; the seed stays with it, so that save() can still write the value compressed
+        out[b].dev = std::make_shared<DeviceResident>(DeviceResident{dev, nullptr, handle, N});
+        out[b].seeded = std::move(sf);
+        continue;
+      }
+      sf->c0.resize((size_t)limbs * N); // only c0 crosses PCIe: c1 is the seed's
+      chk(evah_ct_download_poly(dev->h, view, 0, (uint64_t *)sf->c0.data()));
+      out[b].seeded = std::move(sf);
+    }
+    return out;
+  }
+  // the shape check of a ciphertext that is decrypted on the device
+  void check_device_shape(const std::string &name, const HostCipher &c) const {
+    if (c.size < 1 || c.size > 3 || c.limbs < 1 || c.limbs > host->k - 1 ||
+        (!resident_only(c) && words(c).size() != (size_t)c.size * c.limbs * host->N) || (c.dev && c.dev->N != host->N))
+      throw std::runtime_error("output " + name + ": ciphertext shape does not match its data or the encryption parameters");
+  }
+  // one value of decrypt()
+  std::vector<double> decrypt_value(const std::string &name, const SchemeValue &value, const CKKSSignature &sig) {
+    std::vector<double> v;
+    if (auto *c = std::get_if<HostCipher>(&value)) {
+      if (on_device()) { // dot product with s, inverse transforms, recomposition and the special FFT on the GPU
+        check_device_shape(name, *c);
+        v.resize((size_t)sig.vec_size);
+        if (c->dev && c->dev->root == dev) { // resident on this key pair's device state: read in place
+          chk(evah_decrypt_decode(dev->h, c->dev->h->h, (uint32_t)sig.vec_size, v.data()));
+        } else {
+          evah_ct *h = nullptr;
+          chk(evah_ct_upload(dev->h, c->size, c->limbs, c->scale, (const uint64_t *)words(*c).data(), &h));
+          int rc = evah_decrypt_decode(dev->h, h, (uint32_t)sig.vec_size, v.data());
+          evah_ct_free(dev->h, h);
+          chk(rc);
+        }
+        return v;
+      }
+      (void)words(*c);
+      auto m = decrypt_to_coeff(*host, sk, *c);
+      host->decode_coeff(m.data(), c->limbs, c->scale, v);
+    } else if (auto *p = std::get_if<HostPlain>(&value)) {
+      std::vector<u64> m = p->data;
+      for (uint32_t i = 0; i < p->limbs; i++) host->intt(i, m.data() + (size_t)i * host->N);
+      host->decode_coeff(m.data(), p->limbs, p->scale, v);
+    } else {
+      ConstantValue{std::get<std::vector<double>>(value)}.expand_to(v, (size_t)sig.vec_size);
+    }
+    v.resize((size_t)sig.vec_size);
+    return v;
+  }
   // SEALSecret::decrypt (seal.cpp:124-146)
   Valuation decrypt(const HipValuation &enc, const CKKSSignature &sig) {
     Valuation out;
-    for (auto &kv : enc.values) {
-      std::vector<double> v;
-      if (auto *c = std::get_if<HostCipher>(&kv.second)) {
-        if (on_device()) { // dot product with s, inverse transforms, recomposition and the special FFT on the GPU
-          if (c->size < 1 || c->size > 3 || c->limbs < 1 || c->limbs > host->k - 1 ||
-              (!resident_only(*c) && words(*c).size() != (size_t)c->size * c->limbs * host->N) || (c->dev && c->dev->N != host->N))
-            throw std::runtime_error("output " + kv.first + ": ciphertext shape does not match its data or the encryption parameters");
-          v.resize((size_t)sig.vec_size);
-          if (c->dev && c->dev->root == dev) { // resident on this key pair's device state: read in place
-            chk(evah_decrypt_decode(dev->h, c->dev->h->h, (uint32_t)sig.vec_size, v.data()));
+    for (auto &kv : enc.values) out[kv.first] = decrypt_value(kv.first, kv.second, sig);
+    return out;
+  }
+  // decrypt() of every valuation of a list, bit for bit.  On the device, per output name, runs of
+  // instances of one size, limb count and scale leave in groups of <= 64 as ONE evah_decrypt_decode_many each: resident
+  // values are read in place, the others uploaded first, as decrypt() does.  Everything else is decrypt() per value.
+  std::vector<Valuation> decrypt_batch(const std::vector<const HipValuation *> &encs, const CKKSSignature &sig) {
+    std::vector<Valuation> out(encs.size());
+    for (size_t b = 0; b < encs.size(); b++)
+      if (!encs[b]) throw std::invalid_argument("decrypt_batch: valuation " + std::to_string(b) + " is None");
+    if (!on_device() || sig.vec_size <= 0) {
+      for (size_t b = 0; b < encs.size(); b++) out[b] = decrypt(*encs[b], sig);
+      return out;
+    }
+    std::map<std::string, std::vector<std::pair<size_t, const HostCipher *>>> by_name; // name -> (instance, ciphertext) in list order
+    for (size_t b = 0; b < encs.size(); b++)
+      for (auto &kv : encs[b]->values) {
+        if (auto *c = std::get_if<HostCipher>(&kv.second)) by_name[kv.first].emplace_back(b, c);
+        else out[b][kv.first] = decrypt_value(kv.first, kv.second, sig);
+      }
+    const uint32_t n_out = (uint32_t)sig.vec_size;
+    for (auto &nv : by_name) {
+      const auto &list = nv.second;
+      for (size_t i0 = 0; i0 < list.size();) {
+        const HostCipher *first = list[i0].second;
+        size_t i1 = i0;
+        std::vector<CtHandle> uploaded; // the group's values that were not resident here
+        std::vector<const evah_ct *> hs;
+        while (i1 < list.size() && i1 - i0 < CLIENT_BATCH_MAX) {
+          const HostCipher *c = list[i1].second;
+          if (c->size != first->size || c->limbs != first->limbs || c->scale != first->scale) break;
+          check_device_shape(nv.first, *c);
+          if (c->dev && c->dev->root == dev) {
+            hs.push_back(c->dev->h->h);
           } else {
             evah_ct *h = nullptr;
             chk(evah_ct_upload(dev->h, c->size, c->limbs, c->scale, (const uint64_t *)words(*c).data(), &h));
-            int rc = evah_decrypt_decode(dev->h, h, (uint32_t)sig.vec_size, v.data());
-            evah_ct_free(dev->h, h);
-            chk(rc);
+            uploaded.emplace_back(dev->h, h);
+            hs.push_back(h);
           }
-          out[kv.first] = std::move(v);
-          continue;
+          i1++;
         }
-        (void)words(*c);
-        auto m = decrypt_to_coeff(*host, sk, *c);
-        host->decode_coeff(m.data(), c->limbs, c->scale, v);
-      } else if (auto *p = std::get_if<HostPlain>(&kv.second)) {
-        std::vector<u64> m = p->data;
-        for (uint32_t i = 0; i < p->limbs; i++) host->intt(i, m.data() + (size_t)i * host->N);
-        host->decode_coeff(m.data(), p->limbs, p->scale, v);
-      } else {
-        ConstantValue{std::get<std::vector<double>>(kv.second)}.expand_to(v, (size_t)sig.vec_size);
+        std::vector<double> flat(hs.size() * n_out);
+        chk(evah_decrypt_decode_many(dev->h, hs.data(), (uint32_t)hs.size(), n_out, flat.data()));
+        for (size_t i = i0; i < i1; i++)
+          out[list[i].first][nv.first].assign(flat.begin() + (i - i0) * n_out, flat.begin() + (i - i0 + 1) * n_out);
+        std::fill(flat.begin(), flat.end(), 0.0);
+        i0 = i1;
       }
-      v.resize((size_t)sig.vec_size);
-      out[kv.first] = std::move(v);
     }
     return out;
   }

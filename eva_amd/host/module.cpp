@@ -334,6 +334,12 @@ PYBIND11_MODULE(_eva, m) {
         v.params = p.host;
         return v;
       }, py::arg("inputs"), py::arg("signature"))
+      .def("encrypt_batch", [](HipPublic &p, const std::vector<Valuation> &inputs, const CKKSSignature &sig) {
+        std::vector<HipValuation> out = p.encrypt_batch(inputs, sig);
+        for (HipValuation &v : out) v.params = p.host;
+        return out;
+      }, py::arg("inputs"), py::arg("signature"),
+           "encrypt() for a list of input valuations with the same input names; per name the instances are encoded and encrypted 64 at a time in one device call")
       .def("execute", [](HipPublic &p, Program &program, const HipValuation &inputs) {
         HipValuation v = p.execute(program, inputs);
         v.params = p.host;
@@ -459,7 +465,16 @@ PYBIND11_MODULE(_eva, m) {
       }, py::arg("inputs"), py::arg("signature"), py::arg("seed") = 0,
          "Secret-key encryption: every ciphertext is c0 plus the 32-byte seed of c1 (half the bytes of SEALPublic.encrypt). "
          "seed != 0: reproducible test streams, not secret-grade")
+      .def("encrypt_batch", [](HipSecret &s, const std::vector<Valuation> &inputs, const CKKSSignature &sig, uint64_t seed) {
+        std::vector<HipValuation> out = s.encrypt_batch(inputs, sig, seed);
+        for (HipValuation &v : out) v.params = s.host;
+        return out;
+      }, py::arg("inputs"), py::arg("signature"), py::arg("seed") = 0,
+         "encrypt() for a list of input valuations with the same input names: one pair of random streams for the call, instances in list "
+         "order and names sorted within an instance, so instance 0 of a seeded call equals encrypt() and no two values share a seed")
       .def("decrypt", &HipSecret::decrypt, py::arg("enc_outputs"), py::arg("signature"))
+      .def("decrypt_batch", &HipSecret::decrypt_batch, py::arg("enc_outputs"), py::arg("signature"),
+           "decrypt() of every valuation of a list, bit for bit; on the device up to 64 outputs of one name are decrypted and decoded in one call")
       .def_readwrite("device", &HipSecret::device, "device of the secret half's state when it is not shared with a public context")
       // test hook (as relin_key() on the public side): the secret key under every key prime, NTT form [k][N]
       .def("_secret_key_ntt", [](const HipSecret &s) { return to_numpy(s.sk.s_ntt, {(py::ssize_t)s.host->k, (py::ssize_t)s.host->N}); });

@@ -84,6 +84,8 @@ public:
 
   // SEALPublic::encrypt (seal.cpp:24-102)
   HipValuation encrypt(const Valuation &inputs, const CKKSSignature &sig);
+  // encrypt() of every valuation of a list, the device work batched per input name (client.h)
+  std::vector<HipValuation> encrypt_batch(const std::vector<Valuation> &inputs, const CKKSSignature &sig);
 
   // SEALPublic::execute (seal.cpp:104-122) — THE hot path.  First call for a program: upload
   // inputs, walk the DAG issuing HIP work over the queues, download outputs.  From the second call
@@ -504,6 +506,9 @@ private:
   bool device_encodable(const std::vector<double> &in, double scale, uint32_t limbs) const;
   // coeff_pt: the host encoder's coefficient-form plaintext, or (null) values: the slot values for the device encoder
   HostCipher encrypt_on_device(const HostPlain *coeff_pt, const std::vector<double> *values, double scale, uint32_t limbs, SecureRng &rng);
+  // <= 64 instances of one input as one evah_encode_encrypt_many; the values encrypt_on_device would return
+  std::vector<HostCipher> encrypt_group_on_device(const std::vector<const std::vector<double> *> &vals, double scale, uint32_t limbs,
+                                                  SecureRng &rng);
 
   // eval_keys = false: encryption and limb-sharded execution (whose shards hold their own rows of the
   // keys) do not need the whole evaluation keys in this device's memory

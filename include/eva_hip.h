@@ -328,6 +328,23 @@ int evah_ct_write_seeded(evah_ctx *ctx, evah_ct *ct, const uint64_t *c0, const u
 /* polynomial `poly` of a single ciphertext -> out [limbs][N] (c0 of a seeded value: its c1 is the seed's) */
 int evah_ct_download_poly(evah_ctx *ctx, const evah_ct *ct, uint32_t poly, uint64_t *out);
 
+/* ---- the client calls for a batch per call: what a loop of SEALPublic::encrypt (seal.cpp:24-102:
+ * encoder.encode + encryptor.encrypt per input) and of SEALSecret::decrypt (seal.cpp:124-146: decryptor.decrypt +
+ * encoder.decode per output) does for the instances of evah_execute's batches, as one launch set whose length does not
+ * depend on the batch.  1 <= batch, n <= 64.  One host->device copy per input array, one device->host copy of the
+ * result and one drain of ctx's queue per call; the plaintexts exist only in pool scratch. */
+/* instance b = evah_pt_encode(values[b]) -> evah_encrypt(small[b]) word for word (seal.cpp:24-102); values
+ * [batch][n_values], small int8 [batch][3][N]; out: one batched handle [batch][2][limbs][N] */
+int evah_encode_encrypt_many(evah_ctx *ctx, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale,
+                             const int8_t *small, evah_ct **out);
+/* instance b = evah_pt_encode(values[b]) -> evah_encrypt_symmetric(e[b], seeds[b]) word for word (seal.cpp:24-102 with
+ * Encryptor::encrypt_symmetric); e int8 [batch][N], seeds [batch][32]; needs EVAH_KEY_SECRET */
+int evah_encode_encrypt_symmetric_many(evah_ctx *ctx, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs,
+                                       double scale, const int8_t *e, const uint8_t *seeds, evah_ct **out);
+/* out[i] = the n_out doubles evah_decrypt_decode(cts[i]) returns, bit pattern for bit pattern (seal.cpp:124-146); the n
+ * single ciphertexts (views included) share one size, limb count and scale and are read in place; out [n][n_out] */
+int evah_decrypt_decode_many(evah_ctx *ctx, const evah_ct *const *cts, uint32_t n, uint32_t n_out, double *out);
+
 /* ---- whole-DAG submit: a topologically sorted flat op list over a value table.
  * One call replaces the per-node loop ProgramTraversal::forwardPass + SEALExecutor::operator()
  * (program_traversal.h:36-93, seal_executor.h:279-404) for the encrypted part of a program.

@@ -1,0 +1,98 @@
+"""The client side of a batch: what encrypting all inputs and decrypting all outputs costs around
+execute_batch, one ciphertext at a time and with the batched calls.
+
+  python scripts/client_batch_probe.py c4 --batch 0|1
+      BASELINE config 4's shape: 256 Sobel inputs, N = 2^14.
+  python scripts/client_batch_probe.py c3 --batch 0|1
+      BASELINE config 3's shape: 64 Harris inputs, N = 2^15.
+
+--batch 0 is the baseline: a loop of public_ctx.encrypt / secret_ctx.decrypt, the only path before the batched calls, on
+the same box.  --batch 1 is public_ctx.encrypt_batch / secret_ctx.decrypt_batch.  Both legs run the same execute_batch
+between them.  Each run prints one line: the median wall time of the three phases over --repeat runs after --warmup
+runs (the first run builds tables and plans).  --secret encrypts with the secret key (seeded ciphertexts) instead.
+
+Kernel launches per call: run one leg under the profiler, which this script never starts itself and with no counters in
+that run,
+
+  rocprofv3 --kernel-trace --output-format csv -d <dir> -- python scripts/client_batch_probe.py c4 --batch 1 --repeat 1 --warmup 0 --phase encrypt
+
+and count the rows of the kernel trace (--phase encrypt | decrypt runs that phase's calls alone after the set-up, so the
+difference between two instance counts, --instances, is the launches the extra instances cost: 0 for the batched calls
+up to 64 instances).
+"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+ap.add_argument("what", choices=["c4", "c3"])
+ap.add_argument("--batch", type=int, choices=[0, 1], default=1)
+ap.add_argument("--instances", type=int, default=0, help="instances (default: 256 for c4, 64 for c3)")
+ap.add_argument("--repeat", type=int, default=5)
+ap.add_argument("--warmup", type=int, default=1)
+ap.add_argument("--secret", action="store_true", help="secret-key encryption (seeded ciphertexts)")
+ap.add_argument("--phase", choices=["all", "encrypt", "decrypt"], default="all",
+                help="encrypt: no execute_batch and no decryption; decrypt: one untimed encryption and execute_batch, then decryptions alone")
+args = ap.parse_args()
+
+from eva.seal import generate_keys
+from eva_amd import workloads
+
+compiled, params, sig, _ = workloads.compile_config(args.what)
+B = args.instances or {"c4": 256, "c3": 64}[args.what]
+xs = [workloads.image(4096, shift=b) for b in range(B)]
+pub, sec = generate_keys(params, 1)
+batched = bool(args.batch)
+enc_ctx = sec if args.secret else pub
+
+
+def encrypt():
+    return enc_ctx.encrypt_batch(xs, sig) if batched else [enc_ctx.encrypt(x, sig) for x in xs]
+
+
+def decrypt(outs):
+    return sec.decrypt_batch(outs, sig) if batched else [sec.decrypt(o, sig) for o in outs]
+
+
+t_enc, t_exe, t_dec = [], [], []
+outs = None
+if args.phase == "decrypt":
+    outs = pub.execute_batch(compiled, encrypt())
+    pub.synchronize()
+for run in range(args.warmup + args.repeat):
+    keep = run >= args.warmup
+    if args.phase != "decrypt":
+        pub.synchronize()
+        t0 = time.perf_counter()
+        encs = encrypt()
+        pub.synchronize()
+        t1 = time.perf_counter()
+        if keep:
+            t_enc.append(t1 - t0)
+        if args.phase == "encrypt":
+            continue
+        outs = pub.execute_batch(compiled, encs)
+        pub.synchronize()
+        t2 = time.perf_counter()
+        if keep:
+            t_exe.append(t2 - t1)
+    t2 = time.perf_counter()
+    got = decrypt(outs)
+    t3 = time.perf_counter()
+    if keep:
+        t_dec.append(t3 - t2)
+    assert len(got) == B
+
+
+def med(t):
+    return f"{statistics.median(t) * 1e3:.2f} ms" if t else "-"
+
+
+print(f"{args.what} batch={int(batched)} secret={int(args.secret)}: N={pub.poly_modulus_degree} k={len(pub.primes)} instances={B}; "
+      f"medians over {args.repeat} runs after {args.warmup} warm-up: encrypt all inputs {med(t_enc)}, execute_batch {med(t_exe)}, "
+      f"decrypt all outputs {med(t_dec)}")
