@@ -118,6 +118,11 @@ _SIGS = {
     "evah_encode_encrypt_symmetric_many": [_vp, C.c_uint32, C.POINTER(C.c_double), C.c_uint32, C.c_uint32, C.c_double,
                                            C.POINTER(C.c_int8), C.POINTER(C.c_uint8), _vpp],
     "evah_decrypt_decode_many": [_vp, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.POINTER(C.c_double)],
+    # the same with the small polynomials drawn on the device from a 32-byte key per instance
+    "evah_encode_encrypt_sampled_many": [_vp, C.c_uint32, C.POINTER(C.c_double), C.c_uint32, C.c_uint32, C.c_double,
+                                         C.POINTER(C.c_uint8), _vpp],
+    "evah_encode_encrypt_symmetric_sampled_many": [_vp, C.c_uint32, C.POINTER(C.c_double), C.c_uint32, C.c_uint32, C.c_double,
+                                                   C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _vpp],
     # seed-compressed evaluation keys
     "evah_key_upload_seeded": [_vp, C.c_int, C.c_uint32, C.c_uint32, _u64p, C.POINTER(C.c_uint8)],
     "evah_keygen_switch": [_vp, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_int8), C.POINTER(C.c_uint8), C.c_int, _u64p],
@@ -221,6 +226,15 @@ def _chk(rc):
 def _p(a):
     assert a.dtype == np.uint64 and a.flags["C_CONTIGUOUS"]
     return a.ctypes.data_as(_u64p)
+
+
+def _keys32(keys, n):
+    """n 32-byte strings as one uint8 [n][32] argument (None: the null pointer)"""
+    if keys is None:
+        return None
+    flat = b"".join(bytes(k) for k in keys)
+    assert len(keys) == n and len(flat) == 32 * n
+    return (C.c_uint8 * max(len(flat), 1)).from_buffer_copy(flat or b"\0")
 
 
 def device_count():
@@ -524,6 +538,27 @@ class Context:
         _chk(_lib.evah_encode_encrypt_symmetric_many(self.h, v.shape[0], v.ctypes.data_as(C.POINTER(C.c_double)), v.shape[1],
                                                      int(limbs), float(scale), e.ctypes.data_as(C.POINTER(C.c_int8)),
                                                      sd.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(h)))
+        return Ciphertext(self, h)
+
+    def encode_encrypt_sampled_many(self, values, limbs, scale, rkeys):
+        """encode_encrypt_many with small[b] = (u, e0, e1) drawn on the device from the 32-byte randomness key rkeys[b]
+        (DESIGN.md 1.7); rkeys: one 32-byte string per instance, or None (the null pointer, which the call refuses)"""
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        assert v.ndim == 2
+        h = C.c_void_p()
+        _chk(_lib.evah_encode_encrypt_sampled_many(self.h, v.shape[0], v.ctypes.data_as(C.POINTER(C.c_double)), v.shape[1], int(limbs),
+                                                   float(scale), _keys32(rkeys, v.shape[0]), C.byref(h)))
+        return Ciphertext(self, h)
+
+    def encode_encrypt_symmetric_sampled_many(self, values, limbs, scale, ekeys, seeds):
+        """encode_encrypt_symmetric_many with e[b] drawn on the device from the 32-byte randomness key ekeys[b]; ekeys,
+        seeds: one 32-byte string per instance each, or None (the null pointer, which the call refuses)"""
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        assert v.ndim == 2
+        h = C.c_void_p()
+        _chk(_lib.evah_encode_encrypt_symmetric_sampled_many(self.h, v.shape[0], v.ctypes.data_as(C.POINTER(C.c_double)), v.shape[1],
+                                                             int(limbs), float(scale), _keys32(ekeys, v.shape[0]),
+                                                             _keys32(seeds, v.shape[0]), C.byref(h)))
         return Ciphertext(self, h)
 
     def decrypt_decode_many(self, cts, n_out):

@@ -4,6 +4,8 @@
 // evah_encrypt / evah_encrypt_symmetric and evah_decrypt_decode give for it: the modular kernels are the single ones with
 // an instance index, and the FP64 special FFT runs the single path's butterflies — same operands, same roots, same
 // rounded operations, no FMA — in another order among independent butterflies only.  No launch count depends on the batch.
+// The encryption calls also come with the small polynomials drawn here from a 32-byte randomness key per instance
+// (k_sample_small) in place of the host's int8 draws: same checks, launches and words.
 //
 // The FFT (k_fft_tile): a workgroup keeps 2048 complex points in LDS and runs every stage whose butterflies stay inside
 // the tile before it writes.  2048 double2 are 32 KiB: twice that is the whole 64 KiB a kernel may declare statically (no
@@ -28,6 +30,7 @@
 #include "launch.hip.h"
 #include "client.hip.h"
 #include "seeded.hip.h"
+#include "sampled.hip.h"
 
 namespace evah {
 
@@ -173,6 +176,48 @@ k_encrypt_symmetric_b(DevCtx cx, Seeds8 seeds, const uint32_t *__restrict__ seed
   st2(c0 + 2, make_ulonglong2(b[2], b[3]));
 }
 
+// ---- the small polynomials drawn where they are used (sampled.hip.h)
+// Polynomials p0 .. p0 + n_polys - 1 of instance inst = blockIdx.y / n_polys from its randomness key rkeys[inst][8],
+// straight into residues out [batch][n_polys][limbs][N] under the chain primes 0 .. limbs - 1, k_small_to_residues'
+// words (v < 0 ? q - |v| : v).  A workgroup draws SAMPLE_TILE consecutive coefficients — one ChaCha20 block of 8 per
+// thread, kept as 8 bytes in LDS — and then writes them limb by limb, thread t the coefficients 2 t, 2 t + 1 (+ 512 r):
+// one 16-byte store per lane, 1 KiB contiguous per wave instruction, and no block is computed twice.  N / 8 may be
+// below one workgroup (N = 1024: 128 blocks): the idle threads draw nothing and still take part in the stores.
+constexpr uint32_t SAMPLE_THREADS = 256, SAMPLE_TILE = 8 * SAMPLE_THREADS;
+__global__ void __launch_bounds__(SAMPLE_THREADS)
+k_sample_small(DevCtx cx, const uint32_t *__restrict__ rkeys, uint32_t n_polys, uint32_t p0, uint32_t limbs, u64 *out) {
+  __shared__ u64 tile8[SAMPLE_THREADS];
+  const uint32_t tid = threadIdx.x, inst = blockIdx.y / n_polys, p = p0 + blockIdx.y % n_polys;
+  const uint32_t blk = blockIdx.x * SAMPLE_THREADS + tid;
+  if (blk < cx.N / 8) {
+    uint32_t key[8];
+#pragma unroll
+    for (int w = 0; w < 8; w++) key[w] = rkeys[8 * inst + w];
+    tile8[tid] = sampled_block(key, p, blk);
+  }
+  __syncthreads();
+  const int8_t *tile = reinterpret_cast<const int8_t *>(tile8);
+  const uint32_t base = blockIdx.x * SAMPLE_TILE, pairs = min(SAMPLE_TILE, cx.N - base) / 2; // N is a multiple of 256
+  int v[SAMPLE_TILE / 2 / SAMPLE_THREADS][2];
+#pragma unroll
+  for (uint32_t r = 0; r < SAMPLE_TILE / 2 / SAMPLE_THREADS; r++) {
+    const uint32_t e = tid + r * SAMPLE_THREADS;
+    v[r][0] = e < pairs ? tile[2 * e] : 0;
+    v[r][1] = e < pairs ? tile[2 * e + 1] : 0;
+  }
+  u64 *rows = out + (size_t)blockIdx.y * limbs * cx.N + base;
+  for (uint32_t i = 0; i < limbs; i++) {
+    const u64 q = cx.primes[cx.prime_of(i)].q;
+#pragma unroll
+    for (uint32_t r = 0; r < SAMPLE_TILE / 2 / SAMPLE_THREADS; r++) {
+      const uint32_t e = tid + r * SAMPLE_THREADS;
+      if (e < pairs)
+        st2(rows + (size_t)i * cx.N + 2 * e, make_ulonglong2(v[r][0] < 0 ? q - (u64)(-v[r][0]) : (u64)v[r][0],
+                                                              v[r][1] < 0 ? q - (u64)(-v[r][1]) : (u64)v[r][1]));
+    }
+  }
+}
+
 // ---- the decryptor's small kernels with an instance index
 // the ciphertexts of a call: separate allocations, possibly views with a polynomial stride of their own
 struct DotTab {
@@ -229,7 +274,7 @@ struct Wipe {
   evah_ctx *c;
   void *d;
   size_t bytes;
-  bool done = false;
+  bool done = false; // set at construction: nothing to wipe
   void now() { // the success path: a wipe that fails is an error, as in the single calls
     done = true;
     HIPCHK(hipMemsetAsync(d, 0, bytes, c->stream));
@@ -266,27 +311,41 @@ static void encode_many(evah_ctx *c, uint32_t batch, const double *values, uint3
   ntt_forward<OpPlain>(c, p, batch * limbs);
 }
 
-} // namespace evah
+// the randomness keys [batch][32] (host) into `keys` on the queue, then NTT forms [batch][n_polys][limbs][N] of the
+// polynomials p0 .. p0 + n_polys - 1 of every instance: what the int8 copy and small_to_ntt make of the host's draws
+static void sample_to_ntt(evah_ctx *c, uint32_t batch, const uint8_t *rkeys, u64 *keys, uint32_t n_polys, uint32_t p0, uint32_t limbs, u64 *out) {
+  HIPCHK(hipMemcpyAsync(keys, rkeys, (size_t)32 * batch, hipMemcpyHostToDevice, c->stream));
+  EW_LAUNCH(k_sample_small, dim3((c->N + SAMPLE_TILE - 1) / SAMPLE_TILE, batch * n_polys), dim3(SAMPLE_THREADS), 0, c->stream, c->dev,
+            reinterpret_cast<const uint32_t *>(keys), n_polys, p0, limbs, out);
+  OpPlain::Params fp{out, out, (size_t)limbs * c->N, (size_t)limbs * c->N, limbs, 0, 0, {}};
+  ntt_forward<OpPlain>(c, fp, batch * n_polys * limbs);
+}
+// host -> device bytes of a batched encryption call: the values, its randomness and (symmetric) the seeds
+static void count_client_h2d(evah_ctx *c, size_t bytes) { c->sh->xfer[4] += bytes; }
 
-extern "C" {
-
-int evah_encode_encrypt_many(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale,
-                             const int8_t *small, evah_ct **out) {
-  API_BEGIN
+// evah_encode_encrypt_many (small: the host's draws) and evah_encode_encrypt_sampled_many (rkeys: drawn here)
+static void encode_encrypt_many(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale,
+                                const int8_t *small, const uint8_t *rkeys, evah_ct **out) {
   use(c);
   encode_many_checks(c, batch, values, n_values, limbs, out);
-  if (!small) throw std::invalid_argument("randomness pointer is null");
+  if (!small && !rkeys) throw std::invalid_argument("randomness pointer is null");
   if (!c->sh->pk.d) throw std::invalid_argument("public key not present");
   const uint32_t l = limbs, up = l + 1;
   if (up > c->k) throw std::invalid_argument("plaintext level is not valid for encryption");
   const size_t N = c->N, B = batch;
-  Scratch vals(c, B * n_values), cbuf(c, B * 2 * N), pt(c, B * l * N), sm8(c, (3 * B * N + 7) / 8), sm(c, 3 * B * up * N),
+  Scratch vals(c, B * n_values), cbuf(c, B * 2 * N), pt(c, B * l * N), sm8(c, rkeys ? 4 * B : (3 * B * N + 7) / 8), sm(c, 3 * B * up * N),
       ct(c, 2 * B * up * N), r(c, 2 * B * N);
   evah_ct *o = ct_new(c, 2, l, scale, batch);
   try {
+    // drawn here, u, e0, e1 and their keys exist nowhere else: they do not stay behind in pool memory the next call reuses
+    Wipe w_keys{c, sm8.d, (size_t)32 * B, !rkeys}, w_sm{c, sm.d, sizeof(u64) * 3 * B * up * N, !rkeys};
     encode_many(c, batch, values, n_values, l, scale, vals.d, reinterpret_cast<double2 *>(cbuf.d), pt.d);
-    HIPCHK(hipMemcpyAsync(sm8.d, small, 3 * B * N, hipMemcpyHostToDevice, c->stream));
-    small_to_ntt(c, sm8.d, 3 * batch, up, sm.d);
+    if (rkeys) {
+      sample_to_ntt(c, batch, rkeys, sm8.d, 3, 0, up, sm.d);
+    } else {
+      HIPCHK(hipMemcpyAsync(sm8.d, small, 3 * B * N, hipMemcpyHostToDevice, c->stream));
+      small_to_ntt(c, sm8.d, 3 * batch, up, sm.d);
+    }
     EW_LAUNCH(k_encrypt_zero_b, dim3(c->N / 256, up, 2 * batch), dim3(256), 0, c->stream, c->dev, c->sh->pk.d, sm.d, up, ct.d);
     HIPCHK(hipGetLastError());
     // divide and round by prime `l` (the last of the up primes), then add instance b's plaintext to its c0
@@ -296,34 +355,42 @@ int evah_encode_encrypt_many(evah_ctx *c, uint32_t batch, const double *values, 
     mp.use_add_tab = true;
     for (uint32_t b = 0; b < batch; b++) mp.add_tab.p[2 * b] = pt.d + b * l * N;
     ntt_forward<OpModDown>(c, mp, 2 * batch * l);
-    HIPCHK(hipStreamSynchronize(c->stream)); // `values` and `small` are pageable host memory
+    if (rkeys) {
+      w_keys.now();
+      w_sm.now();
+    }
+    HIPCHK(hipStreamSynchronize(c->stream)); // `values` and `small` / `rkeys` are pageable host memory
   } catch (...) {
     (void)hipStreamSynchronize(c->stream);
     evah_ct_free(c, o);
     throw;
   }
+  count_client_h2d(c, sizeof(double) * B * n_values + (rkeys ? 32 * B : 3 * B * N));
   *out = o;
-  API_END
 }
 
-int evah_encode_encrypt_symmetric_many(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale,
-                                       const int8_t *e, const uint8_t *seeds, evah_ct **out) {
-  API_BEGIN
+// evah_encode_encrypt_symmetric_many (e: the host's draws) and evah_encode_encrypt_symmetric_sampled_many (ekeys: drawn here)
+static void encode_encrypt_symmetric_many(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale,
+                                          const int8_t *e, const uint8_t *ekeys, const uint8_t *seeds, evah_ct **out) {
   use(c);
   encode_many_checks(c, batch, values, n_values, limbs, out);
   if (!c->sh->sk.d) throw std::invalid_argument("secret key not present");
-  if (!e || !seeds) throw std::invalid_argument("error polynomial and seed are required");
+  if ((!e && !ekeys) || !seeds) throw std::invalid_argument("error polynomial and seed are required");
   const uint32_t l = limbs;
   const size_t N = c->N, B = batch;
-  Scratch vals(c, B * n_values), cbuf(c, B * 2 * N), pt(c, B * l * N), e8(c, (B * N + 7) / 8), en(c, B * l * N);
+  Scratch vals(c, B * n_values), cbuf(c, B * 2 * N), pt(c, B * l * N), e8(c, ekeys ? 4 * B : (B * N + 7) / 8), en(c, B * l * N);
   std::unique_ptr<Scratch> seed_dev; // more than 8 instances: the seeds as a device buffer, returned to the pool after the drain
   evah_ct *o = ct_new(c, 2, l, scale, batch);
   try {
-    // the errors do not stay behind in pool memory the next call reuses
-    Wipe w_en{c, en.d, sizeof(u64) * B * l * N}, w_e8{c, e8.d, B * N};
+    // the errors (or the keys they are drawn from) do not stay behind in pool memory the next call reuses
+    Wipe w_en{c, en.d, sizeof(u64) * B * l * N}, w_e8{c, e8.d, ekeys ? 32 * B : B * N};
     encode_many(c, batch, values, n_values, l, scale, vals.d, reinterpret_cast<double2 *>(cbuf.d), pt.d);
-    HIPCHK(hipMemcpyAsync(e8.d, e, B * N, hipMemcpyHostToDevice, c->stream));
-    small_to_ntt(c, e8.d, batch, l, en.d);
+    if (ekeys) {
+      sample_to_ntt(c, batch, ekeys, e8.d, 1, 1, l, en.d);
+    } else {
+      HIPCHK(hipMemcpyAsync(e8.d, e, B * N, hipMemcpyHostToDevice, c->stream));
+      small_to_ntt(c, e8.d, batch, l, en.d);
+    }
     Seeds8 s8;
     std::memset(&s8, 0, sizeof s8);
     const uint32_t *seed_buf = nullptr;
@@ -344,12 +411,44 @@ int evah_encode_encrypt_symmetric_many(evah_ctx *c, uint32_t batch, const double
     throw;
   }
   try {
-    HIPCHK(hipStreamSynchronize(c->stream)); // `values`, `e` and `seeds` are pageable host memory
+    HIPCHK(hipStreamSynchronize(c->stream)); // `values`, `e` / `ekeys` and `seeds` are pageable host memory
   } catch (...) {
     evah_ct_free(c, o);
     throw;
   }
+  count_client_h2d(c, sizeof(double) * B * n_values + (ekeys ? 32 * B : B * N) + 32 * B);
   *out = o;
+}
+
+} // namespace evah
+
+extern "C" {
+
+int evah_encode_encrypt_many(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale,
+                             const int8_t *small, evah_ct **out) {
+  API_BEGIN
+  encode_encrypt_many(c, batch, values, n_values, limbs, scale, small, nullptr, out);
+  API_END
+}
+
+int evah_encode_encrypt_sampled_many(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale,
+                                     const uint8_t *rkeys, evah_ct **out) {
+  API_BEGIN
+  encode_encrypt_many(c, batch, values, n_values, limbs, scale, nullptr, rkeys, out);
+  API_END
+}
+
+int evah_encode_encrypt_symmetric_many(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale,
+                                       const int8_t *e, const uint8_t *seeds, evah_ct **out) {
+  API_BEGIN
+  encode_encrypt_symmetric_many(c, batch, values, n_values, limbs, scale, e, nullptr, seeds, out);
+  API_END
+}
+
+int evah_encode_encrypt_symmetric_sampled_many(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs,
+                                               double scale, const uint8_t *ekeys, const uint8_t *seeds, evah_ct **out) {
+  API_BEGIN
+  encode_encrypt_symmetric_many(c, batch, values, n_values, limbs, scale, nullptr, ekeys, seeds, out);
   API_END
 }
 

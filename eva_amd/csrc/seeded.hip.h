@@ -22,11 +22,12 @@ __device__ __forceinline__ uint32_t rotl32(uint32_t x, int r) { return (x << r) 
   a += b; d = rotl32(d ^ a, 8);                    \
   c += d; b = rotl32(b ^ c, 7);
 
-// the four coefficients of block `blk` of limb `prime` (the chain index) as canonical residues
-__device__ __forceinline__ void seeded_block(const uint32_t *key, uint32_t prime, uint64_t blk, const DevPrime &pm, u64 out[4]) {
+// the 16 output words of the ChaCha20 block with key `key`, block counter blk (state words 12-13) and nonce (n0, n1)
+// (words 14-15): the one block function of the device, shared with sampled.hip.h
+__device__ __forceinline__ void chacha_block(const uint32_t *key, uint64_t blk, uint32_t n0, uint32_t n1, uint32_t x[16]) {
   const uint32_t s0 = 0x61707865u, s1 = 0x3320646eu, s2 = 0x79622d32u, s3 = 0x6b206574u;
   const uint32_t k0 = key[0], k1 = key[1], k2 = key[2], k3 = key[3], k4 = key[4], k5 = key[5], k6 = key[6], k7 = key[7];
-  const uint32_t c0 = (uint32_t)blk, c1 = (uint32_t)(blk >> 32), n0 = prime, n1 = SEED_NONCE_HI;
+  const uint32_t c0 = (uint32_t)blk, c1 = (uint32_t)(blk >> 32);
   uint32_t x0 = s0, x1 = s1, x2 = s2, x3 = s3, x4 = k0, x5 = k1, x6 = k2, x7 = k3;
   uint32_t x8 = k4, x9 = k5, x10 = k6, x11 = k7, x12 = c0, x13 = c1, x14 = n0, x15 = n1;
 #pragma unroll
@@ -34,15 +35,19 @@ __device__ __forceinline__ void seeded_block(const uint32_t *key, uint32_t prime
     CHACHA_QR(x0, x4, x8, x12) CHACHA_QR(x1, x5, x9, x13) CHACHA_QR(x2, x6, x10, x14) CHACHA_QR(x3, x7, x11, x15)
     CHACHA_QR(x0, x5, x10, x15) CHACHA_QR(x1, x6, x11, x12) CHACHA_QR(x2, x7, x8, x13) CHACHA_QR(x3, x4, x9, x14)
   }
-  x0 += s0; x1 += s1; x2 += s2; x3 += s3; x4 += k0; x5 += k1; x6 += k2; x7 += k3;
-  x8 += k4; x9 += k5; x10 += k6; x11 += k7; x12 += c0; x13 += c1; x14 += n0; x15 += n1;
-  auto w64 = [](uint32_t lo, uint32_t hi) { return (u64)lo | ((u64)hi << 32); };
-  out[0] = barrett128(u128_t{w64(x0, x1), w64(x2, x3)}, pm);
-  out[1] = barrett128(u128_t{w64(x4, x5), w64(x6, x7)}, pm);
-  out[2] = barrett128(u128_t{w64(x8, x9), w64(x10, x11)}, pm);
-  out[3] = barrett128(u128_t{w64(x12, x13), w64(x14, x15)}, pm);
+  x[0] = x0 + s0; x[1] = x1 + s1; x[2] = x2 + s2; x[3] = x3 + s3; x[4] = x4 + k0; x[5] = x5 + k1; x[6] = x6 + k2; x[7] = x7 + k3;
+  x[8] = x8 + k4; x[9] = x9 + k5; x[10] = x10 + k6; x[11] = x11 + k7; x[12] = x12 + c0; x[13] = x13 + c1; x[14] = x14 + n0; x[15] = x15 + n1;
 }
 #undef CHACHA_QR
+__device__ __forceinline__ u64 chacha_w64(const uint32_t x[16], int w) { return (u64)x[2 * w] | ((u64)x[2 * w + 1] << 32); }
+
+// the four coefficients of block `blk` of limb `prime` (the chain index) as canonical residues
+__device__ __forceinline__ void seeded_block(const uint32_t *key, uint32_t prime, uint64_t blk, const DevPrime &pm, u64 out[4]) {
+  uint32_t x[16];
+  chacha_block(key, blk, prime, SEED_NONCE_HI, x);
+#pragma unroll
+  for (int r = 0; r < 4; r++) out[r] = barrett128(u128_t{chacha_w64(x, 2 * r), chacha_w64(x, 2 * r + 1)}, pm);
+}
 
 inline Seeds8 seeds_of(const uint8_t *const *seeds, uint32_t first, uint32_t n) {
   Seeds8 s;

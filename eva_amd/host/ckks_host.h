@@ -397,6 +397,27 @@ inline void wipe(std::vector<int8_t> &v) {
   for (size_t i = 0, n = v.size(); i < n; i++) p[i] = 0;
 }
 
+// the same for randomness keys and other secret bytes
+inline void wipe_bytes(void *p, size_t n) {
+  volatile unsigned char *v = static_cast<volatile unsigned char *>(p);
+  while (n--) *v++ = 0;
+}
+// the next 32-byte key of a stream: 4 words, little-endian, as the seeds of DESIGN.md 1.3 are drawn
+inline std::array<uint8_t, 32> draw_key32(SecureRng &rng) {
+  std::array<uint8_t, 32> k;
+  for (int w = 0; w < 4; w++) {
+    const uint64_t x = rng();
+    std::memcpy(k.data() + 8 * w, &x, 8);
+  }
+  return k;
+}
+// (u, e0, e1) of a randomness key as int8 [3][N]
+inline std::vector<int8_t> sampled_small3(const std::array<uint8_t, 32> &rk, uint32_t N) {
+  std::vector<int8_t> small((size_t)3 * N);
+  for (uint32_t p = 0; p < 3; p++) sampled_small(rk.data(), p, N, small.data() + (size_t)p * N);
+  return small;
+}
+
 // Key material in the layout libeva_hip.so expects.
 struct SwitchKey {
   uint32_t n_digits = 0;
@@ -651,13 +672,12 @@ inline void materialise_seeded(const SeededForm &sf, uint32_t limbs, CipherWords
 
 // Public-key encryption of an NTT-form plaintext at `limbs` data limbs (A.10): encrypt zero one
 // level up (limbs+1 primes), divide-and-round by that extra prime, add the plaintext to c0.
-inline HostCipher encrypt(const HostContext &cx, const PublicKey &pk, const HostPlain &pt, SecureRng &rng) {
+// The randomness is the caller's: u ternary, e0 and e1 error polynomials, N coefficients each.
+inline HostCipher encrypt(const HostContext &cx, const PublicKey &pk, const HostPlain &pt, const std::vector<int8_t> &u,
+                          const std::vector<int8_t> &e0, const std::vector<int8_t> &e1) {
   const uint32_t N = cx.N, l = pt.limbs, up = l + 1;
   if (up > cx.k) throw std::invalid_argument("plaintext level is not valid for encryption");
-  std::vector<int8_t> u, e0, e1;
-  cx.sample_ternary(rng, u);
-  cx.sample_error(rng, e0);
-  cx.sample_error(rng, e1);
+  if (u.size() != N || e0.size() != N || e1.size() != N) throw std::invalid_argument("encryption randomness must be three polynomials of N coefficients");
   std::vector<u64> c((size_t)2 * up * N), un(N), en(N);
   for (uint32_t i = 0; i < up; i++) {
     const u64 q = cx.primes[i];
@@ -695,6 +715,16 @@ inline HostCipher encrypt(const HostContext &cx, const PublicKey &pk, const Host
     }
   }
   return out;
+}
+
+// the same with u, e0, e1 drawn from rng, in that order
+inline HostCipher encrypt(const HostContext &cx, const PublicKey &pk, const HostPlain &pt, SecureRng &rng) {
+  if (pt.limbs + 1 > cx.k) throw std::invalid_argument("plaintext level is not valid for encryption");
+  std::vector<int8_t> u, e0, e1;
+  cx.sample_ternary(rng, u);
+  cx.sample_error(rng, e0);
+  cx.sample_error(rng, e1);
+  return encrypt(cx, pk, pt, u, e0, e1);
 }
 
 // m = c0 + c1 s (+ c2 s^2), NTT form -> coefficient form per limb

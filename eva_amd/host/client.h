@@ -99,11 +99,6 @@ inline bool HipPublic::device_encodable(const std::vector<double> &in, double sc
 
 // coeff_pt: the host encoder's coefficient-form plaintext, or (null) values: the slot values for the device encoder
 inline HostCipher HipPublic::encrypt_on_device(const HostPlain *coeff_pt, const std::vector<double> *values, double scale, uint32_t limbs, SecureRng &rng) {
-  ensure_device(false);
-  if (!pk_uploaded) {
-    chk(evah_client_key_upload(dev->h, EVAH_KEY_PUBLIC, (const uint64_t *)pk.data.data()));
-    pk_uploaded = true;
-  }
   const uint32_t N = host->N;
   std::vector<int8_t> u, e0, e1, small((size_t)3 * N);
   host->sample_ternary(rng, u);
@@ -112,6 +107,16 @@ inline HostCipher HipPublic::encrypt_on_device(const HostPlain *coeff_pt, const 
   std::copy(u.begin(), u.end(), small.begin());
   std::copy(e0.begin(), e0.end(), small.begin() + N);
   std::copy(e1.begin(), e1.end(), small.begin() + 2 * (size_t)N);
+  return encrypt_on_device_with(coeff_pt, values, scale, limbs, small);
+}
+inline HostCipher HipPublic::encrypt_on_device_with(const HostPlain *coeff_pt, const std::vector<double> *values, double scale, uint32_t limbs,
+                                                    const std::vector<int8_t> &small) {
+  ensure_device(false);
+  if (!pk_uploaded) {
+    chk(evah_client_key_upload(dev->h, EVAH_KEY_PUBLIC, (const uint64_t *)pk.data.data()));
+    pk_uploaded = true;
+  }
+  const uint32_t N = host->N;
   evah_pt *p = nullptr;
   if (coeff_pt) chk(evah_pt_upload_coeff(dev->h, limbs, scale, (const uint64_t *)coeff_pt->data.data(), &p));
   else chk(evah_pt_encode(dev->h, values->data(), (uint32_t)values->size(), limbs, scale, &p));
@@ -134,18 +139,96 @@ inline HostCipher HipPublic::encrypt_on_device(const HostPlain *coeff_pt, const 
   return out;
 }
 
+// the Cipher branch of encrypt() for one input, the randomness given: device encoder + encryptor, host encoder + device
+// encryptor, or the host alone — the same words on each
+inline HostCipher HipPublic::encrypt_value_with(const std::vector<double> &v, double scale, uint32_t limbs, const std::vector<int8_t> &small) {
+  if (client_on_device() && device_encodable(v, scale, limbs)) return encrypt_on_device_with(nullptr, &v, scale, limbs, small);
+  const size_t slots = host->N / 2, N = host->N;
+  HostPlain pt;
+  pt.limbs = limbs;
+  pt.scale = scale;
+  pt.data.resize((size_t)limbs * N);
+  std::vector<double> vec(slots);
+  for (size_t r = 0; r < slots / v.size(); r++) std::copy(v.begin(), v.end(), vec.begin() + r * v.size());
+  host->encode_coeff(vec.data(), scale, limbs, pt.data.data());
+  if (client_on_device()) return encrypt_on_device_with(&pt, nullptr, scale, limbs, small);
+  for (uint32_t i = 0; i < limbs; i++) host->ntt(i, pt.data.data() + (size_t)i * N);
+  std::vector<int8_t> u(small.begin(), small.begin() + N), e0(small.begin() + N, small.begin() + 2 * N), e1(small.begin() + 2 * N, small.end());
+  HostCipher out = evahost::encrypt(*host, pk, pt, u, e0, e1);
+  wipe(u); wipe(e0); wipe(e1);
+  return out;
+}
+
 // encrypt() for a list of input valuations of one signature.  Per input name the instances leave in
 // groups of <= 64 as ONE evah_encode_encrypt_many each — a launch set whose length does not depend on the group — and
 // come back as views of the group's handle (evah_ct_unstack).  A name with an instance the device encoder cannot take,
 // plain and raw inputs, and every input without a device take encrypt()'s path per instance.
-inline std::vector<HipValuation> HipPublic::encrypt_batch(const std::vector<Valuation> &inputs, const CKKSSignature &sig) {
+// device_sampling: all draws first — instances in list order, names sorted within an instance, one 32-byte
+// randomness key (4 words) per encrypted input — then the groups go out as evah_encode_encrypt_sampled_many, and every
+// other path expands the same keys with the host twin.
+inline std::vector<HipValuation> HipPublic::encrypt_batch(const std::vector<Valuation> &inputs, const CKKSSignature &sig, bool device_sampling,
+                                                          uint64_t seed) {
   const size_t slots = host->N / 2;
+  if (seed && !device_sampling) throw std::invalid_argument("encrypt_batch: seed is the test hook of device_sampling and needs device_sampling=True");
   if (sig.vec_size <= 0) throw std::runtime_error("Signature vector size must be positive");
   if (slots < (size_t)sig.vec_size) throw std::runtime_error("Vector size cannot be larger than slot count");
   if (slots % sig.vec_size) throw std::runtime_error("Vector size must exactly divide the slot count");
   std::vector<HipValuation> out(inputs.size());
   if (inputs.empty()) return out;
   const std::vector<std::string> names = batch_input_names(inputs);
+  if (device_sampling) {
+    std::unique_ptr<SecureRng> stream = seed ? std::make_unique<SecureRng>(seed, 5) : std::make_unique<SecureRng>();
+    std::vector<std::vector<std::array<uint8_t, 32>>> rkeys(names.size()); // per name, per instance
+    struct WipeKeys {
+      std::vector<std::vector<std::array<uint8_t, 32>>> &k;
+      ~WipeKeys() { for (auto &n : k) for (auto &x : n) wipe_bytes(x.data(), 32); }
+    } wipe_keys{rkeys};
+    std::vector<const CKKSEncodingInfo *> infos(names.size());
+    for (size_t i = 0; i < names.size(); i++) {
+      auto it = sig.inputs.find(names[i]);
+      if (it == sig.inputs.end()) throw std::out_of_range("No input named " + names[i] + " in the signature");
+      infos[i] = &it->second;
+      if (it->second.input_type == Type::Cipher && (uint32_t)it->second.level >= host->k - 1) throw std::runtime_error("Input level exceeds the modulus chain");
+    }
+    for (size_t b = 0; b < inputs.size(); b++)
+      for (size_t i = 0; i < names.size(); i++) {
+        if (inputs[b].at(names[i]).size() != (size_t)sig.vec_size) throw std::runtime_error("Input size does not match program vector size");
+        if (infos[i]->input_type == Type::Cipher) rkeys[i].push_back(draw_key32(*stream));
+      }
+    for (size_t i = 0; i < names.size(); i++) {
+      const std::string &name = names[i];
+      if (infos[i]->input_type != Type::Cipher) { // plain and raw inputs take no randomness: encrypt()'s path
+        for (size_t b = 0; b < inputs.size(); b++) {
+          HipValuation one = encrypt(Valuation{{name, inputs[b].at(name)}}, sig);
+          out[b].values[name] = std::move(one.values.at(name));
+        }
+        continue;
+      }
+      const uint32_t limbs = host->k - 1 - (uint32_t)infos[i]->level;
+      const double scale = std::pow(2.0, (double)infos[i]->scale);
+      bool grouped = client_on_device();
+      for (size_t b = 0; grouped && b < inputs.size(); b++) grouped = device_encodable(inputs[b].at(name), scale, limbs);
+      if (!grouped) { // the same keys through the host twin, instance by instance
+        for (size_t b = 0; b < inputs.size(); b++) {
+          std::vector<int8_t> small = sampled_small3(rkeys[i][b], host->N);
+          struct WipeSmall {
+            std::vector<int8_t> &s;
+            ~WipeSmall() { wipe(s); }
+          } wipe_small{small};
+          out[b].values[name] = encrypt_value_with(inputs[b].at(name), scale, limbs, small);
+        }
+        continue;
+      }
+      for (size_t b0 = 0; b0 < inputs.size(); b0 += CLIENT_BATCH_MAX) {
+        const size_t n = std::min<size_t>(CLIENT_BATCH_MAX, inputs.size() - b0);
+        std::vector<const std::vector<double> *> vals(n);
+        for (size_t b = 0; b < n; b++) vals[b] = &inputs[b0 + b].at(name);
+        std::vector<HostCipher> cts = encrypt_group_sampled(vals, scale, limbs, rkeys[i].data() + b0);
+        for (size_t b = 0; b < n; b++) out[b0 + b].values[name] = std::move(cts[b]);
+      }
+    }
+    return out;
+  }
   SecureRng rng; // one fresh ChaCha20 stream keyed from the OS for the whole call
   for (const std::string &name : names) {
     auto it = sig.inputs.find(name);
@@ -207,6 +290,32 @@ inline std::vector<HostCipher> HipPublic::encrypt_group_on_device(const std::vec
   const int rc = evah_encode_encrypt_many(dev->h, (uint32_t)B, flat.data(), (uint32_t)nv, limbs, scale, small.data(), &c);
   wipe(u); wipe(e0); wipe(e1); wipe(small);
   chk(rc);
+  return group_results(c, B, scale, limbs);
+}
+
+inline std::vector<HostCipher> HipPublic::encrypt_group_sampled(const std::vector<const std::vector<double> *> &vals, double scale, uint32_t limbs,
+                                                                const std::array<uint8_t, 32> *rkeys) {
+  ensure_device(false);
+  if (!pk_uploaded) {
+    chk(evah_client_key_upload(dev->h, EVAH_KEY_PUBLIC, (const uint64_t *)pk.data.data()));
+    pk_uploaded = true;
+  }
+  const size_t B = vals.size(), nv = vals[0]->size();
+  std::vector<double> flat(B * nv);
+  std::vector<uint8_t> keys(B * 32);
+  for (size_t b = 0; b < B; b++) {
+    std::copy(vals[b]->begin(), vals[b]->end(), flat.begin() + b * nv);
+    std::copy(rkeys[b].begin(), rkeys[b].end(), keys.begin() + b * 32);
+  }
+  evah_ct *c = nullptr;
+  const int rc = evah_encode_encrypt_sampled_many(dev->h, (uint32_t)B, flat.data(), (uint32_t)nv, limbs, scale, keys.data(), &c);
+  wipe_bytes(keys.data(), keys.size());
+  chk(rc);
+  return group_results(c, B, scale, limbs);
+}
+
+inline std::vector<HostCipher> HipPublic::group_results(evah_ct *c, size_t B, double scale, uint32_t limbs) {
+  const uint32_t N = host->N;
   CtHandle group(dev->h, c); // the instances share its allocation, which lives until the last view is freed
   std::vector<HostCipher> out(B);
   for (size_t b = 0; b < B; b++) {
@@ -361,7 +470,11 @@ public:
   // share a seed.  The draws made, each name's instances leave in groups of <= 64 as one
   // evah_encode_encrypt_symmetric_many (views of the group's handle come back); a name with an instance the device
   // encoder cannot take, and every input without a device, takes encrypt()'s path per instance with the same draws.
-  std::vector<HipValuation> encrypt_batch(const std::vector<Valuation> &inputs, const CKKSSignature &sig, uint64_t seed = 0) {
+  // device_sampling: the error of an encrypted input is a 32-byte key — 4 words of the secret stream in
+  // place of its N sample_error draws —, expanded on the device by the grouped call and by the host twin (csprng.h
+  // sampled_small(key, 1)) on every other path; the seeds of c1 are drawn exactly as without the option.
+  std::vector<HipValuation> encrypt_batch(const std::vector<Valuation> &inputs, const CKKSSignature &sig, uint64_t seed = 0,
+                                          bool device_sampling = false) {
     const size_t slots = host->N / 2;
     if (sig.vec_size <= 0) throw std::runtime_error("Signature vector size must be positive");
     if (slots < (size_t)sig.vec_size) throw std::runtime_error("Vector size cannot be larger than slot count");
@@ -374,13 +487,19 @@ public:
     struct Drawn {
       std::vector<std::vector<int8_t>> e;          // per instance
       std::vector<std::array<uint8_t, 32>> sd;
+      std::vector<std::array<uint8_t, 32>> ek;     // device_sampling: the error keys, e filled from them where the host needs it
       uint32_t limbs = 0;
       double scale = 0;
     };
     std::vector<Drawn> drawn(names.size());
     struct WipeAll {
       std::vector<Drawn> &d;
-      ~WipeAll() { for (auto &x : d) for (auto &e : x.e) wipe(e); }
+      ~WipeAll() {
+        for (auto &x : d) {
+          for (auto &e : x.e) wipe(e);
+          for (auto &k : x.ek) wipe_bytes(k.data(), 32);
+        }
+      }
     } wipe_all{drawn};
     for (size_t b = 0; b < inputs.size(); b++) {
       for (size_t i = 0; i < names.size(); i++) {
@@ -412,7 +531,8 @@ public:
           std::memcpy(d.sd.back().data() + 8 * w, &x, 8);
         }
         d.e.emplace_back();
-        host->sample_error(*errors, d.e.back());
+        if (device_sampling) d.ek.push_back(draw_key32(*errors));
+        else host->sample_error(*errors, d.e.back());
       }
     }
     for (size_t i = 0; i < names.size(); i++) {
@@ -424,6 +544,10 @@ public:
       if (!grouped) { // encrypt()'s path, instance by instance
         for (size_t b = 0; b < inputs.size(); b++) {
           const auto &v = inputs[b].at(name);
+          if (device_sampling) { // the same key through the host twin
+            drawn[i].e[b].resize(host->N);
+            sampled_small(d.ek[b].data(), 1, host->N, drawn[i].e[b].data());
+          }
           if (on_device()) {
             out[b].values[name] = encrypt_on_device(v, d.scale, d.limbs, d.e[b], d.sd[b]);
           } else {
@@ -438,28 +562,36 @@ public:
         const size_t n = std::min<size_t>(CLIENT_BATCH_MAX, inputs.size() - b0);
         std::vector<const std::vector<double> *> vals(n);
         for (size_t b = 0; b < n; b++) vals[b] = &inputs[b0 + b].at(name);
-        std::vector<HostCipher> cts = encrypt_group_on_device(vals, d.scale, d.limbs, d.e.data() + b0, d.sd.data() + b0);
+        std::vector<HostCipher> cts = encrypt_group_on_device(vals, d.scale, d.limbs, d.e.data() + b0, d.sd.data() + b0,
+                                                              device_sampling ? d.ek.data() + b0 : nullptr);
         for (size_t b = 0; b < n; b++) out[b0 + b].values[name] = std::move(cts[b]);
       }
     }
     return out;
   }
-  // one group of encrypt_batch on the device: instance b from (vals[b], e[b], sd[b]); the values encrypt_on_device returns
+  // one group of encrypt_batch on the device: instance b from (vals[b], e[b], sd[b]) — or, ek given, from (vals[b], the
+  // error the device draws from ek[b], sd[b]); the values encrypt_on_device returns
   std::vector<HostCipher> encrypt_group_on_device(const std::vector<const std::vector<double> *> &vals, double scale, uint32_t limbs,
-                                                  const std::vector<int8_t> *e, const std::array<uint8_t, 32> *sd) {
+                                                  const std::vector<int8_t> *e, const std::array<uint8_t, 32> *sd,
+                                                  const std::array<uint8_t, 32> *ek = nullptr) {
     const uint32_t N = host->N;
     const size_t B = vals.size(), nv = vals[0]->size();
     std::vector<double> flat(B * nv);
-    std::vector<int8_t> errs(B * N);
-    std::vector<uint8_t> seeds(B * 32);
+    std::vector<int8_t> errs(ek ? 0 : B * N);
+    std::vector<uint8_t> seeds(B * 32), ekeys(ek ? B * 32 : 0);
     for (size_t b = 0; b < B; b++) {
       std::copy(vals[b]->begin(), vals[b]->end(), flat.begin() + b * nv);
-      std::copy(e[b].begin(), e[b].end(), errs.begin() + b * N);
+      if (ek) std::copy(ek[b].begin(), ek[b].end(), ekeys.begin() + b * 32);
+      else std::copy(e[b].begin(), e[b].end(), errs.begin() + b * N);
       std::copy(sd[b].begin(), sd[b].end(), seeds.begin() + b * 32);
     }
     evah_ct *c = nullptr;
-    const int rc = evah_encode_encrypt_symmetric_many(dev->h, (uint32_t)B, flat.data(), (uint32_t)nv, limbs, scale, errs.data(), seeds.data(), &c);
+    const int rc = ek ? evah_encode_encrypt_symmetric_sampled_many(dev->h, (uint32_t)B, flat.data(), (uint32_t)nv, limbs, scale, ekeys.data(),
+                                                                   seeds.data(), &c)
+                      : evah_encode_encrypt_symmetric_many(dev->h, (uint32_t)B, flat.data(), (uint32_t)nv, limbs, scale, errs.data(),
+                                                           seeds.data(), &c);
     wipe(errs);
+    wipe_bytes(ekeys.data(), ekeys.size());
     chk(rc);
     CtHandle group(dev->h, c); // the instances share its allocation, which lives until the last view is freed
     std::vector<HostCipher> out(B);

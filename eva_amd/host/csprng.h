@@ -55,6 +55,36 @@ inline void seeded_limb(const uint8_t seed[32], uint32_t prime, uint64_t q, uint
   }
 }
 
+// Small polynomial p of the value whose 32-byte randomness key is rk: p = 0 the ternary u, p = 1 the
+// error e0 (the one error of a symmetric encryption), p = 2 the error e1.  Coefficient j takes the little-endian u64
+// word w = j % 8 of the ChaCha20 block with key = rk, block counter j / 8 (state words 12-13), nonce
+// 0x736d000000000000 | p (words 14-15).  Ternary: floor(3 w / 2^64) - 1, no rejection, every outcome within 2^-64 of
+// 1/3.  Error: HostContext::sample_error's rule on w.  The device twin is csrc/sampled.hip.h.
+inline void sampled_small(const uint8_t rk[32], uint32_t p, uint32_t N, int8_t *out) {
+  static const uint32_t sigma[4] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u};
+  uint32_t st[16], w[16];
+  std::memcpy(st, sigma, 16);
+  std::memcpy(st + 4, rk, 32);
+  const uint64_t nonce = 0x736d000000000000ull | p;
+  st[14] = (uint32_t)nonce;
+  st[15] = (uint32_t)(nonce >> 32);
+  for (uint32_t j0 = 0; j0 < N; j0 += 8) {
+    const uint64_t blk = j0 / 8;
+    st[12] = (uint32_t)blk;
+    st[13] = (uint32_t)(blk >> 32);
+    chacha20_block(st, w);
+    for (uint32_t r = 0; r < 8 && j0 + r < N; r++) {
+      const uint64_t x = (uint64_t)w[2 * r] | ((uint64_t)w[2 * r + 1] << 32);
+      out[j0 + r] = p == 0 ? (int8_t)((int)(uint64_t)(((unsigned __int128)x * 3) >> 64) - 1)
+                           : (int8_t)(__builtin_popcountll(x & 0x1FFFFF) - __builtin_popcountll((x >> 21) & 0x1FFFFF));
+    }
+  }
+  volatile uint32_t *v = st; // the key and the last block do not stay on the stack
+  for (int i = 0; i < 16; i++) v[i] = 0;
+  v = w;
+  for (int i = 0; i < 16; i++) v[i] = 0;
+}
+
 class SecureRng {
 public:
   using result_type = uint64_t;

@@ -263,6 +263,14 @@ PYBIND11_MODULE(_eva, m) {
     return kp;
   }, py::arg("abstract_params"), py::arg("seed") = 0, py::arg("devices") = py::none(), py::arg("shard") = py::none(),
      py::arg("compress_keys") = false, py::arg("device_keygen") = false);
+  // test hook: small polynomial p of a 32-byte randomness key (csprng.h sampled_small) -> int8 [N]
+  mseal.def("_sampled_small", [](py::bytes rk, uint32_t p, uint32_t N) {
+    const std::string k = rk;
+    if (k.size() != 32) throw std::invalid_argument("a randomness key is 32 bytes");
+    py::array_t<int8_t> out({(py::ssize_t)N});
+    sampled_small((const uint8_t *)k.data(), p, N, out.mutable_data());
+    return out;
+  }, py::arg("rkey"), py::arg("p"), py::arg("N"));
   py::class_<HipValuation>(mseal, "SEALValuation", "Inputs or outputs of execute(): ciphertexts, plaintexts or raw vectors")
       .def(py::init<>())
       .def("_set_cipher", [](HipValuation &v, const std::string &name, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> data, double scale) {
@@ -334,12 +342,35 @@ PYBIND11_MODULE(_eva, m) {
         v.params = p.host;
         return v;
       }, py::arg("inputs"), py::arg("signature"))
-      .def("encrypt_batch", [](HipPublic &p, const std::vector<Valuation> &inputs, const CKKSSignature &sig) {
-        std::vector<HipValuation> out = p.encrypt_batch(inputs, sig);
+      .def("encrypt_batch", [](HipPublic &p, const std::vector<Valuation> &inputs, const CKKSSignature &sig, bool device_sampling, uint64_t seed) {
+        std::vector<HipValuation> out = p.encrypt_batch(inputs, sig, device_sampling, seed);
         for (HipValuation &v : out) v.params = p.host;
         return out;
-      }, py::arg("inputs"), py::arg("signature"),
-           "encrypt() for a list of input valuations with the same input names; per name the instances are encoded and encrypted 64 at a time in one device call")
+      }, py::arg("inputs"), py::arg("signature"), py::arg("device_sampling") = false, py::arg("seed") = 0,
+           "encrypt() for a list of input valuations with the same input names; per name the instances are encoded and encrypted 64 at a time in one device call. "
+           "device_sampling: each encrypted input's u, e0, e1 are expanded from a 32-byte randomness key, on the device in the grouped calls "
+           "(DESIGN.md 1.7); seed != 0 (with device_sampling only): reproducible test stream, not secret-grade")
+      // test hook: the host encoder + the host encryptor on the caller's randomness, small = int8 [3][N] = (u, e0, e1)
+      .def("_encrypt_with", [](const HipPublic &p, const std::vector<double> &values, uint32_t scale_bits, uint32_t level,
+                               py::array_t<int8_t, py::array::c_style | py::array::forcecast> small) {
+        const HostContext &h = *p.host;
+        const size_t slots = h.N / 2, N = h.N;
+        if (values.empty() || slots % values.size()) throw std::runtime_error("Size must exactly divide slots");
+        if (level >= h.k - 1) throw std::runtime_error("Encode level exceeds the modulus chain");
+        if (small.ndim() != 2 || small.shape(0) != 3 || small.shape(1) != (py::ssize_t)N) throw std::invalid_argument("small must be int8 [3][N]");
+        HostPlain pt;
+        pt.limbs = h.k - 1 - level;
+        pt.scale = std::pow(2.0, (double)scale_bits);
+        pt.data.resize((size_t)pt.limbs * N);
+        std::vector<double> vec;
+        for (size_t r = slots / values.size(); r > 0; --r) vec.insert(vec.end(), values.begin(), values.end());
+        h.encode_coeff(vec.data(), pt.scale, pt.limbs, pt.data.data());
+        for (uint32_t i = 0; i < pt.limbs; i++) h.ntt(i, pt.data.data() + (size_t)i * N);
+        const int8_t *d = small.data();
+        const HostCipher c = evahost::encrypt(h, p.pk, pt, std::vector<int8_t>(d, d + N), std::vector<int8_t>(d + N, d + 2 * N),
+                                              std::vector<int8_t>(d + 2 * N, d + 3 * N));
+        return to_numpy(c.data, {2, (py::ssize_t)c.limbs, (py::ssize_t)N});
+      }, py::arg("values"), py::arg("scale_bits"), py::arg("level"), py::arg("small"))
       .def("execute", [](HipPublic &p, Program &program, const HipValuation &inputs) {
         HipValuation v = p.execute(program, inputs);
         v.params = p.host;
@@ -465,13 +496,14 @@ PYBIND11_MODULE(_eva, m) {
       }, py::arg("inputs"), py::arg("signature"), py::arg("seed") = 0,
          "Secret-key encryption: every ciphertext is c0 plus the 32-byte seed of c1 (half the bytes of SEALPublic.encrypt). "
          "seed != 0: reproducible test streams, not secret-grade")
-      .def("encrypt_batch", [](HipSecret &s, const std::vector<Valuation> &inputs, const CKKSSignature &sig, uint64_t seed) {
-        std::vector<HipValuation> out = s.encrypt_batch(inputs, sig, seed);
+      .def("encrypt_batch", [](HipSecret &s, const std::vector<Valuation> &inputs, const CKKSSignature &sig, uint64_t seed, bool device_sampling) {
+        std::vector<HipValuation> out = s.encrypt_batch(inputs, sig, seed, device_sampling);
         for (HipValuation &v : out) v.params = s.host;
         return out;
-      }, py::arg("inputs"), py::arg("signature"), py::arg("seed") = 0,
+      }, py::arg("inputs"), py::arg("signature"), py::arg("seed") = 0, py::arg("device_sampling") = false,
          "encrypt() for a list of input valuations with the same input names: one pair of random streams for the call, instances in list "
-         "order and names sorted within an instance, so instance 0 of a seeded call equals encrypt() and no two values share a seed")
+         "order and names sorted within an instance, so instance 0 of a seeded call equals encrypt() and no two values share a seed. "
+         "device_sampling: each error polynomial is expanded from a 32-byte key of the secret stream, on the device in the grouped calls (DESIGN.md 1.7)")
       .def("decrypt", &HipSecret::decrypt, py::arg("enc_outputs"), py::arg("signature"))
       .def("decrypt_batch", &HipSecret::decrypt_batch, py::arg("enc_outputs"), py::arg("signature"),
            "decrypt() of every valuation of a list, bit for bit; on the device up to 64 outputs of one name are decrypted and decoded in one call")

@@ -85,7 +85,12 @@ public:
   // SEALPublic::encrypt (seal.cpp:24-102)
   HipValuation encrypt(const Valuation &inputs, const CKKSSignature &sig);
   // encrypt() of every valuation of a list, the device work batched per input name (client.h)
-  std::vector<HipValuation> encrypt_batch(const std::vector<Valuation> &inputs, const CKKSSignature &sig);
+  // device_sampling: every encrypted input draws a 32-byte randomness key instead of 3 N coefficients and
+  // its u, e0, e1 are expanded from it — on the device for the grouped calls, by the host twin (csprng.h sampled_small)
+  // on every other path, so one (seed, inputs) gives one ciphertext wherever it is computed.  seed != 0 (with
+  // device_sampling only): the reproducible test stream SecureRng(seed, 5), NOT secret-grade.
+  std::vector<HipValuation> encrypt_batch(const std::vector<Valuation> &inputs, const CKKSSignature &sig, bool device_sampling = false,
+                                          uint64_t seed = 0);
 
   // SEALPublic::execute (seal.cpp:104-122) — THE hot path.  First call for a program: upload
   // inputs, walk the DAG issuing HIP work over the queues, download outputs.  From the second call
@@ -506,9 +511,19 @@ private:
   bool device_encodable(const std::vector<double> &in, double scale, uint32_t limbs) const;
   // coeff_pt: the host encoder's coefficient-form plaintext, or (null) values: the slot values for the device encoder
   HostCipher encrypt_on_device(const HostPlain *coeff_pt, const std::vector<double> *values, double scale, uint32_t limbs, SecureRng &rng);
+  // the same with the caller's randomness: small = (u, e0, e1) as int8 [3][N]
+  HostCipher encrypt_on_device_with(const HostPlain *coeff_pt, const std::vector<double> *values, double scale, uint32_t limbs,
+                                    const std::vector<int8_t> &small);
+  // one Cipher input of encrypt() with the caller's randomness, on the path encrypt() would take for it
+  HostCipher encrypt_value_with(const std::vector<double> &v, double scale, uint32_t limbs, const std::vector<int8_t> &small);
   // <= 64 instances of one input as one evah_encode_encrypt_many; the values encrypt_on_device would return
   std::vector<HostCipher> encrypt_group_on_device(const std::vector<const std::vector<double> *> &vals, double scale, uint32_t limbs,
                                                   SecureRng &rng);
+  // the same as one evah_encode_encrypt_sampled_many: instance b's randomness is drawn on the device from rkeys[b]
+  std::vector<HostCipher> encrypt_group_sampled(const std::vector<const std::vector<double> *> &vals, double scale, uint32_t limbs,
+                                                const std::array<uint8_t, 32> *rkeys);
+  // the resident views (or downloads) of a group's batched handle: what both group calls return
+  std::vector<HostCipher> group_results(evah_ct *c, size_t B, double scale, uint32_t limbs);
 
   // eval_keys = false: encryption and limb-sharded execution (whose shards hold their own rows of the
   // keys) do not need the whole evaluation keys in this device's memory

@@ -341,6 +341,21 @@ int evah_encode_encrypt_many(evah_ctx *ctx, uint32_t batch, const double *values
  * Encryptor::encrypt_symmetric); e int8 [batch][N], seeds [batch][32]; needs EVAH_KEY_SECRET */
 int evah_encode_encrypt_symmetric_many(evah_ctx *ctx, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs,
                                        double scale, const int8_t *e, const uint8_t *seeds, evah_ct **out);
+/* The same two calls with the small polynomials drawn on the device in place of the randomness that
+ * seal.cpp:85 `encryptor.encrypt` takes from SEAL's generator on the host: a 32-byte randomness key per instance travels
+ * instead of 3 N (N) int8 coefficients.  sampled_small(key, p) is the expansion of eva_amd/host/csprng.h.  The keys are
+ * secrets: they go up as a pool buffer on ctx's queue, and that buffer, the sampled residues and their NTT forms are
+ * zeroed on the queue before they return to the pool, also when the call fails.  Checks, messages, launches per call
+ * and the one drain are those of the calls above. */
+/* evah_encode_encrypt_many with small[b] = (sampled_small(rkeys[b], 0), sampled_small(rkeys[b], 1),
+ * sampled_small(rkeys[b], 2)) word for word (seal.cpp:24-102); rkeys [batch][32] */
+int evah_encode_encrypt_sampled_many(evah_ctx *ctx, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs,
+                                     double scale, const uint8_t *rkeys, evah_ct **out);
+/* evah_encode_encrypt_symmetric_many with e[b] = sampled_small(ekeys[b], 1) word for word (seal.cpp:24-102 with
+ * Encryptor::encrypt_symmetric); ekeys [batch][32] (secret), seeds [batch][32] (public) */
+int evah_encode_encrypt_symmetric_sampled_many(evah_ctx *ctx, uint32_t batch, const double *values, uint32_t n_values,
+                                               uint32_t limbs, double scale, const uint8_t *ekeys, const uint8_t *seeds,
+                                               evah_ct **out);
 /* out[i] = the n_out doubles evah_decrypt_decode(cts[i]) returns, bit pattern for bit pattern (seal.cpp:124-146); the n
  * single ciphertexts (views included) share one size, limb count and scale and are read in place; out [n][n_out] */
 int evah_decrypt_decode_many(evah_ctx *ctx, const evah_ct *const *cts, uint32_t n, uint32_t n_out, double *out);

@@ -10,6 +10,8 @@ execute_batch, one ciphertext at a time and with the batched calls.
 the same box.  --batch 1 is public_ctx.encrypt_batch / secret_ctx.decrypt_batch.  Both legs run the same execute_batch
 between them.  Each run prints one line: the median wall time of the three phases over --repeat runs after --warmup
 runs (the first run builds tables and plans).  --secret encrypts with the secret key (seeded ciphertexts) instead.
+--sampling device (with --batch 1) draws the encryption randomness on the device from a 32-byte key per value
+(DESIGN.md 1.7); --sampling host, the default, is the host sampler.
 
 Kernel launches per call: run one leg under the profiler, which this script never starts itself and with no counters in
 that run,
@@ -36,9 +38,13 @@ ap.add_argument("--instances", type=int, default=0, help="instances (default: 25
 ap.add_argument("--repeat", type=int, default=5)
 ap.add_argument("--warmup", type=int, default=1)
 ap.add_argument("--secret", action="store_true", help="secret-key encryption (seeded ciphertexts)")
+ap.add_argument("--sampling", choices=["host", "device"], default="host",
+                help="device: encrypt_batch(..., device_sampling=True), the randomness drawn on the device (needs --batch 1)")
 ap.add_argument("--phase", choices=["all", "encrypt", "decrypt"], default="all",
                 help="encrypt: no execute_batch and no decryption; decrypt: one untimed encryption and execute_batch, then decryptions alone")
 args = ap.parse_args()
+if args.sampling == "device" and not args.batch:
+    ap.error("--sampling device needs --batch 1: the single calls sample on the host")
 
 from eva.seal import generate_keys
 from eva_amd import workloads
@@ -49,10 +55,11 @@ xs = [workloads.image(4096, shift=b) for b in range(B)]
 pub, sec = generate_keys(params, 1)
 batched = bool(args.batch)
 enc_ctx = sec if args.secret else pub
+on_device = args.sampling == "device"
 
 
 def encrypt():
-    return enc_ctx.encrypt_batch(xs, sig) if batched else [enc_ctx.encrypt(x, sig) for x in xs]
+    return enc_ctx.encrypt_batch(xs, sig, device_sampling=on_device) if batched else [enc_ctx.encrypt(x, sig) for x in xs]
 
 
 def decrypt(outs):
@@ -93,6 +100,6 @@ def med(t):
     return f"{statistics.median(t) * 1e3:.2f} ms" if t else "-"
 
 
-print(f"{args.what} batch={int(batched)} secret={int(args.secret)}: N={pub.poly_modulus_degree} k={len(pub.primes)} instances={B}; "
+print(f"{args.what} batch={int(batched)} secret={int(args.secret)} sampling={args.sampling}: N={pub.poly_modulus_degree} k={len(pub.primes)} instances={B}; "
       f"medians over {args.repeat} runs after {args.warmup} warm-up: encrypt all inputs {med(t_enc)}, execute_batch {med(t_exe)}, "
       f"decrypt all outputs {med(t_dec)}")
