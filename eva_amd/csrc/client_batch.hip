@@ -285,7 +285,8 @@ struct Wipe {
 };
 
 // the checks both encryption calls share, in the order evah_pt_encode and the encryptors make them
-static void encode_many_checks(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, evah_ct **out) {
+static void encode_many_checks(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale,
+                               evah_ct **out) {
   if (c->capturing) throw std::logic_error("this call synchronises with the host and cannot be captured into a graph");
   if (batch < 1 || batch > (uint32_t)KS_BATCH_MAX) throw std::invalid_argument("batch must be 1..64");
   if (!values) throw std::invalid_argument("value pointer is null");
@@ -294,6 +295,7 @@ static void encode_many_checks(evah_ctx *c, uint32_t batch, const double *values
   const uint32_t slots = c->N >> 1;
   if (n_values < 1 || n_values > slots || slots % n_values) throw std::invalid_argument("value count must divide the slot count");
   if (c->N % 256) throw std::invalid_argument("encryption needs N divisible by 256");
+  check_encodable(c, values, batch, n_values, scale); // evah_pt_encode's: "encoded values are too large"
 }
 // values [batch][n_values] (host) -> NTT-form plaintexts pt [batch][limbs][N] on the queue; vals, cbuf: the call's scratch
 static void encode_many(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale, u64 *vals,
@@ -327,7 +329,7 @@ static void count_client_h2d(evah_ctx *c, size_t bytes) { c->sh->xfer[4] += byte
 static void encode_encrypt_many(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale,
                                 const int8_t *small, const uint8_t *rkeys, evah_ct **out) {
   use(c);
-  encode_many_checks(c, batch, values, n_values, limbs, out);
+  encode_many_checks(c, batch, values, n_values, limbs, scale, out);
   if (!small && !rkeys) throw std::invalid_argument("randomness pointer is null");
   if (!c->sh->pk.d) throw std::invalid_argument("public key not present");
   const uint32_t l = limbs, up = l + 1;
@@ -373,7 +375,7 @@ static void encode_encrypt_many(evah_ctx *c, uint32_t batch, const double *value
 static void encode_encrypt_symmetric_many(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale,
                                           const int8_t *e, const uint8_t *ekeys, const uint8_t *seeds, evah_ct **out) {
   use(c);
-  encode_many_checks(c, batch, values, n_values, limbs, out);
+  encode_many_checks(c, batch, values, n_values, limbs, scale, out);
   if (!c->sh->sk.d) throw std::invalid_argument("secret key not present");
   if ((!e && !ekeys) || !seeds) throw std::invalid_argument("error polynomial and seed are required");
   const uint32_t l = limbs;

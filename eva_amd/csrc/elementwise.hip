@@ -411,9 +411,9 @@ void enc_tables(evah_ctx *c) {
 extern "C" {
 
 // CKKSEncoder::encode of `n_values` reals replicated over the N/2 slots, at 2^scale_bits... (scale is
-// passed as the double SEAL takes), to `limbs` primes, NTT form.  The caller guarantees that every
-// coefficient round(x * scale / N) is below 2^62 in magnitude (the host checks a bound on
-// sum |values|); larger encodings take the host's multi-precision path + evah_pt_upload_coeff.
+// passed as the double SEAL takes), to `limbs` primes, NTT form.  Every coefficient round(x * scale / N)
+// must be below 2^62 in magnitude: check_encodable refuses non-finite values and a bound on sum |values|
+// of 62 bits or more; larger encodings take the host's multi-precision path + evah_pt_upload_coeff.
 int evah_pt_encode(evah_ctx *c, const double *values, uint32_t n_values, uint32_t limbs, double scale, evah_pt **out) {
   API_BEGIN
   use(c);
@@ -421,6 +421,8 @@ int evah_pt_encode(evah_ctx *c, const double *values, uint32_t n_values, uint32_
   if (limbs < 1 || limbs > c->k - 1) throw std::invalid_argument("invalid limb count for this context");
   const uint32_t N = c->N, slots = N >> 1;
   if (n_values < 1 || n_values > slots || slots % n_values) throw std::invalid_argument("value count must divide the slot count");
+  if (!values) throw std::invalid_argument("value pointer is null");
+  check_encodable(c, values, 1, n_values, scale);
   enc_tables(c);
   evah_pt *t = pt_new(c, limbs, scale);
   try {

@@ -641,6 +641,25 @@ inline void check_scale(evah_ctx *c, double scale, uint32_t limbs) {
   if (!(scale > 0) || (int)std::log2(scale) >= c->total_bits[limbs])
     throw std::invalid_argument("scale out of bounds");
 }
+// what the device encoder can represent (k_enc_round: |coefficient| as one u64 word, documented below 2^62): every
+// value finite, and the a-priori coefficient bound of the host's device_encodable (eva_amd/host/client.h) — no
+// coefficient exceeds it — below 2^62, per instance of values [batch][n_values].  device_encodable itself stops two
+// bits earlier (bit count with sign < 62), so the product's wrappers never reach this refusal.  SEAL's message for a
+// coefficient beyond the modulus; the total-modulus rule itself is not applied.  Nothing has been launched when this
+// throws.
+inline void check_encodable(const evah_ctx *c, const double *values, uint32_t batch, uint32_t n_values, double scale) {
+  const uint32_t slots = c->N >> 1;
+  for (uint32_t b = 0; b < batch; b++) {
+    double sum = 0;
+    for (uint32_t i = 0; i < n_values; i++) {
+      const double x = values[(size_t)b * n_values + i];
+      if (!std::isfinite(x)) throw std::invalid_argument("encoded values are too large");
+      sum += std::fabs(x);
+    }
+    const double bound = 2.0 * sum * (double)(slots / n_values) * scale / (double)c->N;
+    if (!(bound < 4611686018427387904.0)) throw std::invalid_argument("encoded values are too large"); // 2^62; also inf
+  }
+}
 inline bool same_scale(double a, double b) {
   // SEAL util::are_close<double>
   double scale_factor = std::max({std::fabs(a), std::fabs(b), 1.0});

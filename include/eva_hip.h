@@ -177,9 +177,12 @@ int evah_pt_upload_coeff(evah_ctx *ctx, uint32_t limbs, double scale, const uint
                          evah_pt **out);
 /* encoder.encode (seal_executor.h:242) entirely on the device: `n_values` reals (replicated over
  * the N/2 slots as seal_executor.h:226-240 does) -> inverse special FFT in FP64 -> round(x*scale/N)
- * -> residues -> NTT.  Bit-identical to the host encoder followed by evah_pt_upload_coeff; valid when
- * every rounded coefficient is below 2^62 in magnitude (the caller checks a bound), otherwise use
- * the host's multi-precision path */
+ * -> residues -> NTT.  Bit-identical to the host encoder followed by evah_pt_upload_coeff.  The device
+ * keeps |coefficient| in one 64-bit word, so the call refuses, before anything is launched and with SEAL's
+ * "encoded values are too large", a non-finite value and an a-priori coefficient bound that reaches 2^62:
+ *   bound = 2 * sum |values| * (slots / n_values) * scale / N  (no coefficient exceeds it),  refused unless bound < 2^62.
+ * Such encodings take the host's multi-precision path + evah_pt_upload_coeff.  SEAL's own total-modulus
+ * rule is not applied here.  The four evah_encode_encrypt_*many calls below make the same check per instance. */
 int evah_pt_encode(evah_ctx *ctx, const double *values, uint32_t n_values, uint32_t limbs, double scale, evah_pt **out);
 /* plaintext whose every slot is the same residue per limb: encode of a uniform constant
  * (Program::makeUniformConstant, program.h:58-60) — value[i] = round(c*scale) mod primes[i]. */
@@ -332,7 +335,9 @@ int evah_ct_download_poly(evah_ctx *ctx, const evah_ct *ct, uint32_t poly, uint6
  * encoder.encode + encryptor.encrypt per input) and of SEALSecret::decrypt (seal.cpp:124-146: decryptor.decrypt +
  * encoder.decode per output) does for the instances of evah_execute's batches, as one launch set whose length does not
  * depend on the batch.  1 <= batch, n <= 64.  One host->device copy per input array, one device->host copy of the
- * result and one drain of ctx's queue per call; the plaintexts exist only in pool scratch. */
+ * result and one drain of ctx's queue per call; the plaintexts exist only in pool scratch.  The encryption calls
+ * refuse what evah_pt_encode refuses ("encoded values are too large": a non-finite value or a coefficient bound of
+ * 2^62 or more in any instance), before anything is launched. */
 /* instance b = evah_pt_encode(values[b]) -> evah_encrypt(small[b]) word for word (seal.cpp:24-102); values
  * [batch][n_values], small int8 [batch][3][N]; out: one batched handle [batch][2][limbs][N] */
 int evah_encode_encrypt_many(evah_ctx *ctx, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale,
