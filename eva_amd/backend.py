@@ -42,6 +42,7 @@ _SIGS = {
     "evah_ct_assign": [_vp, _vp, _vp],
     "evah_ctx_wait": [_vp, _vp],
     "evah_ctx_transfer_stats": [_vp, _u64p],
+    "evah_ctx_modup_variant": [_vp, C.POINTER(C.c_uint32)],
     "evah_ctx_key_bytes": [_vp, _u64p],
     "evah_ctx_key_bytes_detail": [_vp, _u64p],
     "evah_ctx_key_upload_stats": [_vp, _u64p],
@@ -599,6 +600,12 @@ class Context:
         out = (C.c_uint64 * 6)()
         _chk(_lib.evah_ctx_transfer_stats(self.h, out))
         return tuple(int(x) for x in out)
+
+    def modup_variant(self):
+        """(log2 coefficients per thread, top-bit butterflies only, lazy conversion only) of this context's mod-up kernel"""
+        out = (C.c_uint32 * 3)()
+        _chk(_lib.evah_ctx_modup_variant(self.h, out))
+        return int(out[0]), bool(out[1]), bool(out[2])
 
     def key_bytes(self):
         """bytes of HBM the evaluation keys of this device state occupy (a limb shard holds its prime rows only)"""

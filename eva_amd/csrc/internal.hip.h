@@ -328,6 +328,13 @@ struct Tunables {
   // launch, a workgroup per digit tile (ntt_modup_kernel, ntt_modup.hip.h); 0 = the strided inverse pass storing the
   // canonical digits, then the OpKsDigit strided pass reading each digit tile once per output prime
   bool modup = true;
+  // EVAH_MODUP_LR (3): log2 coefficients per thread of ntt_modup_kernel on its 2048-coefficient tile — 3 = 256 threads
+  // (84 VGPRs, 5 waves per SIMD at P = 8: headline +2.6 % over the r07 kernel), 2 = 512 threads (62 VGPRs, 8 waves per
+  // SIMD, a fourth LDS round trip per pass: level with the r07 kernel, so not the default) — profiles/r08_modup_notes.md
+  // EVAH_MODUP_SPEC (1): the mod-up runs the instantiation specialised to what the context's primes allow
+  // (evah_ctx::modup_tb / modup_lazy: top-bit butterflies only, lazy digit conversion only); 0 = the generic kernel
+  int modup_lr = 3;
+  bool modup_spec = true;
   // EVAH_LDS_EXTRA (0): bytes of dynamic LDS added to every ntt_pass_kernel launch — an occupancy probe for the
   // tuning notes (fewer workgroups per CU), never set in production
   uint32_t lds_extra = 0;
@@ -368,6 +375,8 @@ struct Tunables {
     flag("EVAH_CHAIN_BATCHED", t.chain_batched);
     count("EVAH_CHAIN_FUSE_BLOCKS", t.chain_fuse_blocks);
     flag("EVAH_MODUP", t.modup);
+    if (const char *e = std::getenv("EVAH_MODUP_LR")) t.modup_lr = std::atoi(e) == 2 ? 2 : 3;
+    flag("EVAH_MODUP_SPEC", t.modup_spec);
     count("EVAH_HOIST_V", t.hoist_v);
     if (const char *e = std::getenv("EVAH_KS_GROUPS")) t.ks_groups = std::max(1, std::atoi(e));
     if (const char *e = std::getenv("EVAH_KS_THREADS")) {
@@ -394,6 +403,10 @@ struct evah_ctx {
   std::vector<hipEvent_t> sync_events; // recycled events for cross-queue ordering
   Tunables tun; // launch-shape decisions, read from the environment once when the context is created
   bool all_tb = false; // every prime is 2^b - c with b > 32, c < 2^32 (DevPrime::tb_c != 0) or below 2^54: ks_inner_kernel<MAC3> applies
+  // what ntt_modup_kernel may assume of this context's primes (modup_variant below): every prime has the top-bit
+  // shape (tb_c != 0 — stricter than all_tb, whose "< 2^54" clause admits other shapes) / q_J <= 8 q_kappa for every
+  // digit prime J < k - 1 and every output prime kappa < k (the special prime included), so at every level
+  bool modup_tb = false, modup_lazy = false;
   // per-launch profile
   bool prof_on = false;
   std::vector<ProfRec> prof_recs;
@@ -403,6 +416,18 @@ struct evah_ctx {
 };
 
 namespace evah {
+
+// the instantiation a context's mod-up launches take (launch_modup, launch.hip.h): coefficients per thread and the two
+// specialisations its primes allow (ntt_modup.hip.h); EVAH_MODUP_SPEC=0, or a build without the top-bit butterflies
+// (EVAH_TOPBIT=0, ntt.hip.h), keeps the generic kernel
+#ifndef EVAH_TOPBIT
+#define EVAH_TOPBIT 1
+#endif
+struct ModupVariant { int lr; bool tbonly, lazyonly; };
+inline ModupVariant modup_variant(const evah_ctx *c) {
+  const bool tb = c->tun.modup_spec && EVAH_TOPBIT && c->modup_tb;
+  return {c->tun.modup_lr, tb, tb && c->modup_lazy};
+}
 
 inline void use(evah_ctx *c) { HIPCHK(hipSetDevice(c->device)); }
 inline void count_h2d(evah_ctx *c, size_t bytes, bool plain = false) { c->sh->xfer[plain ? 2 : 0]++; c->sh->xfer[4] += bytes; }

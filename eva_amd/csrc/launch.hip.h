@@ -194,16 +194,32 @@ template <class Op> static void launch_inv_fwd(evah_ctx *c, const typename Op::P
 // ---- the key switch's mod-up at throughput size: strided inverse pass of each digit, then its conversion and forward
 // strided pass under every output prime of prm (i0 = 0, istep = 1), one workgroup per (column tile, digit, instance) —
 // ntt_modup_kernel (ntt_modup.hip.h).  n = instances; the digits' contiguous inverse pass left its intermediate in prm.t
+// Both shapes (Tunables::modup_lr) work on 2048-coefficient tiles: N >= 2048 and P <= 9.
 static inline bool modup_fits(evah_ctx *c) { return c->N >= ((uint32_t)NTT_THREADS << 3) && (c->logN + 1) / 2 <= 9; }
-template <int P, class Op> static void launch_modup_p(evah_ctx *c, const typename Op::Params &prm, uint32_t n) {
+template <int P, int LR, class Op, bool TBONLY, bool LAZYONLY>
+static void launch_modup_v(evah_ctx *c, const typename Op::Params &prm, uint32_t n) {
   ProfScope ps(c, OpClass<Op>::fwd_a);
-  constexpr int LR = 3;
-  const uint32_t tile = (uint32_t)NTT_THREADS << LR, n_tiles = c->N / tile;
+  // 8 coefficients per thread: 256 threads; 4 per thread: 512 threads.  Either way a 2048-coefficient tile, 2^(11 - P)
+  // columns wide — at P = 8 a row segment of 64 bytes (4 per thread on 256 threads, a 1024-coefficient tile with 32-byte
+  // segments, ran 2.8 times slower: profiles/r08_modup_notes.md)
+  constexpr int NT = LR == 2 ? 2 * NTT_THREADS : NTT_THREADS;
+  const uint32_t tile = (uint32_t)NT << LR, n_tiles = c->N / tile;
   const int logC = (int)ilog2(tile) - P;
   const size_t lds = ((((size_t)1 << logC) * lds_sub_stride<P>() + 1) & ~(size_t)1) * sizeof(u64) + ((size_t)1 << P) * sizeof(ulonglong2);
-  hipLaunchKernelGGL((ntt_modup_kernel<P, LR, Op>), dim3(n_tiles * prm.l, 1, n), dim3(NTT_THREADS), lds, c->stream, c->dev, prm,
-                     (int)ilog2(n_tiles));
+  hipLaunchKernelGGL((ntt_modup_kernel<P, LR, Op, TBONLY, LAZYONLY, NT>), dim3(n_tiles * prm.l, 1, n), dim3(NT), lds, c->stream,
+                     c->dev, prm, (int)ilog2(n_tiles));
   HIPCHK(hipGetLastError());
+}
+template <int P, class Op> static void launch_modup_p(evah_ctx *c, const typename Op::Params &prm, uint32_t n) {
+  const ModupVariant v = modup_variant(c);
+  auto go = [&](auto lrtag) {
+    constexpr int LR = decltype(lrtag)::value;
+    if (v.lazyonly) launch_modup_v<P, LR, Op, true, true>(c, prm, n);
+    else if (v.tbonly) launch_modup_v<P, LR, Op, true, false>(c, prm, n);
+    else launch_modup_v<P, LR, Op, false, false>(c, prm, n);
+  };
+  if (v.lr == 2) go(std::integral_constant<int, 2>{});
+  else go(std::integral_constant<int, 3>{});
 }
 template <class Op> static void launch_modup(evah_ctx *c, const typename Op::Params &prm, uint32_t n) {
   if (!modup_fits(c) || prm.i0 != 0 || prm.istep != 1) throw std::logic_error("mod-up kernel outside its shapes");

@@ -15,14 +15,29 @@ namespace evah {
 // it once per output row).  t never reaches memory, and the digit tile is read once instead of l times.
 // Each row's forward twiddles are requested during the previous row's butterflies and staged in the one twiddle
 // buffer once those are done: LDS holds the tile and 2^P twiddles, as the stand-alone strided pass.
-// grid = (n_tiles * l, 1, batch) with the tile in the low log_tiles bits of x, block = NTT_THREADS, tile = NTT_THREADS << LR.
-template <int P, int LR, class Op>
-__global__ void __launch_bounds__(NTT_THREADS)
+// grid = (n_tiles * l, 1, batch) with the tile in the low log_tiles bits of x, block = NT, tile = NT << LR.
+// The host launches LR = 3 on 256 threads or LR = 2 on 512 (a fourth LDS round trip per pass at P = 8, fewer registers):
+// either way a 2048-coefficient tile whose row segments are 2^(11 - P) words (launch_modup_v, launch.hip.h).
+// The row loop is what decides the kernel's registers, and with them the waves per SIMD.  Two facts about a context's
+// primes, established once on the host (evah_ctx::modup_tb / modup_lazy), each remove a code path that would otherwise
+// be live beside the one taken:
+//   TBONLY    every prime has the top-bit shape (DevPrime::tb_c != 0): the forward rounds are the top-bit RoundSeq, no
+//             block-uniform choice between it and the compare-and-subtract family
+//   LAZYONLY  q_J <= 8 q_kappa for every digit / output prime pair: only Op::conv<true> is instantiated (jb.lazy holds
+//             for every job)
+// A context that fails either test runs the generic instantiation; all of them leave the same words.
+// A row's words leave through ONE buffer descriptor on the row's (workgroup-uniform) base: the per-thread part of the
+// address is a single 32-bit offset (8 n0) and the per-element part a scalar offset (8 it nstep), where flat stores made
+// the compiler keep 2^LR 64-bit addresses live across the row loop.  A row is at most 2^17 * 8 bytes: offsets fit 32 bits.
+// NT = threads per workgroup (this kernel only): the tile is NT << LR coefficients, 2^(log2 NT + LR - P) columns wide.
+template <int P, int LR, class Op, bool TBONLY = false, bool LAZYONLY = false, int NT = NTT_THREADS>
+__global__ void __launch_bounds__(NT)
 ntt_modup_kernel(DevCtx cx, typename Op::Params prm, int log_tiles) {
+  static_assert(NT == 256 || NT == 512, "ntt_modup_kernel: 256 or 512 threads");
   extern __shared__ __attribute__((aligned(16))) u64 lds[];
   constexpr int NTT_R = 1 << LR;
   constexpr int S = 1 << P, TPS = S / NTT_R, SP = lds_sub_stride<P>();
-  constexpr int logC = 8 + LR - P, C = 1 << logC, T = NTT_THREADS;
+  constexpr int logC = (NT == 512 ? 9 : 8) + LR - P, C = 1 << logC, T = NT;
   constexpr int TWR = (S + T - 1) / T; // twiddles staged per thread
   if (cx.skipped()) return;
   const uint32_t tile_idx = blockIdx.x & ((1u << log_tiles) - 1u), J = blockIdx.x >> log_tiles, b = blockIdx.z;
@@ -80,8 +95,8 @@ ntt_modup_kernel(DevCtx cx, typename Op::Params prm, int log_tiles) {
 #pragma unroll
       for (int it = 0; it < NTT_R; it++) lds[lds_at(it)] = Op::template conv<LZ>(jb, pm, t[it]);
     };
-    if (jb.lazy) convert(std::true_type{});
-    else convert(std::false_type{});
+    if (LAZYONLY || jb.lazy) convert(std::true_type{});
+    else if constexpr (!LAZYONLY) convert(std::false_type{});
     // next row with a job (block-uniform); its twiddles are in flight during this row's butterflies
     typename Op::Job jn;
     uint32_t in = iy + 1;
@@ -89,10 +104,19 @@ ntt_modup_kernel(DevCtx cx, typename Op::Params prm, int log_tiles) {
     const bool more = in < prm.ni;
     if (more) tw_request(jn.prime);
     __syncthreads();
-    forward_rounds<P, LR, true, false>(lds + sub * SP, tid, 0, 0, twl, pm);
+    if constexpr (TBONLY) RoundSeq<P, LR, 0, false, true, false, true, true>::run(lds + sub * SP, tid, 0, 0, twl, pm);
+    else forward_rounds<P, LR, true, false>(lds + sub * SP, tid, 0, 0, twl, pm);
     __syncthreads();
+    const __amdgpu_buffer_rsrc_t row = __builtin_amdgcn_make_buffer_rsrc(jb.dst, 0, 0x7fffffff, 0x00020000);
 #pragma unroll
-    for (int it = 0; it < NTT_R; it++) jb.dst[n0 + it * nstep] = lds[lds_at(it)]; // lazy intermediate of the forward transform
+    for (int it = 0; it < NTT_R; it++) { // lazy intermediate of the forward transform, at jb.dst[n0 + it * nstep]
+      typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+      const u64 v = lds[lds_at(it)];
+      u32x2 w;
+      w.x = (uint32_t)v;
+      w.y = (uint32_t)(v >> 32);
+      __builtin_amdgcn_raw_buffer_store_b64(w, row, 8u * n0, 8u * (uint32_t)it * nstep, 0);
+    }
     if (!more) break;
     jb = jn;
     iy = in;

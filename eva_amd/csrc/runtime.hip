@@ -154,6 +154,11 @@ int evah_ctx_create(uint32_t N, uint32_t k, const uint64_t *primes, int device, 
 #else
     for (uint32_t i = 0; i < k; i++) c->all_tb = c->all_tb && (hp[i].tb_c != 0 || hp[i].q < ((u64)1 << 54));
 #endif
+    c->modup_tb = c->modup_lazy = true;
+    for (uint32_t i = 0; i < k; i++) {
+      c->modup_tb = c->modup_tb && hp[i].tb_c != 0;
+      for (uint32_t J = 0; J + 1 < k; J++) c->modup_lazy = c->modup_lazy && c->primes[J] <= 8 * c->primes[i];
+    }
     c->sh = std::make_shared<SharedDev>();
     c->sh->device = device;
     HIPCHK(hipMalloc(&c->sh->d_tables, total));
@@ -195,6 +200,8 @@ int evah_ctx_fork(evah_ctx *parent, evah_ctx **out) {
     c->dev = parent->dev;
     c->tun = parent->tun;
     c->all_tb = parent->all_tb;
+    c->modup_tb = parent->modup_tb;
+    c->modup_lazy = parent->modup_lazy;
     HIPCHK(hipStreamCreateWithFlags(&c->own, hipStreamNonBlocking));
     c->stream = c->own;
     HIPCHK(hipEventCreate(&c->ev0));
@@ -655,6 +662,15 @@ int evah_ctx_wait(evah_ctx *waiter, evah_ctx *signaller) {
   use(waiter);
   if (waiter->capturing || signaller->capturing) throw std::logic_error("evah_ctx_wait cannot be captured into a graph");
   stream_wait(waiter, signaller);
+  API_END
+}
+
+int evah_ctx_modup_variant(evah_ctx *c, uint32_t out[3]) {
+  API_BEGIN
+  const ModupVariant v = modup_variant(c);
+  out[0] = (uint32_t)v.lr;
+  out[1] = v.tbonly;
+  out[2] = v.lazyonly;
   API_END
 }
 

@@ -151,6 +151,11 @@ int evah_ctx_wait(evah_ctx *waiter, evah_ctx *signaller);
  * The valuation of the reference "may hold device handles" (SURVEY.md 8(b)); tests assert that
  * encrypt -> execute -> decrypt moves no ciphertext across. */
 int evah_ctx_transfer_stats(evah_ctx *ctx, uint64_t out[6]);
+/* the instantiation of the key switch's mod-up kernel this context launches (EVAH_MODUP_LR / EVAH_MODUP_SPEC and the
+ * context's primes): out[0] = log2 coefficients per thread (3 or 2), out[1] = 1 when only the top-bit butterflies are
+ * compiled in (every prime 2^b - c, b > 32, c < 2^32), out[2] = 1 when only the lazy digit conversion is
+ * (q_J <= 8 q_kappa for every digit / output prime pair).  All of them compute the same words. */
+int evah_ctx_modup_variant(evah_ctx *ctx, uint32_t out[3]);
 /* bytes of HBM the evaluation keys (relinearization + Galois) of this context's device state occupy.  After
  * evah_ctx_set_shard(ctx, s, G) an upload keeps only shard s's prime rows of a key (its data limbs and the
  * special prime): (ceil((k-1)/G) + 1) / k of the whole key. */
