@@ -29,7 +29,7 @@ def _hipcc():
     raise RuntimeError("hipcc not found (need ROCm to build the gfx950 backend)")
 
 
-HIP_UNITS = ("runtime.hip", "elementwise.hip", "ewprogram.hip", "keyswitch.hip", "rotate.hip", "windows.hip", "shard.hip", "client.hip", "client_batch.hip", "seeded.hip", "scheduler.hip")
+HIP_UNITS = ("runtime.hip", "elementwise.hip", "ewprogram.hip", "keyswitch.hip", "rotate.hip", "windows.hip", "shard.hip", "client.hip", "seeded.hip", "scheduler.hip")
 HIP_HEADERS = tuple(sorted(f for f in os.listdir(CSRC) if f.endswith(".h")))  # every header of csrc/: a new one must not be missed (r6)
 
 

@@ -1,8 +1,10 @@
-// client.hip — the host-side neighbours of execute() on the device (SURVEY.md 8(f) row 3):
-// public-key encryption of an encoded plaintext and decryption + decoding of a result, i.e. the
-// arithmetic of SEALPublic::encrypt and SEALSecret::decrypt (/root/reference/eva/seal/seal.cpp:24-102,
-// 124-146: encoder.encode + encryptor.encrypt; decryptor.decrypt + encoder.decode).  Randomness stays on the host (csprng.h): the sampled small polynomials
-// travel as int8 arrays (3 N bytes per encryption); everything of size N log N or l N runs here.
+// client.hip — the host-side neighbours of execute() on the device (SURVEY.md 8(f) row 3, DESIGN.md 1.6 and 1.7):
+// encryption of encoded plaintexts and decryption + decoding of results, i.e. the arithmetic of SEALPublic::encrypt and
+// SEALSecret::decrypt (seal.cpp:24-102, 124-146: encoder.encode + encryptor.encrypt; decryptor.decrypt + encoder.decode).
+// Each operation is ONE body for up to 64 instances per call, and no launch count depends on the batch; the calls that
+// take one handle (evah_encrypt, evah_encrypt_symmetric, evah_decrypt_decode) are the batch of one behind check prologues
+// of their own.  Randomness comes from the host (csprng.h) as int8 arrays, or is drawn here from a 32-byte randomness key
+// per instance (k_sample_small): same launches, same words.
 //   encrypt  : c = (pk0 u + e0, pk1 u + e1) at l+1 limbs, divided-and-rounded by the extra prime
 //              (same rule as rescale A.5), plus the plaintext on c0
 //   encrypt_symmetric : c1 = a expanded from a 32-byte seed (seeded.hip.h), c0 = pt - (a s + NTT(e)) at pt's limbs
@@ -12,13 +14,135 @@
 //              (CKKSEncoder::decode_internal), slot values out.  FP64 with SEAL's operation order and no
 //              FMA contraction: the doubles are those of the oracle's evo_decode and of the host
 //              decoder, bit for bit (tests/test_decode_parity.py)
+//
+// The FFT (k_fft_tile): a workgroup keeps 2048 complex points in LDS and runs every stage whose butterflies stay inside
+// the tile before it writes.  2048 double2 are 32 KiB: twice that is the whole 64 KiB a kernel may declare statically (no
+// room left for the layout below, one workgroup per 64 KiB), while 2048 points already cover every supported N
+// (2^10 .. 2^17) in two launches — 11 stages in the contiguous pass, the remaining logN - 11 <= 6 in the strided one —
+// and leave room for several workgroups per CU, which a transform of 16 .. 64 tiles per instance needs more than depth.
+//   contiguous pass: tile = 2048 consecutive points, the stages with gap 1 .. 1024
+//   strided pass   : tile = R = N / 2048 rows (row stride 2048 points) by C = 2048 / R consecutive columns, the stages
+//                    with gap 2048 .. N / 2; a row piece is C >= 32 consecutive double2 (512 B), so the accesses coalesce
+// The encoder (Gentleman-Sande, gaps ascending) runs contiguous then strided, the decoder (Cooley-Tukey, gaps descending)
+// strided then contiguous; N <= 2048 is the contiguous pass alone.
+// LDS layout: a double2 fills one of the 16 slots of 16 bytes of a 256-byte bank row, and a ds_read_b128 is served in
+// groups of 16 lanes.  Lane bf of a stage with gap 2^s reads element a = bf with a zero bit inserted at position s, so
+// for s >= 4 the 16 lanes of a group read 16 consecutive elements, which the linear layout already spreads over the 16
+// slots; it is the stages with gap 1 .. 8 that are 2-way in the linear layout, where a and a + 16 fall on one slot.
+// Element e lives at e ^ (e >> 4 & 15) ^ (e >> 8): the slot index is the XOR of the three nibbles of e, which moves
+// a + 16 to another slot and, being a permutation within each aligned run of 16 elements, keeps the stages with s >= 4
+// and the tile's consecutive loads and stores conflict-free.  The XOR stays inside a 256-byte row, so the tile keeps its
+// 32 KiB (the padding of DESIGN.md 4 "LDS layout" without its extra words).  This is counted from the access pattern;
+// the layout has not been timed against the linear one.
 
 #include "launch.hip.h"
-#include "client.hip.h"
 #include "seeded.hip.h"
+#include "sampled.hip.h"
 
 namespace evah {
 
+// ---- the tiled FP64 special FFT
+constexpr uint32_t FFT_LOG_TILE = 11, FFT_TILE = 1u << FFT_LOG_TILE, FFT_THREADS = 256;
+
+__device__ __forceinline__ uint32_t fft_lds_at(uint32_t e) { return e ^ ((e >> 4) & 15u) ^ (e >> 8); }
+
+// c [batch][N] complex points, instance = blockIdx.y, tile = blockIdx.x; the stages with global gap 2^L for
+// L = L0 .. L0 + n_stages - 1, ascending (ENC) or descending (decoder).  lt = log2 points per tile (logN below one tile).
+// ENC : k_enc_fft_stage's butterfly (elementwise.hip) with root inv_seq[N - 2 (N >> L + 1) + 1 + g]; the stage
+//       L = logN - 1 is k_enc_fft_last's (sum times fix, difference times the pre-scaled root)
+// !ENC: DWTHandler::transform_to_rev of SEAL 3.6 (Cooley-Tukey) with root roots[(N >> L + 1) + g]: x = u + v r,
+//       y = u - v r, the complex product as four rounded multiplies, a rounded difference and a rounded sum
+// g = the butterfly's group in the whole transform = its upper index >> (L + 1).  No FMA contraction in either.
+template <bool ENC, bool STRIDED>
+__global__ void __launch_bounds__(FFT_THREADS)
+k_fft_tile(double2 *c, const double2 *__restrict__ roots, uint32_t logN, uint32_t lt, uint32_t L0, uint32_t n_stages, double2 scaled_root,
+           double fix) {
+#pragma clang fp contract(off)
+  __shared__ double2 tile[FFT_TILE];
+  const uint32_t N = 1u << logN, T = 1u << lt, tid = threadIdx.x;
+  double2 *x = c + (size_t)blockIdx.y * N;
+  const uint32_t logC = STRIDED ? 2 * FFT_LOG_TILE - logN : 0; // columns per strided tile: 2048 / (N / 2048)
+  auto global_of = [&](uint32_t e) -> uint32_t {
+    if (STRIDED) return ((e >> logC) << FFT_LOG_TILE) + (blockIdx.x << logC) + (e & ((1u << logC) - 1));
+    return (blockIdx.x << lt) + e;
+  };
+  for (uint32_t e = tid; e < T; e += FFT_THREADS) tile[fft_lds_at(e)] = x[global_of(e)];
+  __syncthreads();
+  for (uint32_t s = 0; s < n_stages; s++) {
+    const uint32_t L = ENC ? L0 + s : L0 + n_stages - 1 - s;
+    const uint32_t ll = STRIDED ? L - FFT_LOG_TILE + logC : L, gap = 1u << ll; // the gap inside the tile
+    const uint32_t groups = N >> (L + 1);
+    for (uint32_t bf = tid; bf < (T >> 1); bf += FFT_THREADS) {
+      const uint32_t a = ((bf >> ll) << (ll + 1)) + (bf & (gap - 1)), b = a + gap;
+      const uint32_t g = global_of(a) >> (L + 1);
+      const uint32_t ia = fft_lds_at(a), ib = fft_lds_at(b);
+      const double2 u = tile[ia], v = tile[ib];
+      if (ENC) {
+        if (L + 1 == logN) { // k_enc_fft_last
+          tile[ia] = make_double2((u.x + v.x) * fix, (u.y + v.y) * fix);
+          const double dx = u.x - v.x, dy = u.y - v.y;
+          const double p = dx * scaled_root.x, q = dy * scaled_root.y, sx = dx * scaled_root.y, t = dy * scaled_root.x;
+          tile[ib] = make_double2(p - q, sx + t);
+        } else { // k_enc_fft_stage
+          const double2 r = roots[N - 2 * groups + 1 + g];
+          tile[ia] = make_double2(u.x + v.x, u.y + v.y);
+          const double dx = u.x - v.x, dy = u.y - v.y;
+          const double p = dx * r.x, q = dy * r.y, sx = dx * r.y, t = dy * r.x;
+          tile[ib] = make_double2(p - q, sx + t);
+        }
+      } else {
+        const double2 w = roots[groups + g];
+        const double ac = v.x * w.x, bd = v.y * w.y, ad = v.x * w.y, bc = v.y * w.x;
+        const double tx = ac - bd, ty = ad + bc;
+        tile[ia] = make_double2(u.x + tx, u.y + ty);
+        tile[ib] = make_double2(u.x - tx, u.y - ty);
+      }
+    }
+    __syncthreads();
+  }
+  for (uint32_t e = tid; e < T; e += FFT_THREADS) x[global_of(e)] = tile[fft_lds_at(e)];
+}
+
+// the special FFT of `batch` instances in c [batch][N]: one launch for N <= 2048, two above
+template <bool ENC> static void fft_batched(evah_ctx *c, double2 *cd, const double2 *roots, uint32_t batch, double2 scaled_root, double fix) {
+  const uint32_t logN = c->logN;
+  if (logN < 10 || logN > 2 * FFT_LOG_TILE - 5) throw std::invalid_argument("the batched client calls need N from 2^10 to 2^17");
+  const uint32_t lt = std::min(logN, FFT_LOG_TILE), low = lt, high = logN - lt;
+  const dim3 grid(c->N >> lt, batch), block(FFT_THREADS);
+  ProfScope ps(c, KC_EW);
+  if (ENC || !high) hipLaunchKernelGGL((k_fft_tile<ENC, false>), grid, block, 0, c->stream, cd, roots, logN, lt, 0u, low, scaled_root, fix);
+  if (high) hipLaunchKernelGGL((k_fft_tile<ENC, true>), grid, block, 0, c->stream, cd, roots, logN, lt, FFT_LOG_TILE, high, scaled_root, fix);
+  if (!ENC && high) hipLaunchKernelGGL((k_fft_tile<ENC, false>), grid, block, 0, c->stream, cd, roots, logN, lt, 0u, low, scaled_root, fix);
+  HIPCHK(hipGetLastError());
+}
+
+// ---- the encoder of the _many calls: evah_pt_encode's small kernels (elementwise.hip) with an instance index (grid.y)
+__global__ void __launch_bounds__(256)
+k_enc_scatter_many(const double *vals, uint32_t n_vals, const uint32_t *slot_map, double2 *c, uint32_t slots) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= slots) return;
+  const double v = vals[(size_t)blockIdx.y * n_vals + i % n_vals];
+  c += (size_t)blockIdx.y * 2 * slots;
+  c[slot_map[i]] = make_double2(v, 0.0);
+  c[slot_map[slots + i]] = make_double2(v, -0.0); // conjugate of a real value
+}
+__global__ void __launch_bounds__(256)
+k_enc_round_many(DevCtx cx, const double2 *c, uint32_t limbs, u64 *out) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= cx.N) return;
+  const double t = c[(size_t)blockIdx.y * cx.N + j].x;
+  const double x = fabs(t) < 4503599627370496.0 ? round(t) : t; // >= 2^52: already an integer
+  const bool neg = signbit(x);
+  const u64 mant = (u64)fabs(x); // |x| < 2^63 is guaranteed by the caller's bound
+  out += (size_t)blockIdx.y * limbs * cx.N;
+  for (uint32_t i = 0; i < limbs; i++) {
+    const DevPrime pm = cx.primes[cx.prime_of(i)];
+    const u64 r = barrett64(mant, pm.q, pm.brt);
+    out[(size_t)i * cx.N + j] = (neg && r) ? pm.q - r : r;
+  }
+}
+
+// ---- the small polynomials: the host's int8 draws, or drawn where they are used (sampled.hip.h)
 __global__ void __launch_bounds__(256)
 k_small_to_residues(DevCtx cx, const int8_t *small, uint32_t n_polys, uint32_t limbs, u64 *out) {
   // out[p][i][n] = small[p][n] mod primes[i] (negative -> q - |v|)
@@ -29,86 +153,457 @@ k_small_to_residues(DevCtx cx, const int8_t *small, uint32_t n_polys, uint32_t l
   out[((size_t)p * limbs + i) * cx.N + n] = v < 0 ? q - (u64)(-v) : (u64)v;
 }
 // NTT forms [n_polys][limbs][N] of n_polys small polynomials (int8 [n_polys][N] on the device) under the chain primes
-// 0 .. limbs - 1, on the calling queue: what evah_encrypt_symmetric and evah_keygen_switch (seeded.hip) make of their errors
+// 0 .. limbs - 1, on the calling queue: what the encryptions here and evah_keygen_switch (seeded.hip) make of their draws
 void small_to_ntt(evah_ctx *c, const u64 *small8, uint32_t n_polys, uint32_t limbs, u64 *out) {
   EW_LAUNCH(k_small_to_residues, dim3(c->N / 256, limbs, n_polys), dim3(256), 0, c->stream, c->dev, reinterpret_cast<const int8_t *>(small8), n_polys, limbs, out);
   OpPlain::Params fp{out, out, (size_t)limbs * c->N, (size_t)limbs * c->N, limbs, 0, 0, {}};
   ntt_forward<OpPlain>(c, fp, n_polys * limbs);
 }
-// c[K][i] = pk[K][i] * u[i] + e_K[i]; small = NTT forms [3][up][N] of (u, e0, e1); pk [2][k][N]
+// Polynomials p0 .. p0 + n_polys - 1 of instance inst = blockIdx.y / n_polys from its randomness key rkeys[inst][8],
+// straight into residues out [batch][n_polys][limbs][N] under the chain primes 0 .. limbs - 1, k_small_to_residues'
+// words (v < 0 ? q - |v| : v).  A workgroup draws SAMPLE_TILE consecutive coefficients — one ChaCha20 block of 8 per
+// thread, kept as 8 bytes in LDS — and then writes them limb by limb, thread t the coefficients 2 t, 2 t + 1 (+ 512 r):
+// one 16-byte store per lane, 1 KiB contiguous per wave instruction, and no block is computed twice.  N / 8 may be
+// below one workgroup (N = 1024: 128 blocks): the idle threads draw nothing and still take part in the stores.
+constexpr uint32_t SAMPLE_THREADS = 256, SAMPLE_TILE = 8 * SAMPLE_THREADS;
+__global__ void __launch_bounds__(SAMPLE_THREADS)
+k_sample_small(DevCtx cx, const uint32_t *__restrict__ rkeys, uint32_t n_polys, uint32_t p0, uint32_t limbs, u64 *out) {
+  __shared__ u64 tile8[SAMPLE_THREADS];
+  const uint32_t tid = threadIdx.x, inst = blockIdx.y / n_polys, p = p0 + blockIdx.y % n_polys;
+  const uint32_t blk = blockIdx.x * SAMPLE_THREADS + tid;
+  if (blk < cx.N / 8) {
+    uint32_t key[8];
+#pragma unroll
+    for (int w = 0; w < 8; w++) key[w] = rkeys[8 * inst + w];
+    tile8[tid] = sampled_block(key, p, blk);
+  }
+  __syncthreads();
+  const int8_t *tile = reinterpret_cast<const int8_t *>(tile8);
+  const uint32_t base = blockIdx.x * SAMPLE_TILE, pairs = min(SAMPLE_TILE, cx.N - base) / 2; // N is a multiple of 256
+  int v[SAMPLE_TILE / 2 / SAMPLE_THREADS][2];
+#pragma unroll
+  for (uint32_t r = 0; r < SAMPLE_TILE / 2 / SAMPLE_THREADS; r++) {
+    const uint32_t e = tid + r * SAMPLE_THREADS;
+    v[r][0] = e < pairs ? tile[2 * e] : 0;
+    v[r][1] = e < pairs ? tile[2 * e + 1] : 0;
+  }
+  u64 *rows = out + (size_t)blockIdx.y * limbs * cx.N + base;
+  for (uint32_t i = 0; i < limbs; i++) {
+    const u64 q = cx.primes[cx.prime_of(i)].q;
+#pragma unroll
+    for (uint32_t r = 0; r < SAMPLE_TILE / 2 / SAMPLE_THREADS; r++) {
+      const uint32_t e = tid + r * SAMPLE_THREADS;
+      if (e < pairs)
+        st2(rows + (size_t)i * cx.N + 2 * e, make_ulonglong2(v[r][0] < 0 ? q - (u64)(-v[r][0]) : (u64)v[r][0],
+                                                              v[r][1] < 0 ? q - (u64)(-v[r][1]) : (u64)v[r][1]));
+    }
+  }
+}
+// the randomness keys [batch][32] (host) into `keys` on the queue, then NTT forms [batch][n_polys][limbs][N] of the
+// polynomials p0 .. p0 + n_polys - 1 of every instance: what the int8 copy and small_to_ntt make of the host's draws
+static void sample_to_ntt(evah_ctx *c, uint32_t batch, const uint8_t *rkeys, u64 *keys, uint32_t n_polys, uint32_t p0, uint32_t limbs, u64 *out) {
+  HIPCHK(hipMemcpyAsync(keys, rkeys, (size_t)32 * batch, hipMemcpyHostToDevice, c->stream));
+  EW_LAUNCH(k_sample_small, dim3((c->N + SAMPLE_TILE - 1) / SAMPLE_TILE, batch * n_polys), dim3(SAMPLE_THREADS), 0, c->stream, c->dev,
+            reinterpret_cast<const uint32_t *>(keys), n_polys, p0, limbs, out);
+  OpPlain::Params fp{out, out, (size_t)limbs * c->N, (size_t)limbs * c->N, limbs, 0, 0, {}};
+  ntt_forward<OpPlain>(c, fp, batch * n_polys * limbs);
+}
+
+// ---- the encryptors' kernels
+// c[inst][K][i] = pk[K][i] * u[i] + e_K[i], grid.z = 2 inst + K; small = NTT forms [batch][3][up][N] of (u, e0, e1);
+// pk [2][k][N]; c [batch][2][up][N]
 __global__ void __launch_bounds__(256)
 k_encrypt_zero(DevCtx cx, const u64 *pk, const u64 *small, uint32_t up, u64 *c) {
   const size_t n = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t i = blockIdx.y, K = blockIdx.z;
+  const uint32_t i = blockIdx.y, inst = blockIdx.z >> 1, K = blockIdx.z & 1u;
   const DevPrime pm = cx.primes[i];
+  small += (size_t)inst * 3 * up * cx.N;
   const u64 u = small[(size_t)i * cx.N + n], e = small[((size_t)(1 + K) * up + i) * cx.N + n];
   const u64 p = pk[((size_t)K * cx.k + i) * cx.N + n];
-  c[((size_t)K * up + i) * cx.N + n] = addmod(mulmod(p, u, pm), e, pm.q);
+  c[(((size_t)2 * inst + K) * up + i) * cx.N + n] = addmod(mulmod(p, u, pm), e, pm.q);
 }
-// c1 = a, c0 = m - (a s + en) for l limbs; m (NTT plaintext) [l][N], en (NTT error) [l][N], sk [k][N] by prime
+// c1 = a, c0 = m - (a s + en) for l limbs of instance z (grid.z): m (NTT plaintexts), en (NTT errors) [batch][l][N],
+// sk [k][N] by prime, ct [batch][2][l][N]; seeds as k_key_expand takes them
 __global__ void __launch_bounds__(256)
-k_encrypt_symmetric(DevCtx cx, Seeds8 seed, const u64 *m, const u64 *en, const u64 *sk, uint32_t l, u64 *c0, u64 *c1) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
+k_encrypt_symmetric(DevCtx cx, Seeds8 seeds, const uint32_t *__restrict__ seed_buf, const u64 *m, const u64 *en, const u64 *sk, uint32_t l,
+                    u64 *ct) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y, z = blockIdx.z;
   if (t >= cx.N / 4 || i >= l) return;
   const uint32_t prime = cx.prime_of(i);
   const DevPrime pm = cx.primes[prime];
+  uint32_t key[8];
+  if (seed_buf) {
+#pragma unroll
+    for (int w = 0; w < 8; w++) key[w] = seed_buf[8 * z + w];
+  } else {
+#pragma unroll
+    for (int w = 0; w < 8; w++) key[w] = seeds.w[z][w];
+  }
   u64 a[4];
-  seeded_block(seed.w[0], prime, t, pm, a);
-  const size_t off = (size_t)i * cx.N + 4 * (size_t)t;
+  seeded_block(key, prime, t, pm, a);
+  const size_t row = (size_t)l * cx.N, off = (size_t)i * cx.N + 4 * (size_t)t, in = z * row + off;
   const u64 *s = sk + (size_t)prime * cx.N + 4 * (size_t)t;
-  const ulonglong2 m01 = ld2(m + off), m23 = ld2(m + off + 2), e01 = ld2(en + off), e23 = ld2(en + off + 2);
+  const ulonglong2 m01 = ld2(m + in), m23 = ld2(m + in + 2), e01 = ld2(en + in), e23 = ld2(en + in + 2);
   const ulonglong2 s01 = ld2(s), s23 = ld2(s + 2);
   const u64 mv[4] = {m01.x, m01.y, m23.x, m23.y}, ev[4] = {e01.x, e01.y, e23.x, e23.y}, sv[4] = {s01.x, s01.y, s23.x, s23.y};
   u64 b[4];
 #pragma unroll
   for (int r = 0; r < 4; r++) b[r] = submod(mv[r], addmod(mulmod(a[r], sv[r], pm), ev[r], pm.q), pm.q);
-  st2(c1 + off, make_ulonglong2(a[0], a[1]));
-  st2(c1 + off + 2, make_ulonglong2(a[2], a[3]));
-  st2(c0 + off, make_ulonglong2(b[0], b[1]));
-  st2(c0 + off + 2, make_ulonglong2(b[2], b[3]));
+  u64 *c0 = ct + (size_t)2 * z * row + off, *c1 = c0 + row;
+  st2(c1, make_ulonglong2(a[0], a[1]));
+  st2(c1 + 2, make_ulonglong2(a[2], a[3]));
+  st2(c0, make_ulonglong2(b[0], b[1]));
+  st2(c0 + 2, make_ulonglong2(b[2], b[3]));
 }
 
-// m[i] = c0 + c1 s + c2 s^2 (size 2 or 3; a size-1 value is its own message)
+// ---- the decryptor's kernels
+// the ciphertexts of a call: separate allocations, possibly views with a polynomial stride of their own
+struct DotTab {
+  const u64 *ct[KS_BATCH_MAX];
+  uint32_t ct_ps[KS_BATCH_MAX]; // poly strides in units of N coefficients
+};
+// m[inst][i] = c0 + c1 s (+ c2 s^2) of ciphertext inst (grid.z); a size-1 value is its own message
 __global__ void __launch_bounds__(256)
-k_decrypt_dot(DevCtx cx, const u64 *ct, size_t ps, uint32_t size, const u64 *sk, u64 *m) {
+k_decrypt_dot(DevCtx cx, DotTab tab, uint32_t size, uint32_t l, const u64 *sk, u64 *m) {
   const size_t n = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t i = blockIdx.y;
+  const uint32_t i = blockIdx.y, inst = blockIdx.z;
   const DevPrime pm = cx.primes[i];
-  const size_t off = (size_t)i * cx.N + n;
+  const size_t off = (size_t)i * cx.N + n, ps = (size_t)tab.ct_ps[inst] * cx.N;
+  const u64 *ct = tab.ct[inst];
   const u64 s = sk[off];
   u64 acc = ct[off], sp = s;
   for (uint32_t p = 1; p < size; p++) {
     acc = addmod(acc, mulmod(ct[p * ps + off], sp, pm), pm.q);
     sp = mulmod(sp, s, pm);
   }
-  m[off] = acc;
+  m[(size_t)inst * l * cx.N + off] = acc;
 }
-// one double per decrypted coefficient (crt_to_double, client.hip.h), as the real part of the FFT's input
+
+// Garner tables of a level: inv_prefix[i] = (q_0..q_{i-1})^-1 mod q_i, pre_mod[i][t] = q_0..q_{t-1} mod q_i,
+// prefix[i][w] = word w of q_0..q_{i-1} (base 2^64, l words), qwords[w] / half[w] = word w of Q / of floor(Q/2)
+struct CrtTab {
+  const u64 *inv_prefix, *pre_mod, *prefix, *qwords, *half;
+};
+// the tables in one array of 2 l^2 + 3 l words: [inv_prefix l][pre_mod l*l][prefix l*l][Q l][floor(Q/2) l]
+static CrtTab crt_tab_at(const u64 *d, uint32_t l) {
+  return CrtTab{d, d + l, d + l + (size_t)l * l, d + l + (size_t)2 * l * l, d + 2 * l + (size_t)2 * l * l};
+}
+static std::vector<u64> crt_tab_build(const evah_ctx *c, uint32_t l) {
+  std::vector<u64> tab((size_t)2 * l * l + 3 * l, 0);
+  u64 *inv_prefix = tab.data(), *pre_mod = inv_prefix + l, *prefix = pre_mod + (size_t)l * l,
+      *qwords = prefix + (size_t)l * l, *half = qwords + l;
+  std::vector<u64> w{1}; // q_0..q_{i-1}, little-endian words
+  for (uint32_t i = 0; i < l; i++) {
+    const u64 qi = c->primes[i];
+    u64 acc = 1 % qi;
+    for (uint32_t j = 0; j < i; j++) {
+      pre_mod[i * l + j] = acc;
+      acc = mulmod(acc, c->primes[j] % qi, qi);
+    }
+    inv_prefix[i] = invmod(acc, qi);
+    for (size_t t = 0; t < w.size() && t < l; t++) prefix[(size_t)i * l + t] = w[t];
+    u64 carry = 0;
+    for (auto &x : w) { u128 t = (u128)x * qi + carry; x = (u64)t; carry = (u64)(t >> 64); }
+    if (carry) w.push_back(carry);
+  }
+  for (size_t t = 0; t < w.size() && t < l; t++) qwords[t] = w[t];
+  for (size_t t = 0; t < w.size() && t < l; t++) half[t] = (w[t] >> 1) | (t + 1 < w.size() ? w[t + 1] << 63 : 0);
+  return tab;
+}
+// the tables of level l on the device, built once per context family (freed with it)
+static CrtTab crt_tab_cached(evah_ctx *c, uint32_t l) {
+  auto it = c->sh->crt_tabs.find(l);
+  if (it == c->sh->crt_tabs.end()) {
+    const std::vector<u64> tab = crt_tab_build(c, l);
+    u64 *d = nullptr;
+    HIPCHK(hipMalloc(&d, sizeof(u64) * tab.size()));
+    try {
+      h2d_now(c, d, tab.data(), sizeof(u64) * tab.size());
+    } catch (...) {
+      (void)hipFree(d);
+      throw;
+    }
+    it = c->sh->crt_tabs.emplace(l, d).first;
+  }
+  return crt_tab_at(it->second, l);
+}
+// forward roots zeta^br(j) of the decoder's special FFT (hostmath.h), once per context family
+static void dec_tables(evah_ctx *c) {
+  if (c->sh->dec_roots) return;
+  const uint32_t N = c->N;
+  const CkksRoots cr = ckks_roots(N);
+  std::vector<double> roots(2 * (size_t)N);
+  for (uint32_t j = 0; j < N; j++) { roots[2 * j] = cr.fwd[j].real(); roots[2 * j + 1] = cr.fwd[j].imag(); }
+  HIPCHK(hipMalloc(&c->sh->dec_roots, sizeof(double2) * N));
+  h2d_now(c, c->sh->dec_roots, roots.data(), sizeof(double2) * N);
+}
+
+__device__ __forceinline__ void garner(const DevCtx &cx, const CrtTab &t, uint32_t l, const u64 *r, u64 *v) {
+  for (uint32_t i = 0; i < l; i++) {
+    const DevPrime pm = cx.primes[i];
+    u128_t acc = {0, 0};
+    for (uint32_t j = 0; j < i; j++) acc128(acc, v[j] >= pm.q ? barrett64(v[j], pm.q, pm.brt) : v[j], t.pre_mod[i * l + j]);
+    const u64 a = barrett128(acc, pm);
+    v[i] = i ? mulmod(submod(r[i], a, pm.q), t.inv_prefix[i], pm) : r[0];
+  }
+}
+// SEAL 3.6 CKKSEncoder::decode_internal between the inverse NTTs and the FFT: the composed coefficient
+// x in [0, Q) as l base-2^64 words (here from the mixed-radix digits: x = sum_i v_i q_0..q_{i-1}, exact),
+// then ONE double from the words, least significant first, with inv_scale folded into the running power
+// of 2^64; x >= (Q + 1) / 2 is negative and accumulates the signed per-word differences against Q's
+// words.  Same operations in the same order as the oracle's evo_decode and the host decoder: same doubles.
+// coeff = limb 0 of the message [l][N], n = the coefficient.
+__device__ __forceinline__ double crt_to_double(const DevCtx &cx, const CrtTab &t, uint32_t l, const u64 *coeff, size_t n, double inv_scale) {
+#pragma clang fp contract(off)
+  u64 r[62], v[62], x[63];
+  for (uint32_t i = 0; i < l; i++) r[i] = coeff[(size_t)i * cx.N + n];
+  garner(cx, t, l, r, v);
+  for (uint32_t w = 0; w <= l; w++) x[w] = 0;
+  for (uint32_t i = 0; i < l; i++) { // x += v_i * prefix_i (prefix_i has at most i words; the sum stays below Q)
+    u64 carry = 0;
+    const u64 *pf = t.prefix + (size_t)i * l;
+    for (uint32_t w = 0; w < l; w++) {
+      u128_t p = mul128(pf[w], v[i]);
+      const u64 lo = p.lo + carry;
+      u64 hi = p.hi + (lo < carry);
+      const u64 sum = x[w] + lo;
+      hi += (sum < lo);
+      x[w] = sum;
+      carry = hi;
+    }
+  }
+  bool negative = false; // x > floor(Q/2), compared from the most significant word
+  for (int w = (int)l - 1; w >= 0; w--)
+    if (x[w] != t.half[w]) { negative = x[w] > t.half[w]; break; }
+  const double two_pow_64 = 18446744073709551616.0;
+  double acc = 0.0, scaled = inv_scale;
+  for (uint32_t w = 0; w < l; w++, scaled *= two_pow_64) {
+    const u64 xw = x[w], qw = t.qwords[w];
+    if (!negative) {
+      acc += xw ? (double)xw * scaled : 0.0;
+    } else if (xw > qw) {
+      const u64 diff = xw - qw;
+      acc += diff ? (double)diff * scaled : 0.0;
+    } else {
+      const u64 diff = qw - xw;
+      acc -= diff ? (double)diff * scaled : 0.0;
+    }
+  }
+  return acc;
+}
+// one double per decrypted coefficient of instance blockIdx.y, as the real part of the FFT's input
 __global__ void __launch_bounds__(256)
 k_crt_to_double(DevCtx cx, CrtTab t, uint32_t l, const u64 *coeff, double inv_scale, double2 *out) {
-  const size_t n = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  out[n] = make_double2(crt_to_double(cx, t, l, coeff, n, inv_scale), 0.0);
-}
-// forward special FFT stage (Cooley-Tukey): group g of `groups` uses roots[groups + g]
-// (DWTHandler::transform_to_rev of SEAL 3.6: x = u + v r, y = u - v r; the complex product as four rounded
-// multiplies, a rounded difference and a rounded sum — no FMA contraction, as in the encoder)
-__global__ void __launch_bounds__(256)
-k_dec_fft_stage(double2 *c, const double2 *roots, uint32_t groups, uint32_t log_gap, uint32_t half_n) {
-#pragma clang fp contract(off)
-  const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= half_n) return;
-  const uint32_t gap = 1u << log_gap, g = idx >> log_gap, j = idx & (gap - 1);
-  const uint32_t a = 2 * g * gap + j, b = a + gap;
-  const double2 w = roots[groups + g], u = c[a], y = c[b];
-  const double ac = y.x * w.x, bd = y.y * w.y, ad = y.x * w.y, bc = y.y * w.x;
-  const double tx = ac - bd, ty = ad + bc;
-  c[a] = make_double2(u.x + tx, u.y + ty);
-  c[b] = make_double2(u.x - tx, u.y - ty);
+  const size_t n = (size_t)blockIdx.x * blockDim.x + threadIdx.x, inst = blockIdx.y;
+  out[inst * cx.N + n] = make_double2(crt_to_double(cx, t, l, coeff + inst * l * cx.N, n, inv_scale), 0.0);
 }
 __global__ void __launch_bounds__(256)
-k_dec_gather(const double2 *c, const uint32_t *slot_map, uint32_t n_out, double *out) {
+k_dec_gather(const double2 *c, const uint32_t *slot_map, uint32_t n_out, uint32_t N, double *out) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n_out) out[i] = c[slot_map[i]].x;
+  if (i < n_out) out[(size_t)blockIdx.y * n_out + i] = c[(size_t)blockIdx.y * N + slot_map[i]].x;
+}
+
+// ---- one body per operation: no argument checks inside, every entry point below makes its own
+// queue-ordered zeroing of a pool temporary that held something secret, also when the call fails
+struct Wipe {
+  evah_ctx *c;
+  void *d;
+  size_t bytes;
+  bool done = false; // set at construction: nothing to wipe
+  void now() { // the success path: a wipe that fails is an error
+    if (done) return;
+    done = true;
+    HIPCHK(hipMemsetAsync(d, 0, bytes, c->stream));
+  }
+  ~Wipe() {
+    if (!done) (void)hipMemsetAsync(d, 0, bytes, c->stream);
+  }
+};
+
+// SEAL Encryptor::encrypt of `batch` NTT-form plaintexts pt [batch][l][N] (a handle's words, or the call's scratch) into
+// one handle [batch][2][l][N].  Randomness: small = the host's (u ternary, e0, e1 error polynomials) as int8 [batch][3][N], or
+// (rkeys) drawn here from a 32-byte key per instance.  Drains the queue: `small` / `rkeys` are pageable host memory.
+static evah_ct *encrypt_public(evah_ctx *c, uint32_t batch, uint32_t l, double scale, const u64 *pt, const int8_t *small,
+                               const uint8_t *rkeys) {
+  const uint32_t up = l + 1;
+  const size_t N = c->N, B = batch;
+  Scratch sm8(c, rkeys ? 4 * B : (3 * B * N + 7) / 8), sm(c, 3 * B * up * N), ct(c, 2 * B * up * N), r(c, 2 * B * N);
+  evah_ct *o = ct_new(c, 2, l, scale, batch);
+  try {
+    // drawn here, u, e0, e1 and their keys exist nowhere else: they do not stay behind in pool memory the next call reuses
+    Wipe w_keys{c, sm8.d, (size_t)32 * B, !rkeys}, w_sm{c, sm.d, sizeof(u64) * 3 * B * up * N, !rkeys};
+    if (rkeys) {
+      sample_to_ntt(c, batch, rkeys, sm8.d, 3, 0, up, sm.d);
+    } else {
+      HIPCHK(hipMemcpyAsync(sm8.d, small, 3 * B * N, hipMemcpyHostToDevice, c->stream));
+      small_to_ntt(c, sm8.d, 3 * batch, up, sm.d);
+    }
+    EW_LAUNCH(k_encrypt_zero, dim3(c->N / 256, up, 2 * batch), dim3(256), 0, c->stream, c->dev, c->sh->pk.d, sm.d, up, ct.d);
+    HIPCHK(hipGetLastError());
+    // divide and round by prime `l` (the last of the up primes), then add instance b's plaintext to its c0
+    OpPlain::Params ip{ct.d + (size_t)l * N, r.d, (size_t)up * N, N, 1, l, 1, {}};
+    ntt_inverse<OpPlain>(c, ip, 2 * batch);
+    OpModDown::Params mp{r.d, N, ct.d, (size_t)up * N, nullptr, 0, 0, o->d, o->ps, l, l};
+    mp.use_add_tab = true;
+    for (uint32_t b = 0; b < batch; b++) mp.add_tab.p[2 * b] = pt + b * l * N;
+    ntt_forward<OpModDown>(c, mp, 2 * batch * l);
+    w_keys.now();
+    w_sm.now();
+    HIPCHK(hipStreamSynchronize(c->stream));
+  } catch (...) {
+    (void)hipStreamSynchronize(c->stream);
+    evah_ct_free(c, o);
+    throw;
+  }
+  return o;
+}
+
+// Encryptor::encrypt_symmetric of `batch` NTT-form plaintexts m [batch][l][N] into one handle: c1 = a from seeds[b],
+// c0 = m - (a s + NTT(e)).  e = the host's error polynomials as int8 [batch][N], or (ekeys) drawn here from a 32-byte
+// key per instance.  Drains the queue: `e` / `ekeys` and `seeds` are pageable host memory.
+static evah_ct *encrypt_symmetric(evah_ctx *c, uint32_t batch, uint32_t l, double scale, const u64 *m, const int8_t *e,
+                                  const uint8_t *ekeys, const uint8_t *seeds) {
+  const size_t N = c->N, B = batch;
+  Scratch e8(c, ekeys ? 4 * B : (B * N + 7) / 8), en(c, B * l * N);
+  std::unique_ptr<Scratch> seed_dev; // more than 8 instances: the seeds as a device buffer, returned to the pool after the drain
+  evah_ct *o = ct_new(c, 2, l, scale, batch);
+  try {
+    // the errors (or the keys they are drawn from) do not stay behind in pool memory the next call reuses
+    Wipe w_en{c, en.d, sizeof(u64) * B * l * N}, w_e8{c, e8.d, ekeys ? 32 * B : B * N};
+    if (ekeys) {
+      sample_to_ntt(c, batch, ekeys, e8.d, 1, 1, l, en.d);
+    } else {
+      HIPCHK(hipMemcpyAsync(e8.d, e, B * N, hipMemcpyHostToDevice, c->stream));
+      small_to_ntt(c, e8.d, batch, l, en.d);
+    }
+    Seeds8 s8;
+    std::memset(&s8, 0, sizeof s8);
+    const uint32_t *seed_buf = nullptr;
+    if (batch <= SEEDS_PER_LAUNCH) {
+      std::memcpy(s8.w, seeds, (size_t)32 * batch); // little-endian key words, as the host generator reads its key
+    } else {
+      seed_dev = std::make_unique<Scratch>(c, (size_t)4 * batch);
+      HIPCHK(hipMemcpyAsync(seed_dev->d, seeds, (size_t)32 * batch, hipMemcpyHostToDevice, c->stream));
+      seed_buf = reinterpret_cast<const uint32_t *>(seed_dev->d);
+    }
+    EW_LAUNCH(k_encrypt_symmetric, seeded_grid(c, l, batch), dim3(256), 0, c->stream, c->dev, s8, seed_buf, m, en.d, c->sh->sk.d, l, o->d);
+    HIPCHK(hipGetLastError());
+    w_en.now();
+    w_e8.now();
+    HIPCHK(hipStreamSynchronize(c->stream));
+  } catch (...) {
+    (void)hipStreamSynchronize(c->stream);
+    evah_ct_free(c, o);
+    throw;
+  }
+  return o;
+}
+
+// SEAL Decryptor::decrypt + CKKSEncoder::decode of n single ciphertexts of one size, limb count and scale, read in place:
+// the first n_out slot values of each into out [n][n_out] (host)
+static void decrypt_decode(evah_ctx *c, const evah_ct *const *cts, uint32_t n, uint32_t n_out, double *out) {
+  const uint32_t l = cts[0]->limbs, N = c->N;
+  enc_tables(c);
+  dec_tables(c);
+  const CrtTab t = crt_tab_cached(c, l);
+  DotTab tab{};
+  for (uint32_t i = 0; i < n; i++) {
+    acquire(c, cts[i]->buf);
+    tab.ct[i] = cts[i]->d;
+    tab.ct_ps[i] = (uint32_t)(cts[i]->ps / N);
+  }
+  const size_t B = n;
+  Scratch m(c, B * l * N), cbuf(c, B * 2 * N), outd(c, B * n_out);
+  {
+    // the decrypted messages, their FP images and the slot values do not stay behind in pool memory the next call reuses
+    Wipe w_m{c, m.d, sizeof(u64) * B * l * N}, w_c{c, cbuf.d, sizeof(double2) * B * N}, w_o{c, outd.d, sizeof(double) * B * n_out};
+    EW_LAUNCH(k_decrypt_dot, dim3(N / 256, l, n), dim3(256), 0, c->stream, c->dev, tab, cts[0]->size, l, c->sh->sk.d, m.d);
+    OpPlain::Params ip{m.d, m.d, (size_t)l * N, (size_t)l * N, l, 0, 0, {}};
+    ntt_inverse<OpPlain>(c, ip, n * l);
+    double2 *cd = reinterpret_cast<double2 *>(cbuf.d);
+    EW_LAUNCH(k_crt_to_double, dim3(N / 256, n), dim3(256), 0, c->stream, c->dev, t, l, m.d, 1.0 / cts[0]->scale, cd);
+    HIPCHK(hipGetLastError());
+    fft_batched<false>(c, cd, c->sh->dec_roots, n, make_double2(0.0, 0.0), 0.0);
+    EW_LAUNCH(k_dec_gather, dim3((n_out + 255) / 256, n), dim3(256), 0, c->stream, cd, c->sh->enc_slot_map, n_out, N,
+              reinterpret_cast<double *>(outd.d));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, outd.d, sizeof(double) * B * n_out, hipMemcpyDeviceToHost, c->stream));
+    w_m.now();
+    w_c.now();
+    w_o.now();
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
+}
+
+// ---- the _many calls: values in, one batched handle out
+// the checks both encryption calls share, in the order evah_pt_encode and the encryptors make them
+static void encode_many_checks(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale,
+                               evah_ct **out) {
+  if (c->capturing) throw std::logic_error("this call synchronises with the host and cannot be captured into a graph");
+  if (batch < 1 || batch > (uint32_t)KS_BATCH_MAX) throw std::invalid_argument("batch must be 1..64");
+  if (!values) throw std::invalid_argument("value pointer is null");
+  if (!out) throw std::invalid_argument("output pointer is null");
+  if (limbs < 1 || limbs > c->k - 1) throw std::invalid_argument("invalid limb count for this context");
+  const uint32_t slots = c->N >> 1;
+  if (n_values < 1 || n_values > slots || slots % n_values) throw std::invalid_argument("value count must divide the slot count");
+  if (c->N % 256) throw std::invalid_argument("encryption needs N divisible by 256");
+  check_encodable(c, values, batch, n_values, scale); // evah_pt_encode's: "encoded values are too large"
+}
+// values [batch][n_values] (host) -> NTT-form plaintexts pt [batch][limbs][N] on the queue; vals, cbuf: the call's scratch
+static void encode_many(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale, u64 *vals,
+                        double2 *cd, u64 *pt) {
+  const uint32_t N = c->N, slots = N >> 1;
+  enc_tables(c);
+  HIPCHK(hipMemcpyAsync(vals, values, sizeof(double) * (size_t)batch * n_values, hipMemcpyHostToDevice, c->stream));
+  EW_LAUNCH(k_enc_scatter_many, dim3((slots + 255) / 256, batch), dim3(256), 0, c->stream, reinterpret_cast<const double *>(vals), n_values,
+            c->sh->enc_slot_map, cd, slots);
+  const double fix = scale / (double)N;
+  fft_batched<true>(c, cd, c->sh->enc_roots, batch, make_double2(c->sh->enc_last_root[0] * fix, c->sh->enc_last_root[1] * fix), fix);
+  EW_LAUNCH(k_enc_round_many, dim3((N + 255) / 256, batch), dim3(256), 0, c->stream, c->dev, cd, limbs, pt);
+  HIPCHK(hipGetLastError());
+  OpPlain::Params p{pt, pt, (size_t)limbs * N, (size_t)limbs * N, limbs, 0, 0, {}};
+  ntt_forward<OpPlain>(c, p, batch * limbs);
+}
+// host -> device bytes of a batched encryption call: the values, its randomness and (symmetric) the seeds
+static void count_client_h2d(evah_ctx *c, size_t bytes) { c->sh->xfer[4] += bytes; }
+
+// evah_encode_encrypt_many (small: the host's draws) and evah_encode_encrypt_sampled_many (rkeys: drawn here)
+static void encode_encrypt_many(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale,
+                                const int8_t *small, const uint8_t *rkeys, evah_ct **out) {
+  use(c);
+  encode_many_checks(c, batch, values, n_values, limbs, scale, out);
+  if (!small && !rkeys) throw std::invalid_argument("randomness pointer is null");
+  if (!c->sh->pk.d) throw std::invalid_argument("public key not present");
+  if (limbs + 1 > c->k) throw std::invalid_argument("plaintext level is not valid for encryption");
+  const size_t N = c->N, B = batch;
+  Scratch vals(c, B * n_values), cbuf(c, B * 2 * N), pt(c, B * limbs * N);
+  try {
+    encode_many(c, batch, values, n_values, limbs, scale, vals.d, reinterpret_cast<double2 *>(cbuf.d), pt.d);
+    *out = encrypt_public(c, batch, limbs, scale, pt.d, small, rkeys);
+  } catch (...) {
+    (void)hipStreamSynchronize(c->stream); // `values` is pageable host memory
+    throw;
+  }
+  count_client_h2d(c, sizeof(double) * B * n_values + (rkeys ? 32 * B : 3 * B * N));
+}
+
+// evah_encode_encrypt_symmetric_many (e: the host's draws) and evah_encode_encrypt_symmetric_sampled_many (ekeys: drawn here)
+static void encode_encrypt_symmetric_many(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale,
+                                          const int8_t *e, const uint8_t *ekeys, const uint8_t *seeds, evah_ct **out) {
+  use(c);
+  encode_many_checks(c, batch, values, n_values, limbs, scale, out);
+  if (!c->sh->sk.d) throw std::invalid_argument("secret key not present");
+  if ((!e && !ekeys) || !seeds) throw std::invalid_argument("error polynomial and seed are required");
+  const size_t N = c->N, B = batch;
+  Scratch vals(c, B * n_values), cbuf(c, B * 2 * N), pt(c, B * limbs * N);
+  try {
+    encode_many(c, batch, values, n_values, limbs, scale, vals.d, reinterpret_cast<double2 *>(cbuf.d), pt.d);
+    *out = encrypt_symmetric(c, batch, limbs, scale, pt.d, e, ekeys, seeds);
+  } catch (...) {
+    (void)hipStreamSynchronize(c->stream); // `values` is pageable host memory
+    throw;
+  }
+  count_client_h2d(c, sizeof(double) * B * n_values + (ekeys ? 32 * B : B * N) + 32 * B);
 }
 
 } // namespace evah
@@ -142,29 +637,8 @@ int evah_encrypt(evah_ctx *c, const evah_pt *pt, const int8_t *small, evah_ct **
   if (c->capturing) throw std::logic_error("this call synchronises with the host and cannot be captured into a graph");
   if (!c->sh->pk.d) throw std::invalid_argument("public key not present");
   acquire(c, pt->buf);
-  const uint32_t l = pt->limbs, up = l + 1;
-  if (up > c->k) throw std::invalid_argument("plaintext level is not valid for encryption");
-  const size_t N = c->N;
-  Scratch sm8(c, (3 * N + 7) / 8), sm(c, (size_t)3 * up * N), ct(c, (size_t)2 * up * N), r(c, 2 * N);
-  HIPCHK(hipMemcpyAsync(sm8.d, small, 3 * N, hipMemcpyHostToDevice, c->stream));
-  EW_LAUNCH(k_small_to_residues, dim3(c->N / 256, up, 3), dim3(256), 0, c->stream, c->dev, reinterpret_cast<const int8_t *>(sm8.d), 3u, up, sm.d);
-  OpPlain::Params fp{sm.d, sm.d, (size_t)up * N, (size_t)up * N, up, 0, 0, {}};
-  ntt_forward<OpPlain>(c, fp, 3 * up);
-  EW_LAUNCH(k_encrypt_zero, dim3(c->N / 256, up, 2), dim3(256), 0, c->stream, c->dev, c->sh->pk.d, sm.d, up, ct.d);
-  HIPCHK(hipGetLastError());
-  // divide and round by prime `l` (the last of the up primes), then add the plaintext to c0
-  evah_ct *o = ct_new(c, 2, l, pt->scale);
-  try {
-    OpPlain::Params ip{ct.d + (size_t)l * N, r.d, (size_t)up * N, N, 1, l, 1, {}};
-    ntt_inverse<OpPlain>(c, ip, 2);
-    OpModDown::Params mp{r.d, N, ct.d, (size_t)up * N, pt->d, 0, 1, o->d, o->ps, l, l};
-    ntt_forward<OpModDown>(c, mp, 2 * l);
-    HIPCHK(hipStreamSynchronize(c->stream)); // `small` is pageable host memory
-  } catch (...) {
-    evah_ct_free(c, o);
-    throw;
-  }
-  *out = o;
+  if (pt->limbs + 1 > c->k) throw std::invalid_argument("plaintext level is not valid for encryption");
+  *out = encrypt_public(c, 1, pt->limbs, pt->scale, pt->d, small, nullptr);
   API_END
 }
 
@@ -177,27 +651,37 @@ int evah_encrypt_symmetric(evah_ctx *c, const evah_pt *pt, const int8_t *e, cons
   if (!c->sh->sk.d) throw std::invalid_argument("secret key not present");
   if (!e || !seed32) throw std::invalid_argument("error polynomial and seed are required");
   if (c->N % 256) throw std::invalid_argument("encryption needs N divisible by 256");
-  const uint32_t l = pt->limbs;
-  if (l < 1 || l > c->k - 1) throw std::invalid_argument("plaintext level is not valid for encryption"); // no special prime
+  if (pt->limbs < 1 || pt->limbs > c->k - 1) throw std::invalid_argument("plaintext level is not valid for encryption"); // no special prime
   acquire(c, pt->buf);
-  const size_t N = c->N;
-  Scratch e8(c, (N + 7) / 8), en(c, (size_t)l * N);
-  HIPCHK(hipMemcpyAsync(e8.d, e, N, hipMemcpyHostToDevice, c->stream));
-  small_to_ntt(c, e8.d, 1, l, en.d);
-  evah_ct *o = ct_new(c, 2, l, pt->scale);
-  try {
-    const Seeds8 s = seeds_of(&seed32, 0, 1);
-    EW_LAUNCH(k_encrypt_symmetric, seeded_grid(c, l, 1), dim3(256), 0, c->stream, c->dev, s, pt->d, en.d, c->sh->sk.d, l, o->d, o->d + o->ps);
-    HIPCHK(hipGetLastError());
-    // the error does not stay behind in pool memory the next call reuses
-    HIPCHK(hipMemsetAsync(en.d, 0, sizeof(u64) * (size_t)l * N, c->stream));
-    HIPCHK(hipMemsetAsync(e8.d, 0, N, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream)); // `e` is pageable host memory
-  } catch (...) {
-    evah_ct_free(c, o);
-    throw;
-  }
-  *out = o;
+  *out = encrypt_symmetric(c, 1, pt->limbs, pt->scale, pt->d, e, nullptr, seed32);
+  API_END
+}
+
+int evah_encode_encrypt_many(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale,
+                             const int8_t *small, evah_ct **out) {
+  API_BEGIN
+  encode_encrypt_many(c, batch, values, n_values, limbs, scale, small, nullptr, out);
+  API_END
+}
+
+int evah_encode_encrypt_sampled_many(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale,
+                                     const uint8_t *rkeys, evah_ct **out) {
+  API_BEGIN
+  encode_encrypt_many(c, batch, values, n_values, limbs, scale, nullptr, rkeys, out);
+  API_END
+}
+
+int evah_encode_encrypt_symmetric_many(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale,
+                                       const int8_t *e, const uint8_t *seeds, evah_ct **out) {
+  API_BEGIN
+  encode_encrypt_symmetric_many(c, batch, values, n_values, limbs, scale, e, nullptr, seeds, out);
+  API_END
+}
+
+int evah_encode_encrypt_symmetric_sampled_many(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs,
+                                               double scale, const uint8_t *ekeys, const uint8_t *seeds, evah_ct **out) {
+  API_BEGIN
+  encode_encrypt_symmetric_many(c, batch, values, n_values, limbs, scale, nullptr, ekeys, seeds, out);
   API_END
 }
 
@@ -208,33 +692,34 @@ int evah_decrypt_decode(evah_ctx *c, const evah_ct *ct, uint32_t n_out, double *
   if (c->capturing) throw std::logic_error("this call synchronises with the host and cannot be captured into a graph");
   if (!c->sh->sk.d) throw std::invalid_argument("secret key not present");
   if (ct->batch != 1) throw std::invalid_argument("decrypt takes a single ciphertext");
-  acquire(c, ct->buf);
-  const uint32_t l = ct->limbs, N = c->N, slots = N >> 1;
-  if (n_out < 1 || n_out > slots) throw std::invalid_argument("slot count out of range");
-  if (l > 61) throw std::invalid_argument("too many limbs");
-  check_scale(c, ct->scale, l); // decode_internal: "scale out of bounds"
-  enc_tables(c);
-  dec_tables(c);
-  const std::vector<u64> tab = crt_tab_build(c, l); // Garner tables of this level
-  Scratch m(c, (size_t)l * N), tabd(c, tab.size()), cbuf(c, 2 * (size_t)N), outd(c, n_out);
-  HIPCHK(hipMemcpyAsync(tabd.d, tab.data(), sizeof(u64) * tab.size(), hipMemcpyHostToDevice, c->stream));
-  EW_LAUNCH(k_decrypt_dot, dim3(N / 256, l), dim3(256), 0, c->stream, c->dev, ct->d, ct->ps, ct->size, c->sh->sk.d, m.d);
-  OpPlain::Params ip{m.d, m.d, 0, 0, l, 0, 0, {}};
-  ntt_inverse<OpPlain>(c, ip, l);
-  const CrtTab t = crt_tab_at(tabd.d, l);
-  double2 *cd = reinterpret_cast<double2 *>(cbuf.d);
-  EW_LAUNCH(k_crt_to_double, dim3(N / 256), dim3(256), 0, c->stream, c->dev, t, l, m.d, 1.0 / ct->scale, cd);
-  // the decrypted message and its FP image do not stay behind in pool memory the next call reuses
-  HIPCHK(hipMemsetAsync(m.d, 0, sizeof(u64) * (size_t)l * N, c->stream));
-  for (uint32_t groups = 1, lg = c->logN - 1; groups < N; groups <<= 1, lg--)
-    hipLaunchKernelGGL(k_dec_fft_stage, dim3((slots + 255) / 256), dim3(256), 0, c->stream, cd, c->sh->dec_roots, groups, lg, slots);
-  hipLaunchKernelGGL(k_dec_gather, dim3((n_out + 255) / 256), dim3(256), 0, c->stream, cd, c->sh->enc_slot_map, n_out,
-                     reinterpret_cast<double *>(outd.d));
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, outd.d, sizeof(double) * n_out, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemsetAsync(cbuf.d, 0, sizeof(double2) * (size_t)N, c->stream));
-  HIPCHK(hipMemsetAsync(outd.d, 0, sizeof(double) * n_out, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  if (n_out < 1 || n_out > c->N >> 1) throw std::invalid_argument("slot count out of range");
+  if (ct->limbs > 61) throw std::invalid_argument("too many limbs");
+  check_scale(c, ct->scale, ct->limbs); // decode_internal: "scale out of bounds"
+  decrypt_decode(c, &ct, 1, n_out, out);
+  API_END
+}
+
+int evah_decrypt_decode_many(evah_ctx *c, const evah_ct *const *cts, uint32_t n, uint32_t n_out, double *out) {
+  API_BEGIN
+  use(c);
+  if (c->capturing) throw std::logic_error("this call synchronises with the host and cannot be captured into a graph");
+  if (!c->sh->sk.d) throw std::invalid_argument("secret key not present");
+  if (n < 1 || n > (uint32_t)KS_BATCH_MAX) throw std::invalid_argument("batch must be 1..64");
+  if (!cts || !out) throw std::invalid_argument("ciphertext list and output are required");
+  for (uint32_t i = 0; i < n; i++) {
+    const std::string at = "ciphertext " + std::to_string(i);
+    if (!cts[i]) throw std::invalid_argument(at + " is null");
+    if (cts[i]->batch != 1) throw std::invalid_argument(at + ": decrypt takes a single ciphertext");
+    if (cts[i]->size != cts[0]->size) throw std::invalid_argument(at + ": size differs from ciphertext 0");
+    if (cts[i]->limbs != cts[0]->limbs) throw std::invalid_argument(at + ": limb count differs from ciphertext 0");
+    if (cts[i]->scale != cts[0]->scale) throw std::invalid_argument(at + ": scale differs from ciphertext 0");
+  }
+  if (cts[0]->size < 1 || cts[0]->size > 3) throw std::invalid_argument("ciphertext size out of range");
+  if (n_out < 1 || n_out > c->N >> 1) throw std::invalid_argument("slot count out of range");
+  if (cts[0]->limbs > 61) throw std::invalid_argument("too many limbs");
+  if (c->N % 256) throw std::invalid_argument("decryption needs N divisible by 256");
+  check_scale(c, cts[0]->scale, cts[0]->limbs); // decode_internal: "scale out of bounds"
+  decrypt_decode(c, cts, n, n_out, out);
   API_END
 }
 

@@ -9,8 +9,8 @@
 //   rotate.hip       Galois permutation, rotations, rotation sets (machinery: rotation_sets.hip.h, rot_fallback.hip.h)
 //   windows.hip      evah_rotate_weighted_sums: convolution windows over the same machinery
 //   shard.hip        limb-sharded phases (evah_shard_*), exchange buffers
-//   client.hip       encrypt, decrypt + decode
-//   client_batch.hip the same for a batch per call: tiled FP64 special FFT, batched encrypt / decrypt kernels
+//   client.hip       encrypt, decrypt + decode of up to 64 values per call (one body per operation, the single calls
+//                    are the batch of one): tiled FP64 special FFT, device sampling, encrypt / decrypt kernels
 //   launch.hip.h     launch plumbing of the transform kernels shared by the units above
 //   scheduler.hip  evah_execute: the whole-DAG submit (level scheduler, peepholes)   (no kernels)
 #pragma once
@@ -191,7 +191,7 @@ struct SharedDev {
   KeyDev relin;
   KeyDev pk, sk; // client side (client.hip): public key [2][k][N], secret key in NTT form [k][N]
   double2 *dec_roots = nullptr; // CKKS decoder: zeta^br(j) (forward special FFT, heap order)
-  std::map<uint32_t, u64 *> crt_tabs; // batched decoder (client_batch.hip): the Garner tables of a level, built at its first use
+  std::map<uint32_t, u64 *> crt_tabs; // decoder (client.hip): the Garner tables of a level, built at its first use
   std::map<uint32_t, KeyDev> galois;
   std::map<uint32_t, uint32_t *> perms;
   std::map<uint32_t, uint32_t *> perms_inv; // the inverse tables (hoisted rotation sets)

@@ -1,5 +1,5 @@
 // sampled.hip.h — the small polynomials of an encryption drawn on the device from a 32-byte randomness key per value
-// (DESIGN.md 1.7), used by client_batch.hip: polynomial p (0 = the ternary u, 1 = the error e0 — the one error of a
+// (DESIGN.md 1.7), used by client.hip: polynomial p (0 = the ternary u, 1 = the error e0 — the one error of a
 // symmetric encryption —, 2 = the error e1), coefficient j from the little-endian u64 word w = j % 8 of the ChaCha20
 // block of key = the randomness key, block counter = j / 8 (state words 12-13), nonce = 0x736d000000000000 | p (words
 // 14-15).  Ternary: floor(3 w / 2^64) - 1 (no rejection, every outcome within 2^-64 of 1/3); error:

@@ -1,7 +1,7 @@
 // seeded.hip — ciphertexts whose second polynomial travels as a 32-byte seed (SEAL's Encryptor::encrypt_symmetric
 // followed by a seeded save): uploads of c0 + seed with c1 expanded on the queue (the expansion rule:
 // seeded.hip.h), slot refills of captured graphs, and the download of c0 alone.  The fused symmetric encryption
-// (evah_encrypt_symmetric) lives in client.hip beside evah_encrypt.  Evaluation keys travel the same way:
+// (evah_encrypt_symmetric and its _many forms) lives in client.hip beside the public-key one.  Evaluation keys travel the same way:
 // evah_key_upload_seeded takes c0 and one seed per digit and expands every c1 row — and the split copy — in one launch.
 // evah_keygen_switch makes the whole key here: c0 as well, from the resident secret key and N int8 error
 // draws per digit.

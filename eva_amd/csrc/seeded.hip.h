@@ -1,5 +1,5 @@
 // seeded.hip.h — the expansion of a seeded polynomial, shared by seeded.hip (uploads of c0 + seed)
-// and client.hip (evah_encrypt_symmetric): limb i (chain prime index), coefficient j = (hi 2^64 + lo) mod q_i with
+// and client.hip (k_encrypt_symmetric): limb i (chain prime index), coefficient j = (hi 2^64 + lo) mod q_i with
 // (lo, hi) = the words 2 (j % 4) and 2 (j % 4) + 1 (as little-endian u64) of the ChaCha20 block of key = seed, block
 // counter = j / 4 (state words 12-13), nonce = 0x6331000000000000 | i (words 14-15).  The result is limb i of c1 in NTT
 // form as stored; a limb depends only on (seed, i).  Host twin: eva_amd/host/csprng.h seeded_limb.

@@ -20,66 +20,72 @@ inline std::vector<std::string> batch_input_names(const std::vector<Valuation> &
   return names;
 }
 
-// SEALPublic::encrypt (seal.cpp:24-102)
-inline HipValuation HipPublic::encrypt(const Valuation &inputs, const CKKSSignature &sig) {
-  const size_t slots = host->N / 2;
+// the signature checks every client call makes first
+inline void check_vec_size(const CKKSSignature &sig, size_t slots) {
   if (sig.vec_size <= 0) throw std::runtime_error("Signature vector size must be positive");
   if (slots < (size_t)sig.vec_size) throw std::runtime_error("Vector size cannot be larger than slot count");
   if (slots % sig.vec_size) throw std::runtime_error("Vector size must exactly divide the slot count");
-  HipValuation out;
-  SecureRng rng; // a fresh ChaCha20 stream keyed with 256 bits from the OS for this call (csprng.h)
-  for (auto &kv : inputs) {
-    const auto &v = kv.second;
-    if (v.size() != (size_t)sig.vec_size) throw std::runtime_error("Input size does not match program vector size");
-    auto it = sig.inputs.find(kv.first);
-    if (it == sig.inputs.end()) throw std::out_of_range("No input named " + kv.first + " in the signature");
-    const CKKSEncodingInfo &info = it->second;
-    if (info.input_type == Type::Cipher || info.input_type == Type::Plain) {
-      if ((uint32_t)info.level >= host->k - 1) throw std::runtime_error("Input level exceeds the modulus chain");
-      HostPlain pt;
-      pt.limbs = host->k - 1 - (uint32_t)info.level;
-      pt.scale = std::pow(2.0, (double)info.scale);
-      if (info.input_type == Type::Cipher && client_on_device() && device_encodable(v, pt.scale, pt.limbs)) {
-        // encoder and encryptor both on the GPU (evah_pt_encode -> evah_encrypt): the plaintext never
-        // exists on the host.  Same plaintext as the host encoder bit for bit (tests/test_encode_parity.py)
-        // and the same sampler calls in the same order, hence the same ciphertext as every other path
-        out.values[kv.first] = encrypt_on_device(nullptr, &v, pt.scale, pt.limbs, rng);
-        continue;
-      }
-      pt.data.resize((size_t)pt.limbs * host->N);
-      std::vector<double> vec(slots);
-      for (size_t r = 0; r < slots / v.size(); r++) std::copy(v.begin(), v.end(), vec.begin() + r * v.size());
-      host->encode_coeff(vec.data(), pt.scale, pt.limbs, pt.data.data());
-      if (info.input_type == Type::Cipher && client_on_device()) {
-        // device path: the per-limb transforms, the public-key products and the mod-down run on the
-        // GPU (evah_encrypt); the host keeps the FP64 encoder and the sampling (same sampler calls,
-        // in the same order, as evahost::encrypt — so both paths give the same ciphertext for the
-        // same random stream)
-        out.values[kv.first] = encrypt_on_device(&pt, nullptr, pt.scale, pt.limbs, rng);
-        continue;
-      }
-      for (uint32_t i = 0; i < pt.limbs; i++) host->ntt(i, pt.data.data() + (size_t)i * host->N);
-      if (info.input_type == Type::Cipher) out.values[kv.first] = evahost::encrypt(*host, pk, pt, rng);
-      else out.values[kv.first] = std::move(pt);
-    } else {
-      out.values[kv.first] = v;
-    }
-  }
-  return out;
+}
+inline void check_input_size(const std::vector<double> &v, const CKKSSignature &sig) {
+  if (v.size() != (size_t)sig.vec_size) throw std::runtime_error("Input size does not match program vector size");
+}
+// what the signature makes of an input: Cipher (encoded and encrypted) or Plain (encoded), both with the limb count and
+// scale of their level, or anything else (raw: passed through)
+struct InputClass {
+  Type kind;
+  uint32_t limbs = 0;
+  double scale = 0;
+};
+inline InputClass classify_input(const HostContext &hc, const CKKSSignature &sig, const std::string &name) {
+  auto it = sig.inputs.find(name);
+  if (it == sig.inputs.end()) throw std::out_of_range("No input named " + name + " in the signature");
+  const CKKSEncodingInfo &info = it->second;
+  InputClass in{info.input_type};
+  if (in.kind != Type::Cipher && in.kind != Type::Plain) return in;
+  if ((uint32_t)info.level >= hc.k - 1) throw std::runtime_error("Input level exceeds the modulus chain");
+  in.limbs = hc.k - 1 - (uint32_t)info.level;
+  in.scale = std::pow(2.0, (double)info.scale);
+  return in;
 }
 
-// EVA_DEVICE_CLIENT=0 keeps encrypt on the host; without a HIP device the host path is the only one
-// (encrypt, unlike execute(), is client-side work the reference also does on the CPU)
-inline bool HipPublic::client_on_device() {
-  if (client_device < 0) {
-    const char *e = std::getenv("EVA_DEVICE_CLIENT");
-    int n = 0;
-    client_device = (!e || std::atoi(e) != 0) && evah_device_count(&n) == 0 && n > 0 ? 1 : 0;
+// the host encoder's coefficient-form plaintext of v repeated over the slots; ntt_limbs: to its NTT form, in place
+inline HostPlain encode_host(const HostContext &hc, const std::vector<double> &v, double scale, uint32_t limbs) {
+  const size_t slots = hc.N / 2;
+  HostPlain pt;
+  pt.limbs = limbs;
+  pt.scale = scale;
+  pt.data.resize((size_t)limbs * hc.N);
+  std::vector<double> vec(slots);
+  for (size_t r = 0; r < slots / v.size(); r++) std::copy(v.begin(), v.end(), vec.begin() + r * v.size());
+  hc.encode_coeff(vec.data(), scale, limbs, pt.data.data());
+  return pt;
+}
+inline void ntt_limbs(const HostContext &hc, HostPlain &pt) {
+  for (uint32_t i = 0; i < pt.limbs; i++) hc.ntt(i, pt.data.data() + (size_t)i * hc.N);
+}
+// a Plain input encoded, a raw one passed through; false for a Cipher input, which is the caller's to encrypt
+inline bool unencrypted_value(const HostContext &hc, const InputClass &in, const std::vector<double> &v, SchemeValue &out) {
+  if (in.kind == Type::Cipher) return false;
+  if (in.kind == Type::Plain) {
+    HostPlain pt = encode_host(hc, v, in.scale, in.limbs);
+    ntt_limbs(hc, pt);
+    out = std::move(pt);
+  } else {
+    out = v;
   }
-  return client_device == 1;
+  return true;
 }
 
-// same bound as HipExecutor::device_encodable: every rounded coefficient below 2^62 and inside the modulus
+// EVA_DEVICE_CLIENT=0 keeps the client calls on the host; without a HIP device the host path is the only one
+// (encrypt and decrypt, unlike execute(), are client-side work the reference also does on the CPU)
+inline bool device_client_enabled() {
+  const char *e = std::getenv("EVA_DEVICE_CLIENT");
+  int n = 0;
+  return (!e || std::atoi(e) != 0) && evah_device_count(&n) == 0 && n > 0;
+}
+
+// the bound of HipExecutor::device_encodable — every rounded coefficient below 2^62 and inside the modulus — behind
+// EVA_DEVICE_ENCODE, which the executor reads once when it is made and the client at every call
 inline bool device_encodable(const HostContext &hc, const std::vector<double> &in, double scale, uint32_t limbs) {
   const size_t slots = hc.N / 2;
   if (std::getenv("EVA_DEVICE_ENCODE") && !std::atoi(std::getenv("EVA_DEVICE_ENCODE"))) return false;
@@ -93,30 +99,119 @@ inline bool device_encodable(const HostContext &hc, const std::vector<double> &i
   const int bits = (int)std::ceil(std::log2(std::max(bound, 1.0))) + 1;
   return bits < 62 && bits < hc.total_bits[limbs];
 }
-inline bool HipPublic::device_encodable(const std::vector<double> &in, double scale, uint32_t limbs) const {
-  return evahost::device_encodable(*host, in, scale, limbs);
+
+// A device handle as a value: resident (it stays in HBM, host words on demand) or downloaded.  seed: the value is
+// seeded — the seed stays with it, so that save() can still write the value compressed, and only c0
+// crosses PCIe: c1 is the seed's.
+inline HostCipher cipher_of_handle(const std::shared_ptr<DeviceCtx> &dev, const HostContext &hc, evah_ct *h, uint32_t limbs, double scale,
+                                   bool resident, const std::array<uint8_t, 32> *seed = nullptr) {
+  auto handle = std::make_shared<CtHandle>(dev->h, h);
+  HostCipher out;
+  out.size = 2;
+  out.limbs = limbs;
+  out.scale = scale;
+  out.words_checked = seed || !resident;
+  std::shared_ptr<SeededForm> sf;
+  if (seed) {
+    sf = std::make_shared<SeededForm>();
+    sf->seed = *seed;
+    sf->N = hc.N;
+    sf->primes.assign(hc.primes.begin(), hc.primes.begin() + limbs);
+  }
+  if (resident) {
+    out.dev = std::make_shared<DeviceResident>(DeviceResident{dev, nullptr, handle, hc.N});
+  } else if (sf) {
+    sf->c0.resize((size_t)limbs * hc.N);
+    chk(evah_ct_download_poly(dev->h, h, 0, (uint64_t *)sf->c0.data()));
+  } else {
+    out.data.resize((size_t)2 * limbs * hc.N);
+    chk(evah_ct_download(dev->h, h, (uint64_t *)out.data.data()));
+  }
+  out.seeded = std::move(sf);
+  return out;
+}
+// the instances of a batched handle as values: views that share its allocation, which lives until the last one is freed
+inline std::vector<HostCipher> group_results(const std::shared_ptr<DeviceCtx> &dev, const HostContext &hc, evah_ct *c, size_t B, uint32_t limbs,
+                                             double scale, bool resident, const std::array<uint8_t, 32> *seeds = nullptr) {
+  CtHandle group(dev->h, c);
+  std::vector<HostCipher> out(B);
+  for (size_t b = 0; b < B; b++) {
+    evah_ct *view = nullptr;
+    chk(evah_ct_unstack(dev->h, c, (uint32_t)b, &view));
+    out[b] = cipher_of_handle(dev, hc, view, limbs, scale, resident, seeds ? seeds + b : nullptr);
+  }
+  return out;
+}
+// the device calls of an encrypt_batch: the instances of input `name` in groups of <= 64, fn(the group's values, its
+// first instance) returning the group's ciphertexts
+template <class F> void encrypt_in_groups(const std::vector<Valuation> &inputs, const std::string &name, std::vector<HipValuation> &out, F fn) {
+  for (size_t b0 = 0; b0 < inputs.size(); b0 += CLIENT_BATCH_MAX) {
+    const size_t n = std::min<size_t>(CLIENT_BATCH_MAX, inputs.size() - b0);
+    std::vector<const std::vector<double> *> vals(n);
+    for (size_t b = 0; b < n; b++) vals[b] = &inputs[b0 + b].at(name);
+    std::vector<HostCipher> cts = fn(vals, b0);
+    for (size_t b = 0; b < n; b++) out[b0 + b].values[name] = std::move(cts[b]);
+  }
+}
+inline std::vector<double> flatten(const std::vector<const std::vector<double> *> &vals) {
+  const size_t nv = vals[0]->size();
+  std::vector<double> flat(vals.size() * nv);
+  for (size_t b = 0; b < vals.size(); b++) std::copy(vals[b]->begin(), vals[b]->end(), flat.begin() + b * nv);
+  return flat;
+}
+struct WipeOnExit {
+  std::vector<int8_t> &s;
+  ~WipeOnExit() { wipe(s); }
+};
+// u, e0, e1 of one public-key encryption from rng, in evahost::encrypt's order, as int8 [3][N] at small
+inline void draw_small3(const HostContext &hc, SecureRng &rng, int8_t *small) {
+  std::vector<int8_t> u, e0, e1;
+  hc.sample_ternary(rng, u);
+  hc.sample_error(rng, e0);
+  hc.sample_error(rng, e1);
+  std::copy(u.begin(), u.end(), small);
+  std::copy(e0.begin(), e0.end(), small + hc.N);
+  std::copy(e1.begin(), e1.end(), small + 2 * (size_t)hc.N);
+  wipe(u); wipe(e0); wipe(e1);
 }
 
-// coeff_pt: the host encoder's coefficient-form plaintext, or (null) values: the slot values for the device encoder
-inline HostCipher HipPublic::encrypt_on_device(const HostPlain *coeff_pt, const std::vector<double> *values, double scale, uint32_t limbs, SecureRng &rng) {
-  const uint32_t N = host->N;
-  std::vector<int8_t> u, e0, e1, small((size_t)3 * N);
-  host->sample_ternary(rng, u);
-  host->sample_error(rng, e0);
-  host->sample_error(rng, e1);
-  std::copy(u.begin(), u.end(), small.begin());
-  std::copy(e0.begin(), e0.end(), small.begin() + N);
-  std::copy(e1.begin(), e1.end(), small.begin() + 2 * (size_t)N);
-  return encrypt_on_device_with(coeff_pt, values, scale, limbs, small);
+// SEALPublic::encrypt (seal.cpp:24-102)
+inline HipValuation HipPublic::encrypt(const Valuation &inputs, const CKKSSignature &sig) {
+  check_vec_size(sig, host->N / 2);
+  HipValuation out;
+  SecureRng rng; // a fresh ChaCha20 stream keyed with 256 bits from the OS for this call (csprng.h)
+  for (auto &kv : inputs) {
+    const auto &v = kv.second;
+    check_input_size(v, sig);
+    const InputClass in = classify_input(*host, sig, kv.first);
+    if (unencrypted_value(*host, in, v, out.values[kv.first])) continue;
+    // the encoders consume no randomness: the draws come first on every path, hence the same ciphertext on each
+    std::vector<int8_t> small((size_t)3 * host->N);
+    WipeOnExit wipe_small{small};
+    draw_small3(*host, rng, small.data());
+    out.values[kv.first] = encrypt_value_with(v, in.scale, in.limbs, small);
+  }
+  return out;
 }
-inline HostCipher HipPublic::encrypt_on_device_with(const HostPlain *coeff_pt, const std::vector<double> *values, double scale, uint32_t limbs,
-                                                    const std::vector<int8_t> &small) {
+
+inline bool HipPublic::client_on_device() {
+  if (client_device < 0) client_device = device_client_enabled() ? 1 : 0;
+  return client_device == 1;
+}
+inline void HipPublic::ensure_public_key() {
   ensure_device(false);
   if (!pk_uploaded) {
     chk(evah_client_key_upload(dev->h, EVAH_KEY_PUBLIC, (const uint64_t *)pk.data.data()));
     pk_uploaded = true;
   }
-  const uint32_t N = host->N;
+}
+
+// coeff_pt: the host encoder's coefficient-form plaintext, or (null) values: the slot values for the device encoder
+// (evah_pt_encode: the plaintext never exists on the host, and is the host encoder's bit for bit,
+// tests/test_encode_parity.py); then evah_encrypt with small = (u, e0, e1) as int8 [3][N]
+inline HostCipher HipPublic::encrypt_on_device_with(const HostPlain *coeff_pt, const std::vector<double> *values, double scale, uint32_t limbs,
+                                                    const std::vector<int8_t> &small) {
+  ensure_public_key();
   evah_pt *p = nullptr;
   if (coeff_pt) chk(evah_pt_upload_coeff(dev->h, limbs, scale, (const uint64_t *)coeff_pt->data.data(), &p));
   else chk(evah_pt_encode(dev->h, values->data(), (uint32_t)values->size(), limbs, scale, &p));
@@ -124,35 +219,18 @@ inline HostCipher HipPublic::encrypt_on_device_with(const HostPlain *coeff_pt, c
   int rc = evah_encrypt(dev->h, p, small.data(), &c);
   evah_pt_free(dev->h, p);
   chk(rc);
-  HostCipher out;
-  out.size = 2;
-  out.limbs = limbs;
-  out.scale = scale;
-  auto handle = std::make_shared<CtHandle>(dev->h, c);
-  if (resident) { // stays in HBM; host words on demand
-    out.dev = std::make_shared<DeviceResident>(DeviceResident{dev, nullptr, handle, host->N});
-    return out;
-  }
-  out.data.resize((size_t)2 * out.limbs * N);
-  out.words_checked = true;
-  chk(evah_ct_download(dev->h, c, (uint64_t *)out.data.data()));
-  return out;
+  return cipher_of_handle(dev, *host, c, limbs, scale, resident);
 }
 
 // the Cipher branch of encrypt() for one input, the randomness given: device encoder + encryptor, host encoder + device
-// encryptor, or the host alone — the same words on each
+// encryptor (the per-limb transforms, the public-key products and the mod-down on the GPU), or the host alone — the same
+// words on each
 inline HostCipher HipPublic::encrypt_value_with(const std::vector<double> &v, double scale, uint32_t limbs, const std::vector<int8_t> &small) {
-  if (client_on_device() && device_encodable(v, scale, limbs)) return encrypt_on_device_with(nullptr, &v, scale, limbs, small);
-  const size_t slots = host->N / 2, N = host->N;
-  HostPlain pt;
-  pt.limbs = limbs;
-  pt.scale = scale;
-  pt.data.resize((size_t)limbs * N);
-  std::vector<double> vec(slots);
-  for (size_t r = 0; r < slots / v.size(); r++) std::copy(v.begin(), v.end(), vec.begin() + r * v.size());
-  host->encode_coeff(vec.data(), scale, limbs, pt.data.data());
+  if (client_on_device() && device_encodable(*host, v, scale, limbs)) return encrypt_on_device_with(nullptr, &v, scale, limbs, small);
+  HostPlain pt = encode_host(*host, v, scale, limbs);
   if (client_on_device()) return encrypt_on_device_with(&pt, nullptr, scale, limbs, small);
-  for (uint32_t i = 0; i < limbs; i++) host->ntt(i, pt.data.data() + (size_t)i * N);
+  ntt_limbs(*host, pt);
+  const size_t N = host->N;
   std::vector<int8_t> u(small.begin(), small.begin() + N), e0(small.begin() + N, small.begin() + 2 * N), e1(small.begin() + 2 * N, small.end());
   HostCipher out = evahost::encrypt(*host, pk, pt, u, e0, e1);
   wipe(u); wipe(e0); wipe(e1);
@@ -168,14 +246,17 @@ inline HostCipher HipPublic::encrypt_value_with(const std::vector<double> &v, do
 // other path expands the same keys with the host twin.
 inline std::vector<HipValuation> HipPublic::encrypt_batch(const std::vector<Valuation> &inputs, const CKKSSignature &sig, bool device_sampling,
                                                           uint64_t seed) {
-  const size_t slots = host->N / 2;
   if (seed && !device_sampling) throw std::invalid_argument("encrypt_batch: seed is the test hook of device_sampling and needs device_sampling=True");
-  if (sig.vec_size <= 0) throw std::runtime_error("Signature vector size must be positive");
-  if (slots < (size_t)sig.vec_size) throw std::runtime_error("Vector size cannot be larger than slot count");
-  if (slots % sig.vec_size) throw std::runtime_error("Vector size must exactly divide the slot count");
+  check_vec_size(sig, host->N / 2);
   std::vector<HipValuation> out(inputs.size());
   if (inputs.empty()) return out;
   const std::vector<std::string> names = batch_input_names(inputs);
+  auto per_instance = [&](const std::string &name) { // encrypt()'s path, instance by instance
+    for (size_t b = 0; b < inputs.size(); b++) {
+      HipValuation one = encrypt(Valuation{{name, inputs[b].at(name)}}, sig);
+      out[b].values[name] = std::move(one.values.at(name));
+    }
+  };
   if (device_sampling) {
     std::unique_ptr<SecureRng> stream = seed ? std::make_unique<SecureRng>(seed, 5) : std::make_unique<SecureRng>();
     std::vector<std::vector<std::array<uint8_t, 32>>> rkeys(names.size()); // per name, per instance
@@ -183,157 +264,84 @@ inline std::vector<HipValuation> HipPublic::encrypt_batch(const std::vector<Valu
       std::vector<std::vector<std::array<uint8_t, 32>>> &k;
       ~WipeKeys() { for (auto &n : k) for (auto &x : n) wipe_bytes(x.data(), 32); }
     } wipe_keys{rkeys};
-    std::vector<const CKKSEncodingInfo *> infos(names.size());
-    for (size_t i = 0; i < names.size(); i++) {
-      auto it = sig.inputs.find(names[i]);
-      if (it == sig.inputs.end()) throw std::out_of_range("No input named " + names[i] + " in the signature");
-      infos[i] = &it->second;
-      if (it->second.input_type == Type::Cipher && (uint32_t)it->second.level >= host->k - 1) throw std::runtime_error("Input level exceeds the modulus chain");
-    }
+    std::vector<InputClass> cls;
+    for (const std::string &name : names) cls.push_back(classify_input(*host, sig, name));
     for (size_t b = 0; b < inputs.size(); b++)
       for (size_t i = 0; i < names.size(); i++) {
-        if (inputs[b].at(names[i]).size() != (size_t)sig.vec_size) throw std::runtime_error("Input size does not match program vector size");
-        if (infos[i]->input_type == Type::Cipher) rkeys[i].push_back(draw_key32(*stream));
+        check_input_size(inputs[b].at(names[i]), sig);
+        if (cls[i].kind == Type::Cipher) rkeys[i].push_back(draw_key32(*stream));
       }
     for (size_t i = 0; i < names.size(); i++) {
       const std::string &name = names[i];
-      if (infos[i]->input_type != Type::Cipher) { // plain and raw inputs take no randomness: encrypt()'s path
-        for (size_t b = 0; b < inputs.size(); b++) {
-          HipValuation one = encrypt(Valuation{{name, inputs[b].at(name)}}, sig);
-          out[b].values[name] = std::move(one.values.at(name));
-        }
+      const uint32_t limbs = cls[i].limbs;
+      const double scale = cls[i].scale;
+      if (cls[i].kind != Type::Cipher) { // plain and raw inputs take no randomness
+        per_instance(name);
         continue;
       }
-      const uint32_t limbs = host->k - 1 - (uint32_t)infos[i]->level;
-      const double scale = std::pow(2.0, (double)infos[i]->scale);
       bool grouped = client_on_device();
-      for (size_t b = 0; grouped && b < inputs.size(); b++) grouped = device_encodable(inputs[b].at(name), scale, limbs);
+      for (size_t b = 0; grouped && b < inputs.size(); b++) grouped = device_encodable(*host, inputs[b].at(name), scale, limbs);
       if (!grouped) { // the same keys through the host twin, instance by instance
         for (size_t b = 0; b < inputs.size(); b++) {
           std::vector<int8_t> small = sampled_small3(rkeys[i][b], host->N);
-          struct WipeSmall {
-            std::vector<int8_t> &s;
-            ~WipeSmall() { wipe(s); }
-          } wipe_small{small};
+          WipeOnExit wipe_small{small};
           out[b].values[name] = encrypt_value_with(inputs[b].at(name), scale, limbs, small);
         }
         continue;
       }
-      for (size_t b0 = 0; b0 < inputs.size(); b0 += CLIENT_BATCH_MAX) {
-        const size_t n = std::min<size_t>(CLIENT_BATCH_MAX, inputs.size() - b0);
-        std::vector<const std::vector<double> *> vals(n);
-        for (size_t b = 0; b < n; b++) vals[b] = &inputs[b0 + b].at(name);
-        std::vector<HostCipher> cts = encrypt_group_sampled(vals, scale, limbs, rkeys[i].data() + b0);
-        for (size_t b = 0; b < n; b++) out[b0 + b].values[name] = std::move(cts[b]);
-      }
+      encrypt_in_groups(inputs, name, out, [&](const std::vector<const std::vector<double> *> &vals, size_t b0) {
+        return encrypt_group_sampled(vals, scale, limbs, rkeys[i].data() + b0);
+      });
     }
     return out;
   }
   SecureRng rng; // one fresh ChaCha20 stream keyed from the OS for the whole call
   for (const std::string &name : names) {
-    auto it = sig.inputs.find(name);
-    if (it == sig.inputs.end()) throw std::out_of_range("No input named " + name + " in the signature");
-    const CKKSEncodingInfo &info = it->second;
-    bool grouped = info.input_type == Type::Cipher && client_on_device();
-    uint32_t limbs = 0;
-    double scale = 0;
-    if (grouped) {
-      if ((uint32_t)info.level >= host->k - 1) throw std::runtime_error("Input level exceeds the modulus chain");
-      limbs = host->k - 1 - (uint32_t)info.level;
-      scale = std::pow(2.0, (double)info.scale);
-    }
+    const InputClass in = classify_input(*host, sig, name);
+    bool grouped = in.kind == Type::Cipher && client_on_device();
     for (size_t b = 0; b < inputs.size(); b++) {
       const auto &v = inputs[b].at(name);
-      if (v.size() != (size_t)sig.vec_size) throw std::runtime_error("Input size does not match program vector size");
-      if (grouped && !device_encodable(v, scale, limbs)) grouped = false;
+      check_input_size(v, sig);
+      if (grouped && !device_encodable(*host, v, in.scale, in.limbs)) grouped = false;
     }
-    if (!grouped) { // encrypt()'s path, instance by instance
-      for (size_t b = 0; b < inputs.size(); b++) {
-        HipValuation one = encrypt(Valuation{{name, inputs[b].at(name)}}, sig);
-        out[b].values[name] = std::move(one.values.at(name));
-      }
+    if (!grouped) {
+      per_instance(name);
       continue;
     }
-    for (size_t b0 = 0; b0 < inputs.size(); b0 += CLIENT_BATCH_MAX) {
-      const size_t n = std::min<size_t>(CLIENT_BATCH_MAX, inputs.size() - b0);
-      std::vector<const std::vector<double> *> vals(n);
-      for (size_t b = 0; b < n; b++) vals[b] = &inputs[b0 + b].at(name);
-      std::vector<HostCipher> cts = encrypt_group_on_device(vals, scale, limbs, rng);
-      for (size_t b = 0; b < n; b++) out[b0 + b].values[name] = std::move(cts[b]);
-    }
+    encrypt_in_groups(inputs, name, out, [&](const std::vector<const std::vector<double> *> &vals, size_t) {
+      return encrypt_group_on_device(vals, in.scale, in.limbs, rng);
+    });
   }
   return out;
 }
 
-// one group of encrypt_batch: the sampler calls of encrypt_on_device per instance, in list order, then one device call
+// one group of encrypt_batch: encrypt()'s sampler calls per instance, in list order, then one device call
 inline std::vector<HostCipher> HipPublic::encrypt_group_on_device(const std::vector<const std::vector<double> *> &vals, double scale,
                                                                   uint32_t limbs, SecureRng &rng) {
-  ensure_device(false);
-  if (!pk_uploaded) {
-    chk(evah_client_key_upload(dev->h, EVAH_KEY_PUBLIC, (const uint64_t *)pk.data.data()));
-    pk_uploaded = true;
-  }
-  const uint32_t N = host->N;
-  const size_t B = vals.size(), nv = vals[0]->size();
-  std::vector<double> flat(B * nv);
-  std::vector<int8_t> u, e0, e1, small(B * 3 * N);
-  for (size_t b = 0; b < B; b++) {
-    std::copy(vals[b]->begin(), vals[b]->end(), flat.begin() + b * nv);
-    host->sample_ternary(rng, u);
-    host->sample_error(rng, e0);
-    host->sample_error(rng, e1);
-    std::copy(u.begin(), u.end(), small.begin() + (3 * b) * N);
-    std::copy(e0.begin(), e0.end(), small.begin() + (3 * b + 1) * N);
-    std::copy(e1.begin(), e1.end(), small.begin() + (3 * b + 2) * N);
-  }
+  ensure_public_key();
+  const size_t B = vals.size(), N = host->N;
+  const std::vector<double> flat = flatten(vals);
+  std::vector<int8_t> small(B * 3 * N);
+  WipeOnExit wipe_small{small};
+  for (size_t b = 0; b < B; b++) draw_small3(*host, rng, small.data() + 3 * b * N);
   evah_ct *c = nullptr;
-  const int rc = evah_encode_encrypt_many(dev->h, (uint32_t)B, flat.data(), (uint32_t)nv, limbs, scale, small.data(), &c);
-  wipe(u); wipe(e0); wipe(e1); wipe(small);
-  chk(rc);
-  return group_results(c, B, scale, limbs);
+  chk(evah_encode_encrypt_many(dev->h, (uint32_t)B, flat.data(), (uint32_t)vals[0]->size(), limbs, scale, small.data(), &c));
+  return group_results(dev, *host, c, B, limbs, scale, resident);
 }
 
+// the same as one evah_encode_encrypt_sampled_many: instance b's randomness is drawn on the device from rkeys[b]
 inline std::vector<HostCipher> HipPublic::encrypt_group_sampled(const std::vector<const std::vector<double> *> &vals, double scale, uint32_t limbs,
                                                                 const std::array<uint8_t, 32> *rkeys) {
-  ensure_device(false);
-  if (!pk_uploaded) {
-    chk(evah_client_key_upload(dev->h, EVAH_KEY_PUBLIC, (const uint64_t *)pk.data.data()));
-    pk_uploaded = true;
-  }
-  const size_t B = vals.size(), nv = vals[0]->size();
-  std::vector<double> flat(B * nv);
+  ensure_public_key();
+  const size_t B = vals.size();
+  const std::vector<double> flat = flatten(vals);
   std::vector<uint8_t> keys(B * 32);
-  for (size_t b = 0; b < B; b++) {
-    std::copy(vals[b]->begin(), vals[b]->end(), flat.begin() + b * nv);
-    std::copy(rkeys[b].begin(), rkeys[b].end(), keys.begin() + b * 32);
-  }
+  for (size_t b = 0; b < B; b++) std::copy(rkeys[b].begin(), rkeys[b].end(), keys.begin() + b * 32);
   evah_ct *c = nullptr;
-  const int rc = evah_encode_encrypt_sampled_many(dev->h, (uint32_t)B, flat.data(), (uint32_t)nv, limbs, scale, keys.data(), &c);
+  const int rc = evah_encode_encrypt_sampled_many(dev->h, (uint32_t)B, flat.data(), (uint32_t)vals[0]->size(), limbs, scale, keys.data(), &c);
   wipe_bytes(keys.data(), keys.size());
   chk(rc);
-  return group_results(c, B, scale, limbs);
-}
-
-inline std::vector<HostCipher> HipPublic::group_results(evah_ct *c, size_t B, double scale, uint32_t limbs) {
-  const uint32_t N = host->N;
-  CtHandle group(dev->h, c); // the instances share its allocation, which lives until the last view is freed
-  std::vector<HostCipher> out(B);
-  for (size_t b = 0; b < B; b++) {
-    evah_ct *view = nullptr;
-    chk(evah_ct_unstack(dev->h, c, (uint32_t)b, &view));
-    auto handle = std::make_shared<CtHandle>(dev->h, view);
-    out[b].size = 2;
-    out[b].limbs = limbs;
-    out[b].scale = scale;
-    if (resident) { // stays in HBM; host words on demand
-      out[b].dev = std::make_shared<DeviceResident>(DeviceResident{dev, nullptr, handle, host->N});
-      continue;
-    }
-    out[b].data.resize((size_t)2 * limbs * N);
-    out[b].words_checked = true;
-    chk(evah_ct_download(dev->h, view, (uint64_t *)out[b].data.data()));
-  }
-  return out;
+  return group_results(dev, *host, c, B, limbs, scale, resident);
 }
 
 class HipSecret {
@@ -345,9 +353,7 @@ public:
   // uploaded once, in NTT form, to a context of its own
   bool on_device() {
     if (state < 0) {
-      const char *e = std::getenv("EVA_DEVICE_CLIENT");
-      int n = 0;
-      state = (!e || std::atoi(e) != 0) && evah_device_count(&n) == 0 && n > 0 ? 1 : 0;
+      state = device_client_enabled() ? 1 : 0;
       if (state == 1) {
         // the device state of the key pair (generate_keys shares one holder between both halves), so
         // that the public context's resident results are read in place
@@ -369,10 +375,7 @@ public:
   // as HipPublic::encrypt.  Two streams, as in the keygen: seeds (public) and errors (secret) never share one.
   // seed != 0 is the reproducible test hook (streams (seed, 4) and (seed, 3)) and is NOT secret-grade.
   HipValuation encrypt(const Valuation &inputs, const CKKSSignature &sig, uint64_t seed = 0) {
-    const size_t slots = host->N / 2;
-    if (sig.vec_size <= 0) throw std::runtime_error("Signature vector size must be positive");
-    if (slots < (size_t)sig.vec_size) throw std::runtime_error("Vector size cannot be larger than slot count");
-    if (slots % sig.vec_size) throw std::runtime_error("Vector size must exactly divide the slot count");
+    check_vec_size(sig, host->N / 2);
     std::unique_ptr<SecureRng> seeds = seed ? std::make_unique<SecureRng>(seed, 4) : std::make_unique<SecureRng>();
     std::unique_ptr<SecureRng> errors = seed ? std::make_unique<SecureRng>(seed, 3) : std::make_unique<SecureRng>();
     std::vector<std::string> names; // name order: the same seed gives the same valuation whatever the map's order
@@ -381,88 +384,41 @@ public:
     HipValuation out;
     for (const std::string &name : names) {
       const auto &v = inputs.at(name);
-      if (v.size() != (size_t)sig.vec_size) throw std::runtime_error("Input size does not match program vector size");
-      auto it = sig.inputs.find(name);
-      if (it == sig.inputs.end()) throw std::out_of_range("No input named " + name + " in the signature");
-      const CKKSEncodingInfo &info = it->second;
-      if (info.input_type != Type::Cipher && info.input_type != Type::Plain) {
-        out.values[name] = v;
-        continue;
-      }
-      if ((uint32_t)info.level >= host->k - 1) throw std::runtime_error("Input level exceeds the modulus chain");
-      const uint32_t limbs = host->k - 1 - (uint32_t)info.level;
-      const double scale = std::pow(2.0, (double)info.scale);
-      if (info.input_type == Type::Plain) {
-        HostPlain pt = encode_host(v, scale, limbs);
-        for (uint32_t i = 0; i < limbs; i++) host->ntt(i, pt.data.data() + (size_t)i * host->N);
-        out.values[name] = std::move(pt);
-        continue;
-      }
-      std::array<uint8_t, 32> sd;
-      for (int w = 0; w < 4; w++) {
-        const uint64_t x = (*seeds)();
-        std::memcpy(sd.data() + 8 * w, &x, 8);
-      }
+      check_input_size(v, sig);
+      const InputClass in = classify_input(*host, sig, name);
+      if (unencrypted_value(*host, in, v, out.values[name])) continue;
+      const std::array<uint8_t, 32> sd = draw_key32(*seeds);
       std::vector<int8_t> e;
+      WipeOnExit wipe_e{e};
       host->sample_error(*errors, e);
-      if (on_device()) {
-        out.values[name] = encrypt_on_device(v, scale, limbs, e, sd);
-      } else {
-        HostPlain pt = encode_host(v, scale, limbs);
-        for (uint32_t i = 0; i < limbs; i++) host->ntt(i, pt.data.data() + (size_t)i * host->N);
-        out.values[name] = encrypt_symmetric(*host, sk, pt, e, sd);
-      }
-      wipe(e);
+      out.values[name] = encrypt_value(v, in.scale, in.limbs, e, sd);
     }
     return out;
   }
-  // the host encoder's coefficient-form plaintext of v repeated over the slots
-  HostPlain encode_host(const std::vector<double> &v, double scale, uint32_t limbs) const {
-    const size_t slots = host->N / 2;
-    HostPlain pt;
-    pt.limbs = limbs;
-    pt.scale = scale;
-    pt.data.resize((size_t)limbs * host->N);
-    std::vector<double> vec(slots);
-    for (size_t r = 0; r < slots / v.size(); r++) std::copy(v.begin(), v.end(), vec.begin() + r * v.size());
-    host->encode_coeff(vec.data(), scale, limbs, pt.data.data());
-    return pt;
+  // one encrypted input, its draws made: on the device when one is present, else on the host — the same words bit for bit
+  // (same plaintext, exact modular arithmetic)
+  HostCipher encrypt_value(const std::vector<double> &v, double scale, uint32_t limbs, const std::vector<int8_t> &e,
+                           const std::array<uint8_t, 32> &sd) {
+    if (on_device()) return encrypt_on_device(v, scale, limbs, e, sd);
+    HostPlain pt = encode_host(*host, v, scale, limbs);
+    ntt_limbs(*host, pt);
+    return encrypt_symmetric(*host, sk, pt, e, sd);
   }
-  // evah_pt_encode (or the host encoder + evah_pt_upload_coeff) -> evah_encrypt_symmetric; the same words as the
-  // host path bit for bit (same plaintext, exact modular arithmetic)
+  // evah_pt_encode (or the host encoder + evah_pt_upload_coeff) -> evah_encrypt_symmetric
   HostCipher encrypt_on_device(const std::vector<double> &v, double scale, uint32_t limbs, const std::vector<int8_t> &e,
                                const std::array<uint8_t, 32> &sd) {
-    const uint32_t N = host->N;
     evah_pt *p = nullptr;
     if (device_encodable(*host, v, scale, limbs)) {
       chk(evah_pt_encode(dev->h, v.data(), (uint32_t)v.size(), limbs, scale, &p));
     } else {
-      HostPlain pt = encode_host(v, scale, limbs);
+      HostPlain pt = encode_host(*host, v, scale, limbs);
       chk(evah_pt_upload_coeff(dev->h, limbs, scale, (const uint64_t *)pt.data.data(), &p));
     }
     evah_ct *c = nullptr;
     int rc = evah_encrypt_symmetric(dev->h, p, e.data(), sd.data(), &c);
     evah_pt_free(dev->h, p);
     chk(rc);
-    auto handle = std::make_shared<CtHandle>(dev->h, c);
-    auto sf = std::make_shared<SeededForm>();
-    sf->seed = sd;
-    sf->N = N;
-    sf->primes.assign(host->primes.begin(), host->primes.begin() + limbs);
-    HostCipher out;
-    out.size = 2;
-    out.limbs = limbs;
-    out.scale = scale;
-    out.words_checked = true;
-    if (resident) { // stays in HBM; the seed stays with it, so that save() can still write the value compressed
-      out.dev = std::make_shared<DeviceResident>(DeviceResident{dev, nullptr, handle, N});
-      out.seeded = std::move(sf);
-      return out;
-    }
-    sf->c0.resize((size_t)limbs * N); // only c0 crosses PCIe: c1 is the seed's (host words on demand, words())
-    chk(evah_ct_download_poly(dev->h, c, 0, (uint64_t *)sf->c0.data()));
-    out.seeded = std::move(sf);
-    return out;
+    return cipher_of_handle(dev, *host, c, limbs, scale, resident, &sd);
   }
   // encrypt() for a list of input valuations of one signature.  ONE pair of streams for the call;
   // instances are visited in list order, the names sorted within an instance, and every encrypted input takes 4 seed words
@@ -475,10 +431,7 @@ public:
   // sampled_small(key, 1)) on every other path; the seeds of c1 are drawn exactly as without the option.
   std::vector<HipValuation> encrypt_batch(const std::vector<Valuation> &inputs, const CKKSSignature &sig, uint64_t seed = 0,
                                           bool device_sampling = false) {
-    const size_t slots = host->N / 2;
-    if (sig.vec_size <= 0) throw std::runtime_error("Signature vector size must be positive");
-    if (slots < (size_t)sig.vec_size) throw std::runtime_error("Vector size cannot be larger than slot count");
-    if (slots % sig.vec_size) throw std::runtime_error("Vector size must exactly divide the slot count");
+    check_vec_size(sig, host->N / 2);
     std::vector<HipValuation> out(inputs.size());
     if (inputs.empty()) return out;
     const std::vector<std::string> names = batch_input_names(inputs);
@@ -505,31 +458,13 @@ public:
       for (size_t i = 0; i < names.size(); i++) {
         const std::string &name = names[i];
         const auto &v = inputs[b].at(name);
-        if (v.size() != (size_t)sig.vec_size) throw std::runtime_error("Input size does not match program vector size");
-        auto it = sig.inputs.find(name);
-        if (it == sig.inputs.end()) throw std::out_of_range("No input named " + name + " in the signature");
-        const CKKSEncodingInfo &info = it->second;
-        if (info.input_type != Type::Cipher && info.input_type != Type::Plain) {
-          out[b].values[name] = v;
-          continue;
-        }
-        if ((uint32_t)info.level >= host->k - 1) throw std::runtime_error("Input level exceeds the modulus chain");
-        const uint32_t limbs = host->k - 1 - (uint32_t)info.level;
-        const double scale = std::pow(2.0, (double)info.scale);
-        if (info.input_type == Type::Plain) {
-          HostPlain pt = encode_host(v, scale, limbs);
-          for (uint32_t j = 0; j < limbs; j++) host->ntt(j, pt.data.data() + (size_t)j * host->N);
-          out[b].values[name] = std::move(pt);
-          continue;
-        }
+        check_input_size(v, sig);
+        const InputClass in = classify_input(*host, sig, name);
+        if (unencrypted_value(*host, in, v, out[b].values[name])) continue;
         Drawn &d = drawn[i];
-        d.limbs = limbs;
-        d.scale = scale;
-        d.sd.emplace_back();
-        for (int w = 0; w < 4; w++) {
-          const uint64_t x = (*seeds)();
-          std::memcpy(d.sd.back().data() + 8 * w, &x, 8);
-        }
+        d.limbs = in.limbs;
+        d.scale = in.scale;
+        d.sd.push_back(draw_key32(*seeds));
         d.e.emplace_back();
         if (device_sampling) d.ek.push_back(draw_key32(*errors));
         else host->sample_error(*errors, d.e.back());
@@ -537,35 +472,23 @@ public:
     }
     for (size_t i = 0; i < names.size(); i++) {
       const std::string &name = names[i];
-      const Drawn &d = drawn[i];
+      Drawn &d = drawn[i];
       if (d.e.empty()) continue; // a plain or raw input: done above
       bool grouped = on_device();
       for (size_t b = 0; grouped && b < inputs.size(); b++) grouped = device_encodable(*host, inputs[b].at(name), d.scale, d.limbs);
       if (!grouped) { // encrypt()'s path, instance by instance
         for (size_t b = 0; b < inputs.size(); b++) {
-          const auto &v = inputs[b].at(name);
           if (device_sampling) { // the same key through the host twin
-            drawn[i].e[b].resize(host->N);
-            sampled_small(d.ek[b].data(), 1, host->N, drawn[i].e[b].data());
+            d.e[b].resize(host->N);
+            sampled_small(d.ek[b].data(), 1, host->N, d.e[b].data());
           }
-          if (on_device()) {
-            out[b].values[name] = encrypt_on_device(v, d.scale, d.limbs, d.e[b], d.sd[b]);
-          } else {
-            HostPlain pt = encode_host(v, d.scale, d.limbs);
-            for (uint32_t j = 0; j < d.limbs; j++) host->ntt(j, pt.data.data() + (size_t)j * host->N);
-            out[b].values[name] = encrypt_symmetric(*host, sk, pt, d.e[b], d.sd[b]);
-          }
+          out[b].values[name] = encrypt_value(inputs[b].at(name), d.scale, d.limbs, d.e[b], d.sd[b]);
         }
         continue;
       }
-      for (size_t b0 = 0; b0 < inputs.size(); b0 += CLIENT_BATCH_MAX) {
-        const size_t n = std::min<size_t>(CLIENT_BATCH_MAX, inputs.size() - b0);
-        std::vector<const std::vector<double> *> vals(n);
-        for (size_t b = 0; b < n; b++) vals[b] = &inputs[b0 + b].at(name);
-        std::vector<HostCipher> cts = encrypt_group_on_device(vals, d.scale, d.limbs, d.e.data() + b0, d.sd.data() + b0,
-                                                              device_sampling ? d.ek.data() + b0 : nullptr);
-        for (size_t b = 0; b < n; b++) out[b0 + b].values[name] = std::move(cts[b]);
-      }
+      encrypt_in_groups(inputs, name, out, [&](const std::vector<const std::vector<double> *> &vals, size_t b0) {
+        return encrypt_group_on_device(vals, d.scale, d.limbs, d.e.data() + b0, d.sd.data() + b0, device_sampling ? d.ek.data() + b0 : nullptr);
+      });
     }
     return out;
   }
@@ -574,49 +497,23 @@ public:
   std::vector<HostCipher> encrypt_group_on_device(const std::vector<const std::vector<double> *> &vals, double scale, uint32_t limbs,
                                                   const std::vector<int8_t> *e, const std::array<uint8_t, 32> *sd,
                                                   const std::array<uint8_t, 32> *ek = nullptr) {
-    const uint32_t N = host->N;
-    const size_t B = vals.size(), nv = vals[0]->size();
-    std::vector<double> flat(B * nv);
+    const size_t B = vals.size(), N = host->N;
+    const std::vector<double> flat = flatten(vals);
+    const uint32_t nv = (uint32_t)vals[0]->size();
     std::vector<int8_t> errs(ek ? 0 : B * N);
     std::vector<uint8_t> seeds(B * 32), ekeys(ek ? B * 32 : 0);
     for (size_t b = 0; b < B; b++) {
-      std::copy(vals[b]->begin(), vals[b]->end(), flat.begin() + b * nv);
       if (ek) std::copy(ek[b].begin(), ek[b].end(), ekeys.begin() + b * 32);
       else std::copy(e[b].begin(), e[b].end(), errs.begin() + b * N);
       std::copy(sd[b].begin(), sd[b].end(), seeds.begin() + b * 32);
     }
     evah_ct *c = nullptr;
-    const int rc = ek ? evah_encode_encrypt_symmetric_sampled_many(dev->h, (uint32_t)B, flat.data(), (uint32_t)nv, limbs, scale, ekeys.data(),
-                                                                   seeds.data(), &c)
-                      : evah_encode_encrypt_symmetric_many(dev->h, (uint32_t)B, flat.data(), (uint32_t)nv, limbs, scale, errs.data(),
-                                                           seeds.data(), &c);
+    const int rc = ek ? evah_encode_encrypt_symmetric_sampled_many(dev->h, (uint32_t)B, flat.data(), nv, limbs, scale, ekeys.data(), seeds.data(), &c)
+                      : evah_encode_encrypt_symmetric_many(dev->h, (uint32_t)B, flat.data(), nv, limbs, scale, errs.data(), seeds.data(), &c);
     wipe(errs);
     wipe_bytes(ekeys.data(), ekeys.size());
     chk(rc);
-    CtHandle group(dev->h, c); // the instances share its allocation, which lives until the last view is freed
-    std::vector<HostCipher> out(B);
-    for (size_t b = 0; b < B; b++) {
-      evah_ct *view = nullptr;
-      chk(evah_ct_unstack(dev->h, c, (uint32_t)b, &view));
-      auto handle = std::make_shared<CtHandle>(dev->h, view);
-      auto sf = std::make_shared<SeededForm>();
-      sf->seed = sd[b];
-      sf->N = N;
-      sf->primes.assign(host->primes.begin(), host->primes.begin() + limbs);
-      out[b].size = 2;
-      out[b].limbs = limbs;
-      out[b].scale = scale;
-      out[b].words_checked = true;
-      if (resident) { // stays in HBM; the seed stays with it, so that save() can still write the value compressed
-        out[b].dev = std::make_shared<DeviceResident>(DeviceResident{dev, nullptr, handle, N});
-        out[b].seeded = std::move(sf);
-        continue;
-      }
-      sf->c0.resize((size_t)limbs * N); // only c0 crosses PCIe: c1 is the seed's
-      chk(evah_ct_download_poly(dev->h, view, 0, (uint64_t *)sf->c0.data()));
-      out[b].seeded = std::move(sf);
-    }
-    return out;
+    return group_results(dev, *host, c, B, limbs, scale, resident, sd);
   }
   // the shape check of a ciphertext that is decrypted on the device
   void check_device_shape(const std::string &name, const HostCipher &c) const {

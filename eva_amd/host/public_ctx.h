@@ -502,28 +502,24 @@ private:
     for (int i = 0; i + 1 < want; i++) q.push_back(forks[i]->h);
     return q;
   }
-  // EVA_DEVICE_CLIENT=0 keeps encrypt on the host; without a HIP device the host path is the only one
-  // (encrypt, unlike execute(), is client-side work the reference also does on the CPU)
+  // the client calls run on the device when one is present and EVA_DEVICE_CLIENT does not say 0 (client.h)
   bool client_on_device();
   int client_device = -1;
   bool pk_uploaded = false;
-  // same bound as HipExecutor::device_encodable: every rounded coefficient below 2^62 and inside the modulus
-  bool device_encodable(const std::vector<double> &in, double scale, uint32_t limbs) const;
-  // coeff_pt: the host encoder's coefficient-form plaintext, or (null) values: the slot values for the device encoder
-  HostCipher encrypt_on_device(const HostPlain *coeff_pt, const std::vector<double> *values, double scale, uint32_t limbs, SecureRng &rng);
-  // the same with the caller's randomness: small = (u, e0, e1) as int8 [3][N]
+  // the device state without the evaluation keys, the public key uploaded at its first use
+  void ensure_public_key();
+  // evah_pt_upload_coeff of coeff_pt (the host encoder's coefficient-form plaintext) or, when it is null, evah_pt_encode
+  // of the slot values; then evah_encrypt with the caller's randomness: small = (u, e0, e1) as int8 [3][N]
   HostCipher encrypt_on_device_with(const HostPlain *coeff_pt, const std::vector<double> *values, double scale, uint32_t limbs,
                                     const std::vector<int8_t> &small);
-  // one Cipher input of encrypt() with the caller's randomness, on the path encrypt() would take for it
+  // one Cipher input of encrypt() with the caller's randomness, on the path encrypt() takes for it
   HostCipher encrypt_value_with(const std::vector<double> &v, double scale, uint32_t limbs, const std::vector<int8_t> &small);
-  // <= 64 instances of one input as one evah_encode_encrypt_many; the values encrypt_on_device would return
+  // <= 64 instances of one input as one evah_encode_encrypt_many; the values encrypt_on_device_with would return
   std::vector<HostCipher> encrypt_group_on_device(const std::vector<const std::vector<double> *> &vals, double scale, uint32_t limbs,
                                                   SecureRng &rng);
   // the same as one evah_encode_encrypt_sampled_many: instance b's randomness is drawn on the device from rkeys[b]
   std::vector<HostCipher> encrypt_group_sampled(const std::vector<const std::vector<double> *> &vals, double scale, uint32_t limbs,
                                                 const std::array<uint8_t, 32> *rkeys);
-  // the resident views (or downloads) of a group's batched handle: what both group calls return
-  std::vector<HostCipher> group_results(evah_ct *c, size_t B, double scale, uint32_t limbs);
 
   // eval_keys = false: encryption and limb-sharded execution (whose shards hold their own rows of the
   // keys) do not need the whole evaluation keys in this device's memory

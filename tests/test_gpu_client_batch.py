@@ -99,9 +99,10 @@ def test_encode_encrypt_many_equals_single_calls(env, batch):
                 want = g.encrypt(g.encode_pt(values[b], l, SCALE), small[b]).download()
                 assert np.array_equal(ct.unstack(b).download(), want), f"instance {b} (n_values={n_values}, l={l})"
                 assert np.array_equal(got[b], want)
-            if N == 1024:
-                for b in range(batch):
-                    assert np.array_equal(got[b], env.oracle_encrypt(values[b], l, small[b])), f"oracle, instance {b} (n_values={n_values}, l={l})"
+            # the single call runs the same device body, so the oracle is the independent reference: every instance at
+            # N = 1024, the first and the last of batch 3 at one FFT tile and at the smallest two-pass transform
+            for b in range(batch) if N == 1024 else (0, 2) if batch == 3 else ():
+                assert np.array_equal(got[b], env.oracle_encrypt(values[b], l, small[b])), f"oracle, instance {b} (n_values={n_values}, l={l})"
 
 
 def test_encode_encrypt_many_two_pass_5_plus_11():
@@ -135,6 +136,15 @@ def test_encode_encrypt_symmetric_many_equals_single_calls_and_numpy_expansion(e
                 want = g.encrypt_symmetric(g.encode_pt(values[b], l, SCALE), errs[b], seeds[b]).download()
                 assert np.array_equal(got[0], want[0]), f"c0 of instance {b} (n_values={n_values}, l={l})"
                 assert np.array_equal(got[1], want[1])
+            if batch == 9:   # the single call runs the same device body: an oracle-built c0 = encode(v) - (a s + NTT(e))
+                for b in (0, batch - 1):
+                    m = env.o.encode(l, np.tile(values[b], (N // 2) // n_values), SCALE)
+                    for i in range(l):
+                        q = env.primes[i]
+                        a = expand_limb(seeds[b], i, q, N).astype(object)
+                        en = env.o.ntt(i, np.array([int(v) % q for v in errs[b]], dtype=np.uint64)).astype(object)
+                        want0 = ((m[i].astype(object) - (a * env.sk[i].astype(object) + en)) % q).astype(np.uint64)
+                        assert np.array_equal(ct.unstack(b).download()[0, i], want0), f"oracle c0 of instance {b}, limb {i} (n_values={n_values}, l={l})"
 
 
 # ---- 3. decrypt + decode
@@ -191,6 +201,9 @@ def test_decrypt_decode_many_reads_views_in_place_and_caches_tables(env):
     assert _bits_equal(g.decrypt_decode_many([top], 8)[0], o.decode(o.decrypt(above, env.sk), SCALE)[:8])
     assert _bits_equal(g.decrypt_decode_many(cts, 8), got[:, :8])
     assert _bits_equal(g.decrypt_decode_many([top, top], 8)[1], g.decrypt_decode(top, 8))
+    # the single entry point on an unstack view and on the mod-switched view, against the oracle's doubles themselves
+    for b in (1, 2):
+        assert _bits_equal(g.decrypt_decode(cts[b], N // 2), o.decode(o.decrypt(data[b], env.sk), SCALE)[:N // 2]), f"single call, view {b}"
 
 
 # ---- 4. refusals, with the single calls' messages where one exists

@@ -4,7 +4,7 @@ A. k_fft_tile at every degree 2^10 .. 2^17 on dense inputs, both directions, aga
    (which reach 2^17 here for the first time).
 B. crt_to_double on the sign decision, the word boundaries and the mixed per-word signs, at 1 to 61 limbs: constant
    polynomials against exact rationals and the oracle, and one polynomial of all the edges through the whole FFT.
-C. k_enc_round / k_enc_round_b at the rounding threshold 2^52, at multiples of a prime of both signs and at -0.0,
+C. k_enc_round / k_enc_round_many at the rounding threshold 2^52, at multiples of a prime of both signs and at -0.0,
    against Python integers; and the refusal of what the kernels cannot represent.
 D. k_sample_small at exactly one tile, at four and at 64 tiles per polynomial, against the host twin.
 Every comparison is bit for bit, except B1's bound, which client_edges.b1_bound derives."""
