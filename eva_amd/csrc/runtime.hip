@@ -124,9 +124,12 @@ int evah_ctx_create(uint32_t N, uint32_t k, const uint64_t *primes, int device, 
         d.tb_sh = ok ? b - 32 : 0;
         // a prime of another shape: (c, shift, mask) = (0, 0, ~0) makes the top-bit reduction the identity.  The ordinary
         // passes never use it (tb_c == 0 selects the compare-and-subtract butterflies); ks_inner_kernel<MAC3>, whose rounds
-        // are compiled with the top-bit form only, then runs such a row without any reduction — correct while the 8-stage
-        // lazy growth (9 q in, + 4 q per stage: < 41 q) stays below the 2^60 the radix-2^30 split needs, i.e. q < 2^54
-        // (mac3_ok below): the 20..50-bit scale primes of EVA's chains
+        // are compiled with the top-bit form only, then runs such a row without any reduction.  Such a prime's strided
+        // pass is the compare-and-subtract one, which leaves values below 16 q (not the 9 q of the top-bit schedule),
+        // and each of the contiguous pass's P_b = logN / 2 stages adds 4 q: the transformed digit is below
+        // (16 + 4 P_b) q, 48 q at P_b = 8 (N = 2^16, 2^17).  The radix-2^30 split needs it below 2^60, which q < 2^54
+        // gives up to P_b = 12; mac3_shape_ok below checks the product itself, so a larger degree cannot outgrow it.
+        // These are the 20..50-bit scale primes of EVA's chains
         d.tb_mask = ok ? (uint32_t)(((u64)1 << (b - 32)) - 1) : 0xffffffffu;
         d.tb_pad = 0;
       }
@@ -152,7 +155,13 @@ int evah_ctx_create(uint32_t N, uint32_t k, const uint64_t *primes, int device, 
 #if defined(EVAH_TBMUL) && EVAH_TBMUL // (the build-time experiment multiplies by c = 2^b - q in every top-bit butterfly: strict shape)
     for (uint32_t i = 0; i < k; i++) c->all_tb = c->all_tb && hp[i].tb_c != 0;
 #else
-    for (uint32_t i = 0; i < k; i++) c->all_tb = c->all_tb && (hp[i].tb_c != 0 || hp[i].q < ((u64)1 << 54));
+    // a prime of another shape rides ks_inner_kernel<MAC3> unreduced (see tb_mask above): only while its transformed
+    // digit, below (16 + 4 (logN / 2)) q, stays under the 2^60 of the radix-2^30 split — otherwise the context keeps
+    // the 128-bit inner products
+    auto mac3_shape_ok = [&](u64 q) {
+      return q < ((u64)1 << 54) && (unsigned __int128)(16 + 4 * (c->logN / 2)) * q < ((unsigned __int128)1 << 60);
+    };
+    for (uint32_t i = 0; i < k; i++) c->all_tb = c->all_tb && (hp[i].tb_c != 0 || mac3_shape_ok(hp[i].q));
 #endif
     c->modup_tb = c->modup_lazy = true;
     for (uint32_t i = 0; i < k; i++) {

@@ -103,6 +103,18 @@ def _relinearize_launches(g, A3):
     return {name: n for name, (n, _) in prof.items()}
 
 
+def _same(got, want, what=""):
+    """np.array_equal(got, want), and where it fails: how many words differ and the first one, as (poly, limb, coefficient)"""
+    if np.array_equal(got, want):
+        return
+    if got.shape != want.shape:
+        raise AssertionError(f"{what}: shape {got.shape}, expected {want.shape}")
+    bad = np.argwhere(got != want)
+    at = tuple(int(i) for i in bad[0])
+    raise AssertionError(f"{what}: {len(bad)} of {want.size} words differ, first at (poly, limb, coefficient) = {at}: "
+                         f"got {int(got[at]):#x}, expected {int(want[at]):#x}")
+
+
 def _check_key_switches(g, o, primes, rng, key_kind, forms=None, launches=None):
     """launches: the launch counts one relinearize must show (None: not checked)"""
     N, k = o.N, len(primes)
@@ -121,27 +133,27 @@ def _check_key_switches(g, o, primes, rng, key_kind, forms=None, launches=None):
         a3 = np.stack([p, p, p])
         A3 = g.upload_ct(a3, 2.0 ** 20)
         want = o.relinearize(a3, rk)
-        assert np.array_equal(g.relinearize(A3).download(), want), f"relinearize {name} l={l}"
+        _same(g.relinearize(A3).download(), want, f"relinearize {name} l={l}")
         if launches is not None and name == F[0][0]:
             assert _relinearize_launches(g, A3) == launches
         if l >= 2:
-            assert np.array_equal(g.relinearize_rescale(A3, div).download(), o.rescale(want)), f"relinearize_rescale {name}"
+            _same(g.relinearize_rescale(A3, div).download(), o.rescale(want), f"relinearize_rescale {name}")
             for got in g.relinearize_rescale_many([A3, A3], div):
-                assert np.array_equal(got.download(), o.rescale(want)), f"relinearize_rescale_many {name}"
-            assert np.array_equal(g.rescale_relinearize(A3, div).download(), o.relinearize(o.rescale(a3), rk)), \
-                f"rescale_relinearize {name}"
+                _same(got.download(), o.rescale(want), f"relinearize_rescale_many {name}")
+            _same(g.rescale_relinearize(A3, div).download(), o.relinearize(o.rescale(a3), rk), f"rescale_relinearize {name}")
             for got in g.rescale_relinearize_many([A3, A3], div):
-                assert np.array_equal(got.download(), o.relinearize(o.rescale(a3), rk))
+                _same(got.download(), o.relinearize(o.rescale(a3), rk))
             B3 = g.upload_ct_batch(np.stack([a3, a3]), 2.0 ** 20)
             got = g.relinearize_rescale(B3, div).download()
-            assert np.array_equal(got[0], o.rescale(want)) and np.array_equal(got[1], o.rescale(want)), f"batched {name}"
+            for b in range(2):
+                _same(got[b], o.rescale(want), f"batched {name} instance {b}")
         # rotations of a size-2 ciphertext whose c1 is the poly: one, a hoisted set, a window of weighted sums
         a2 = np.stack([p, p])
         A2 = g.upload_ct(a2, 2.0 ** 20)
         for st in steps:
-            assert np.array_equal(g.rotate(A2, st).download(), o.rotate(a2, st, gks[st])), f"rotate {st} {name} l={l}"
+            _same(g.rotate(A2, st).download(), o.rotate(a2, st, gks[st]), f"rotate {st} {name} l={l}")
         for st, got in zip(steps, g.rotate_many(A2, steps)):
-            assert np.array_equal(got.download(), o.rotate(a2, st, gks[st])), f"rotate_many {st} {name} l={l}"
+            _same(got.download(), o.rotate(a2, st, gks[st]), f"rotate_many {st} {name} l={l}")
         rot = [a2] + [o.rotate(a2, st, gks[st]) for st in steps]
         qm1 = np.stack([np.full(N, primes[i] - 1, dtype=np.uint64) for i in range(l)])
         for wname, wts in (("uniform", [qm1] * 3), ("general", [qm1, p, qm1])):
@@ -151,22 +163,23 @@ def _check_key_switches(g, o, primes, rng, key_kind, forms=None, launches=None):
                 t = o.multiply_plain(r, w)
                 acc = t if acc is None else o.add(acc, t)
             got = g.rotate_weighted_sums([([(A2, st) for st in [0] + steps], [W])])[0]
-            assert np.array_equal(got.download(), acc), f"rotate_weighted_sums {wname} {name} l={l}"
+            _same(got.download(), acc, f"rotate_weighted_sums {wname} {name} l={l}")
         # products: size 3, the op triple and the chain step (multiply -> rescale -> relinearize), single and many
         m = o.multiply(a2, a2)
-        assert np.array_equal(g.multiply(A2, A2).download(), m), f"multiply {name}"
+        _same(g.multiply(A2, A2).download(), m, f"multiply {name}")
         if l >= 2:
             triple = o.rescale(o.relinearize(m, rk))
-            assert np.array_equal(g.multiply_relinearize_rescale(A2, A2, div).download(), triple), f"mrr {name} l={l}"
+            _same(g.multiply_relinearize_rescale(A2, A2, div).download(), triple, f"mrr {name} l={l}")
             for got in g.multiply_relinearize_rescale_many([A2, A2], [A2, A2], div):
-                assert np.array_equal(got.download(), triple)
+                _same(got.download(), triple)
             chain = o.relinearize(o.rescale(m), rk)
-            assert np.array_equal(g.multiply_rescale_relinearize(A2, A2, div).download(), chain), f"chain step {name} l={l}"
+            _same(g.multiply_rescale_relinearize(A2, A2, div).download(), chain, f"chain step {name} l={l}")
             for got in g.multiply_rescale_relinearize_many([A2, A2], [A2, A2], div):
-                assert np.array_equal(got.download(), chain)
+                _same(got.download(), chain)
             AB = g.upload_ct_batch(np.stack([a2, a2]), 2.0 ** 20)
             got = g.multiply_relinearize_rescale(AB, AB, div).download()
-            assert np.array_equal(got[0], triple) and np.array_equal(got[1], triple), f"batched mrr {name}"
+            for b in range(2):
+                _same(got[b], triple, f"batched mrr {name} instance {b}")
 
 
 # (N, primes, knobs): 60-bit CoeffModulus::Create chains on both sides of MAC3's folds (l = 7 | 8, 14 | 15) and its
@@ -209,8 +222,7 @@ def test_key_switch_forms_on_the_mod_up_kernel(name, N, bits, knobs):
     g.close()
 
 
-def _special_chains():
-    N = 4096
+def _special_chains(N=4096):
     c60 = po.coeff_modulus_create(N, [60] * 5)
     below54 = _ntt_prime_below((1 << 54) - (1 << 36), N)  # not of the top-bit shape: MAC3 with an unreduced row
     nontb55 = _ntt_prime_below((1 << 55) - (1 << 40), N)  # not of the top-bit shape, above 2^54: the 128-bit path
@@ -260,7 +272,8 @@ def boundary_chains(N=4096):
     p = _ntt_prime_below(3 << 55, N)
     qA = _ntt_prime_below(8 * p + 1, N)
     qB = _ntt_prime_above(8 * p, N)
-    p2 = _ntt_prime_below(p, N)
+    # the largest NTT prime with 8 p2 < qA (row "p2: p | qA qB"); at N = 2048 the prime next below p is 4096 away and misses it
+    p2 = _ntt_prime_below((qA - 1) // 8 + 1, N)
     special = next(q for q in po.coeff_modulus_create(N, [60] * 3) if q not in (p, p2, qA, qB))
     return {"qA_p_qB": [qA, p, qB, special], "p_qA_p2_qB": [p, qA, p2, qB, special]}, (p, p2, qA, qB, special)
 
@@ -309,7 +322,10 @@ def test_key_switch_at_large_degree(N, l):
 @pytest.mark.parametrize("bits", [[60] * 4, [60, 40, 30, 60], [50, 20, 60]])
 def test_rounding_ties_in_rescale_and_mod_down(bits):
     """The dropped limb at 0, (q_last - 1) / 2, (q_last + 1) / 2, q_last - 1: rescale, the fused forms and the chain step"""
-    N = 4096
+    _check_rounding_ties(4096, bits)
+
+
+def _check_rounding_ties(N, bits):
     primes = po.coeff_modulus_create(N, bits)
     o = po.Oracle(N, primes)
     g = _ctx(N, primes, {})
