@@ -540,37 +540,12 @@ int evah_multiply_many(evah_ctx *c, const evah_ct *const *as, const evah_ct *con
   use(c);
   if (n < 1 || n > (uint32_t)KS_BATCH_MAX) throw std::invalid_argument("multiply_many handles 1..64 products per call");
   const uint32_t l = as[0]->limbs;
-  const size_t N = c->N, ops = (size_t)l * N;
   MulTab tab{};
-  std::vector<double> scales(n);
-  for (uint32_t i = 0; i < n; i++) {
-    const evah_ct *a = as[i], *b = bs[i];
-    if (a->size != 2 || b->size != 2) throw std::invalid_argument("multiply supports size-2 operands only (relinearize first)");
-    if (a->batch != 1 || b->batch != 1) throw std::invalid_argument("multiply_many takes single ciphertexts (a batched handle already multiplies in one launch)");
-    if (a->limbs != l || b->limbs != l) throw std::invalid_argument("encrypted parameter mismatch in batch");
-    scales[i] = a->scale * b->scale;
-    check_scale(c, scales[i], l);
-    acquire(c, a->buf);
-    acquire(c, b->buf);
-    tab.a[i] = a->d;
-    tab.b[i] = b->d;
-    tab.a_ps[i] = (uint32_t)(a->ps / N);
-    tab.b_ps[i] = (uint32_t)(b->ps / N);
-  }
-  Buffer *ob = buf_new(c, (size_t)n * 3 * ops);
-  EW_LAUNCH(k_mul22_many, ew_grid(c, l, n), dim3(256), 0, c->stream, c->dev, tab, ob->d, ops);
+  const std::vector<double> scales = fill_mul_tab(c, as, bs, n, 1, l, "multiply_many takes single ciphertexts (a batched handle already multiplies in one launch)", tab);
+  FreshBuf ob(c, (size_t)n * 3 * l * c->N);
+  EW_LAUNCH(k_mul22_many, ew_grid(c, l, n), dim3(256), 0, c->stream, c->dev, tab, ob.d(), (size_t)l * c->N);
   HIPCHK(hipGetLastError());
-  ob->refs = (int)n;
-  for (uint32_t i = 0; i < n; i++) {
-    evah_ct *t = new evah_ct;
-    t->buf = ob;
-    t->d = ob->d + (size_t)i * 3 * ops;
-    t->size = 3;
-    t->limbs = l;
-    t->ps = ops;
-    t->scale = scales[i];
-    outs[i] = t;
-  }
+  ct_views(c, ob, n, 3, l, 1, [&](uint32_t i) { return scales[i]; }, outs);
   API_END
 }
 
@@ -626,24 +601,10 @@ int evah_multiply_plain_many(evah_ctx *c, const evah_ct *const *cts, const evah_
     tab.pt[i] = b->d;
     tab.ct_ps[i] = (uint32_t)(a->ps / N);
   }
-  Buffer *ob = buf_new(c, (size_t)n * size * ops);
-  EW_LAUNCH(k_mul_plain_many, ew_grid(c, l, n * size), dim3(256), 0, c->stream, c->dev, tab, size, ob->d, ops);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    buf_unref(c, ob);
-    HIPCHK(e);
-  }
-  ob->refs = (int)n;
-  for (uint32_t i = 0; i < n; i++) {
-    evah_ct *t = new evah_ct;
-    t->buf = ob;
-    t->d = ob->d + (size_t)i * size * ops;
-    t->size = size;
-    t->limbs = l;
-    t->ps = ops;
-    t->scale = scales[i];
-    outs[i] = t;
-  }
+  FreshBuf ob(c, (size_t)n * size * ops);
+  EW_LAUNCH(k_mul_plain_many, ew_grid(c, l, n * size), dim3(256), 0, c->stream, c->dev, tab, size, ob.d(), ops);
+  HIPCHK(hipGetLastError());
+  ct_views(c, ob, n, size, l, 1, [&](uint32_t i) { return scales[i]; }, outs);
   API_END
 }
 

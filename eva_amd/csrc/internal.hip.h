@@ -307,9 +307,7 @@ struct Tunables {
   uint32_t loop_n = 8, loop_min = 2, loop_min_wgs = 2048, loop_target_wgs = 8192;
   // EVAH_HOIST_MAP (1): k_hoist_mac's workgroups in the order (xcd | tile | x_hi | I) — the tiles of one coefficient range
   // run back to back on one XCD, so operand rows shared between tiles are read from HBM once; 0 = the r4 grid (x, I, tile)
-  // EVAH_HOIST_V (1): coefficients per thread of k_hoist_mac for tile shapes with <= 4 accumulator pairs (2 = 16-byte accesses)
   bool hoist_map = true;
-  uint32_t hoist_v = 1;
   // EVAH_SIDE_STREAM (0): evah_multiply_rescale_relinearize runs the rescale of d0 / d1 on the queue's side stream beside
   // the key switch of d2.  Measured (r06_tuning_notes.md): eager walks gain (config 5 1.77 -> 1.70 ms), replayed hipGraphs
   // do not — a fork / join inside a graph costs what the overlap returns — so the default is one stream
@@ -377,7 +375,6 @@ struct Tunables {
     flag("EVAH_MODUP", t.modup);
     if (const char *e = std::getenv("EVAH_MODUP_LR")) t.modup_lr = std::atoi(e) == 2 ? 2 : 3;
     flag("EVAH_MODUP_SPEC", t.modup_spec);
-    count("EVAH_HOIST_V", t.hoist_v);
     if (const char *e = std::getenv("EVAH_KS_GROUPS")) t.ks_groups = std::max(1, std::atoi(e));
     if (const char *e = std::getenv("EVAH_KS_THREADS")) {
       const int n = std::atoi(e);
@@ -610,6 +607,36 @@ inline evah_ct *ct_new(evah_ctx *c, uint32_t size, uint32_t limbs, double scale,
   t->ps = (size_t)limbs * c->N;
   t->scale = scale;
   return t;
+}
+// A fresh buffer that the handles of one call will view (ct_views): returned to the pool if the scope is left
+// by an exception before the handles exist.
+struct FreshBuf {
+  evah_ctx *c;
+  Buffer *b;
+  FreshBuf(evah_ctx *c_, size_t elems) : c(c_), b(buf_new(c_, elems)) {}
+  FreshBuf(const FreshBuf &) = delete;
+  FreshBuf &operator=(const FreshBuf &) = delete;
+  ~FreshBuf() { if (b) buf_unref(c, b); }
+  u64 *d() const { return b->d; }
+};
+// outs[i], i < n: a handle of `batch` ciphertexts of `size` polynomials of `limbs` limbs with the scale scale_of(i),
+// viewing ob at stride batch * size * limbs * N.  The handles own the buffer from here on.
+template <class ScaleOf>
+inline void ct_views(evah_ctx *c, FreshBuf &ob, uint32_t n, uint32_t size, uint32_t limbs, uint32_t batch, ScaleOf scale_of, evah_ct **outs) {
+  const size_t ps = (size_t)limbs * c->N;
+  for (uint32_t i = 0; i < n; i++) {
+    evah_ct *t = new evah_ct;
+    t->buf = ob.b;
+    t->d = ob.b->d + (size_t)i * batch * size * ps;
+    t->size = size;
+    t->limbs = limbs;
+    t->ps = ps;
+    t->scale = scale_of(i);
+    t->batch = batch;
+    outs[i] = t;
+  }
+  ob.b->refs = (int)n;
+  ob.b = nullptr;
 }
 inline evah_pt *pt_new(evah_ctx *c, uint32_t limbs, double scale) {
   evah_pt *t = new evah_pt;

@@ -147,6 +147,31 @@ struct KsBatch { // one launch worth of key-switches: regular strides, irregular
   bool diag = false;    // the diagonal digit comes from scratch too (no NTT-form target: the chain step, ntt_chain.hip.h)
   uint32_t fold_row = ~0u; // KS_FOLDMUL: != ~0u adds (P q_a^-1) d_K, a = fold_row, instead of P d_K
 };
+// The operand table of pairs x B products of size-2 ciphertexts at level l — entry i * B + x is instance x of pair i —
+// with the checks every call that multiplies makes of its operands (batch_msg: its text for a handle that does not hold
+// B instances); the operands are acquired.  Returns the products' scales, one per pair.
+inline std::vector<double> fill_mul_tab(evah_ctx *c, const evah_ct *const *as, const evah_ct *const *bs, uint32_t pairs, uint32_t B,
+                                        uint32_t l, const char *batch_msg, MulTab &tab) {
+  std::vector<double> scales(pairs);
+  for (uint32_t i = 0; i < pairs; i++) {
+    const evah_ct *a = as[i], *b = bs[i];
+    if (a->size != 2 || b->size != 2) throw std::invalid_argument("multiply supports size-2 operands only (relinearize first)");
+    if (a->batch != B || b->batch != B) throw std::invalid_argument(batch_msg);
+    if (a->limbs != l || b->limbs != l) throw std::invalid_argument("encrypted parameter mismatch in batch");
+    scales[i] = a->scale * b->scale;
+    check_scale(c, scales[i], l);
+    acquire(c, a->buf);
+    acquire(c, b->buf);
+    for (uint32_t x = 0; x < B; x++) {
+      tab.a[i * B + x] = a->d + (size_t)x * 2 * a->ps;
+      tab.b[i * B + x] = b->d + (size_t)x * 2 * b->ps;
+      tab.a_ps[i * B + x] = (uint32_t)(a->ps / c->N);
+      tab.b_ps[i * B + x] = (uint32_t)(b->ps / c->N);
+    }
+  }
+  return scales;
+}
+
 // second (contiguous) pass of the digit transforms fused with the key inner product (keyswitch.hip)
 void launch_ks_inner(evah_ctx *c, int P, const u64 *target, const u64 *scratch, const KsBatch &key, u64 *prod, uint32_t l);
 

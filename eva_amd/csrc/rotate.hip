@@ -3,6 +3,7 @@
 // decomposition per source) with the exact fallback.  The machinery of the sets is rotation_sets.hip.h
 // (shared with windows.hip, where the sets feed weighted sums).
 #include "rotation_sets.hip.h"
+#include <deque>
 
 namespace evah {
 
@@ -145,37 +146,16 @@ int evah_rotate_many(evah_ctx *c, const evah_ct *a, const int32_t *steps, uint32
   std::vector<size_t> src_ps(B, a->ps);
   for (uint32_t b = 0; b < B; b++) srcs[b] = a->d + (size_t)b * 2 * a->ps;
   const uint32_t m_max = std::max<uint32_t>(1, KS_BATCH_MAX / B);
-  std::vector<evah_ct *> made;
-  std::vector<Buffer *> chunk_buf;
+  std::deque<FreshBuf> bufs; // one buffer per chunk; the chunk's m handles are views into it
   std::vector<RotChunk> chunks;
-  try {
-    for (uint32_t j0 = 0; j0 < n; j0 += m_max) {
-      const uint32_t m = std::min(m_max, n - j0), np = m * B;
-      Buffer *ob = buf_new(c, (size_t)np * 2 * pps); // one buffer for the chunk; the m handles are views into it
-      ob->refs = 0;
-      chunk_buf.push_back(ob);
-      chunks.push_back({j0 * B, np, ob->d});
-      for (uint32_t j = 0; j < m; j++) {
-        evah_ct *t = new evah_ct;
-        t->buf = ob;
-        ob->refs++;
-        t->d = ob->d + (size_t)j * B * 2 * pps;
-        t->size = 2;
-        t->limbs = l;
-        t->ps = pps;
-        t->scale = a->scale;
-        t->batch = B;
-        made.push_back(t);
-      }
-    }
-    rotation_set(c, l, pairs, chunks, srcs, src_ps, hoisted);
-  } catch (...) {
-    for (evah_ct *t : made) evah_ct_free(c, t);
-    if (made.empty())
-      for (Buffer *b : chunk_buf) { b->refs = 1; buf_unref(c, b); }
-    throw;
+  for (uint32_t j0 = 0; j0 < n; j0 += m_max) {
+    const uint32_t np = std::min(m_max, n - j0) * B;
+    bufs.emplace_back(c, (size_t)np * 2 * pps);
+    chunks.push_back({j0 * B, np, bufs.back().d()});
   }
-  for (uint32_t r = 0; r < n; r++) outs[r] = made[r];
+  rotation_set(c, l, pairs, chunks, srcs, src_ps, hoisted);
+  for (size_t ci = 0; ci < chunks.size(); ci++)
+    ct_views(c, bufs[ci], chunks[ci].count / B, 2, l, B, [&](uint32_t) { return a->scale; }, outs + chunks[ci].first / B);
   API_END
 }
 
@@ -208,24 +188,9 @@ int evah_rotate_pairs(evah_ctx *c, const evah_ct *const *cts, const int32_t *ste
   // worth hoisting when sources repeat and the digit transforms of the set are throughput-sized
   bool hoisted = srcs.size() < n && hoist_wanted(c, l, n, 1);
   for (size_t i = 0; i < pairs.size() && hoisted; i++) hoisted = hoist_prepare(c, pairs[i], l); // no room for a table: unhoisted
-  Buffer *ob = buf_new(c, (size_t)n * 2 * pps);
-  try {
-    rotation_set(c, l, pairs, {RotChunk{0, n, ob->d}}, srcs, src_ps, hoisted);
-  } catch (...) {
-    buf_unref(c, ob);
-    throw;
-  }
-  ob->refs = (int)n;
-  for (uint32_t r = 0; r < n; r++) {
-    evah_ct *t = new evah_ct;
-    t->buf = ob;
-    t->d = ob->d + (size_t)r * 2 * pps;
-    t->size = 2;
-    t->limbs = l;
-    t->ps = pps;
-    t->scale = cts[r]->scale;
-    outs[r] = t;
-  }
+  FreshBuf ob(c, (size_t)n * 2 * pps);
+  rotation_set(c, l, pairs, {RotChunk{0, n, ob.d()}}, srcs, src_ps, hoisted);
+  ct_views(c, ob, n, 2, l, 1, [&](uint32_t r) { return cts[r]->scale; }, outs);
   API_END
 }
 
