@@ -128,6 +128,11 @@ _SIGS = {
     "evah_key_upload_seeded": [_vp, C.c_int, C.c_uint32, C.c_uint32, _u64p, C.POINTER(C.c_uint8)],
     "evah_keygen_switch": [_vp, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_int8), C.POINTER(C.c_uint8), C.c_int, _u64p],
     "evah_test_key_words": [_vp, C.c_int, C.c_uint32, C.c_int, _u64p],
+    # the whole key set generated on the device from 32-byte randomness keys
+    "evah_keygen_set": [_vp, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint8),
+                        C.POINTER(C.c_uint8), C.c_int, _u64p],
+    "evah_keygen_public": [_vp, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_int, _u64p],
+    "evah_key_download_c0": [_vp, C.c_int, C.c_uint32, C.c_uint32, _u64p],
     # limb-sharded execution
     "evah_ctx_set_shard": [_vp, C.c_uint32, C.c_uint32],
     "evah_ctx_shard_info": [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
@@ -687,6 +692,35 @@ class Context:
         _chk(_lib.evah_keygen_switch(self.h, int(kind), int(elt), errors.shape[0], errors.ctypes.data_as(C.POINTER(C.c_int8)),
                                      seeds.ctypes.data_as(C.POINTER(C.c_uint8)), int(bool(install)), _p(c0)))
         return c0
+
+    def keygen_set(self, keys, ekeys, seeds, install=True, download=True):
+        """evah_keygen_set: keys = [(kind, elt), ...] under the uploaded secret key from ekeys and seeds
+        [n_keys][digits][32] uint8 — digit J's error is sampled_small(ekeys[key][J], 1), drawn on the device; returns c0
+        [n_keys][digits][k][N], or None with download=False"""
+        ekeys = np.ascontiguousarray(ekeys, dtype=np.uint8)
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint8)
+        n, D = len(keys), ekeys.shape[1]
+        assert ekeys.shape == seeds.shape == (n, D, 32)
+        kinds = (C.c_int * max(n, 1))(*[int(k) for k, _ in keys])
+        elts = (C.c_uint32 * max(n, 1))(*[int(e) for _, e in keys])
+        c0 = np.empty((n, D, self.k, self.N), dtype=np.uint64) if download else None
+        u8p = C.POINTER(C.c_uint8)
+        _chk(_lib.evah_keygen_set(self.h, n, kinds, elts, D, ekeys.ctypes.data_as(u8p), seeds.ctypes.data_as(u8p), int(bool(install)),
+                                  _p(c0) if download else None))
+        return c0
+
+    def keygen_public(self, ekey, seed, install=True):
+        """evah_keygen_public: the public key [2][k][N] under the uploaded secret key, a from the 32-byte
+        `seed` and e = sampled_small(ekey, 1) drawn on the device"""
+        pk = np.empty((2, self.k, self.N), dtype=np.uint64)
+        _chk(_lib.evah_keygen_public(self.h, _keys32([ekey], 1), _keys32([seed], 1), int(bool(install)), _p(pk)))
+        return pk
+
+    def key_download_c0(self, kind, elt=0, digits=None):
+        """evah_key_download_c0: c0 [digits][k][N] of an installed key"""
+        out = np.empty((self.k - 1 if digits is None else int(digits), self.k, self.N), dtype=np.uint64)
+        _chk(_lib.evah_key_download_c0(self.h, int(kind), int(elt), out.shape[0], _p(out)))
+        return out
 
     def key_words(self, kind, elt=0, which=0, digits=None):
         """test hook (evah_test_key_words): the device words of an installed key as [digits][2][rows][N] — rows = k, or

@@ -201,7 +201,8 @@ k_sample_small(DevCtx cx, const uint32_t *__restrict__ rkeys, uint32_t n_polys, 
 }
 // the randomness keys [batch][32] (host) into `keys` on the queue, then NTT forms [batch][n_polys][limbs][N] of the
 // polynomials p0 .. p0 + n_polys - 1 of every instance: what the int8 copy and small_to_ntt make of the host's draws
-static void sample_to_ntt(evah_ctx *c, uint32_t batch, const uint8_t *rkeys, u64 *keys, uint32_t n_polys, uint32_t p0, uint32_t limbs, u64 *out) {
+// (also evah_keygen_set's and evah_keygen_public's errors, seeded.hip)
+void sample_to_ntt(evah_ctx *c, uint32_t batch, const uint8_t *rkeys, u64 *keys, uint32_t n_polys, uint32_t p0, uint32_t limbs, u64 *out) {
   HIPCHK(hipMemcpyAsync(keys, rkeys, (size_t)32 * batch, hipMemcpyHostToDevice, c->stream));
   EW_LAUNCH(k_sample_small, dim3((c->N + SAMPLE_TILE - 1) / SAMPLE_TILE, batch * n_polys), dim3(SAMPLE_THREADS), 0, c->stream, c->dev,
             reinterpret_cast<const uint32_t *>(keys), n_polys, p0, limbs, out);
@@ -404,22 +405,6 @@ k_dec_gather(const double2 *c, const uint32_t *slot_map, uint32_t n_out, uint32_
 }
 
 // ---- one body per operation: no argument checks inside, every entry point below makes its own
-// queue-ordered zeroing of a pool temporary that held something secret, also when the call fails
-struct Wipe {
-  evah_ctx *c;
-  void *d;
-  size_t bytes;
-  bool done = false; // set at construction: nothing to wipe
-  void now() { // the success path: a wipe that fails is an error
-    if (done) return;
-    done = true;
-    HIPCHK(hipMemsetAsync(d, 0, bytes, c->stream));
-  }
-  ~Wipe() {
-    if (!done) (void)hipMemsetAsync(d, 0, bytes, c->stream);
-  }
-};
-
 // SEAL Encryptor::encrypt of `batch` NTT-form plaintexts pt [batch][l][N] (a handle's words, or the call's scratch) into
 // one handle [batch][2][l][N].  Randomness: small = the host's (u ternary, e0, e1 error polynomials) as int8 [batch][3][N], or
 // (rkeys) drawn here from a 32-byte key per instance.  Drains the queue: `small` / `rkeys` are pageable host memory.

@@ -336,6 +336,11 @@ struct Tunables {
   // EVAH_LDS_EXTRA (0): bytes of dynamic LDS added to every ntt_pass_kernel launch — an occupancy probe for the
   // tuning notes (fewer workgroups per CU), never set in production
   uint32_t lds_extra = 0;
+  // EVAH_KEYGEN_SET_WORDS (2^27 = 1 GiB): evah_keygen_set keeps the NTT-form errors of at most this many words
+  // (keys x digits x k x N) in scratch at a time; a larger set runs as chunks of whole keys, one launch list per chunk,
+  // at least one key each.  The largest key set of eva_amd/workloads.py — config 5: 10 keys x 12 digits x 13 primes x
+  // 2^16 = 102 236 160 words, 780 MiB — is one chunk.  Every value gives the same keys.
+  uint32_t keygen_set_words = 1u << 27;
 
   static Tunables from_env(uint32_t N) {
     Tunables t;
@@ -367,6 +372,7 @@ struct Tunables {
     count("EVAH_LOOP_MIN_WGS", t.loop_min_wgs);
     count("EVAH_LOOP_TARGET_WGS", t.loop_target_wgs);
     count("EVAH_LDS_EXTRA", t.lds_extra);
+    count("EVAH_KEYGEN_SET_WORDS", t.keygen_set_words);
     flag("EVAH_HOIST_MAP", t.hoist_map);
     flag("EVAH_SIDE_STREAM", t.side_stream);
     flag("EVAH_CHAIN_STEP", t.chain_step);

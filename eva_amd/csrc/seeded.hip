@@ -4,7 +4,9 @@
 // (evah_encrypt_symmetric and its _many forms) lives in client.hip beside the public-key one.  Evaluation keys travel the same way:
 // evah_key_upload_seeded takes c0 and one seed per digit and expands every c1 row — and the split copy — in one launch.
 // evah_keygen_switch makes the whole key here: c0 as well, from the resident secret key and N int8 error
-// draws per digit.
+// draws per digit.  evah_keygen_set makes a whole set of them, and evah_keygen_public the public key, from
+// 32-byte randomness keys the device expands itself — one k_keygen_set launch for the set —, and evah_key_download_c0
+// hands c0 of such a key to the host when it is first needed there.
 
 #include "launch.hip.h"
 #include "seeded.hip.h"
@@ -123,6 +125,95 @@ k_keygen_switch(DevCtx cx, Seeds8 seeds, const uint32_t *__restrict__ seed_buf, 
     st2(d_split + at1, make_ulonglong2(split30(a[0]), split30(a[1])));
     st2(d_split + at1 + 2, make_ulonglong2(split30(a[2]), split30(a[3])));
   }
+}
+
+// One key of a set, read wave-uniformly by k_keygen_set: where its words go and what s' is
+enum : uint32_t { KS_SPRIME_SQUARE = 0, KS_SPRIME_PERM = 1, KS_SPRIME_NONE = 2 };
+struct KeySetEntry {
+  u64 *d, *d_split;     // [digit][2][k][N] each; d_split null: no split copy
+  const uint32_t *perm; // KS_SPRIME_PERM: the Galois element's permutation table
+  uint32_t sprime, pad; // s' = s^2 (relinearization), s through perm (Galois), or no s' row at all (the public key)
+};
+
+// k_keygen_switch for every key of a set in one launch: blockIdx.z = key * n_digits + J; the key's
+// {d, d_split, perm} come from tab[key], digit z's seed from seed_buf [z][8] and its NTT-form error from en [z][k][N]
+// (z counts within the launch).  Same mapping otherwise: one thread per ChaCha block (4 coefficients), 16-byte accesses,
+// the i == J branch uniform over the block, the split copy from the same registers.  A one-entry table with
+// KS_SPRIME_NONE and one digit is the public key (-(a s + NTT(e)), a) in its [2][k][N] layout.
+// grid = (ceil(N / 4 / 256), k, keys * n_digits)
+__global__ void __launch_bounds__(256)
+k_keygen_set(DevCtx cx, const uint32_t *__restrict__ seed_buf, const u64 *__restrict__ en, const u64 *__restrict__ sk,
+             const KeySetEntry *__restrict__ tab, uint32_t n_digits) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y, z = blockIdx.z;
+  if (t >= cx.N / 4 || i >= cx.k) return;
+  const uint32_t J = z % n_digits;
+  const KeySetEntry ke = tab[z / n_digits];
+  const DevPrime pm = cx.primes[i];
+  uint32_t key[8];
+#pragma unroll
+  for (int w = 0; w < 8; w++) key[w] = seed_buf[8 * (size_t)z + w];
+  u64 a[4], b[4];
+  seeded_block(key, i, t, pm, a);
+  const size_t n0 = 4 * (size_t)t;
+  const u64 *s = sk + (size_t)i * cx.N, *e = en + ((size_t)z * cx.k + i) * cx.N + n0;
+  const ulonglong2 s01 = ld2(s + n0), s23 = ld2(s + n0 + 2), e01 = ld2(e), e23 = ld2(e + 2);
+  const u64 sv[4] = {s01.x, s01.y, s23.x, s23.y}, ev[4] = {e01.x, e01.y, e23.x, e23.y};
+#pragma unroll
+  for (int r = 0; r < 4; r++) b[r] = negmod(addmod(mulmod(a[r], sv[r], pm), ev[r], pm.q), pm.q);
+  if (i == J && ke.sprime != KS_SPRIME_NONE) {
+    const u64 pmod = cx.modq[(size_t)(cx.k - 1) * cx.k + J].x; // P mod q_J
+    u64 sp[4];
+    if (ke.sprime == KS_SPRIME_PERM) {
+      const uint4 pi = *reinterpret_cast<const uint4 *>(ke.perm + n0);
+      sp[0] = s[pi.x]; sp[1] = s[pi.y]; sp[2] = s[pi.z]; sp[3] = s[pi.w];
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; r++) sp[r] = mulmod(sv[r], sv[r], pm);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; r++) b[r] = addmod(b[r], mulmod(sp[r], pmod, pm), pm.q);
+  }
+  const size_t at0 = ((size_t)2 * J * cx.k + i) * cx.N + n0, at1 = at0 + (size_t)cx.k * cx.N;
+  st2(ke.d + at0, make_ulonglong2(b[0], b[1]));
+  st2(ke.d + at0 + 2, make_ulonglong2(b[2], b[3]));
+  st2(ke.d + at1, make_ulonglong2(a[0], a[1]));
+  st2(ke.d + at1 + 2, make_ulonglong2(a[2], a[3]));
+  if (ke.d_split) {
+    st2(ke.d_split + at0, make_ulonglong2(split30(b[0]), split30(b[1])));
+    st2(ke.d_split + at0 + 2, make_ulonglong2(split30(b[2]), split30(b[3])));
+    st2(ke.d_split + at1, make_ulonglong2(split30(a[0]), split30(a[1])));
+    st2(ke.d_split + at1 + 2, make_ulonglong2(split30(a[2]), split30(a[3])));
+  }
+}
+
+// The keys [first, first + n) of a set — or the public key (n = 1, one digit) — into their allocations tab[.].d: the
+// launch list of DESIGN.md 1.8.  ekeys / seeds [n][n_digits][32] (host); out (host, or null): entry j's first polynomial
+// of every digit, [n_digits][k][N] each, from d[J][0].  Enqueues only: the caller drains the queue.
+static void keygen_chunk(evah_ctx *c, const KeySetEntry *tab, uint32_t n, uint32_t n_digits, const uint8_t *ekeys, const uint8_t *seeds,
+                         uint64_t *out) {
+  const size_t Z = (size_t)n * n_digits, poly = (size_t)c->k * c->N, tab_words = (sizeof(KeySetEntry) * n + 7) / 8;
+  Scratch ek(c, 4 * Z), sd(c, 4 * Z), tb(c, tab_words), en(c, Z * poly);
+  // the error keys, the sampled residues and their NTT forms do not stay behind in pool memory the next call reuses
+  Wipe w_ek{c, ek.d, 32 * Z}, w_en{c, en.d, sizeof(u64) * Z * poly};
+  HIPCHK(hipMemcpyAsync(sd.d, seeds, 32 * Z, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(tb.d, tab, sizeof(KeySetEntry) * n, hipMemcpyHostToDevice, c->stream));
+  sample_to_ntt(c, (uint32_t)Z, ekeys, ek.d, 1, 1, c->k, en.d);
+  EW_LAUNCH(k_keygen_set, seeded_grid(c, c->k, (uint32_t)Z), dim3(256), 0, c->stream, c->dev, reinterpret_cast<const uint32_t *>(sd.d), en.d,
+            c->sh->sk.d, reinterpret_cast<const KeySetEntry *>(tb.d), n_digits);
+  HIPCHK(hipGetLastError());
+  if (out) // one linear copy per digit (evah_ct_download on 2-D copies and pageable memory)
+    for (uint32_t j = 0; j < n; j++)
+      for (uint32_t J = 0; J < n_digits; J++)
+        HIPCHK(hipMemcpyAsync(out + ((size_t)j * n_digits + J) * poly, tab[j].d + (size_t)J * 2 * poly, sizeof(u64) * poly, hipMemcpyDeviceToHost,
+                              c->stream));
+  w_ek.now();
+  w_en.now();
+}
+
+// the refusals evah_keygen_switch, evah_keygen_set and evah_keygen_public share, with evah_keygen_switch's messages
+static void keygen_checks(evah_ctx *c) {
+  if (c->dev.pstep > 1) throw std::invalid_argument("a limb shard holds no whole secret key");
+  if (c->capturing) throw std::logic_error("this call synchronises with the host and cannot be captured into a graph");
 }
 
 } // namespace evah
@@ -248,6 +339,146 @@ int evah_keygen_switch(evah_ctx *c, int kind, uint32_t galois_elt, uint32_t n_di
     (void)hipFree(kd.d);
     if (kd.d_split) (void)hipFree(kd.d_split);
   }
+  API_END
+}
+
+// A whole set of relinearization / Galois keys generated on the device from 32-byte randomness keys: key
+// kappa, digit J is evah_keygen_switch with errors[J] = sampled_small(ekeys[kappa][J], 1), word for word, in a number of
+// launches that does not depend on the number of keys.  All or nothing: a failure installs no key of the set.
+int evah_keygen_set(evah_ctx *c, uint32_t n_keys, const int *kinds, const uint32_t *elts, uint32_t n_digits, const uint8_t *ekeys,
+                    const uint8_t *seeds, int install, uint64_t *c0_out) {
+  API_BEGIN
+  use(c);
+  keygen_checks(c);
+  const KeyDev shape = key_shape(c, n_digits);
+  if (n_keys == 0) throw std::invalid_argument("a key set needs at least one key");
+  if (!kinds || !elts) throw std::invalid_argument("key list pointer is null");
+  if ((uint64_t)n_keys * n_digits > 65535) throw std::invalid_argument("a key set holds at most 65535 digits");
+  for (uint32_t j = 0; j < n_keys; j++) {
+    if (kinds[j] != EVAH_KEY_RELIN && kinds[j] != EVAH_KEY_GALOIS) throw std::invalid_argument("unknown key kind");
+    if (kinds[j] == EVAH_KEY_GALOIS && (!(elts[j] & 1) || elts[j] >= 2 * c->N)) throw std::invalid_argument("Galois element is not valid");
+    for (uint32_t i = 0; i < j; i++)
+      if (kinds[i] == kinds[j] && (kinds[j] == EVAH_KEY_RELIN || elts[i] == elts[j]))
+        throw std::invalid_argument("key " + std::to_string(j) + " repeats key " + std::to_string(i));
+  }
+  if (!ekeys) throw std::invalid_argument("error pointer is null");
+  if (!seeds) throw std::invalid_argument("seed pointer is null");
+  if (!install && !c0_out) throw std::invalid_argument("the key is neither installed nor returned");
+  if (c->N % 256) throw std::invalid_argument("key generation needs N divisible by 256");
+  if (!c->sh->sk.d) throw std::invalid_argument("secret key not present");
+  const size_t poly = (size_t)c->k * c->N, key_words = (size_t)n_digits * poly;
+  std::vector<KeySetEntry> tab(n_keys, KeySetEntry{nullptr, nullptr, nullptr, KS_SPRIME_SQUARE, 0});
+  auto free_all = [&] {
+    for (KeySetEntry &ke : tab) {
+      if (ke.d) (void)hipFree(ke.d);
+      if (ke.d_split) (void)hipFree(ke.d_split);
+    }
+  };
+  try {
+    for (uint32_t j = 0; j < n_keys; j++) { // the permutation tables before the first launch (first use: a copy of its own)
+      if (kinds[j] != EVAH_KEY_GALOIS) continue;
+      tab[j].perm = perm_table(c, elts[j]);
+      tab[j].sprime = KS_SPRIME_PERM;
+    }
+    for (KeySetEntry &ke : tab) {
+      HIPCHK(hipMalloc(&ke.d, shape.bytes));
+      if (c->all_tb && c->tun.mac3 && hipMalloc(&ke.d_split, shape.bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        ke.d_split = nullptr; // no memory for the second copy: the 128-bit accumulation is used
+      }
+    }
+    // whole keys per launch list: as many as Tunables::keygen_set_words of NTT-form errors hold, at least one
+    const uint32_t per_chunk = (uint32_t)std::min<size_t>(n_keys, std::max<size_t>(1, c->tun.keygen_set_words / key_words));
+    for (uint32_t j0 = 0; j0 < n_keys; j0 += per_chunk) {
+      const uint32_t n = std::min(per_chunk, n_keys - j0);
+      const size_t at = (size_t)32 * j0 * n_digits;
+      keygen_chunk(c, tab.data() + j0, n, n_digits, ekeys + at, seeds + at, c0_out ? c0_out + (size_t)j0 * key_words : nullptr);
+    }
+    HIPCHK(hipStreamSynchronize(c->stream)); // `ekeys`, `seeds` and c0_out are pageable; complete before any queue reads a key
+  } catch (...) {
+    (void)hipStreamSynchronize(c->stream);
+    free_all();
+    throw;
+  }
+  c->sh->xfer[4] += (size_t)64 * n_keys * n_digits;
+  if (c0_out) c->sh->xfer[5] += sizeof(u64) * n_keys * key_words;
+  if (!install) {
+    free_all();
+  } else {
+    for (uint32_t j = 0; j < n_keys; j++) {
+      KeyDev kd = shape;
+      kd.d = tab[j].d;
+      kd.d_split = tab[j].d_split;
+      key_install(c, kinds[j], elts[j], kd); // cannot refuse: kinds and elements were checked above
+    }
+  }
+  API_END
+}
+
+// The public key (-(a s + NTT(e)), a) generated on the device: a_i = the expansion of seed32 under chain
+// prime i, e = sampled_small(ekey32, 1) — k_keygen_set with a one-entry table and no s' row, whose one digit is exactly
+// the [2][k][N] layout of the public key
+int evah_keygen_public(evah_ctx *c, const uint8_t *ekey32, const uint8_t *seed32, int install, uint64_t *pk_out) {
+  API_BEGIN
+  use(c);
+  keygen_checks(c);
+  if (!ekey32) throw std::invalid_argument("error pointer is null");
+  if (!seed32) throw std::invalid_argument("seed pointer is null");
+  if (!install && !pk_out) throw std::invalid_argument("the key is neither installed nor returned");
+  if (c->N % 256) throw std::invalid_argument("key generation needs N divisible by 256");
+  if (!c->sh->sk.d) throw std::invalid_argument("secret key not present");
+  KeyDev kd;
+  kd.n_digits = 1;
+  kd.bytes = sizeof(u64) * (size_t)2 * c->k * c->N;
+  HIPCHK(hipMalloc(&kd.d, kd.bytes));
+  try {
+    const KeySetEntry ke{kd.d, nullptr, nullptr, KS_SPRIME_NONE, 0};
+    keygen_chunk(c, &ke, 1, 1, ekey32, seed32, nullptr);
+    if (pk_out) HIPCHK(hipMemcpyAsync(pk_out, kd.d, kd.bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream)); // the arguments are pageable; complete before any queue reads the key
+  } catch (...) {
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(kd.d);
+    throw;
+  }
+  c->sh->xfer[4] += 64;
+  if (pk_out) c->sh->xfer[5] += kd.bytes;
+  if (install) {
+    if (c->sh->pk.d) (void)hipFree(c->sh->pk.d);
+    c->sh->pk = kd;
+  } else {
+    (void)hipFree(kd.d);
+  }
+  API_END
+}
+
+// c0 of an installed relinearization or Galois key -> out [n_digits][k][N]: what a key generated in place
+// (evah_keygen_set with c0_out = NULL) owes the host when somebody saves it or uploads it elsewhere
+int evah_key_download_c0(evah_ctx *c, int kind, uint32_t galois_elt, uint32_t n_digits, uint64_t *out) {
+  API_BEGIN
+  use(c);
+  if (c->dev.pstep > 1) throw std::invalid_argument("a limb shard holds rows of the keys, not whole keys");
+  if (c->capturing) throw std::logic_error("this call synchronises with the host and cannot be captured into a graph");
+  if (kind != EVAH_KEY_RELIN && kind != EVAH_KEY_GALOIS) throw std::invalid_argument("unknown key kind");
+  if (!out) throw std::invalid_argument("output pointer is null");
+  const KeyDev *kd = nullptr;
+  if (kind == EVAH_KEY_RELIN) {
+    if (c->sh->relin.d) kd = &c->sh->relin;
+  } else {
+    auto it = c->sh->galois.find(galois_elt);
+    if (it != c->sh->galois.end()) kd = &it->second;
+  }
+  if (!kd) throw std::invalid_argument("key not present");
+  if (kd->rows != c->k) throw std::invalid_argument("a limb shard holds rows of the keys, not whole keys");
+  if (n_digits != kd->n_digits) throw std::invalid_argument("invalid key digit count");
+  const size_t poly = (size_t)c->k * c->N;
+  hipError_t e = hipSuccess;
+  for (uint32_t J = 0; J < n_digits && e == hipSuccess; J++) // one linear copy per digit
+    e = hipMemcpyAsync(out + (size_t)J * poly, kd->d + (size_t)J * 2 * poly, sizeof(u64) * poly, hipMemcpyDeviceToHost, c->stream);
+  const hipError_t drained = hipStreamSynchronize(c->stream);
+  HIPCHK(e);
+  HIPCHK(drained);
+  c->sh->xfer[5] += sizeof(u64) * n_digits * poly;
   API_END
 }
 

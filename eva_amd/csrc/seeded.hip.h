@@ -60,6 +60,24 @@ inline Seeds8 seeds_of(const uint8_t *const *seeds, uint32_t first, uint32_t n) 
 }
 // client.hip: small polynomials (int8 on the device) to their NTT forms under the first `limbs` chain primes
 void small_to_ntt(evah_ctx *c, const u64 *small8, uint32_t n_polys, uint32_t limbs, u64 *out);
+// client.hip: the randomness keys rkeys [batch][32] (host) copied into `keys` on the queue, then the NTT forms
+// [batch][n_polys][limbs][N] of the small polynomials p0 .. p0 + n_polys - 1 each key expands to
+void sample_to_ntt(evah_ctx *c, uint32_t batch, const uint8_t *rkeys, u64 *keys, uint32_t n_polys, uint32_t p0, uint32_t limbs, u64 *out);
+// queue-ordered zeroing of a pool temporary that held something secret, also when the call fails
+struct Wipe { // shared by client.hip and seeded.hip
+  evah_ctx *c;
+  void *d;
+  size_t bytes;
+  bool done = false; // set at construction: nothing to wipe
+  void now() { // the success path: a wipe that fails is an error
+    if (done) return;
+    done = true;
+    HIPCHK(hipMemsetAsync(d, 0, bytes, c->stream));
+  }
+  ~Wipe() {
+    if (!done) (void)hipMemsetAsync(d, 0, bytes, c->stream);
+  }
+};
 inline dim3 seeded_grid(const evah_ctx *c, uint32_t limbs, uint32_t z) { return dim3((c->N / 4 + 255) / 256, limbs, z); }
 
 } // namespace evah

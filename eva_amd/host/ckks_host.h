@@ -11,6 +11,8 @@
 #include <cmath>
 #include <complex>
 #include <cstdint>
+#include <functional>
+#include <map>
 #include <memory>
 #include <random>
 #include <stdexcept>
@@ -424,13 +426,24 @@ struct SwitchKey {
   std::vector<u64> data; // [digit][2][k][N], NTT form; empty while the key is kept in its compressed form
   // the compressed form: c1 of digit J is public and uniform, so it is kept as the 32-byte seed it is
   // expanded from — row i = seeded_limb(seed_J, i, q_i, N) — beside c0.  Half the words in memory, in files and over PCIe.
-  std::vector<u64> c0;        // [digit][k][N]
+  // [digit][k][N].  Empty while a key generated in place (generate_keys(..., device_keygen, device_sampling), DESIGN.md
+  // 1.8) has its c0 only on the device: c0_words() fetches it on first need through `source` and keeps it
+  mutable std::vector<u64> c0;
   std::vector<uint8_t> seeds; // [digit][32]
+  std::function<void(std::vector<u64> &)> source; // fills c0 from where the key lives (evah_key_download_c0)
   bool compressed() const { return !seeds.empty(); }
+  // the one way to read c0: a key generated in place becomes an ordinary compressed key at its first call
+  const std::vector<u64> &c0_words() const {
+    if (c0.empty() && source) source(c0);
+    return c0;
+  }
+  // words of c0 / data held on the host right now
+  size_t host_words() const { return c0.size() + data.size(); }
   // the full words [digit][2][k][N]: `data`, or materialised into `tmp` (never stored back: a compressed key stays compressed)
   const std::vector<u64> &words(const HostContext &cx, std::vector<u64> &tmp) const {
     if (!compressed()) return data;
     const size_t poly = (size_t)cx.k * cx.N;
+    const std::vector<u64> &c0 = c0_words();
     if (c0.size() != n_digits * poly || seeds.size() != (size_t)32 * n_digits) throw std::runtime_error("compressed key: c0 or its seeds do not match the shape");
     tmp.resize((size_t)n_digits * 2 * poly);
     for (uint32_t J = 0; J < n_digits; J++) {
@@ -459,7 +472,20 @@ public:
   // OS (getrandom); seed != 0 is the reproducible test hook (csprng.h).
   std::unique_ptr<SecureRng> secret, pub;
   SecretKey sk;
-  KeyGenerator(const HostContext &c, uint64_t seed) : cx(c) {
+  // The sampled mode (generate_keys(..., device_sampling)): every polynomial has a 32-byte key of its own.
+  // Secret stream, in order: rk_s, ek_pk, then one error key per digit of every evaluation key in key order; public stream:
+  // seed_pk, then one seed per digit — what draw_seeded_digit draws.  s = sampled_small(rk_s, 0), the public key is
+  // (-(a s + NTT(e)), a) with a_i = seeded_limb(seed_pk, i) and e = sampled_small(ek_pk, 1), digit J's error is
+  // sampled_small(ek_J, 1).  The device draws the same polynomials from the same keys (evah_keygen_public, evah_keygen_set).
+  const bool sampled;
+  std::array<uint8_t, 32> ek_pk{}, seed_pk{};
+  // test hook, filled in the sampled mode when seed != 0 only: the keys the secret stream gave
+  struct Randomness {
+    std::vector<uint8_t> rk_s, ek_pk;
+    std::map<uint32_t, std::vector<uint8_t>> ekeys; // 0: the relinearization key's [digits][32], Galois element: that key's
+  } kept;
+  const bool keep;
+  KeyGenerator(const HostContext &c, uint64_t seed, bool sampled_ = false) : cx(c), sampled(sampled_), keep(sampled_ && seed != 0) {
     if (seed) {
       secret = std::make_unique<SecureRng>(seed, 1);
       pub = std::make_unique<SecureRng>(seed, 2);
@@ -467,14 +493,37 @@ public:
       secret = std::make_unique<SecureRng>();
       pub = std::make_unique<SecureRng>();
     }
-    cx.sample_ternary(*secret, sk.s);
+    if (sampled) {
+      std::array<uint8_t, 32> rk_s = draw_key32(*secret);
+      ek_pk = draw_key32(*secret);
+      seed_pk = draw_key32(*pub);
+      sk.s.resize(cx.N);
+      sampled_small(rk_s.data(), 0, cx.N, sk.s.data());
+      if (keep) {
+        kept.rk_s.assign(rk_s.begin(), rk_s.end());
+        kept.ek_pk.assign(ek_pk.begin(), ek_pk.end());
+      }
+      wipe_bytes(rk_s.data(), 32);
+    } else {
+      cx.sample_ternary(*secret, sk.s);
+    }
     sk.s_ntt.resize((size_t)cx.k * cx.N);
     for (uint32_t i = 0; i < cx.k; i++) cx.small_to_ntt(sk.s, i, sk.s_ntt.data() + (size_t)i * cx.N);
   }
+  ~KeyGenerator() { wipe_bytes(ek_pk.data(), 32); }
   PublicKey public_key() {
     PublicKey pk;
     pk.data.resize((size_t)2 * cx.k * cx.N);
-    encrypt_zero_symmetric(pk.data.data(), pk.data.data() + (size_t)cx.k * cx.N);
+    u64 *c0 = pk.data.data(), *c1 = c0 + (size_t)cx.k * cx.N;
+    if (sampled) {
+      for (uint32_t i = 0; i < cx.k; i++) seeded_limb(seed_pk.data(), i, cx.primes[i], cx.N, (uint64_t *)(c1 + (size_t)i * cx.N));
+      std::vector<int8_t> e(cx.N);
+      sampled_small(ek_pk.data(), 1, cx.N, e.data());
+      zero_symmetric(c0, c1, e);
+      wipe(e);
+    } else {
+      encrypt_zero_symmetric(c0, c1);
+    }
     return pk;
   }
   // What one digit of a seed-compressed key draws, and in which order — the one place that says so, for the host
@@ -487,11 +536,31 @@ public:
     }
     cx.sample_error(*secret, e);
   }
+  // The same for the sampled mode, and as much the one place that says so for the host twin below and for the device's
+  // set (client.h): the same 4 words of the public stream, then 4 words of the secret stream — the 32-byte key the
+  // digit's error is expanded from, sampled_small(ekey32, 1)
+  void draw_sampled_digit(uint8_t *seed32, uint8_t *ekey32) {
+    for (int w = 0; w < 4; w++) {
+      const u64 r = (*pub)();
+      std::memcpy(seed32 + 8 * w, &r, 8);
+    }
+    for (int w = 0; w < 4; w++) {
+      const u64 r = (*secret)();
+      std::memcpy(ekey32 + 8 * w, &r, 8);
+    }
+  }
+  // test hook: remember the error keys [digits][32] of key `id` (0: relinearization, else the Galois element)
+  void keep_ekeys(uint32_t id, const uint8_t *ekeys, uint32_t digits) {
+    if (keep) kept.ekeys[id].assign(ekeys, ekeys + (size_t)32 * digits);
+  }
   // key-switch key from s' (NTT form over all k primes) to s: digit J carries P * s' in limb J.
   // seeded: c1 of every digit is the expansion of a 32-byte seed — 4 words of the public stream in place
   // of its k N rejection-sampled draws — and the key is returned as c0 + seeds
-  SwitchKey switch_key(const std::vector<u64> &sprime_ntt, bool seeded = false) {
+  // sampled mode: always seeded, the error of digit J expanded from its 32-byte key; id names the key for the test hook
+  SwitchKey switch_key(const std::vector<u64> &sprime_ntt, bool seeded = false, uint32_t id = 0) {
     const uint32_t N = cx.N, k = cx.k, D = k - 1;
+    seeded = seeded || sampled;
+    std::vector<uint8_t> ekeys(sampled ? (size_t)32 * D : 0);
     SwitchKey key;
     key.n_digits = D;
     if (seeded) {
@@ -507,7 +576,13 @@ public:
       u64 *c0, *c1;
       if (seeded) {
         uint8_t *seed = key.seeds.data() + (size_t)32 * J;
-        draw_seeded_digit(seed, e);
+        if (sampled) {
+          draw_sampled_digit(seed, ekeys.data() + (size_t)32 * J);
+          e.resize(N);
+          sampled_small(ekeys.data() + (size_t)32 * J, 1, N, e.data());
+        } else {
+          draw_seeded_digit(seed, e);
+        }
         a.resize((size_t)k * N);
         for (uint32_t i = 0; i < k; i++) seeded_limb(seed, i, cx.primes[i], N, (uint64_t *)(a.data() + (size_t)i * N));
         c0 = key.c0.data() + (size_t)J * k * N;
@@ -523,6 +598,10 @@ public:
       u64 *dst = c0 + (size_t)J * N;
       const u64 *sp = sprime_ntt.data() + (size_t)J * N;
       for (uint32_t j = 0; j < N; j++) dst[j] = evah::addmod(dst[j], cx.mulm(sp[j], f, J), q);
+    }
+    if (sampled) {
+      keep_ekeys(id, ekeys.data(), D);
+      wipe_bytes(ekeys.data(), ekeys.size());
     }
     return key;
   }
@@ -544,7 +623,7 @@ public:
       uint32_t src = evah::bitrev((uint32_t)raw, cx.logN);
       for (uint32_t i = 0; i < cx.k; i++) sp[(size_t)i * cx.N + j] = sk.s_ntt[(size_t)i * cx.N + src];
     }
-    return switch_key(sp, seeded);
+    return switch_key(sp, seeded, elt);
   }
 
 private:

@@ -349,6 +349,9 @@ public:
   std::shared_ptr<HostContext> host;
   SecretKey sk;
   int device = 0;
+  // test hook of generate_keys(..., seed != 0, device_sampling): the 32-byte keys its secret stream gave;
+  // empty for every other pair
+  KeyGenerator::Randomness key_randomness;
   // decrypt + decode on the GPU when one is present (EVA_DEVICE_CLIENT=0: host); the secret key is
   // uploaded once, in NTT form, to a context of its own
   bool on_device() {
@@ -617,14 +620,18 @@ public:
 // key pair's device state from the host's draws (KeyGenerator::draw_seeded_digit).  devices / shard (null: the
 // environment's defaults) are set before any key is made, so that the device state is created on the right device; in the
 // default single-device mode the keys stay installed there and the first execute() uploads none.
+// device_sampling: every polynomial of the key set is expanded from a 32-byte key of its own
+// (KeyGenerator's sampled mode says which) — compressed keys again.  With device_keygen the device draws them:
+// one evah_keygen_public and one evah_keygen_set for all evaluation keys, and in the default single-device mode no c0
+// comes back until somebody needs it (SwitchKey::c0_words).  Without it the host twin computes the same words.
 inline std::pair<std::shared_ptr<HipPublic>, std::shared_ptr<HipSecret>>
 generate_keys(const CKKSParameters &params, uint64_t seed = 0, bool compress_keys = false, bool device_keygen = false,
-              const std::vector<int> *devices = nullptr, const std::string *shard = nullptr) {
+              const std::vector<int> *devices = nullptr, const std::string *shard = nullptr, bool device_sampling = false) {
   std::vector<int> bits(params.prime_bits.begin(), params.prime_bits.end());
   if (bits.size() < 2) throw std::invalid_argument("need at least two primes (data + special)");
   auto primes = evah::coeff_modulus_create(params.poly_modulus_degree, bits);
   auto host = std::make_shared<HostContext>(params.poly_modulus_degree, primes);
-  KeyGenerator kg(*host, seed); // seed == 0: keyed from the OS; otherwise the reproducible test hook
+  KeyGenerator kg(*host, seed, device_sampling); // seed == 0: keyed from the OS; otherwise the reproducible test hook
   auto pub = std::make_shared<HipPublic>();
   auto sec = std::make_shared<HipSecret>();
   sec->holder = pub->holder; // one device state for the pair: results stay resident from encrypt to decrypt
@@ -637,7 +644,6 @@ generate_keys(const CKKSParameters &params, uint64_t seed = 0, bool compress_key
   pub->host = host;
   sec->host = host;
   sec->sk = kg.sk;
-  pub->pk = kg.public_key();
   const uint32_t N = host->N, m = 2 * N, D = host->k - 1;
   const bool install = pub->devices.empty() && pub->shard_mode.empty(); // every other mode uploads from the host's c0 + seeds
   if (device_keygen) {
@@ -647,6 +653,14 @@ generate_keys(const CKKSParameters &params, uint64_t seed = 0, bool compress_key
   }
   if (device_keygen && !sec->on_device())
     throw std::runtime_error("device_keygen needs a HIP device: none is visible, or EVA_DEVICE_CLIENT=0 keeps the client on the host");
+  const bool device_set = device_keygen && device_sampling;
+  if (device_set) { // the host paths (encrypt without a device, save) need pk, so it comes back
+    pub->pk.data.resize((size_t)2 * host->k * N);
+    chk(evah_keygen_public(sec->dev->h, kg.ek_pk.data(), kg.seed_pk.data(), install ? 1 : 0, (uint64_t *)pub->pk.data.data()));
+    if (install) pub->public_key_installed();
+  } else {
+    pub->pk = kg.public_key();
+  }
   // one key on the device: the draws of switch_key(., seeded) in its order, then evah_keygen_switch
   auto device_key = [&](int kind, uint32_t elt) {
     SwitchKey key;
@@ -664,7 +678,8 @@ generate_keys(const CKKSParameters &params, uint64_t seed = 0, bool compress_key
     chk(rc);
     return key;
   };
-  pub->relin = device_keygen ? device_key(EVAH_KEY_RELIN, 0) : kg.relin_key(compress_keys);
+  // the keys of the set in key order — the relinearization key, then one Galois key per distinct rotation step
+  std::vector<uint32_t> elts;
   for (int step : params.rotations) {
     uint32_t elt;
     if (step == 0) elt = m - 1;
@@ -675,9 +690,50 @@ generate_keys(const CKKSParameters &params, uint64_t seed = 0, bool compress_key
       elt = 1;
       for (uint32_t i = 0; i < s; i++) elt = (elt * 3u) & (m - 1);
     }
-    if (!pub->galois.count(elt)) pub->galois.emplace(elt, device_keygen ? device_key(EVAH_KEY_GALOIS, elt) : kg.galois_key(elt, compress_keys));
+    if (std::find(elts.begin(), elts.end(), elt) == elts.end()) elts.push_back(elt);
+  }
+  if (device_set) {
+    // all draws first, in KeyGenerator's order; then the whole set as one call
+    const size_t n_keys = 1 + elts.size();
+    std::vector<int> kinds(n_keys, EVAH_KEY_GALOIS);
+    std::vector<uint32_t> ids(n_keys, 0);
+    kinds[0] = EVAH_KEY_RELIN;
+    std::copy(elts.begin(), elts.end(), ids.begin() + 1);
+    std::vector<uint8_t> ekeys(n_keys * D * 32), seeds(n_keys * D * 32);
+    for (size_t j = 0; j < n_keys; j++) {
+      for (uint32_t J = 0; J < D; J++) kg.draw_sampled_digit(seeds.data() + (j * D + J) * 32, ekeys.data() + (j * D + J) * 32);
+      kg.keep_ekeys(ids[j], ekeys.data() + j * D * 32, D);
+    }
+    const size_t key_words = (size_t)D * host->k * N;
+    std::vector<u64> c0(install ? 0 : n_keys * key_words); // the default mode leaves c0 where the keys are
+    const int rc = evah_keygen_set(sec->dev->h, (uint32_t)n_keys, kinds.data(), ids.data(), D, ekeys.data(), seeds.data(), install ? 1 : 0,
+                                   install ? nullptr : (uint64_t *)c0.data());
+    wipe_bytes(ekeys.data(), ekeys.size());
+    chk(rc);
+    for (size_t j = 0; j < n_keys; j++) {
+      SwitchKey key;
+      key.n_digits = D;
+      key.seeds.assign(seeds.begin() + j * D * 32, seeds.begin() + (j + 1) * D * 32);
+      if (install) {
+        const int kind = kinds[j];
+        const uint32_t elt = ids[j];
+        key.source = [holder = pub->holder, kind, elt, D, key_words](std::vector<u64> &out) {
+          std::vector<u64> w(key_words);
+          chk(evah_key_download_c0(holder->dev->h, kind, elt, D, (uint64_t *)w.data()));
+          out = std::move(w);
+        };
+      } else {
+        key.c0.assign(c0.begin() + j * key_words, c0.begin() + (j + 1) * key_words);
+      }
+      if (j == 0) pub->relin = std::move(key);
+      else pub->galois.emplace(ids[j], std::move(key));
+    }
+  } else {
+    pub->relin = device_keygen ? device_key(EVAH_KEY_RELIN, 0) : kg.relin_key(compress_keys);
+    for (uint32_t elt : elts) pub->galois.emplace(elt, device_keygen ? device_key(EVAH_KEY_GALOIS, elt) : kg.galois_key(elt, compress_keys));
   }
   if (device_keygen && install) pub->eval_keys_installed();
+  sec->key_randomness = std::move(kg.kept);
   return {pub, sec};
 }
 

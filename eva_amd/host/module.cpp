@@ -252,17 +252,19 @@ PYBIND11_MODULE(_eva, m) {
   // traversal (wrapper.cpp:128-137) — is the number of issue queues independent DAG nodes are spread over.
   // compress_keys: the evaluation keys as c0 + a 32-byte seed per digit, expanded on the GPU at upload
   // device_keygen: the same compressed keys, generated on the GPU from the secret key and the host's draws
-  mseal.def("generate_keys", [](const CKKSParameters &p, uint64_t seed, py::object devices, py::object shard, bool compress_keys, bool device_keygen) {
+  // device_sampling: every polynomial of the key set from a 32-byte key of its own, drawn on the GPU with device_keygen
+  mseal.def("generate_keys", [](const CKKSParameters &p, uint64_t seed, py::object devices, py::object shard, bool compress_keys, bool device_keygen,
+                                bool device_sampling) {
     // devices / shard reach generate_keys before any key is made: device key generation runs on member 0's device
     std::vector<int> dv;
     std::string sh;
     if (!devices.is_none()) dv = devices.cast<std::vector<int>>();
     if (!shard.is_none()) sh = shard.cast<std::string>();
-    auto kp = generate_keys(p, seed, compress_keys, device_keygen, devices.is_none() ? nullptr : &dv, shard.is_none() ? nullptr : &sh);
+    auto kp = generate_keys(p, seed, compress_keys, device_keygen, devices.is_none() ? nullptr : &dv, shard.is_none() ? nullptr : &sh, device_sampling);
     if (g_num_threads > 1) kp.first->num_queues = std::min(g_num_threads, 8);
     return kp;
   }, py::arg("abstract_params"), py::arg("seed") = 0, py::arg("devices") = py::none(), py::arg("shard") = py::none(),
-     py::arg("compress_keys") = false, py::arg("device_keygen") = false);
+     py::arg("compress_keys") = false, py::arg("device_keygen") = false, py::arg("device_sampling") = false);
   // test hook: small polynomial p of a 32-byte randomness key (csprng.h sampled_small) -> int8 [N]
   mseal.def("_sampled_small", [](py::bytes rk, uint32_t p, uint32_t N) {
     const std::string k = rk;
@@ -406,6 +408,7 @@ PYBIND11_MODULE(_eva, m) {
         d["uploads"] = st[0]; d["bytes"] = st[1];
         return d;
       }, "evaluation keys uploaded from the host to the context's own device so far: calls and bytes sent (keys generated on the device count in neither)")
+      .def("key_host_bytes", &HipPublic::key_host_bytes, "bytes of evaluation-key words held on the host right now: 0 while keys generated in place keep their c0 on the device only (DESIGN.md 1.8)")
       .def("key_bytes", &HipPublic::key_bytes, "HBM bytes of evaluation keys: one entry per limb shard (when limb-sharded), then the whole keys on the context's own device (0 if never uploaded)")
       .def("set_limb_dist", [](HipPublic &p, uint32_t rank, uint32_t world, py::object all_gather, py::object broadcast, py::object sum_host,
                                uintptr_t stream) {
@@ -508,6 +511,22 @@ PYBIND11_MODULE(_eva, m) {
       .def("decrypt_batch", &HipSecret::decrypt_batch, py::arg("enc_outputs"), py::arg("signature"),
            "decrypt() of every valuation of a list, bit for bit; on the device up to 64 outputs of one name are decrypted and decoded in one call")
       .def_readwrite("device", &HipSecret::device, "device of the secret half's state when it is not shared with a public context")
+      // test hook: the 32-byte keys generate_keys(..., seed != 0, device_sampling=True) drew from its secret stream —
+      // {"secret": rk_s, "public": ek_pk, 0: the relinearization key's error keys [digits][32], Galois element: that key's};
+      // empty for every other pair
+      .def("_key_randomness", [](const HipSecret &s) {
+        py::dict d;
+        const auto &r = s.key_randomness;
+        if (r.rk_s.empty()) return d;
+        d["secret"] = py::bytes(reinterpret_cast<const char *>(r.rk_s.data()), r.rk_s.size());
+        d["public"] = py::bytes(reinterpret_cast<const char *>(r.ek_pk.data()), r.ek_pk.size());
+        for (auto &kv : r.ekeys) {
+          py::array_t<uint8_t> a({(py::ssize_t)(kv.second.size() / 32), (py::ssize_t)32});
+          std::memcpy(a.mutable_data(), kv.second.data(), kv.second.size());
+          d[py::int_(kv.first)] = a;
+        }
+        return d;
+      })
       // test hook (as relin_key() on the public side): the secret key under every key prime, NTT form [k][N]
       .def("_secret_key_ntt", [](const HipSecret &s) { return to_numpy(s.sk.s_ntt, {(py::ssize_t)s.host->k, (py::ssize_t)s.host->N}); });
 }

@@ -82,6 +82,17 @@ public:
     eval_keys_uploaded = true;
   }
 
+  // generate_keys(..., device_keygen, device_sampling): evah_keygen_public left the public key on the key pair's device
+  // state as well, so the first encrypt() uploads none
+  void public_key_installed() { pk_uploaded = true; }
+  // bytes of evaluation-key words (c0 of compressed keys, the whole words of the others) held on the host right now: 0
+  // while every key generated in place has its c0 only on the device
+  uint64_t key_host_bytes() const {
+    size_t w = relin.host_words();
+    for (auto &kv : galois) w += kv.second.host_words();
+    return sizeof(u64) * w;
+  }
+
   // SEALPublic::encrypt (seal.cpp:24-102)
   HipValuation encrypt(const Valuation &inputs, const CKKSSignature &sig);
   // encrypt() of every valuation of a list, the device work batched per input name (client.h)
@@ -367,7 +378,7 @@ private:
   // and is expanded on the device (evah_key_upload_seeded)
   void upload_eval_keys(evah_ctx *c) {
     auto up = [&](int kind, uint32_t elt, const SwitchKey &k) {
-      if (k.compressed()) chk(evah_key_upload_seeded(c, kind, elt, k.n_digits, (const uint64_t *)k.c0.data(), k.seeds.data()));
+      if (k.compressed()) chk(evah_key_upload_seeded(c, kind, elt, k.n_digits, (const uint64_t *)k.c0_words().data(), k.seeds.data()));
       else chk(evah_key_upload(c, kind, elt, k.n_digits, (const uint64_t *)k.data.data()));
     };
     up(EVAH_KEY_RELIN, 0, relin);

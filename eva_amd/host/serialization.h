@@ -266,7 +266,7 @@ inline std::shared_ptr<HostContext> read_ctx(Reader &r) {
 // has and refuses the file.
 constexpr uint32_t SWITCH_KEY_SEEDED = 0x80000000u;
 inline void write(Writer &w, const SwitchKey &k) {
-  if (k.compressed()) { w.pod<uint32_t>(k.n_digits | SWITCH_KEY_SEEDED); w.vec(k.seeds); w.vec(k.c0); }
+  if (k.compressed()) { w.pod<uint32_t>(k.n_digits | SWITCH_KEY_SEEDED); w.vec(k.seeds); w.vec(k.c0_words()); }
   else { w.pod(k.n_digits); w.vec(k.data); }
 }
 inline SwitchKey read_switch_key(Reader &r) {

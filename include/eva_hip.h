@@ -90,6 +90,30 @@ int evah_key_upload_seeded(evah_ctx *ctx, int kind, uint32_t galois_elt, uint32_
 int evah_keygen_switch(evah_ctx *ctx, int kind, uint32_t galois_elt, uint32_t n_digits,
                        const int8_t *errors /* [n_digits][N] */, const uint8_t *seeds /* [n_digits][32] */,
                        int install, uint64_t *c0_out /* [n_digits][k][N] or NULL */);
+/* A whole key set generated on the device from 32-byte randomness keys (every create_relin_keys /
+ * create_galois_keys call of generateKeys, seal.cpp:174-203, as one call): key j is the relinearization key
+ * (kinds[j] = EVAH_KEY_RELIN, elts[j] ignored) or the Galois key of elts[j], and its digit J is evah_keygen_switch's with
+ * errors[J] = sampled_small(ekeys[j][J], 1) (eva_amd/host/csprng.h) and seeds[j][J], word for word, the installed layouts
+ * included.  The number of launches does not depend on n_keys; sets whose NTT-form errors exceed EVAH_KEYGEN_SET_WORDS
+ * run as chunks of whole keys.  install != 0: every key becomes ctx's; c0_out != NULL: every c0 is copied back.  All or
+ * nothing: when anything fails no key of the set is installed.  The error keys are secrets: they cross as a buffer, never
+ * as launch arguments, and are zeroed on the queue with everything derived from them.  Refuses what evah_keygen_switch
+ * refuses, n_keys == 0, more than 65535 digits in all, and a repeated (kind, element). */
+int evah_keygen_set(evah_ctx *ctx, uint32_t n_keys, const int *kinds /* [n_keys] */, const uint32_t *elts /* [n_keys] */,
+                    uint32_t n_digits, const uint8_t *ekeys /* [n_keys][n_digits][32] */,
+                    const uint8_t *seeds /* [n_keys][n_digits][32] */, int install,
+                    uint64_t *c0_out /* [n_keys][n_digits][k][N] or NULL */);
+/* The public key generated on the device (KeyGenerator::public_key as generateKeys takes it,
+ * seal.cpp:174-203): pk = (-(a s + NTT(e)), a) with a_i = the expansion of seed32 under chain prime i and
+ * e = sampled_small(ekey32, 1), from the secret key evah_client_key_upload(EVAH_KEY_SECRET) left on ctx.  install != 0: it
+ * becomes ctx's public key, as after evah_client_key_upload(EVAH_KEY_PUBLIC); pk_out != NULL: it is copied back. */
+int evah_keygen_public(evah_ctx *ctx, const uint8_t *ekey32, const uint8_t *seed32, int install,
+                       uint64_t *pk_out /* [2][k][N] or NULL */);
+/* c0 of an installed relinearization or Galois key (what saving the RelinKeys / GaloisKeys of
+ * generateKeys, seal.cpp:174-203, needs of a key that was generated in place): d[J][0] of every digit -> out, one
+ * linear copy per digit on ctx's queue, then a drain.  Refuses a key that is not present and a limb shard. */
+int evah_key_download_c0(evah_ctx *ctx, int kind, uint32_t galois_elt, uint32_t n_digits,
+                         uint64_t *out /* [n_digits][k][N] */);
 /* Galois element used by evah_rotate for `steps` (SEAL GaloisTool::get_elt_from_step). */
 int evah_galois_elt_from_step(evah_ctx *ctx, int32_t steps, uint32_t *elt);
 
@@ -168,7 +192,7 @@ int evah_ctx_key_bytes(evah_ctx *ctx, uint64_t *bytes);
 int evah_ctx_key_bytes_detail(evah_ctx *ctx, uint64_t out[3]);
 /* Evaluation keys uploaded from the host into ctx's device state so far (the reference uploads nothing: its keys live
  * where SEALPublic lives, seal.h:58-66): out[0] = installed uploads (evah_key_upload, evah_key_upload_seeded), out[1] =
- * the bytes they sent.  A key generated in place (evah_keygen_switch) is not an upload and counts in neither. */
+ * the bytes they sent.  A key generated in place (evah_keygen_switch, evah_keygen_set) is not an upload and counts in neither. */
 int evah_ctx_key_upload_stats(evah_ctx *ctx, uint64_t out[2]);
 int evah_ct_info(const evah_ct *ct, uint32_t *size, uint32_t *limbs, double *scale);
 int evah_ct_download(evah_ctx *ctx, const evah_ct *ct, uint64_t *out /* [size][limbs][N] */);
