@@ -546,6 +546,9 @@ int evah_execute(evah_ctx *c, const evah_op *ops, uint32_t n_ops, evah_val *tab,
         break;
       }
       case 12:
+        // plain - cipher: the reference's std::get<Ciphertext>(args1) fails (seal_executor.h:139); the message is the one
+        // evah_elementwise_program gives for the same op
+        if (!is_ct(o.src0)) throw std::runtime_error("Unsupported operation encountered");
         if (is_ct(o.src1)) chk(evah_sub(c, ct_of(o.src0), ct_of(o.src1), &out));
         else if (slot(o.src1).kind == EVAH_VAL_PT) chk(evah_sub_plain(c, ct_of(o.src0), static_cast<evah_pt *>(tab[o.src1].h), &out));
         else throw std::runtime_error("Unsupported operation encountered");

@@ -404,13 +404,19 @@ int evah_decrypt_decode_many(evah_ctx *ctx, const evah_ct *const *cts, uint32_t 
  *   imm   : rotation steps (14/15), rescale divisor bits (22)
  *   flags : EVAH_OPF_FREE_SRC0/1 = the caller does not need that operand afterwards: it is released
  *           once its last reader in the list has run (the reference frees at last use under
- *           Galois, multicore_program_traversal.h:62-67)
+ *           Galois, multicore_program_traversal.h:62-67).  The flags are optional and belong to the value,
+ *           not to the reader: a slot is released iff SOME reader names it, and then after its LAST
+ *           reader, whichever of them carried the flag — what running the list op by op and freeing
+ *           the flagged operands once nobody reads them any more gives.  A slot nobody flags, and a
+ *           dst nobody reads, stays with the caller; caller-placed slots may be flagged like any other.
  * Single assignment: every dst slot starts empty and is written by exactly one op; inputs and
  * encoded plaintexts (Encode / Constant nodes) are placed in the table by the caller; on return
  * the slots written by ops hold new handles owned by the caller (unless released by a flag).
  * Operand kinds select the evaluator call exactly as seal_executor.h:114-175 does: Add/Mul swap a
  * plaintext first operand behind the ciphertext, Mul with src0 == src1 is square, Sub needs a
- * ciphertext first.
+ * ciphertext first (plain - cipher is "Unsupported operation encountered", as in evah_elementwise_program).
+ * An op a single entry point would refuse fails the submit with that entry point's message; values the
+ * caller did not flag are untouched by a failed submit.
  * Scheduling inside (same ciphertexts as running the list op by op): ops are taken level by level
  * (depth from the caller-placed values — what MulticoreProgramTraversal's ready set holds), the
  * independent rotations / rescales / relinearizations / ciphertext products of a level go out
