@@ -43,6 +43,7 @@ _SIGS = {
     "evah_ctx_wait": [_vp, _vp],
     "evah_ctx_transfer_stats": [_vp, _u64p],
     "evah_ctx_modup_variant": [_vp, C.POINTER(C.c_uint32)],
+    "evah_ctx_tail_variant": [_vp, C.POINTER(C.c_uint32)],
     "evah_ctx_key_bytes": [_vp, _u64p],
     "evah_ctx_key_bytes_detail": [_vp, _u64p],
     "evah_ctx_key_upload_stats": [_vp, _u64p],
@@ -611,6 +612,12 @@ class Context:
         out = (C.c_uint32 * 3)()
         _chk(_lib.evah_ctx_modup_variant(self.h, out))
         return int(out[0]), bool(out[1]), bool(out[2])
+
+    def tail_variant(self):
+        """(three-launch tail on, top-bit butterflies only, lazy conversion only) of this context's relinearize + rescale tail"""
+        out = (C.c_uint32 * 3)()
+        _chk(_lib.evah_ctx_tail_variant(self.h, out))
+        return bool(out[0]), bool(out[1]), bool(out[2])
 
     def key_bytes(self):
         """bytes of HBM the evaluation keys of this device state occupy (a limb shard holds its prime rows only)"""

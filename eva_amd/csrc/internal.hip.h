@@ -333,6 +333,14 @@ struct Tunables {
   // (evah_ctx::modup_tb / modup_lazy: top-bit butterflies only, lazy digit conversion only); 0 = the generic kernel
   int modup_lr = 3;
   bool modup_spec = true;
+  // EVAH_TAIL_FUSE (1): where the key switch of a relinearize + rescale (stored or fused with the multiply) takes the
+  // mod-up kernel and the combine is the folded form (EVAH_FOLD_PA), its tail runs as three launches — one contiguous
+  // inverse launch for the special and the last rows together (OpTailIntt), ntt_tail_kernel (ntt_tail.hip.h: both strided
+  // inverse passes, r_K and t_K in registers, the strided forward pass under every output prime), OpRRT's contiguous
+  // pass; 0 = the six launches (inverse transform of the special rows storing r, of the last rows storing t, OpRRT's
+  // forward transform reading both once per output prime).  Same words either way.  EVAH_MODUP_SPEC=0 selects the
+  // generic tail kernel as it does the generic mod-up (tail_variant below)
+  bool tail_fuse = true;
   // EVAH_LDS_EXTRA (0): bytes of dynamic LDS added to every ntt_pass_kernel launch — an occupancy probe for the
   // tuning notes (fewer workgroups per CU), never set in production
   uint32_t lds_extra = 0;
@@ -381,6 +389,7 @@ struct Tunables {
     flag("EVAH_MODUP", t.modup);
     if (const char *e = std::getenv("EVAH_MODUP_LR")) t.modup_lr = std::atoi(e) == 2 ? 2 : 3;
     flag("EVAH_MODUP_SPEC", t.modup_spec);
+    flag("EVAH_TAIL_FUSE", t.tail_fuse);
     if (const char *e = std::getenv("EVAH_KS_GROUPS")) t.ks_groups = std::max(1, std::atoi(e));
     if (const char *e = std::getenv("EVAH_KS_THREADS")) {
       const int n = std::atoi(e);
@@ -410,6 +419,9 @@ struct evah_ctx {
   // shape (tb_c != 0 — stricter than all_tb, whose "< 2^54" clause admits other shapes) / q_J <= 8 q_kappa for every
   // digit prime J < k - 1 and every output prime kappa < k (the special prime included), so at every level
   bool modup_tb = false, modup_lazy = false;
+  // what ntt_tail_kernel may assume beside modup_tb: OpRRT::setup's lazy test holds at every level, q_last <= 4 q_i and
+  // P <= 8 q_i for every data prime `last` >= 1 and every i < last
+  bool tail_lazy = false;
   // per-launch profile
   bool prof_on = false;
   std::vector<ProfRec> prof_recs;
@@ -430,6 +442,13 @@ struct ModupVariant { int lr; bool tbonly, lazyonly; };
 inline ModupVariant modup_variant(const evah_ctx *c) {
   const bool tb = c->tun.modup_spec && EVAH_TOPBIT && c->modup_tb;
   return {c->tun.modup_lr, tb, tb && c->modup_lazy};
+}
+// the instantiation a context's fused relinearize + rescale tails take (launch_tail, launch.hip.h): whether the knob is
+// on, and the two specialisations of ntt_tail_kernel its primes allow, under the same EVAH_MODUP_SPEC switch
+struct TailVariant { bool fused, tbonly, lazyonly; };
+inline TailVariant tail_variant(const evah_ctx *c) {
+  const bool tb = c->tun.modup_spec && EVAH_TOPBIT && c->modup_tb;
+  return {c->tun.tail_fuse, tb, tb && c->tail_lazy};
 }
 
 inline void use(evah_ctx *c) { HIPCHK(hipSetDevice(c->device)); }

@@ -121,6 +121,15 @@ void launch_ks_inner(evah_ctx *c, int P, const u64 *target, const u64 *scratch, 
   }
 }
 
+// the launch form of a batch of n key switches at level l (switch_key_products below): the latency-bound one, whose
+// digit passes run as ntt_inv_fwd_kernel, or the throughput-sized one with the mod-up kernel
+static bool ks_small(evah_ctx *c, uint32_t l, uint32_t n) {
+  return c->tun.fuse_mac && std::max(1, c->tun.ks_groups) == 1 && fuse_small_launch(c, n * (l + 1) * l);
+}
+static bool ks_takes_modup(evah_ctx *c, uint32_t l, uint32_t n) {
+  return !ks_small(c, l, n) && c->tun.modup && c->tun.fuse_mac && std::max(1, c->tun.ks_groups) == 1 && modup_fits(c);
+}
+
 // SEAL Evaluator::switch_key_inplace, device version.
 //   out[K] = (add && K < add_polys ? add[K] : 0) + keyswitch(target)[K],  K in {0,1}
 // steps 1-2 of switch_key for a batch of n (target, key) pairs in one set of launches:
@@ -153,10 +162,10 @@ bool switch_key_products(evah_ctx *c, uint32_t l, const u64 *target, size_t targ
   OpKsDigit::Params dp{t.d, sc.d, l, (size_t)l * N, kb.scratch_bs, 0, l + 1};
   // a small key switch is latency-bound: the digits' strided inverse pass and the first pass of the
   // digit conversion then run as one launch
-  const bool small = c->tun.fuse_mac && std::max(1, c->tun.ks_groups) == 1 && fuse_small_launch(c, n * (l + 1) * l);
+  const bool small = ks_small(c, l, n);
   // a throughput-sized one: the strided inverse pass of each digit tile runs once, in the workgroup that converts it for
   // every output prime (ntt_modup_kernel) — t is then the contiguous pass's intermediate, never the canonical digits
-  const bool modup = !small && c->tun.modup && c->tun.fuse_mac && std::max(1, c->tun.ks_groups) == 1 && modup_fits(c);
+  const bool modup = ks_takes_modup(c, l, n);
   if (mul) { // the target is the product's d2, formed on load
     OpMulIntt::Params ip{*mul, t.d, (size_t)l * N, l, fold ? d2.d : nullptr};
     if (small || modup) launch_pass_p<false, true, OpMulIntt>(c, c->logN / 2, ip, n * l);
@@ -304,6 +313,18 @@ static void relin_rescale_core(evah_ctx *c, uint32_t l, uint32_t n, const Size3T
   const bool fold = c->tun.fold_pa && c->tun.fuse_mac; // EVAH_FUSE_MAC=0 (the unfused reference path): the OpRR / OpRRLast forms below
   switch_key_products(c, l, nullptr, 0, keys.data(), n, prod.d, &c2, mul, nullptr, fold, mul ? nullptr : &a_polys, /*lazy_out=*/fold);
   Scratch r(c, (size_t)n * 2 * N), t(c, (size_t)n * 2 * N);
+  if (fold && tail_variant(c).fused && ks_takes_modup(c, l, n)) {
+    // the tail in three launches where the key switch above took the mod-up kernel (the RR_MEM / RR_MUL forms keep the
+    // six below): contiguous inverse pass of the special and the last rows together; both strided inverse passes, r_K
+    // and t_K in registers, and OpRRFolded's strided pass under every output prime (ntt_tail_kernel); its contiguous pass
+    OpRRLastFolded::Params lp{nullptr, 0, prod.d + (size_t)last * N, pps, r.d, N, t.d, N, last, sp, {}};
+    OpTailIntt::Params ip{lp, prod.d + (size_t)l * N, pps, r.d};
+    launch_pass_p<false, true, OpTailIntt>(c, c->logN / 2, ip, 4 * n);
+    OpRRFolded::Params rp{r.d, N, t.d, N, nullptr, 0, prod.d, pps, out_d, ops, sp, last, l - 1, {}};
+    launch_tail(c, lp, rp, 2 * n);
+    launch_pass_p<false, false, OpRRFolded>(c, c->logN / 2, rp, 2 * n * (l - 1));
+    return;
+  }
   // r_K = INTT_P(prod[K][special]) + P/2
   OpPlain::Params spp{prod.d + (size_t)l * N, r.d, pps, N, 1, sp, 1, {}};
   ntt_inverse<OpPlain>(c, spp, 2 * n);

@@ -31,6 +31,7 @@ template <> struct OpClass<OpMulPolyIntt> { static constexpr int fwd_a = KC_NTT_
 template <> struct OpClass<OpModDownMul> { static constexpr int fwd_a = KC_MODDOWN_A, fwd_b = KC_MODDOWN_B; };
 template <int M> struct OpClass<OpRRT<M>> { static constexpr int fwd_a = KC_MODDOWN_A, fwd_b = KC_MODDOWN_B; };
 template <int M> struct OpClass<OpRRLastT<M>> { static constexpr int fwd_a = KC_MODDOWN_A, fwd_b = KC_MODDOWN_B; };
+template <> struct OpClass<OpTailIntt> { static constexpr int fwd_a = KC_MODDOWN_A, fwd_b = KC_MODDOWN_B; };
 template <> struct OpClass<OpChainIntt> { static constexpr int fwd_a = KC_NTT_A, fwd_b = KC_NTT_B; };
 template <> struct OpClass<OpChainT> { static constexpr int fwd_a = KC_INTT_B, fwd_b = KC_INTT_B; };
 template <> struct OpClass<OpChainDigit> { static constexpr int fwd_a = KC_KSDIGIT_A, fwd_b = KC_KSDIGIT_B; };
@@ -254,6 +255,37 @@ template <class Op> static void launch_modup(evah_ctx *c, const typename Op::Par
   case 8: launch_modup_p<8, Op>(c, prm, n); break;
   case 9: launch_modup_p<9, Op>(c, prm, n); break;
   default: throw std::runtime_error("unsupported poly_modulus_degree for the mod-up kernel");
+  }
+}
+// ---- the strided passes of the relinearize + rescale tail at throughput size, one workgroup per (column tile, polynomial):
+// ntt_tail_kernel (ntt_tail.hip.h).  The contiguous inverse pass (OpTailIntt) left the special rows' intermediate in lp.r and
+// the last rows' in lp.t; the lazy first-pass words of OpRRFolded go to rp.dst.  Same shapes as the mod-up (modup_fits).
+template <int P, bool TBONLY, bool LAZYONLY>
+static void launch_tail_v(evah_ctx *c, const OpRRLastFolded::Params &lp, const OpRRFolded::Params &rp, uint32_t polys) {
+  ProfScope ps(c, KC_MODDOWN_A);
+  const uint32_t tile = (uint32_t)NTT_THREADS << 3, n_tiles = c->N / tile;
+  const int logC = (int)ilog2(tile) - P;
+  const size_t lds = ((((size_t)1 << logC) * lds_sub_stride<P>() + 1) & ~(size_t)1) * sizeof(u64) + ((size_t)1 << P) * sizeof(ulonglong2);
+  hipLaunchKernelGGL((ntt_tail_kernel<P, TBONLY, LAZYONLY>), dim3(n_tiles, 1, polys), dim3(NTT_THREADS), lds, c->stream, c->dev, lp, rp);
+  HIPCHK(hipGetLastError());
+}
+// (a template so that only the translation unit that calls it instantiates the kernels)
+template <class RR = OpRRFolded>
+static void launch_tail(evah_ctx *c, const OpRRLastFolded::Params &lp, const typename RR::Params &rp, uint32_t polys) {
+  if (!modup_fits(c) || rp.jl < 1) throw std::logic_error("tail kernel outside its shapes");
+  const TailVariant v = tail_variant(c);
+  auto go = [&](auto ptag) {
+    constexpr int P = decltype(ptag)::value;
+    if (v.lazyonly) launch_tail_v<P, true, true>(c, lp, rp, polys);
+    else if (v.tbonly) launch_tail_v<P, true, false>(c, lp, rp, polys);
+    else launch_tail_v<P, false, false>(c, lp, rp, polys);
+  };
+  switch ((c->logN + 1) / 2) {
+  case 6: go(std::integral_constant<int, 6>{}); break;
+  case 7: go(std::integral_constant<int, 7>{}); break;
+  case 8: go(std::integral_constant<int, 8>{}); break;
+  case 9: go(std::integral_constant<int, 9>{}); break;
+  default: throw std::runtime_error("unsupported poly_modulus_degree for the tail kernel");
   }
 }
 // two strided inverse passes + combine (+ strided forward pass): ntt_inv2_kernel (ntt_chain.hip.h)

@@ -645,4 +645,5 @@ ntt_inv_fwd_kernel(DevCtx cx, typename Op::Params prm, int log_tiles) {
 #include "ntt_ks_inner.hip.h"   // ks_inner_kernel: second pass of the digit transforms fused with the key inner product; operand tables
 #include "ntt_ops.hip.h"        // the fused load / store ops of the passes (OpPlainT, OpMulIntt, OpKsDigit, OpModDownT, OpRR*)
 #include "ntt_modup.hip.h"      // ntt_modup_kernel: the key switch's mod-up at throughput size (one workgroup per digit tile, every output prime)
+#include "ntt_tail.hip.h"       // ntt_tail_kernel: the strided passes of the relinearize + rescale tail at throughput size (one workgroup per tile, every output prime)
 #include "ntt_chain.hip.h"      // the chain step Mul -> Rescale -> Relinearize in six launches: ntt_inv2_kernel and its ops

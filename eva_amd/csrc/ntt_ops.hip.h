@@ -442,10 +442,14 @@ template <int AM> struct OpRRLastT {
     const u64 av = MUL ? product_poly(j.mul, j.K, j.off + n, pm) : j.a[n];
     return addmod(av, pv, pm.q);
   }
-  static __device__ __forceinline__ void store(const DevCtx &, const Job &j, const DevPrime &pm, uint32_t n, u64 x) {
-    const u64 u = submod(barrett64(j.r[n], pm.q, pm.brt), j.halfP, pm.q);
+  // t_K at one coefficient from the inverse transform's canonical word x and r_K there (ntt_tail_kernel has both in registers)
+  static __device__ __forceinline__ u64 combine(const Job &j, const DevPrime &pm, u64 x, u64 r) {
+    const u64 u = submod(barrett64(r, pm.q, pm.brt), j.halfP, pm.q);
     x = submod(x, mul_shoup(u, j.pinv.x, j.pinv.y, pm.q), pm.q);
-    j.dst[n] = addmod(x, pm.q >> 1, pm.q);
+    return addmod(x, pm.q >> 1, pm.q);
+  }
+  static __device__ __forceinline__ void store(const DevCtx &, const Job &j, const DevPrime &pm, uint32_t n, u64 x) {
+    j.dst[n] = combine(j, pm, x, j.r[n]);
   }
 };
 
@@ -499,13 +503,16 @@ template <int AM> struct OpRRT {
     j.lazy = cx.primes[p.last].q <= cx.primes[i].q4 && cx.primes[p.sp].q <= cx.primes[i].q8;
     return true;
   }
+  // u P^-1 + v at one coefficient from r_K and t_K there (ntt_tail_kernel converts from registers)
+  template <bool LZ> static __device__ __forceinline__ u64 conv(const Job &j, const DevPrime &pm, u64 r, u64 t) {
+    if (LZ) return mul_tw_lazy5(r + (pm.q - j.halfP), j.pinv.x, j.pinv.y, pm.nq) + (t + (pm.q - j.halfL));
+    const u64 u = submod(barrett64(r, pm.q, pm.brt), j.halfP, pm.q);
+    const u64 v = submod(barrett64(t, pm.q, pm.brt), j.halfL, pm.q);
+    return addmod(mul_shoup(u, j.pinv.x, j.pinv.y, pm.q), v, pm.q);
+  }
   template <bool LZ>
   static __device__ __forceinline__ u64 load(const DevCtx &, const Job &j, const DevPrime &pm, uint32_t n) {
-    if (LZ)
-      return mul_tw_lazy5(j.r[n] + (pm.q - j.halfP), j.pinv.x, j.pinv.y, pm.nq) + (j.t[n] + (pm.q - j.halfL));
-    const u64 u = submod(barrett64(j.r[n], pm.q, pm.brt), j.halfP, pm.q);
-    const u64 v = submod(barrett64(j.t[n], pm.q, pm.brt), j.halfL, pm.q);
-    return addmod(mul_shoup(u, j.pinv.x, j.pinv.y, pm.q), v, pm.q);
+    return conv<LZ>(j, pm, j.r[n], j.t[n]);
   }
   static __device__ __forceinline__ void store_fwd(const DevCtx &cx, const Job &j, const DevPrime &pm, uint32_t n, u64 W) {
     W += (W >= pm.q8 ? pm.nq8 : 0);                                                  // [0,16q) -> [0,8q)
@@ -539,5 +546,44 @@ using OpRRLastFolded = OpRRLastT<RR_FOLDED>;
 using OpRR = OpRRT<RR_MEM>;
 using OpRRMul = OpRRT<RR_MUL>;
 using OpRRFolded = OpRRT<RR_FOLDED>;
+
+// Contiguous inverse pass of the four rows the relinearize + rescale tail starts from, as one launch (the fused tail,
+// ntt_tail.hip.h): job -> (which = y, poly = z = 2b + K).  which == 0: the special row of prod[poly] modulo P, as
+// OpPlain reads it, lazy intermediate to r[poly]; which == 1: row `last` of prod[poly] * P^-1 modulo q_last
+// (OpRRLastFolded::load), lazy intermediate to lp.t[poly].  Neither has a store epilogue: ntt_tail_kernel finishes both.
+struct OpTailIntt {
+  using Last = OpRRLastT<RR_FOLDED>;
+  struct Params {
+    Last::Params lp;  // prod, t, last, sp (r is not read here)
+    const u64 *spec;  // the special row of prod[0]
+    size_t spec_ps;
+    u64 *r;           // [polys][N] at lp.r_ps
+  };
+  struct Job {
+    uint32_t prime;
+    bool lazy, is_last;
+    const u64 *src;
+    u64 *dst;
+    Last::Job last;
+  };
+  static dim3 grid(const Params &, uint32_t jobs) { return dim3(1, 2, jobs / 2); }
+  static constexpr int loop_axis = 2; // the polynomials of one row kind share its prime (ntt_loop_kernel)
+  static __device__ __forceinline__ bool setup(const DevCtx &cx, const Params &p, uint32_t, uint32_t which, uint32_t poly, Job &j) {
+    Last::setup(cx, p.lp, 0, poly, 0, j.last);
+    j.is_last = which != 0;
+    j.lazy = false;
+    j.prime = j.is_last ? j.last.prime : p.lp.sp;
+    j.src = p.spec + poly * p.spec_ps;
+    j.dst = j.is_last ? j.last.dst : p.r + poly * p.lp.r_ps;
+    return true;
+  }
+  template <bool LZ>
+  static __device__ __forceinline__ u64 load(const DevCtx &cx, const Job &j, const DevPrime &pm, uint32_t n) {
+    if (j.is_last) return Last::template load<LZ>(cx, j.last, pm, n); // block-uniform
+    return j.src[n];
+  }
+  // (the strided pass of these rows is ntt_tail_kernel's: nothing launches this op's second pass)
+  static __device__ __forceinline__ void store(const DevCtx &, const Job &j, const DevPrime &, uint32_t n, u64 v) { j.dst[n] = v; }
+};
 
 } // namespace evah

@@ -168,6 +168,10 @@ int evah_ctx_create(uint32_t N, uint32_t k, const uint64_t *primes, int device, 
       c->modup_tb = c->modup_tb && hp[i].tb_c != 0;
       for (uint32_t J = 0; J + 1 < k; J++) c->modup_lazy = c->modup_lazy && c->primes[J] <= 8 * c->primes[i];
     }
+    c->tail_lazy = true;
+    for (uint32_t last = 1; last + 1 < k; last++)
+      for (uint32_t i = 0; i < last; i++)
+        c->tail_lazy = c->tail_lazy && c->primes[last] <= 4 * c->primes[i] && c->primes[k - 1] <= 8 * c->primes[i];
     c->sh = std::make_shared<SharedDev>();
     c->sh->device = device;
     HIPCHK(hipMalloc(&c->sh->d_tables, total));
@@ -211,6 +215,7 @@ int evah_ctx_fork(evah_ctx *parent, evah_ctx **out) {
     c->all_tb = parent->all_tb;
     c->modup_tb = parent->modup_tb;
     c->modup_lazy = parent->modup_lazy;
+    c->tail_lazy = parent->tail_lazy;
     HIPCHK(hipStreamCreateWithFlags(&c->own, hipStreamNonBlocking));
     c->stream = c->own;
     HIPCHK(hipEventCreate(&c->ev0));
@@ -678,6 +683,15 @@ int evah_ctx_modup_variant(evah_ctx *c, uint32_t out[3]) {
   API_BEGIN
   const ModupVariant v = modup_variant(c);
   out[0] = (uint32_t)v.lr;
+  out[1] = v.tbonly;
+  out[2] = v.lazyonly;
+  API_END
+}
+
+int evah_ctx_tail_variant(evah_ctx *c, uint32_t out[3]) {
+  API_BEGIN
+  const TailVariant v = tail_variant(c);
+  out[0] = v.fused;
   out[1] = v.tbonly;
   out[2] = v.lazyonly;
   API_END

@@ -180,6 +180,11 @@ int evah_ctx_transfer_stats(evah_ctx *ctx, uint64_t out[6]);
  * compiled in (every prime 2^b - c, b > 32, c < 2^32), out[2] = 1 when only the lazy digit conversion is
  * (q_J <= 8 q_kappa for every digit / output prime pair).  All of them compute the same words. */
 int evah_ctx_modup_variant(evah_ctx *ctx, uint32_t out[3]);
+/* the tail of relinearize + rescale where its key switch takes the mod-up kernel (EVAH_TAIL_FUSE / EVAH_MODUP_SPEC and
+ * the context's primes): out[0] = 1 when it runs as three launches (ntt_tail_kernel), 0 = the six launches; out[1] = 1
+ * when that kernel has only the top-bit butterflies compiled in, out[2] = 1 when only the lazy conversion is
+ * (q_last <= 4 q_i and P <= 8 q_i for every pair i < last of data primes).  All of them compute the same words. */
+int evah_ctx_tail_variant(evah_ctx *ctx, uint32_t out[3]);
 /* bytes of HBM the evaluation keys (relinearization + Galois) of this context's device state occupy.  After
  * evah_ctx_set_shard(ctx, s, G) an upload keeps only shard s's prime rows of a key (its data limbs and the
  * special prime): (ceil((k-1)/G) + 1) / k of the whole key. */

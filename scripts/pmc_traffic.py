@@ -9,6 +9,8 @@ CLASS = [("ks_inner_kernel", "ks_mac"), ("k_ks_mac", "ks_mac"), ("OpKsDigit", "k
 
 
 def classify(name):
+    if "ntt_tail_kernel" in name:  # both strided inverse passes of the relinearize + rescale tail + OpRRT's first forward pass: the latter
+        return "moddown_pass1"
     base = None
     for key, cls in CLASS:
         if key in name:
