@@ -16,6 +16,18 @@ LIB_PATH = os.path.join(_HERE, "lib", "libeva_hip.so")
 
 KEY_RELIN = 0
 KEY_GALOIS = 1
+# value types of the array calls (include/eva_hip.h EVAH_F64 / EVAH_F32 / EVAH_U8)
+F64, F32, U8 = 0, 1, 2
+_DTYPES = {np.dtype(np.float64): F64, np.dtype(np.float32): F32, np.dtype(np.uint8): U8}
+
+
+def array_dtype(a):
+    """(array as the array calls take it, its EVAH_* code): C-contiguous uint8 / float32 / float64 arrays as they are,
+    anything else as a C-contiguous float64 copy"""
+    a = np.asarray(a)
+    if a.dtype not in _DTYPES or not a.flags["C_CONTIGUOUS"]:
+        a = np.ascontiguousarray(a, dtype=np.float64)
+    return a, _DTYPES[a.dtype]
 
 
 class EvaHipError(RuntimeError):
@@ -125,6 +137,13 @@ _SIGS = {
                                          C.POINTER(C.c_uint8), _vpp],
     "evah_encode_encrypt_symmetric_sampled_many": [_vp, C.c_uint32, C.POINTER(C.c_double), C.c_uint32, C.c_uint32, C.c_double,
                                                    C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _vpp],
+    # the client calls on arrays and batched handles
+    "evah_encode_encrypt_array": [_vp, C.c_uint32, _vp, C.c_int, C.c_uint32, C.c_uint32, C.c_double, C.POINTER(C.c_uint8), _vpp],
+    "evah_encode_encrypt_symmetric_array": [_vp, C.c_uint32, _vp, C.c_int, C.c_uint32, C.c_uint32, C.c_double, C.POINTER(C.c_uint8),
+                                            C.POINTER(C.c_uint8), _vpp],
+    "evah_decrypt_decode_handles": [_vp, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.c_int, _vp],
+    "evah_ct_slice": [_vp, _vp, C.c_uint32, C.c_uint32, _vpp],
+    "evah_ctx_stack_stats": [_vp, _u64p],
     # seed-compressed evaluation keys
     "evah_key_upload_seeded": [_vp, C.c_int, C.c_uint32, C.c_uint32, _u64p, C.POINTER(C.c_uint8)],
     "evah_keygen_switch": [_vp, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_int8), C.POINTER(C.c_uint8), C.c_int, _u64p],
@@ -301,6 +320,12 @@ class Ciphertext:
     def unstack(self, b):
         h = C.c_void_p()
         _chk(_lib.evah_ct_unstack(self.ctx.h, self.h, int(b), C.byref(h)))
+        return Ciphertext(self.ctx, h)
+
+    def slice(self, b0, n):
+        """instances b0 .. b0 + n - 1 as a batched view of n instances (evah_ct_slice: shares the buffer)"""
+        h = C.c_void_p()
+        _chk(_lib.evah_ct_slice(self.ctx.h, self.h, int(b0), int(n), C.byref(h)))
         return Ciphertext(self.ctx, h)
 
     def free(self):
@@ -576,6 +601,44 @@ class Context:
         ptrs = (C.c_void_p * max(n, 1))(*[ct.h for ct in cts])
         _chk(_lib.evah_decrypt_decode_many(self.h, ptrs, n, int(n_out), out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
+
+    def encode_encrypt_array(self, values, limbs, scale, rkeys, dtype=None):
+        """encode_encrypt_sampled_many on an array [batch][n_values] in its own type: uint8, float32 and
+        float64 cross as they are and are converted on the device; dtype: an EVAH_* code to pass instead of the array's"""
+        v, code = array_dtype(values)
+        assert v.ndim == 2
+        h = C.c_void_p()
+        _chk(_lib.evah_encode_encrypt_array(self.h, v.shape[0], v.ctypes.data_as(_vp), code if dtype is None else int(dtype), v.shape[1],
+                                            int(limbs), float(scale), _keys32(rkeys, v.shape[0]), C.byref(h)))
+        return Ciphertext(self, h)
+
+    def encode_encrypt_symmetric_array(self, values, limbs, scale, ekeys, seeds, dtype=None):
+        """encode_encrypt_symmetric_sampled_many on an array [batch][n_values] in its own type"""
+        v, code = array_dtype(values)
+        assert v.ndim == 2
+        h = C.c_void_p()
+        _chk(_lib.evah_encode_encrypt_symmetric_array(self.h, v.shape[0], v.ctypes.data_as(_vp), code if dtype is None else int(dtype),
+                                                      v.shape[1], int(limbs), float(scale), _keys32(ekeys, v.shape[0]),
+                                                      _keys32(seeds, v.shape[0]), C.byref(h)))
+        return Ciphertext(self, h)
+
+    def decrypt_decode_handles(self, cts, n_out, dtype=np.float64, dtype_code=None):
+        """the first n_out slot values of every instance of the handles of `cts` (single or batched, views and slices
+        included; one size, limb count and scale; at most 64 instances together) -> [instances][n_out] of float64 or
+        float32, rows in list order, then instance order; dtype_code: an EVAH_* code to pass instead of dtype's"""
+        dt = np.dtype(dtype)
+        rows = sum(ct.batch for ct in cts)
+        out = np.empty((rows, int(n_out)), dtype=dt)
+        ptrs = (C.c_void_p * max(len(cts), 1))(*[ct.h for ct in cts])
+        _chk(_lib.evah_decrypt_decode_handles(self.h, ptrs, len(cts), int(n_out), _DTYPES[dt] if dtype_code is None else int(dtype_code),
+                                              out.ctypes.data_as(_vp)))
+        return out
+
+    def stack_stats(self):
+        """(evah_ct_stack calls on this device state, instances they copied)"""
+        out = (C.c_uint64 * 2)()
+        _chk(_lib.evah_ctx_stack_stats(self.h, out))
+        return tuple(int(x) for x in out)
 
     def copy_here(self, value):
         """a copy of a Ciphertext / Plaintext of another context (another GPU: peer copy), owned by this one"""

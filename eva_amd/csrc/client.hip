@@ -117,11 +117,16 @@ template <bool ENC> static void fft_batched(evah_ctx *c, double2 *cd, const doub
 }
 
 // ---- the encoder of the _many calls: evah_pt_encode's small kernels (elementwise.hip) with an instance index (grid.y)
+// T = the type the values arrived in (double, float, uint8_t: evah_encode_encrypt_array); every T converts to
+// double exactly, so the slots hold what the double instantiation holds for the converted array.  One scalar load per
+// thread: row b of a uint8_t array starts at byte b * n_vals, aligned to nothing, and the kernel is bound by its two
+// 16-byte stores per slot, not by the load.
+template <class T>
 __global__ void __launch_bounds__(256)
-k_enc_scatter_many(const double *vals, uint32_t n_vals, const uint32_t *slot_map, double2 *c, uint32_t slots) {
+k_enc_scatter_many(const T *vals, uint32_t n_vals, const uint32_t *slot_map, double2 *c, uint32_t slots) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= slots) return;
-  const double v = vals[(size_t)blockIdx.y * n_vals + i % n_vals];
+  const double v = (double)vals[(size_t)blockIdx.y * n_vals + i % n_vals];
   c += (size_t)blockIdx.y * 2 * slots;
   c[slot_map[i]] = make_double2(v, 0.0);
   c[slot_map[slots + i]] = make_double2(v, -0.0); // conjugate of a real value
@@ -398,10 +403,12 @@ k_crt_to_double(DevCtx cx, CrtTab t, uint32_t l, const u64 *coeff, double inv_sc
   const size_t n = (size_t)blockIdx.x * blockDim.x + threadIdx.x, inst = blockIdx.y;
   out[inst * cx.N + n] = make_double2(crt_to_double(cx, t, l, coeff + inst * l * cx.N, n, inv_scale), 0.0);
 }
+// T = double, or float: the double rounded to nearest-even here, so that half the bytes cross to the host
+template <class T>
 __global__ void __launch_bounds__(256)
-k_dec_gather(const double2 *c, const uint32_t *slot_map, uint32_t n_out, uint32_t N, double *out) {
+k_dec_gather(const double2 *c, const uint32_t *slot_map, uint32_t n_out, uint32_t N, T *out) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n_out) out[(size_t)blockIdx.y * n_out + i] = c[(size_t)blockIdx.y * N + slot_map[i]].x;
+  if (i < n_out) out[(size_t)blockIdx.y * n_out + i] = (T)c[(size_t)blockIdx.y * N + slot_map[i]].x;
 }
 
 // ---- one body per operation: no argument checks inside, every entry point below makes its own
@@ -484,24 +491,31 @@ static evah_ct *encrypt_symmetric(evah_ctx *c, uint32_t batch, uint32_t l, doubl
   return o;
 }
 
-// SEAL Decryptor::decrypt + CKKSEncoder::decode of n single ciphertexts of one size, limb count and scale, read in place:
-// the first n_out slot values of each into out [n][n_out] (host)
-static void decrypt_decode(evah_ctx *c, const evah_ct *const *cts, uint32_t n, uint32_t n_out, double *out) {
+// bytes per value of a value type of the array calls (EVAH_F64 / EVAH_F32 / EVAH_U8); 0: not a type
+static size_t dtype_size(int dtype) { return dtype == EVAH_F64 ? 8 : dtype == EVAH_F32 ? 4 : dtype == EVAH_U8 ? 1 : 0; }
+
+// SEAL Decryptor::decrypt + CKKSEncoder::decode of the n instances that n_handles handles of one size, limb count and
+// scale hold together (a single ciphertext is one instance; instance j of a batched handle is d + j * size * ps), read in
+// place: the first n_out slot values of each into out [n][n_out] (host) as double (EVAH_F64) or float (EVAH_F32), rows
+// in list order, then instance order
+static void decrypt_decode(evah_ctx *c, const evah_ct *const *cts, uint32_t n_handles, uint32_t n, uint32_t n_out, int dtype_out, void *out) {
   const uint32_t l = cts[0]->limbs, N = c->N;
   enc_tables(c);
   dec_tables(c);
   const CrtTab t = crt_tab_cached(c, l);
   DotTab tab{};
-  for (uint32_t i = 0; i < n; i++) {
+  for (uint32_t i = 0, r = 0; i < n_handles; i++) {
     acquire(c, cts[i]->buf);
-    tab.ct[i] = cts[i]->d;
-    tab.ct_ps[i] = (uint32_t)(cts[i]->ps / N);
+    for (uint32_t j = 0; j < cts[i]->batch; j++, r++) {
+      tab.ct[r] = cts[i]->d + (size_t)j * cts[i]->size * cts[i]->ps;
+      tab.ct_ps[r] = (uint32_t)(cts[i]->ps / N);
+    }
   }
-  const size_t B = n;
-  Scratch m(c, B * l * N), cbuf(c, B * 2 * N), outd(c, B * n_out);
+  const size_t B = n, out_bytes = dtype_size(dtype_out) * B * n_out;
+  Scratch m(c, B * l * N), cbuf(c, B * 2 * N), outd(c, (out_bytes + 7) / 8);
   {
     // the decrypted messages, their FP images and the slot values do not stay behind in pool memory the next call reuses
-    Wipe w_m{c, m.d, sizeof(u64) * B * l * N}, w_c{c, cbuf.d, sizeof(double2) * B * N}, w_o{c, outd.d, sizeof(double) * B * n_out};
+    Wipe w_m{c, m.d, sizeof(u64) * B * l * N}, w_c{c, cbuf.d, sizeof(double2) * B * N}, w_o{c, outd.d, out_bytes};
     EW_LAUNCH(k_decrypt_dot, dim3(N / 256, l, n), dim3(256), 0, c->stream, c->dev, tab, cts[0]->size, l, c->sh->sk.d, m.d);
     OpPlain::Params ip{m.d, m.d, (size_t)l * N, (size_t)l * N, l, 0, 0, {}};
     ntt_inverse<OpPlain>(c, ip, n * l);
@@ -509,10 +523,14 @@ static void decrypt_decode(evah_ctx *c, const evah_ct *const *cts, uint32_t n, u
     EW_LAUNCH(k_crt_to_double, dim3(N / 256, n), dim3(256), 0, c->stream, c->dev, t, l, m.d, 1.0 / cts[0]->scale, cd);
     HIPCHK(hipGetLastError());
     fft_batched<false>(c, cd, c->sh->dec_roots, n, make_double2(0.0, 0.0), 0.0);
-    EW_LAUNCH(k_dec_gather, dim3((n_out + 255) / 256, n), dim3(256), 0, c->stream, cd, c->sh->enc_slot_map, n_out, N,
-              reinterpret_cast<double *>(outd.d));
+    if (dtype_out == EVAH_F32)
+      EW_LAUNCH(k_dec_gather<float>, dim3((n_out + 255) / 256, n), dim3(256), 0, c->stream, cd, c->sh->enc_slot_map, n_out, N,
+                reinterpret_cast<float *>(outd.d));
+    else
+      EW_LAUNCH(k_dec_gather<double>, dim3((n_out + 255) / 256, n), dim3(256), 0, c->stream, cd, c->sh->enc_slot_map, n_out, N,
+                reinterpret_cast<double *>(outd.d));
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, outd.d, sizeof(double) * B * n_out, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out, outd.d, out_bytes, hipMemcpyDeviceToHost, c->stream));
     w_m.now();
     w_c.now();
     w_o.now();
@@ -522,7 +540,7 @@ static void decrypt_decode(evah_ctx *c, const evah_ct *const *cts, uint32_t n, u
 
 // ---- the _many calls: values in, one batched handle out
 // the checks both encryption calls share, in the order evah_pt_encode and the encryptors make them
-static void encode_many_checks(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale,
+static void encode_many_checks(evah_ctx *c, uint32_t batch, const void *values, int dtype, uint32_t n_values, uint32_t limbs, double scale,
                                evah_ct **out) {
   if (c->capturing) throw std::logic_error("this call synchronises with the host and cannot be captured into a graph");
   if (batch < 1 || batch > (uint32_t)KS_BATCH_MAX) throw std::invalid_argument("batch must be 1..64");
@@ -532,16 +550,27 @@ static void encode_many_checks(evah_ctx *c, uint32_t batch, const double *values
   const uint32_t slots = c->N >> 1;
   if (n_values < 1 || n_values > slots || slots % n_values) throw std::invalid_argument("value count must divide the slot count");
   if (c->N % 256) throw std::invalid_argument("encryption needs N divisible by 256");
-  check_encodable(c, values, batch, n_values, scale); // evah_pt_encode's: "encoded values are too large"
+  // evah_pt_encode's: "encoded values are too large", on the values in the type they came in (the verdict on their
+  // float64 image: the conversion is exact, and a float NaN or infinity is a double NaN or infinity)
+  if (dtype == EVAH_F64) check_encodable(c, static_cast<const double *>(values), batch, n_values, scale);
+  else if (dtype == EVAH_F32) check_encodable(c, static_cast<const float *>(values), batch, n_values, scale);
+  else if (dtype == EVAH_U8) check_encodable(c, static_cast<const uint8_t *>(values), batch, n_values, scale);
+  else throw std::invalid_argument("unknown value dtype (EVAH_F64, EVAH_F32 or EVAH_U8)");
 }
-// values [batch][n_values] (host) -> NTT-form plaintexts pt [batch][limbs][N] on the queue; vals, cbuf: the call's scratch
-static void encode_many(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale, u64 *vals,
+// values [batch][n_values] of `dtype` (host) -> NTT-form plaintexts pt [batch][limbs][N] on the queue; vals, cbuf: the
+// call's scratch.  The values cross in their own type and become doubles in the scatter.
+static void encode_many(evah_ctx *c, uint32_t batch, const void *values, int dtype, uint32_t n_values, uint32_t limbs, double scale, u64 *vals,
                         double2 *cd, u64 *pt) {
   const uint32_t N = c->N, slots = N >> 1;
   enc_tables(c);
-  HIPCHK(hipMemcpyAsync(vals, values, sizeof(double) * (size_t)batch * n_values, hipMemcpyHostToDevice, c->stream));
-  EW_LAUNCH(k_enc_scatter_many, dim3((slots + 255) / 256, batch), dim3(256), 0, c->stream, reinterpret_cast<const double *>(vals), n_values,
-            c->sh->enc_slot_map, cd, slots);
+  HIPCHK(hipMemcpyAsync(vals, values, dtype_size(dtype) * (size_t)batch * n_values, hipMemcpyHostToDevice, c->stream));
+  const dim3 grid((slots + 255) / 256, batch);
+  if (dtype == EVAH_F32)
+    EW_LAUNCH(k_enc_scatter_many<float>, grid, dim3(256), 0, c->stream, reinterpret_cast<const float *>(vals), n_values, c->sh->enc_slot_map, cd, slots);
+  else if (dtype == EVAH_U8)
+    EW_LAUNCH(k_enc_scatter_many<uint8_t>, grid, dim3(256), 0, c->stream, reinterpret_cast<const uint8_t *>(vals), n_values, c->sh->enc_slot_map, cd, slots);
+  else
+    EW_LAUNCH(k_enc_scatter_many<double>, grid, dim3(256), 0, c->stream, reinterpret_cast<const double *>(vals), n_values, c->sh->enc_slot_map, cd, slots);
   const double fix = scale / (double)N;
   fft_batched<true>(c, cd, c->sh->enc_roots, batch, make_double2(c->sh->enc_last_root[0] * fix, c->sh->enc_last_root[1] * fix), fix);
   EW_LAUNCH(k_enc_round_many, dim3((N + 255) / 256, batch), dim3(256), 0, c->stream, c->dev, cd, limbs, pt);
@@ -552,43 +581,45 @@ static void encode_many(evah_ctx *c, uint32_t batch, const double *values, uint3
 // host -> device bytes of a batched encryption call: the values, its randomness and (symmetric) the seeds
 static void count_client_h2d(evah_ctx *c, size_t bytes) { c->sh->xfer[4] += bytes; }
 
-// evah_encode_encrypt_many (small: the host's draws) and evah_encode_encrypt_sampled_many (rkeys: drawn here)
-static void encode_encrypt_many(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale,
+// evah_encode_encrypt_many (small: the host's draws), evah_encode_encrypt_sampled_many (rkeys: drawn here) and
+// evah_encode_encrypt_array (rkeys, values of `dtype`)
+static void encode_encrypt_many(evah_ctx *c, uint32_t batch, const void *values, int dtype, uint32_t n_values, uint32_t limbs, double scale,
                                 const int8_t *small, const uint8_t *rkeys, evah_ct **out) {
   use(c);
-  encode_many_checks(c, batch, values, n_values, limbs, scale, out);
+  encode_many_checks(c, batch, values, dtype, n_values, limbs, scale, out);
   if (!small && !rkeys) throw std::invalid_argument("randomness pointer is null");
   if (!c->sh->pk.d) throw std::invalid_argument("public key not present");
   if (limbs + 1 > c->k) throw std::invalid_argument("plaintext level is not valid for encryption");
   const size_t N = c->N, B = batch;
-  Scratch vals(c, B * n_values), cbuf(c, B * 2 * N), pt(c, B * limbs * N);
+  Scratch vals(c, (dtype_size(dtype) * B * n_values + 7) / 8), cbuf(c, B * 2 * N), pt(c, B * limbs * N);
   try {
-    encode_many(c, batch, values, n_values, limbs, scale, vals.d, reinterpret_cast<double2 *>(cbuf.d), pt.d);
+    encode_many(c, batch, values, dtype, n_values, limbs, scale, vals.d, reinterpret_cast<double2 *>(cbuf.d), pt.d);
     *out = encrypt_public(c, batch, limbs, scale, pt.d, small, rkeys);
   } catch (...) {
     (void)hipStreamSynchronize(c->stream); // `values` is pageable host memory
     throw;
   }
-  count_client_h2d(c, sizeof(double) * B * n_values + (rkeys ? 32 * B : 3 * B * N));
+  count_client_h2d(c, dtype_size(dtype) * B * n_values + (rkeys ? 32 * B : 3 * B * N));
 }
 
-// evah_encode_encrypt_symmetric_many (e: the host's draws) and evah_encode_encrypt_symmetric_sampled_many (ekeys: drawn here)
-static void encode_encrypt_symmetric_many(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale,
-                                          const int8_t *e, const uint8_t *ekeys, const uint8_t *seeds, evah_ct **out) {
+// evah_encode_encrypt_symmetric_many (e: the host's draws), evah_encode_encrypt_symmetric_sampled_many (ekeys: drawn here)
+// and evah_encode_encrypt_symmetric_array (ekeys, values of `dtype`)
+static void encode_encrypt_symmetric_many(evah_ctx *c, uint32_t batch, const void *values, int dtype, uint32_t n_values, uint32_t limbs,
+                                          double scale, const int8_t *e, const uint8_t *ekeys, const uint8_t *seeds, evah_ct **out) {
   use(c);
-  encode_many_checks(c, batch, values, n_values, limbs, scale, out);
+  encode_many_checks(c, batch, values, dtype, n_values, limbs, scale, out);
   if (!c->sh->sk.d) throw std::invalid_argument("secret key not present");
   if ((!e && !ekeys) || !seeds) throw std::invalid_argument("error polynomial and seed are required");
   const size_t N = c->N, B = batch;
-  Scratch vals(c, B * n_values), cbuf(c, B * 2 * N), pt(c, B * limbs * N);
+  Scratch vals(c, (dtype_size(dtype) * B * n_values + 7) / 8), cbuf(c, B * 2 * N), pt(c, B * limbs * N);
   try {
-    encode_many(c, batch, values, n_values, limbs, scale, vals.d, reinterpret_cast<double2 *>(cbuf.d), pt.d);
+    encode_many(c, batch, values, dtype, n_values, limbs, scale, vals.d, reinterpret_cast<double2 *>(cbuf.d), pt.d);
     *out = encrypt_symmetric(c, batch, limbs, scale, pt.d, e, ekeys, seeds);
   } catch (...) {
     (void)hipStreamSynchronize(c->stream); // `values` is pageable host memory
     throw;
   }
-  count_client_h2d(c, sizeof(double) * B * n_values + (ekeys ? 32 * B : B * N) + 32 * B);
+  count_client_h2d(c, dtype_size(dtype) * B * n_values + (ekeys ? 32 * B : B * N) + 32 * B);
 }
 
 } // namespace evah
@@ -645,28 +676,43 @@ int evah_encrypt_symmetric(evah_ctx *c, const evah_pt *pt, const int8_t *e, cons
 int evah_encode_encrypt_many(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale,
                              const int8_t *small, evah_ct **out) {
   API_BEGIN
-  encode_encrypt_many(c, batch, values, n_values, limbs, scale, small, nullptr, out);
+  encode_encrypt_many(c, batch, values, EVAH_F64, n_values, limbs, scale, small, nullptr, out);
   API_END
 }
 
 int evah_encode_encrypt_sampled_many(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale,
                                      const uint8_t *rkeys, evah_ct **out) {
   API_BEGIN
-  encode_encrypt_many(c, batch, values, n_values, limbs, scale, nullptr, rkeys, out);
+  encode_encrypt_many(c, batch, values, EVAH_F64, n_values, limbs, scale, nullptr, rkeys, out);
   API_END
 }
 
 int evah_encode_encrypt_symmetric_many(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs, double scale,
                                        const int8_t *e, const uint8_t *seeds, evah_ct **out) {
   API_BEGIN
-  encode_encrypt_symmetric_many(c, batch, values, n_values, limbs, scale, e, nullptr, seeds, out);
+  encode_encrypt_symmetric_many(c, batch, values, EVAH_F64, n_values, limbs, scale, e, nullptr, seeds, out);
   API_END
 }
 
 int evah_encode_encrypt_symmetric_sampled_many(evah_ctx *c, uint32_t batch, const double *values, uint32_t n_values, uint32_t limbs,
                                                double scale, const uint8_t *ekeys, const uint8_t *seeds, evah_ct **out) {
   API_BEGIN
-  encode_encrypt_symmetric_many(c, batch, values, n_values, limbs, scale, nullptr, ekeys, seeds, out);
+  encode_encrypt_symmetric_many(c, batch, values, EVAH_F64, n_values, limbs, scale, nullptr, ekeys, seeds, out);
+  API_END
+}
+
+// the two sampled calls on an array in its own type: the same bodies, the values converted in the scatter
+int evah_encode_encrypt_array(evah_ctx *c, uint32_t batch, const void *values, int dtype, uint32_t n_values, uint32_t limbs, double scale,
+                              const uint8_t *rkeys, evah_ct **out) {
+  API_BEGIN
+  encode_encrypt_many(c, batch, values, dtype, n_values, limbs, scale, nullptr, rkeys, out);
+  API_END
+}
+
+int evah_encode_encrypt_symmetric_array(evah_ctx *c, uint32_t batch, const void *values, int dtype, uint32_t n_values, uint32_t limbs,
+                                        double scale, const uint8_t *ekeys, const uint8_t *seeds, evah_ct **out) {
+  API_BEGIN
+  encode_encrypt_symmetric_many(c, batch, values, dtype, n_values, limbs, scale, nullptr, ekeys, seeds, out);
   API_END
 }
 
@@ -680,7 +726,7 @@ int evah_decrypt_decode(evah_ctx *c, const evah_ct *ct, uint32_t n_out, double *
   if (n_out < 1 || n_out > c->N >> 1) throw std::invalid_argument("slot count out of range");
   if (ct->limbs > 61) throw std::invalid_argument("too many limbs");
   check_scale(c, ct->scale, ct->limbs); // decode_internal: "scale out of bounds"
-  decrypt_decode(c, &ct, 1, n_out, out);
+  decrypt_decode(c, &ct, 1, 1, n_out, EVAH_F64, out);
   API_END
 }
 
@@ -704,7 +750,36 @@ int evah_decrypt_decode_many(evah_ctx *c, const evah_ct *const *cts, uint32_t n,
   if (cts[0]->limbs > 61) throw std::invalid_argument("too many limbs");
   if (c->N % 256) throw std::invalid_argument("decryption needs N divisible by 256");
   check_scale(c, cts[0]->scale, cts[0]->limbs); // decode_internal: "scale out of bounds"
-  decrypt_decode(c, cts, n, n_out, out);
+  decrypt_decode(c, cts, n, n, n_out, EVAH_F64, out);
+  API_END
+}
+
+// evah_decrypt_decode_many over handles that may be batched: the same checks in the same order, the
+// instances counted over the whole list
+int evah_decrypt_decode_handles(evah_ctx *c, const evah_ct *const *cts, uint32_t n_handles, uint32_t n_out, int dtype_out, void *out) {
+  API_BEGIN
+  use(c);
+  if (c->capturing) throw std::logic_error("this call synchronises with the host and cannot be captured into a graph");
+  if (!c->sh->sk.d) throw std::invalid_argument("secret key not present");
+  if (n_handles < 1) throw std::invalid_argument("batch must be 1..64");
+  if (!cts || !out) throw std::invalid_argument("ciphertext list and output are required");
+  uint64_t n = 0;
+  for (uint32_t i = 0; i < n_handles; i++) {
+    const std::string at = "ciphertext " + std::to_string(i);
+    if (!cts[i]) throw std::invalid_argument(at + " is null");
+    if (cts[i]->size != cts[0]->size) throw std::invalid_argument(at + ": size differs from ciphertext 0");
+    if (cts[i]->limbs != cts[0]->limbs) throw std::invalid_argument(at + ": limb count differs from ciphertext 0");
+    if (cts[i]->scale != cts[0]->scale) throw std::invalid_argument(at + ": scale differs from ciphertext 0");
+    n += cts[i]->batch;
+  }
+  if (n > (uint64_t)KS_BATCH_MAX) throw std::invalid_argument("the handles hold more than 64 instances in total");
+  if (dtype_out != EVAH_F64 && dtype_out != EVAH_F32) throw std::invalid_argument("unknown output dtype (EVAH_F64 or EVAH_F32)");
+  if (cts[0]->size < 1 || cts[0]->size > 3) throw std::invalid_argument("ciphertext size out of range");
+  if (n_out < 1 || n_out > c->N >> 1) throw std::invalid_argument("slot count out of range");
+  if (cts[0]->limbs > 61) throw std::invalid_argument("too many limbs");
+  if (c->N % 256) throw std::invalid_argument("decryption needs N divisible by 256");
+  check_scale(c, cts[0]->scale, cts[0]->limbs); // decode_internal: "scale out of bounds"
+  decrypt_decode(c, cts, n_handles, (uint32_t)n, n_out, dtype_out, out);
   API_END
 }
 

@@ -205,6 +205,7 @@ struct SharedDev {
   uint32_t key_rows = 0, key_shard = 0; // evaluation keys: 0 none yet, 1 whole, 2 the prime rows of limb shard `key_shard`
   uint64_t xfer[6] = {0, 0, 0, 0, 0, 0}; // evah_ctx_transfer_stats: ct up / down, pt up / down, bytes up / down
   uint64_t key_up[2] = {0, 0}; // evah_ctx_key_upload_stats: evaluation keys uploaded from the host (calls, bytes sent)
+  uint64_t stacked[2] = {0, 0}; // evah_ctx_stack_stats: evah_ct_stack calls, instances they copied
   ~SharedDev() {
     (void)hipSetDevice(device);
     if (enc_roots) (void)hipFree(enc_roots);
@@ -724,12 +725,14 @@ inline void check_scale(evah_ctx *c, double scale, uint32_t limbs) {
 // bits earlier (bit count with sign < 62), so the product's wrappers never reach this refusal.  SEAL's message for a
 // coefficient beyond the modulus; the total-modulus rule itself is not applied.  Nothing has been launched when this
 // throws.
-inline void check_encodable(const evah_ctx *c, const double *values, uint32_t batch, uint32_t n_values, double scale) {
+// T: the type the values are held in (double; float and uint8_t for the array calls, client.hip) — each read as the double
+// it converts to exactly, so the verdict is the one on the float64 image of the array.
+template <class T> inline void check_encodable(const evah_ctx *c, const T *values, uint32_t batch, uint32_t n_values, double scale) {
   const uint32_t slots = c->N >> 1;
   for (uint32_t b = 0; b < batch; b++) {
     double sum = 0;
     for (uint32_t i = 0; i < n_values; i++) {
-      const double x = values[(size_t)b * n_values + i];
+      const double x = (double)values[(size_t)b * n_values + i];
       if (!std::isfinite(x)) throw std::invalid_argument("encoded values are too large");
       sum += std::fabs(x);
     }

@@ -606,6 +606,8 @@ int evah_ct_stack(evah_ctx *c, const evah_ct *const *cts, uint32_t n, evah_ct **
     evah_ct_free(c, o);
     throw;
   }
+  c->sh->stacked[0]++;
+  c->sh->stacked[1] += n;
   *out = o;
   API_END
 }
@@ -618,6 +620,20 @@ int evah_ct_unstack(evah_ctx *c, const evah_ct *ct, uint32_t b, evah_ct **out) {
   evah_ct *o = new evah_ct(*ct);
   o->d = ct->d + (size_t)b * ct->size * ct->ps;
   o->batch = 1;
+  o->buf->refs++;
+  *out = o;
+  API_END
+}
+
+// instances b0 .. b0 + n - 1 of a batched handle as a batched view of n instances (shares the buffer); the stride of a
+// mod-switched view and the offset of an earlier slice carry over, so a slice of a slice is a slice
+int evah_ct_slice(evah_ctx *c, const evah_ct *ct, uint32_t b0, uint32_t n, evah_ct **out) {
+  API_BEGIN
+  (void)c;
+  if (n < 1 || b0 > ct->batch || n > ct->batch - b0) throw std::invalid_argument("instance range out of range");
+  evah_ct *o = new evah_ct(*ct);
+  o->d = ct->d + (size_t)b0 * ct->size * ct->ps;
+  o->batch = n;
   o->buf->refs++;
   *out = o;
   API_END
@@ -717,6 +733,15 @@ int evah_ctx_key_upload_stats(evah_ctx *c, uint64_t out[2]) {
   API_BEGIN
   out[0] = c->sh->key_up[0];
   out[1] = c->sh->key_up[1];
+  API_END
+}
+
+// evah_ct_stack calls made on this device state and the instances they copied: a consumer that takes batched handles as
+// they are (evah_ct_slice) leaves both where they were
+int evah_ctx_stack_stats(evah_ctx *c, uint64_t out[2]) {
+  API_BEGIN
+  out[0] = c->sh->stacked[0];
+  out[1] = c->sh->stacked[1];
   API_END
 }
 

@@ -6,27 +6,25 @@
 
 namespace evahost {
 
-inline std::vector<HipValuation> HipPublic::execute_batch(Program &program, const std::vector<const HipValuation *> &inputs) {
-  ensure_device();
-  if (batch_chunk < 1 || batch_chunk > 64) throw std::runtime_error("batch_chunk must be 1..64");
-  std::vector<HipValuation> all(inputs.size());
+// client.h
+HipValuation batch_instance(const HipValuationBatch &vb, size_t b);
+HipValuationBatch batch_of_list(const std::vector<const HipValuation *> &list, const std::shared_ptr<DeviceCtx> &dev,
+                                const std::shared_ptr<HostContext> &host);
+
+// The pipeline both execute_batch calls share, over n_instances instances: set_in(ex, i0, n) hands the executor of a
+// group its inputs, get_out(ex, i0, n, queue) takes its outputs (queue: the fork the group ran on, null for the root).
+// in_hbm: the call's ciphertexts live in HBM already (the auto depth); cuts: instance indices no group may span.
+template <class SetIn, class GetOut>
+inline void HipPublic::run_batch_groups(Program &program, size_t n_instances, bool in_hbm, const std::vector<size_t> &cuts, SetIn set_in,
+                                        GetOut get_out) {
   // Groups rotate over batch_depth issue queues (r6 default: three on resident valuations — +9 % over four and +11 % over two on
   // config 4 — four when the call moves host words over PCIe) and nothing waits in between: each group's uploads,
   // launches and downloads are enqueued in queue order (evah_ct_*_instances_async), so the copies
   // of one group overlap the kernels of the other and the host never idles the device.  Device
   // memory stays at two groups' working sets (the pools recycle in queue order); the inputs belong
   // to the caller and the outputs are allocated up front, so both outlive the final synchronisation.
-  if (devices.size() > 1 && shard_mode == "dag") return execute_batch_multi(program, inputs);
   uint32_t depth = batch_depth;
-  if (depth == 0) { // auto: do the call's ciphertexts live in HBM already?
-    bool in_hbm = resident && !inputs.empty();
-    if (in_hbm) {
-      in_hbm = false;
-      for (auto &kv : inputs[0]->values)
-        if (auto *c0 = std::get_if<HostCipher>(&kv.second)) { in_hbm = (bool)c0->dev; break; }
-    }
-    depth = in_hbm ? 3 : 4;
-  }
+  if (depth == 0) depth = in_hbm ? 3 : 4; // auto: do the call's ciphertexts live in HBM already?
   if (depth < 2 || depth > 8) throw std::runtime_error("batch_depth must be 2..8 (0: chosen by the call's valuations)");
   while (batch_forks.size() + 1 < depth) batch_forks.push_back(std::make_shared<Fork>(dev));
   std::vector<evah_ctx *> qs{dev->h};
@@ -56,7 +54,7 @@ inline std::vector<HipValuation> HipPublic::execute_batch(Program &program, cons
   // (8, 24, 32, ..., 32, 24, 8 for 256 instances), so the pipeline fills and drains on a quarter of a group's copies.
   std::vector<size_t> sizes;
   {
-    const size_t n = inputs.size(), c = batch_chunk, q = c / 4;
+    const size_t n = n_instances, c = batch_chunk, q = c / 4;
     if (batch_ramp && q >= 1 && n >= 4 * c) {
       sizes = {q, c - q};
       for (size_t left = n - 2 * c; left > 0; left -= std::min(left, c)) sizes.push_back(std::min(left, c));
@@ -70,12 +68,26 @@ inline std::vector<HipValuation> HipPublic::execute_batch(Program &program, cons
     } else {
       for (size_t left = n; left > 0; left -= std::min(left, c)) sizes.push_back(std::min(left, c));
     }
+    if (!cuts.empty()) { // no group spans a cut: the group it falls into becomes two
+      std::vector<size_t> split;
+      size_t i0 = 0;
+      for (size_t sz : sizes) {
+        for (size_t cut : cuts)
+          if (cut > i0 && cut < i0 + sz) {
+            split.push_back(cut - i0);
+            sz -= cut - i0;
+            i0 = cut;
+          }
+        split.push_back(sz);
+        i0 += sz;
+      }
+      sizes = std::move(split);
+    }
   }
   const auto t_begin = std::chrono::steady_clock::now();
   try {
     for (size_t i0 = 0; g < sizes.size(); i0 += sizes[g], g++) {
       const size_t n = sizes[g];
-      std::vector<const HipValuation *> chunk(inputs.begin() + i0, inputs.begin() + i0 + n);
       if (bounded && g >= Q) chk(evah_ctx_sync(qs[g % Q])); // group g-Q (same queue) has left the device
       HipExecutor ex(program, *host, std::vector<evah_ctx *>{qs[g % Q]}, dev.get());
       if (fresh) {
@@ -89,18 +101,10 @@ inline std::vector<HipValuation> HipPublic::execute_batch(Program &program, cons
         for (TermId t = 0; t < program.size(); t++)
           if (done[t]) ex.set_value(t, consts[t]);
       }
-      ex.set_inputs_batch(chunk, true);
+      set_in(ex, i0, n);
       if (library_scheduler) ex.run_library(&done, true);
       else run_counted(program, ex, &done);
-      // r6: resident valuations (`resident`, the default) — inputs that encrypt() / execute() left in HBM were stacked device
-      // to device, and the outputs leave as handles (views of the group's batched output): no ciphertext crosses PCIe in
-      // the call.  Host valuations (resident = false, or inputs that hold host words only): uploads and downloads as before.
-      if (resident && ex.batch_inputs_resident) {
-        const DeviceResident res{dev, g % Q ? batch_forks[g % Q - 1] : nullptr, nullptr, host->N};
-        ex.get_outputs_batch(all.data() + i0, n, true, &res);
-      } else {
-        ex.get_outputs_batch(all.data() + i0, n, true);
-      }
+      get_out(ex, i0, n, g % Q ? batch_forks[g % Q - 1] : nullptr);
     }
   } catch (...) {
     for (evah_ctx *q : qs) (void)evah_ctx_sync(q); // copies in flight still target `all` and the caller's inputs
@@ -112,7 +116,69 @@ inline std::vector<HipValuation> HipPublic::execute_batch(Program &program, cons
     std::fprintf(stderr, "EVA: execute_batch issued %zu groups in %.3f ms, done after %.3f ms\n", g,
                  std::chrono::duration<double, std::milli>(t_issued - t_begin).count(),
                  std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
+}
+
+inline std::vector<HipValuation> HipPublic::execute_batch(Program &program, const std::vector<const HipValuation *> &inputs) {
+  ensure_device();
+  if (batch_chunk < 1 || batch_chunk > 64) throw std::runtime_error("batch_chunk must be 1..64");
+  std::vector<HipValuation> all(inputs.size());
+  if (devices.size() > 1 && shard_mode == "dag") return execute_batch_multi(program, inputs);
+  bool in_hbm = resident && !inputs.empty();
+  if (in_hbm) {
+    in_hbm = false;
+    for (auto &kv : inputs[0]->values)
+      if (auto *c0 = std::get_if<HostCipher>(&kv.second)) { in_hbm = (bool)c0->dev; break; }
+  }
+  run_batch_groups(
+      program, inputs.size(), in_hbm, {},
+      [&](HipExecutor &ex, size_t i0, size_t n) {
+        std::vector<const HipValuation *> chunk(inputs.begin() + i0, inputs.begin() + i0 + n);
+        ex.set_inputs_batch(chunk, true);
+      },
+      [&](HipExecutor &ex, size_t i0, size_t n, const std::shared_ptr<Fork> &queue) {
+        // r6: resident valuations (`resident`, the default) — inputs that encrypt() / execute() left in HBM were stacked device
+        // to device, and the outputs leave as handles (views of the group's batched output): no ciphertext crosses PCIe in
+        // the call.  Host valuations (resident = false, or inputs that hold host words only): uploads and downloads as before.
+        if (resident && ex.batch_inputs_resident) {
+          const DeviceResident res{dev, queue, nullptr, host->N};
+          ex.get_outputs_batch(all.data() + i0, n, true, &res);
+        } else {
+          ex.get_outputs_batch(all.data() + i0, n, true);
+        }
+      });
   return all;
+}
+
+inline HipValuationBatch HipPublic::execute_batch(Program &program, const HipValuationBatch &inputs) {
+  ensure_device();
+  if (batch_chunk < 1 || batch_chunk > 64) throw std::runtime_error("batch_chunk must be 1..64");
+  if (devices.size() > 1 || !shard_mode.empty()) { // the multi-device modes: through the list path
+    std::vector<HipValuation> list(inputs.B);
+    std::vector<const HipValuation *> ptrs(inputs.B);
+    for (size_t b = 0; b < inputs.B; b++) {
+      list[b] = batch_instance(inputs, b);
+      ptrs[b] = &list[b];
+    }
+    const std::vector<HipValuation> outs = execute_batch(program, ptrs);
+    for (size_t b = 0; b < inputs.B; b++) ptrs[b] = &outs[b];
+    return batch_of_list(ptrs, dev, host);
+  }
+  if (inputs.root != dev) throw std::runtime_error("execute_batch: the batch lives on the device state of another key pair");
+  HipValuationBatch out;
+  out.B = inputs.B;
+  out.root = dev;
+  out.params = host;
+  std::vector<size_t> cuts; // where an input segment ends
+  for (auto &kv : inputs.ciphers) {
+    size_t end = 0;
+    for (const BatchSegment &s : kv.second.segments) cuts.push_back(end += s.n);
+    if (end != inputs.B) throw std::runtime_error("execute_batch: the segments of input " + kv.first + " do not hold every instance");
+  }
+  std::sort(cuts.begin(), cuts.end());
+  run_batch_groups(
+      program, inputs.B, resident, cuts, [&](HipExecutor &ex, size_t i0, size_t n) { ex.set_inputs_slices(inputs, i0, n); },
+      [&](HipExecutor &ex, size_t, size_t n, const std::shared_ptr<Fork> &queue) { ex.get_outputs_segments(out, n, queue); });
+  return out;
 }
 
 // "dag" mode (BASELINE config 4): the groups of a batch are dealt over the members

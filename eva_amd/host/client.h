@@ -86,18 +86,24 @@ inline bool device_client_enabled() {
 
 // the bound of HipExecutor::device_encodable — every rounded coefficient below 2^62 and inside the modulus — behind
 // EVA_DEVICE_ENCODE, which the executor reads once when it is made and the client at every call
-inline bool device_encodable(const HostContext &hc, const std::vector<double> &in, double scale, uint32_t limbs) {
+// T: the type the n values are held in (double; float and uint8_t rows of encrypt_array), each read as the double it
+// converts to exactly
+template <class T> inline bool device_encodable(const HostContext &hc, const T *in, size_t n, double scale, uint32_t limbs) {
   const size_t slots = hc.N / 2;
   if (std::getenv("EVA_DEVICE_ENCODE") && !std::atoi(std::getenv("EVA_DEVICE_ENCODE"))) return false;
-  if (in.empty() || in.size() > slots || slots % in.size()) return false;
+  if (n == 0 || n > slots || slots % n) return false;
   double sum = 0;
-  for (double x : in) {
+  for (size_t i = 0; i < n; i++) {
+    const double x = (double)in[i];
     if (!std::isfinite(x)) return false;
     sum += std::fabs(x);
   }
-  const double bound = 2.0 * sum * (double)(slots / in.size()) * scale / (double)hc.N;
+  const double bound = 2.0 * sum * (double)(slots / n) * scale / (double)hc.N;
   const int bits = (int)std::ceil(std::log2(std::max(bound, 1.0))) + 1;
   return bits < 62 && bits < hc.total_bits[limbs];
+}
+inline bool device_encodable(const HostContext &hc, const std::vector<double> &in, double scale, uint32_t limbs) {
+  return device_encodable(hc, in.data(), in.size(), scale, limbs);
 }
 
 // A device handle as a value: resident (it stays in HBM, host words on demand) or downloaded.  seed: the value is
@@ -163,6 +169,142 @@ struct WipeOnExit {
   std::vector<int8_t> &s;
   ~WipeOnExit() { wipe(s); }
 };
+
+// ---- the array calls
+// What encrypt_array makes of its arguments before anything is drawn: the sorted names of the call with their classes
+// (arr[i] set for an encrypted input), B, every check, and the shared values encoded into `out`.  The array path has no
+// host twin: a row the device encoder cannot take is an error.
+struct ArrayInputs {
+  std::vector<std::string> names;
+  std::vector<InputClass> cls;
+  std::vector<const ArrayView *> arr;
+};
+inline ArrayInputs plan_array_inputs(const HostContext &hc, const std::map<std::string, ArrayView> &arrays, const Valuation &shared,
+                                     const CKKSSignature &sig, HipValuationBatch &out) {
+  check_vec_size(sig, hc.N / 2);
+  if (arrays.empty()) throw std::invalid_argument("encrypt_array: no encrypted input array was given");
+  ArrayInputs in;
+  for (auto &kv : arrays) in.names.push_back(kv.first);
+  for (auto &kv : shared) {
+    if (arrays.count(kv.first)) throw std::invalid_argument("encrypt_array: input " + kv.first + " is given twice");
+    in.names.push_back(kv.first);
+  }
+  std::sort(in.names.begin(), in.names.end());
+  out.B = arrays.begin()->second.B;
+  if (out.B < 1) throw std::invalid_argument("encrypt_array: input " + arrays.begin()->first + " has no instances");
+  for (const std::string &name : in.names) {
+    const InputClass c = classify_input(hc, sig, name);
+    auto it = arrays.find(name);
+    if (it == arrays.end()) {
+      if (c.kind == Type::Cipher) throw std::invalid_argument("encrypt_array: encrypted input " + name + " needs an array [B, n], one row per instance");
+      const auto &v = shared.at(name);
+      check_input_size(v, sig);
+      unencrypted_value(hc, c, v, out.shared[name]);
+    } else {
+      const ArrayView &a = it->second;
+      if (c.kind != Type::Cipher) throw std::invalid_argument("encrypt_array: input " + name + " is not encrypted: it is one value shared by all instances");
+      if (a.n != (size_t)sig.vec_size) throw std::runtime_error("Input size does not match program vector size (input " + name + ")");
+      if (a.B != out.B)
+        throw std::invalid_argument("encrypt_array: input " + name + " has " + std::to_string(a.B) + " instances, " + arrays.begin()->first + " has " +
+                                    std::to_string(out.B));
+      for (size_t b = 0; b < a.B; b++) {
+        const bool ok = a.dtype == EVAH_F64   ? device_encodable(hc, static_cast<const double *>(a.row(b)), a.n, c.scale, c.limbs)
+                        : a.dtype == EVAH_F32 ? device_encodable(hc, static_cast<const float *>(a.row(b)), a.n, c.scale, c.limbs)
+                                              : device_encodable(hc, static_cast<const uint8_t *>(a.row(b)), a.n, c.scale, c.limbs);
+        if (!ok)
+          throw std::runtime_error("encrypt_array: input " + name + ", instance " + std::to_string(b) +
+                                   ": the device encoder cannot take these values (non-finite, too large for the scale, or EVA_DEVICE_ENCODE=0); "
+                                   "encrypt_batch has a host path for them");
+      }
+    }
+    in.cls.push_back(c);
+    in.arr.push_back(it == arrays.end() ? nullptr : &it->second);
+  }
+  return in;
+}
+inline void require_array_path(bool on_device, bool resident) {
+  if (!on_device) throw std::runtime_error("encrypt_array needs a HIP device: none is visible, or EVA_DEVICE_CLIENT=0 keeps the client on the host");
+  if (!resident) throw std::runtime_error("encrypt_array needs resident valuations: resident = False (EVA_RESIDENT=0) keeps them on the host");
+}
+inline std::vector<uint8_t> keys_flat(const std::array<uint8_t, 32> *keys, size_t n) {
+  std::vector<uint8_t> flat(n * 32);
+  for (size_t b = 0; b < n; b++) std::copy(keys[b].begin(), keys[b].end(), flat.begin() + b * 32);
+  return flat;
+}
+// instance b of a batch as an ordinary valuation: every ciphertext a view of its segment (evah_ct_unstack), a symmetric
+// one with its seed, so that save() still writes it compressed — the bridge to decrypt, save and execute
+inline HipValuation batch_instance(const HipValuationBatch &vb, size_t b) {
+  if (b >= vb.B) throw std::out_of_range("instance index out of range");
+  HipValuation out;
+  out.params = vb.params;
+  out.values = vb.shared;
+  for (auto &kv : vb.ciphers) {
+    size_t first = 0;
+    for (const BatchSegment &s : kv.second.segments) {
+      if (b >= first + s.n) { first += s.n; continue; }
+      evah_ctx *ctx = s.queue ? s.queue->h : vb.root->h;
+      evah_ct *view = nullptr;
+      chk(evah_ct_unstack(ctx, s.h->h, (uint32_t)(b - first), &view));
+      HostCipher c;
+      c.size = s.size;
+      c.limbs = s.limbs;
+      c.scale = s.scale;
+      c.dev = std::make_shared<DeviceResident>(DeviceResident{vb.root, s.queue, std::make_shared<CtHandle>(ctx, view), vb.params->N});
+      if (!kv.second.seeds.empty()) {
+        auto sf = std::make_shared<SeededForm>();
+        sf->seed = kv.second.seeds[b];
+        sf->N = vb.params->N;
+        sf->primes.assign(vb.params->primes.begin(), vb.params->primes.begin() + s.limbs);
+        c.seeded = std::move(sf);
+        c.words_checked = true;
+      }
+      out.values[kv.first] = std::move(c);
+      break;
+    }
+  }
+  return out;
+}
+// a list of valuations as a batch on `dev`: a ciphertext resident there is a segment of one that shares its handle, any
+// other is uploaded first (as decrypt() does); plaintexts and raw vectors are taken from instance 0
+inline HipValuationBatch batch_of_list(const std::vector<const HipValuation *> &list, const std::shared_ptr<DeviceCtx> &dev,
+                                       const std::shared_ptr<HostContext> &host) {
+  const HostContext &hc = *host;
+  HipValuationBatch vb;
+  vb.B = list.size();
+  vb.root = dev;
+  vb.params = host;
+  for (size_t b = 0; b < list.size(); b++) {
+    if (!list[b]) throw std::invalid_argument("valuation " + std::to_string(b) + " is None");
+    for (auto &kv : list[b]->values) {
+      auto *c = std::get_if<HostCipher>(&kv.second);
+      if (!c) {
+        if (b == 0) vb.shared[kv.first] = kv.second;
+        continue;
+      }
+      BatchCipher &bc = vb.ciphers[kv.first];
+      if (bc.segments.size() != b) throw std::runtime_error("value " + kv.first + " is not a ciphertext in every valuation of the list");
+      BatchSegment s;
+      s.n = 1;
+      s.size = c->size;
+      s.limbs = c->limbs;
+      s.scale = c->scale;
+      if (c->dev && c->dev->root == dev) {
+        s.h = c->dev->h;
+        s.queue = c->dev->queue;
+      } else {
+        if (c->size < 1 || c->size > 3 || c->limbs < 1 || c->limbs > hc.k - 1 || words(*c).size() != (size_t)c->size * c->limbs * hc.N)
+          throw std::runtime_error("value " + kv.first + ": ciphertext shape does not match its data or the encryption parameters");
+        evah_ct *h = nullptr;
+        chk(evah_ct_upload(dev->h, c->size, c->limbs, c->scale, (const uint64_t *)words(*c).data(), &h));
+        s.h = std::make_shared<CtHandle>(dev->h, h);
+      }
+      bc.segments.push_back(std::move(s));
+    }
+  }
+  for (auto &kv : vb.ciphers)
+    if (kv.second.segments.size() != vb.B) throw std::runtime_error("value " + kv.first + " is not a ciphertext in every valuation of the list");
+  return vb;
+}
 // u, e0, e1 of one public-key encryption from rng, in evahost::encrypt's order, as int8 [3][N] at small
 inline void draw_small3(const HostContext &hc, SecureRng &rng, int8_t *small) {
   std::vector<int8_t> u, e0, e1;
@@ -344,6 +486,45 @@ inline std::vector<HostCipher> HipPublic::encrypt_group_sampled(const std::vecto
   return group_results(dev, *host, c, B, limbs, scale, resident);
 }
 
+// encrypt_batch(..., device_sampling = true, seed) for arrays [B][n] in the caller's own type: the same
+// draws in the same order — instances in order, names sorted within an instance, one 32-byte randomness key per
+// encrypted input — so instance b is encrypt_batch's instance b word for word.  Per name the rows leave in segments of
+// <= 64 as ONE evah_encode_encrypt_array each, in the array's type, and the batched handles are kept whole.  Device and
+// resident valuations only: there is no host path behind this call.
+inline HipValuationBatch HipPublic::encrypt_array(const std::map<std::string, ArrayView> &arrays, const Valuation &shared, const CKKSSignature &sig,
+                                                  uint64_t seed) {
+  require_array_path(client_on_device(), resident);
+  HipValuationBatch out;
+  out.params = host;
+  const ArrayInputs in = plan_array_inputs(*host, arrays, shared, sig, out);
+  ensure_public_key();
+  out.root = dev;
+  std::unique_ptr<SecureRng> stream = seed ? std::make_unique<SecureRng>(seed, 5) : std::make_unique<SecureRng>();
+  std::vector<std::vector<std::array<uint8_t, 32>>> rkeys(in.names.size()); // per name, per instance
+  struct WipeKeys {
+    std::vector<std::vector<std::array<uint8_t, 32>>> &k;
+    ~WipeKeys() { for (auto &n : k) for (auto &x : n) wipe_bytes(x.data(), 32); }
+  } wipe_keys{rkeys};
+  for (size_t b = 0; b < out.B; b++)
+    for (size_t i = 0; i < in.names.size(); i++)
+      if (in.arr[i]) rkeys[i].push_back(draw_key32(*stream));
+  for (size_t i = 0; i < in.names.size(); i++) {
+    if (!in.arr[i]) continue;
+    const ArrayView &a = *in.arr[i];
+    BatchCipher &bc = out.ciphers[in.names[i]];
+    for (size_t b0 = 0; b0 < out.B; b0 += CLIENT_BATCH_MAX) {
+      const size_t n = std::min<size_t>(CLIENT_BATCH_MAX, out.B - b0);
+      std::vector<uint8_t> keys = keys_flat(rkeys[i].data() + b0, n);
+      evah_ct *c = nullptr;
+      const int rc = evah_encode_encrypt_array(dev->h, (uint32_t)n, a.row(b0), a.dtype, (uint32_t)a.n, in.cls[i].limbs, in.cls[i].scale, keys.data(), &c);
+      wipe_bytes(keys.data(), keys.size());
+      chk(rc);
+      bc.segments.push_back(BatchSegment{std::make_shared<CtHandle>(dev->h, c), (uint32_t)n, nullptr, 2, in.cls[i].limbs, in.cls[i].scale});
+    }
+  }
+  return out;
+}
+
 class HipSecret {
 public:
   std::shared_ptr<HostContext> host;
@@ -517,6 +698,78 @@ public:
     wipe_bytes(ekeys.data(), ekeys.size());
     chk(rc);
     return group_results(dev, *host, c, B, limbs, scale, resident, sd);
+  }
+  // encrypt_batch(..., seed, device_sampling = true) for arrays [B][n] in their own type: the same two
+  // streams and the same draws — per instance, names sorted, 4 seed words and a 4-word error key per encrypted input —
+  // so instance b is encrypt_batch's word for word.  Per name the rows leave in segments of <= 64 as ONE
+  // evah_encode_encrypt_symmetric_array each; the handles are kept whole and the seeds stay with the batch.
+  HipValuationBatch encrypt_array(const std::map<std::string, ArrayView> &arrays, const Valuation &shared, const CKKSSignature &sig,
+                                  uint64_t seed = 0) {
+    require_array_path(on_device(), resident);
+    HipValuationBatch out;
+    out.params = host;
+    out.root = dev;
+    const ArrayInputs in = plan_array_inputs(*host, arrays, shared, sig, out);
+    std::unique_ptr<SecureRng> seeds = seed ? std::make_unique<SecureRng>(seed, 4) : std::make_unique<SecureRng>();
+    std::unique_ptr<SecureRng> errors = seed ? std::make_unique<SecureRng>(seed, 3) : std::make_unique<SecureRng>();
+    std::vector<std::vector<std::array<uint8_t, 32>>> ek(in.names.size()); // per name, per instance
+    struct WipeKeys {
+      std::vector<std::vector<std::array<uint8_t, 32>>> &k;
+      ~WipeKeys() { for (auto &n : k) for (auto &x : n) wipe_bytes(x.data(), 32); }
+    } wipe_keys{ek};
+    for (size_t b = 0; b < out.B; b++)
+      for (size_t i = 0; i < in.names.size(); i++)
+        if (in.arr[i]) {
+          out.ciphers[in.names[i]].seeds.push_back(draw_key32(*seeds));
+          ek[i].push_back(draw_key32(*errors));
+        }
+    for (size_t i = 0; i < in.names.size(); i++) {
+      if (!in.arr[i]) continue;
+      const ArrayView &a = *in.arr[i];
+      BatchCipher &bc = out.ciphers[in.names[i]];
+      for (size_t b0 = 0; b0 < out.B; b0 += CLIENT_BATCH_MAX) {
+        const size_t n = std::min<size_t>(CLIENT_BATCH_MAX, out.B - b0);
+        std::vector<uint8_t> ekeys = keys_flat(ek[i].data() + b0, n);
+        const std::vector<uint8_t> sd = keys_flat(bc.seeds.data() + b0, n);
+        evah_ct *c = nullptr;
+        const int rc = evah_encode_encrypt_symmetric_array(dev->h, (uint32_t)n, a.row(b0), a.dtype, (uint32_t)a.n, in.cls[i].limbs, in.cls[i].scale,
+                                                           ekeys.data(), sd.data(), &c);
+        wipe_bytes(ekeys.data(), ekeys.size());
+        chk(rc);
+        bc.segments.push_back(BatchSegment{std::make_shared<CtHandle>(dev->h, c), (uint32_t)n, nullptr, 2, in.cls[i].limbs, in.cls[i].scale});
+      }
+    }
+    return out;
+  }
+  // decrypt_batch for a batch of batched handles: per name, consecutive segments of one size, limb count
+  // and scale are packed into calls of <= 64 instances of evah_decrypt_decode_handles, each writing straight into the rows
+  // rows[name] + first instance * vec_size * itemsize of the caller's array [B][vec_size] (dtype_out: EVAH_F64, the doubles
+  // of decrypt_batch bit for bit, or EVAH_F32).  Needs the device; the batch lives on this key pair's device state.
+  void decrypt_array(const HipValuationBatch &vb, const CKKSSignature &sig, int dtype_out, const std::map<std::string, void *> &rows) {
+    if (!on_device()) throw std::runtime_error("decrypt_array needs a HIP device: none is visible, or EVA_DEVICE_CLIENT=0 keeps the client on the host");
+    if (sig.vec_size <= 0) throw std::runtime_error("Signature vector size must be positive");
+    if (vb.root != dev) throw std::runtime_error("decrypt_array: the batch lives on the device state of another key pair");
+    const uint32_t n_out = (uint32_t)sig.vec_size;
+    const size_t row_bytes = (size_t)n_out * (dtype_out == EVAH_F32 ? 4 : 8);
+    for (auto &kv : vb.ciphers) {
+      char *out = static_cast<char *>(rows.at(kv.first));
+      const auto &segs = kv.second.segments;
+      size_t row = 0;
+      for (size_t s0 = 0; s0 < segs.size();) {
+        std::vector<const evah_ct *> hs;
+        size_t n = 0, s1 = s0;
+        while (s1 < segs.size() && n + segs[s1].n <= CLIENT_BATCH_MAX && segs[s1].size == segs[s0].size && segs[s1].limbs == segs[s0].limbs &&
+               segs[s1].scale == segs[s0].scale) {
+          hs.push_back(segs[s1].h->h);
+          n += segs[s1++].n;
+        }
+        if (s1 == s0) throw std::runtime_error("output " + kv.first + ": a segment holds more than 64 instances");
+        chk(evah_decrypt_decode_handles(dev->h, hs.data(), (uint32_t)hs.size(), n_out, dtype_out, out + row * row_bytes));
+        row += n;
+        s0 = s1;
+      }
+      if (row != vb.B) throw std::runtime_error("output " + kv.first + ": the segments do not hold every instance");
+    }
   }
   // the shape check of a ciphertext that is decrypted on the device
   void check_device_shape(const std::string &name, const HostCipher &c) const {

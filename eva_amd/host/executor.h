@@ -257,6 +257,71 @@ public:
     }
   }
 
+  // set_inputs_batch for instances i0 .. i0 + n - 1 of a batch of batched handles: every encrypted input
+  // is a slice of the segment that holds the group (evah_ct_slice: a view, nothing is copied; ordering per buffer is the
+  // library's); the shared plaintexts and raw vectors as set_inputs_batch takes them
+  void set_inputs_slices(const HipValuationBatch &vb, size_t i0, size_t n) {
+    for (auto &kv : vb.ciphers) {
+      const TermId t = program.input(kv.first);
+      size_t first = 0;
+      const BatchSegment *seg = nullptr;
+      for (const BatchSegment &s : kv.second.segments) {
+        if (i0 < first + s.n) { seg = &s; break; }
+        first += s.n;
+      }
+      if (!seg || i0 + n > first + seg->n) throw std::runtime_error("execute_batch: a group of input " + kv.first + " spans two segments");
+      if (seg->size < 1 || seg->size > 3 || seg->limbs < 1 || seg->limbs > host.k - 1)
+        throw std::runtime_error("input " + kv.first + ": ciphertext shape does not match the encryption parameters");
+      evah_ct *h = nullptr;
+      chk(evah_ct_slice(ctx, seg->h->h, (uint32_t)(i0 - first), (uint32_t)n, &h));
+      objects[t] = std::make_shared<CtHandle>(ctx, h);
+    }
+    batch_inputs_resident = true;
+    for (auto &kv : vb.shared) {
+      const TermId t = program.input(kv.first);
+      if (auto *p = std::get_if<HostPlain>(&kv.second)) {
+        check_shape(kv.first, *p);
+        evah_pt *h = nullptr;
+        chk(evah_pt_upload(ctx, p->limbs, p->scale, (const uint64_t *)p->data.data(), &h));
+        objects[t] = std::make_shared<PtHandle>(ctx, h);
+      } else if (auto *raw = std::get_if<std::vector<double>>(&kv.second)) {
+        std::vector<double> v;
+        ConstantValue{*raw}.expand_to(v, program.vec_size());
+        objects[t] = std::move(v);
+      } else {
+        throw std::runtime_error("execute_batch: shared input " + kv.first + " is a ciphertext");
+      }
+    }
+  }
+  // get_outputs_batch for a batch of batched handles: the group's batched output handle is one more segment of `out`, as it
+  // is (no evah_ct_unstack, no per-instance values); queue: the fork the group ran on (null: the root's own queue)
+  void get_outputs_segments(HipValuationBatch &out, size_t n_outs, const std::shared_ptr<Fork> &queue) {
+    for (auto &kv : program.outputs()) {
+      auto &o = objects[kv.second];
+      if (auto *c = std::get_if<std::shared_ptr<CtHandle>>(&o)) {
+        BatchSegment s;
+        s.h = *c;
+        s.queue = queue;
+        chk(evah_ct_info((*c)->h, &s.size, &s.limbs, &s.scale));
+        chk(evah_ct_batch((*c)->h, &s.n));
+        if (s.n != n_outs) throw std::runtime_error("Output " + kv.first + " does not depend on an encrypted input of the batch");
+        out.ciphers[kv.first].segments.push_back(std::move(s));
+      } else if (!out.shared.count(kv.first)) {
+        if (auto *p = std::get_if<std::shared_ptr<PtHandle>>(&o)) {
+          HostPlain hp;
+          chk(evah_pt_info((*p)->h, &hp.limbs, &hp.scale));
+          hp.data.resize((size_t)hp.limbs * host.N);
+          chk(evah_pt_download(ctx, (*p)->h, (uint64_t *)hp.data.data()));
+          out.shared[kv.first] = std::move(hp);
+        } else if (auto *r = std::get_if<std::vector<double>>(&o)) {
+          out.shared[kv.first] = *r;
+        } else {
+          throw std::runtime_error("Output " + kv.first + " was not computed");
+        }
+      }
+    }
+  }
+
   void operator()(TermId t) {
     const Term &x = program.at(t);
     if (verbosity() >= 2) {

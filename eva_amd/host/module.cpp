@@ -35,6 +35,27 @@ template <class Vec> py::array_t<uint64_t> to_numpy(const Vec &v, std::vector<py
 
 static int g_num_threads = 1;
 
+// the arrays of encrypt_array as the library takes them: C-contiguous [B][n] of float64, float32 or uint8 — what
+// eva_amd.seal.normalise_arrays hands over (it converts everything else), so anything else here is an error
+std::map<std::string, ArrayView> array_views(const std::map<std::string, py::array> &arrays) {
+  std::map<std::string, ArrayView> out;
+  for (auto &kv : arrays) {
+    const py::array &a = kv.second;
+    const char kind = a.dtype().kind();
+    ArrayView v;
+    if (kind == 'f' && a.itemsize() == 8) v.dtype = EVAH_F64;
+    else if (kind == 'f' && a.itemsize() == 4) v.dtype = EVAH_F32;
+    else if (kind == 'u' && a.itemsize() == 1) v.dtype = EVAH_U8;
+    else throw std::invalid_argument("input " + kv.first + ": the array must be float64, float32 or uint8");
+    if (a.ndim() != 2 || !(a.flags() & py::array::c_style)) throw std::invalid_argument("input " + kv.first + ": the array must be C-contiguous [B, n]");
+    v.data = a.data();
+    v.B = (size_t)a.shape(0);
+    v.n = (size_t)a.shape(1);
+    out.emplace(kv.first, v);
+  }
+  return out;
+}
+
 } // namespace
 
 PYBIND11_MODULE(_eva, m) {
@@ -338,7 +359,49 @@ PYBIND11_MODULE(_eva, m) {
         }
         return py::make_tuple("raw", 0, 0, 1.0, py::cast(std::get<std::vector<double>>(it->second)));
       });
+  py::class_<HipValuationBatch>(mseal, "SEALValuationBatch",
+                                "B valuations of one shape as batched device handles (DESIGN.md 1.9): what encrypt_array returns, "
+                                "execute_batch takes and returns, and decrypt_array reads")
+      .def("__len__", [](const HipValuationBatch &v) { return v.B; })
+      .def("names", [](const HipValuationBatch &v) {
+        std::vector<std::string> n;
+        for (auto &kv : v.ciphers) n.push_back(kv.first);
+        for (auto &kv : v.shared) n.push_back(kv.first);
+        return n;
+      })
+      .def("segments", [](const HipValuationBatch &v, const std::string &name) {
+        auto it = v.ciphers.find(name);
+        if (it == v.ciphers.end()) throw std::out_of_range("No encrypted value named " + name);
+        std::vector<uint32_t> n;
+        for (auto &s : it->second.segments) n.push_back(s.n);
+        return n;
+      }, py::arg("name"), "instances per batched handle of an encrypted value, in instance order")
+      .def("__getitem__", [](const HipValuationBatch &v, py::ssize_t b) {
+        if (b < 0) b += (py::ssize_t)v.B;
+        if (b < 0 || (size_t)b >= v.B) throw py::index_error("instance index out of range");
+        return batch_instance(v, (size_t)b);
+      }, "instance b as a SEALValuation whose ciphertexts are views of the batched handles")
+      .def("to_list", [](const HipValuationBatch &v) {
+        std::vector<HipValuation> out;
+        for (size_t b = 0; b < v.B; b++) out.push_back(batch_instance(v, b));
+        return out;
+      }, "every instance as a SEALValuation (views; a symmetric value keeps its seed, so save() still writes it compressed)");
   py::class_<HipPublic, std::shared_ptr<HipPublic>>(mseal, "SEALPublic", "Public context: encryption and execution on the MI355X")
+      .def("_encrypt_array", [](HipPublic &p, const std::map<std::string, py::array> &arrays, const Valuation &shared, const CKKSSignature &sig,
+                                uint64_t seed) { return p.encrypt_array(array_views(arrays), shared, sig, seed); },
+           py::arg("arrays"), py::arg("shared"), py::arg("signature"), py::arg("seed") = 0,
+           "encrypt_array on normalised arguments (eva_amd.seal.normalise_arrays): C-contiguous [B, n] arrays of float64, float32 or uint8")
+      .def("execute_batch", [](HipPublic &p, Program &program, const HipValuationBatch &inputs) { return p.execute_batch(program, inputs); },
+           py::arg("program"), py::arg("inputs"),
+           "execute_batch on a SEALValuationBatch: each group's inputs are slices of the batch's handles and its batched outputs are the "
+           "segments of the returned SEALValuationBatch; nothing is stacked, unstacked or copied. In the multi-device modes (devices or shard "
+           "set) the call goes through to_list() and the list path")
+      .def("stack_stats", [](HipPublic &p) {
+        auto st = p.stack_stats();
+        py::dict d;
+        d["calls"] = st[0]; d["instances"] = st[1];
+        return d;
+      }, "evah_ct_stack calls on the context's device state so far and the instances they copied")
       .def("encrypt", [](HipPublic &p, const Valuation &inputs, const CKKSSignature &sig) {
         HipValuation v = p.encrypt(inputs, sig);
         v.params = p.host;
@@ -507,6 +570,45 @@ PYBIND11_MODULE(_eva, m) {
          "encrypt() for a list of input valuations with the same input names: one pair of random streams for the call, instances in list "
          "order and names sorted within an instance, so instance 0 of a seeded call equals encrypt() and no two values share a seed. "
          "device_sampling: each error polynomial is expanded from a 32-byte key of the secret stream, on the device in the grouped calls (DESIGN.md 1.7)")
+      .def("_encrypt_array", [](HipSecret &s, const std::map<std::string, py::array> &arrays, const Valuation &shared, const CKKSSignature &sig,
+                                uint64_t seed) { return s.encrypt_array(array_views(arrays), shared, sig, seed); },
+           py::arg("arrays"), py::arg("shared"), py::arg("signature"), py::arg("seed") = 0,
+           "encrypt_array on normalised arguments (eva_amd.seal.normalise_arrays); every ciphertext is seeded")
+      .def("decrypt_array", [](HipSecret &s, py::object enc, const CKKSSignature &sig, py::object dtype) {
+        const py::dtype dt = py::dtype::from_args(dtype);
+        int code;
+        if (dt.kind() == 'f' && dt.itemsize() == 8) code = EVAH_F64;
+        else if (dt.kind() == 'f' && dt.itemsize() == 4) code = EVAH_F32;
+        else throw std::invalid_argument("decrypt_array: dtype must be float64 or float32");
+        if (sig.vec_size <= 0) throw std::runtime_error("Signature vector size must be positive");
+        HipValuationBatch from_list;
+        const HipValuationBatch *vb;
+        if (py::isinstance<HipValuationBatch>(enc)) {
+          vb = &enc.cast<const HipValuationBatch &>();
+        } else {
+          if (!s.on_device()) throw std::runtime_error("decrypt_array needs a HIP device: none is visible, or EVA_DEVICE_CLIENT=0 keeps the client on the host");
+          from_list = batch_of_list(enc.cast<std::vector<const HipValuation *>>(), s.dev, s.host);
+          vb = &from_list;
+        }
+        py::dict out;
+        std::map<std::string, void *> rows;
+        for (auto &kv : vb->ciphers) {
+          py::array a(dt, std::vector<py::ssize_t>{(py::ssize_t)vb->B, (py::ssize_t)sig.vec_size});
+          rows[kv.first] = a.mutable_data();
+          out[py::str(kv.first)] = a;
+        }
+        s.decrypt_array(*vb, sig, code, rows);
+        for (auto &kv : vb->shared) { // one value for all instances: decrypt()'s doubles in every row
+          const std::vector<double> v = s.decrypt_value(kv.first, kv.second, sig);
+          py::array_t<double> a({(py::ssize_t)vb->B, (py::ssize_t)sig.vec_size});
+          for (size_t b = 0; b < vb->B; b++) std::copy(v.begin(), v.end(), a.mutable_data() + b * v.size());
+          out[py::str(kv.first)] = code == EVAH_F32 ? py::array(a.attr("astype")(dt)) : py::array(a);
+        }
+        return out;
+      }, py::arg("enc_outputs"), py::arg("signature"), py::arg("dtype") = py::module_::import("numpy").attr("float64"),
+           "decrypt a SEALValuationBatch (or a list of SEALValuations) into {name: ndarray[B, vec_size]}: up to 64 instances of one name per "
+           "device call, written straight into the array's rows; float64 rows are decrypt_batch's doubles bit for bit, float32 rows are those "
+           "doubles rounded to nearest-even on the device")
       .def("decrypt", &HipSecret::decrypt, py::arg("enc_outputs"), py::arg("signature"))
       .def("decrypt_batch", &HipSecret::decrypt_batch, py::arg("enc_outputs"), py::arg("signature"),
            "decrypt() of every valuation of a list, bit for bit; on the device up to 64 outputs of one name are decrypted and decoded in one call")

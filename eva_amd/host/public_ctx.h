@@ -102,6 +102,10 @@ public:
   // device_sampling only): the reproducible test stream SecureRng(seed, 5), NOT secret-grade.
   std::vector<HipValuation> encrypt_batch(const std::vector<Valuation> &inputs, const CKKSSignature &sig, bool device_sampling = false,
                                           uint64_t seed = 0);
+  // encrypt_batch(..., device_sampling = true, seed) for arrays [B][n] in their own type, one per encrypted input, kept as
+  // batched handles (client.h); `shared`: the plain and raw inputs, one value for all instances
+  HipValuationBatch encrypt_array(const std::map<std::string, ArrayView> &arrays, const Valuation &shared, const CKKSSignature &sig,
+                                  uint64_t seed = 0);
 
   // SEALPublic::execute (seal.cpp:104-122) — THE hot path.  First call for a program: upload
   // inputs, walk the DAG issuing HIP work over the queues, download outputs.  From the second call
@@ -328,6 +332,19 @@ public:
   // group sizes make some calls 3-6 ms longer (pool misses), so the median is no better
   bool batch_ramp = std::getenv("EVA_BATCH_RAMP") ? std::atoi(std::getenv("EVA_BATCH_RAMP")) != 0 : false;
   std::vector<HipValuation> execute_batch(Program &program, const std::vector<const HipValuation *> &inputs);
+  // The same on a batch that is batched handles already: the groups are additionally cut where an input
+  // segment ends, each group's inputs are slices of their segments (evah_ct_slice: no evah_ct_stack, no copy) and each
+  // group's batched outputs are the segments of the result (no evah_ct_unstack, no per-instance values), so the result of
+  // one program can be the input of the next.  Scheduler, constants and issue queues are execute_batch's.  In the
+  // multi-device modes (`devices` with more than one member, or shard_mode set) the call goes through the list path:
+  // the instances as valuations, execute_batch above, and its results as segments of one.
+  HipValuationBatch execute_batch(Program &program, const HipValuationBatch &inputs);
+  // (evah_ct_stack calls, instances they copied) on this context's device state so far (evah_ctx_stack_stats)
+  std::array<uint64_t, 2> stack_stats() {
+    std::array<uint64_t, 2> st{0, 0};
+    if (dev) chk(evah_ctx_stack_stats(dev->h, st.data()));
+    return st;
+  }
 
   // "dag" mode (BASELINE config 4): the groups of a batch are dealt over the members
   // of `devices` — group g on member g mod G, batch_depth issue queues per member so a member's copies overlap its
@@ -364,6 +381,9 @@ private:
   std::shared_ptr<DeviceCtx> dev; // == holder->dev once a device is in use
   std::vector<std::shared_ptr<Fork>> forks;
   std::vector<std::shared_ptr<Fork>> batch_forks; // the further issue queues of execute_batch
+  // the pipeline of both execute_batch calls (batch.h)
+  template <class SetIn, class GetOut>
+  void run_batch_groups(Program &program, size_t n_instances, bool in_hbm, const std::vector<size_t> &cuts, SetIn set_in, GetOut get_out);
 
   std::shared_ptr<Fork> exec_q[2];  // the two issue queues resident execute() calls alternate between
   unsigned exec_turn = 0;

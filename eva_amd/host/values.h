@@ -152,6 +152,36 @@ struct DeviceResident {
   uint32_t N = 0;                  // poly_modulus_degree: words per limb
   evah_ctx *ctx() const { return queue ? queue->h : root->h; }
 };
+// ---- a batch of valuations as batched device handles: what encrypt_array returns, execute_batch takes
+// and returns as it is, and decrypt_array reads.  Per encrypted name the B instances are an ordered list of segments —
+// a batched handle each, kept whole — where the list path keeps B values with a view each.
+struct BatchSegment {
+  std::shared_ptr<CtHandle> h;  // a batched handle (or a slice, or a single ciphertext: a segment of one)
+  uint32_t n = 0;               // its instances
+  std::shared_ptr<Fork> queue;  // the issue queue whose pool holds the buffer (null: the root's own)
+  uint32_t size = 0, limbs = 0;
+  double scale = 0;
+};
+struct BatchCipher {
+  std::vector<BatchSegment> segments;
+  std::vector<std::array<uint8_t, 32>> seeds; // symmetric encryptions: the seed of c1 per instance, else empty
+};
+struct HipValuationBatch {
+  size_t B = 0;
+  std::map<std::string, BatchCipher> ciphers;
+  std::unordered_map<std::string, SchemeValue> shared; // plaintexts and raw vectors: one value for all instances
+  std::shared_ptr<DeviceCtx> root;                     // the device state every segment lives on
+  std::shared_ptr<const HostContext> params;
+};
+// an array [B][n] of the caller's, in its own type (EVAH_F64 / EVAH_F32 / EVAH_U8), C-contiguous
+struct ArrayView {
+  const void *data = nullptr;
+  int dtype = EVAH_F64;
+  size_t B = 0, n = 0;
+  size_t itemsize() const { return dtype == EVAH_F64 ? 8 : dtype == EVAH_F32 ? 4 : 1; }
+  const void *row(size_t b) const { return static_cast<const char *>(data) + b * n * itemsize(); }
+};
+
 // host words of a ciphertext value, downloaded on first use (waits for the value to be computed) or expanded
 // from its seeded form (c0 + seed)
 inline const CipherWords &words(const HostCipher &c) {

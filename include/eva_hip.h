@@ -153,6 +153,10 @@ int evah_ct_batch(const evah_ct *ct, uint32_t *batch);
 int evah_ct_stack(evah_ctx *ctx, const evah_ct *const *cts, uint32_t n, evah_ct **out);
 /* instance b of a batched handle as a single-ciphertext view (shares the buffer; free separately) */
 int evah_ct_unstack(evah_ctx *ctx, const evah_ct *ct, uint32_t b, evah_ct **out);
+/* instances b0 .. b0 + n - 1 of a batched handle as a batched view of n instances (shares the buffer; free separately):
+ * what passes a group of a batch to the evaluator where seal_executor.h:264-277 copies its inputs in.  Mod-switched
+ * views and slices can be sliced again; n = 0 or b0 + n > batch is refused. */
+int evah_ct_slice(evah_ctx *ctx, const evah_ct *ct, uint32_t b0, uint32_t n, evah_ct **out);
 
 /* a copy of a value owned by another context: another GPU (peer copy over xGMI — the P2P step at the
  * join of independent sub-DAGs) or another issue queue; asynchronous, ordered
@@ -199,6 +203,10 @@ int evah_ctx_key_bytes_detail(evah_ctx *ctx, uint64_t out[3]);
  * where SEALPublic lives, seal.h:58-66): out[0] = installed uploads (evah_key_upload, evah_key_upload_seeded), out[1] =
  * the bytes they sent.  A key generated in place (evah_keygen_switch, evah_keygen_set) is not an upload and counts in neither. */
 int evah_ctx_key_upload_stats(evah_ctx *ctx, uint64_t out[2]);
+/* evah_ct_stack calls made on ctx's device state so far (the deep copies of seal_executor.h:264-277, device to device):
+ * out[0] = calls, out[1] = the instances they copied.  A batch passed on as slices of its handles (evah_ct_slice) counts
+ * in neither. */
+int evah_ctx_stack_stats(evah_ctx *ctx, uint64_t out[2]);
 int evah_ct_info(const evah_ct *ct, uint32_t *size, uint32_t *limbs, double *scale);
 int evah_ct_download(evah_ctx *ctx, const evah_ct *ct, uint64_t *out /* [size][limbs][N] */);
 void evah_ct_free(evah_ctx *ctx, evah_ct *ct);
@@ -398,6 +406,32 @@ int evah_encode_encrypt_symmetric_sampled_many(evah_ctx *ctx, uint32_t batch, co
 /* out[i] = the n_out doubles evah_decrypt_decode(cts[i]) returns, bit pattern for bit pattern (seal.cpp:124-146); the n
  * single ciphertexts (views included) share one size, limb count and scale and are read in place; out [n][n_out] */
 int evah_decrypt_decode_many(evah_ctx *ctx, const evah_ct *const *cts, uint32_t n, uint32_t n_out, double *out);
+
+/* ---- the client calls on arrays and batched handles -----------------------------------------
+ * The inputs of seal.cpp:24-102 arrive as one array [batch][n_values] in the type the caller holds them in, cross PCIe
+ * in that type (batch * n_values * itemsize bytes) and become doubles on the device, exactly: the encoder's scatter reads
+ * the source type.  Checks, messages, launches per call, wipes and the one drain are those of the _sampled_many calls;
+ * "encoded values are too large" is decided on the typed data with the verdict of its float64 image (a float NaN or
+ * infinity is refused as the double is).  An unknown dtype is refused. */
+#define EVAH_F64 0
+#define EVAH_F32 1
+#define EVAH_U8 2
+/* evah_encode_encrypt_sampled_many on the float64 image of values, word for word (seal.cpp:24-102); values
+ * [batch][n_values] of dtype, rkeys [batch][32] */
+int evah_encode_encrypt_array(evah_ctx *ctx, uint32_t batch, const void *values, int dtype, uint32_t n_values, uint32_t limbs,
+                              double scale, const uint8_t *rkeys, evah_ct **out);
+/* evah_encode_encrypt_symmetric_sampled_many on the float64 image of values, word for word (seal.cpp:24-102 with
+ * Encryptor::encrypt_symmetric); ekeys [batch][32] (secret), seeds [batch][32] (public) */
+int evah_encode_encrypt_symmetric_array(evah_ctx *ctx, uint32_t batch, const void *values, int dtype, uint32_t n_values,
+                                        uint32_t limbs, double scale, const uint8_t *ekeys, const uint8_t *seeds, evah_ct **out);
+/* evah_decrypt_decode_many (seal.cpp:124-146) over handles that are each single or batched, views and slices included,
+ * at most 64 instances together: instance j of a handle is read in place at d + j * size * stride.  out [instances][n_out]
+ * of dtype_out, rows in list order, then instance order: EVAH_F64 rows are evah_decrypt_decode_many's bit patterns on the
+ * unstacked instances, EVAH_F32 rows are those doubles rounded to nearest-even on the device (half the bytes come back).
+ * Refusals and messages are evah_decrypt_decode_many's (mismatches by argument index), plus more than 64 instances in
+ * total and an unknown dtype_out. */
+int evah_decrypt_decode_handles(evah_ctx *ctx, const evah_ct *const *cts, uint32_t n_handles, uint32_t n_out, int dtype_out,
+                                void *out);
 
 /* ---- whole-DAG submit: a topologically sorted flat op list over a value table.
  * One call replaces the per-node loop ProgramTraversal::forwardPass + SEALExecutor::operator()

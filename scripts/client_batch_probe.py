@@ -12,6 +12,9 @@ between them.  Each run prints one line: the median wall time of the three phase
 runs (the first run builds tables and plans).  --secret encrypts with the secret key (seeded ciphertexts) instead.
 --sampling device (with --batch 1) draws the encryption randomness on the device from a 32-byte key per value
 (DESIGN.md 1.7); --sampling host, the default, is the host sampler.
+--arrays 1 runs the three phases through the array calls: encrypt_array on a uint8 array (c4: the pixels
+0 .. 255 themselves) or a float32 array (c3), execute_batch on the SEALValuationBatch, decrypt_array; the line then also
+reports the bytes that crossed PCIe in the last run's encrypt phase and the evah_ct_stack counters over its execute_batch.
 
 Kernel launches per call: run one leg under the profiler, which this script never starts itself and with no counters in
 that run,
@@ -42,9 +45,13 @@ ap.add_argument("--sampling", choices=["host", "device"], default="host",
                 help="device: encrypt_batch(..., device_sampling=True), the randomness drawn on the device (needs --batch 1)")
 ap.add_argument("--phase", choices=["all", "encrypt", "decrypt"], default="all",
                 help="encrypt: no execute_batch and no decryption; decrypt: one untimed encryption and execute_batch, then decryptions alone")
+ap.add_argument("--arrays", type=int, choices=[0, 1], default=0,
+                help="1: encrypt_array / execute_batch on the batch / decrypt_array, uint8 input for c4 and float32 input for c3")
 args = ap.parse_args()
 if args.sampling == "device" and not args.batch:
     ap.error("--sampling device needs --batch 1: the single calls sample on the host")
+
+import numpy as np
 
 from eva.seal import generate_keys
 from eva_amd import workloads
@@ -56,18 +63,29 @@ pub, sec = generate_keys(params, 1)
 batched = bool(args.batch)
 enc_ctx = sec if args.secret else pub
 on_device = args.sampling == "device"
+arrays = None
+if args.arrays:
+    if args.what == "c4":   # the pixels as the camera gives them
+        arrays = {'image': np.array([workloads.image(4096, shift=b, scale=1.0)['image'] for b in range(B)], dtype=np.uint8)}
+    else:
+        arrays = {'image': np.array([x['image'] for x in xs], dtype=np.float32)}
 
 
 def encrypt():
+    if arrays:
+        return enc_ctx.encrypt_array(arrays, sig)
     return enc_ctx.encrypt_batch(xs, sig, device_sampling=on_device) if batched else [enc_ctx.encrypt(x, sig) for x in xs]
 
 
 def decrypt(outs):
+    if arrays:
+        return next(iter(sec.decrypt_array(outs, sig).values()))
     return sec.decrypt_batch(outs, sig) if batched else [sec.decrypt(o, sig) for o in outs]
 
 
 t_enc, t_exe, t_dec = [], [], []
 outs = None
+h2d = stacked = None
 if args.phase == "decrypt":
     outs = pub.execute_batch(compiled, encrypt())
     pub.synchronize()
@@ -75,17 +93,22 @@ for run in range(args.warmup + args.repeat):
     keep = run >= args.warmup
     if args.phase != "decrypt":
         pub.synchronize()
+        before = pub.transfer_stats()
         t0 = time.perf_counter()
         encs = encrypt()
         pub.synchronize()
         t1 = time.perf_counter()
+        h2d = pub.transfer_stats()["h2d_bytes"] - before["h2d_bytes"]
         if keep:
             t_enc.append(t1 - t0)
         if args.phase == "encrypt":
             continue
+        s0 = pub.stack_stats()
         outs = pub.execute_batch(compiled, encs)
         pub.synchronize()
         t2 = time.perf_counter()
+        s1 = pub.stack_stats()
+        stacked = (s1["calls"] - s0["calls"], s1["instances"] - s0["instances"])
         if keep:
             t_exe.append(t2 - t1)
     t2 = time.perf_counter()
@@ -97,9 +120,14 @@ for run in range(args.warmup + args.repeat):
 
 
 def med(t):
-    return f"{statistics.median(t) * 1e3:.2f} ms" if t else "-"
+    return f"{statistics.median(t) * 1e3:.2f} ms ({min(t) * 1e3:.2f} .. {max(t) * 1e3:.2f})" if t else "-"
 
 
-print(f"{args.what} batch={int(batched)} secret={int(args.secret)} sampling={args.sampling}: N={pub.poly_modulus_degree} k={len(pub.primes)} instances={B}; "
+extra = ""
+if h2d is not None:
+    extra += f", encrypt h2d {h2d} bytes"
+if stacked is not None:
+    extra += f", evah_ct_stack over execute_batch {stacked[0]} calls / {stacked[1]} instances"
+print(f"{args.what} batch={int(batched)} secret={int(args.secret)} sampling={args.sampling} arrays={args.arrays}: N={pub.poly_modulus_degree} k={len(pub.primes)} instances={B}; "
       f"medians over {args.repeat} runs after {args.warmup} warm-up: encrypt all inputs {med(t_enc)}, execute_batch {med(t_exe)}, "
-      f"decrypt all outputs {med(t_dec)}")
+      f"decrypt all outputs {med(t_dec)}{extra}")
