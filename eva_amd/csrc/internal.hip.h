@@ -264,7 +264,8 @@ struct Tunables {
   // (hoisting) when the set is at least this many tiles of digit transforms
   bool hoist = true;
   uint32_t hoist_min_tiles = 2048;
-  // EVAH_HOIST_DEBUG (0): print the zero-coefficient count of every hoisted set (synchronises)
+  // EVAH_HOIST_DEBUG (0): one line per rotation-set / window-sum call on stderr: hoisted or fused, the zero-coefficient
+  // count, and per chunk its pairs, tile shape, tiles and k_hoist_mac launches (rotation_sets.hip.h; synchronises)
   bool hoist_debug = false;
   // EVAH_PEER_SELF_CHECK (0): tests only — evah_ctx_enable_peer asks the runtime about the pair even when both contexts
   // are on one device (where it answers "no"), so the refusal path can run on a 1-GPU box

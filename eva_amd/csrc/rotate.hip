@@ -62,11 +62,18 @@ extern "C" {
 static void rotation_set(evah_ctx *c, uint32_t l, const std::vector<RotPair> &pairs, const std::vector<RotChunk> &chunks,
                          const std::vector<const u64 *> &srcs, const std::vector<size_t> &src_ps, bool hoisted) {
   const size_t N = c->N, pps = (size_t)l * N, prod_bs = (size_t)2 * (l + 1) * N;
+  const bool debug = hoist_debug_on(c);
+  std::string note; // EVAH_HOIST_DEBUG: the chunks of this set
+  const uint32_t n_src = (uint32_t)srcs.size();
   if (!hoisted) {
-    for (const RotChunk &ch : chunks) rot_chunk_plain(c, l, pairs.data() + ch.first, ch.count, ch.out);
+    for (const RotChunk &ch : chunks) {
+      rot_chunk_plain(c, l, pairs.data() + ch.first, ch.count, ch.out);
+      if (debug) note += " | pairs=" + std::to_string(ch.count);
+    }
+    if (debug)
+      std::fprintf(stderr, "rotation set: hoisted=0 pairs=%zu sources=%u l=%u chunks=%zu%s\n", pairs.size(), n_src, l, chunks.size(), note.c_str());
     return;
   }
-  const uint32_t n_src = (uint32_t)srcs.size();
   if (n_src > (uint32_t)KS_BATCH_MAX) throw std::logic_error("hoisted rotation set with too many sources");
   // one barrier word per chunk (k_rot_fallback), then the zero-coefficient count and the recorded positions: the words
   // that must start at zero are adjacent (cleared by the first pass of hoist_digits)
@@ -86,7 +93,8 @@ static void rotation_set(evah_ctx *c, uint32_t l, const std::vector<RotPair> &pa
       Scratch perm(c, fold ? 1 : (size_t)np * 2 * pps);
       if (!fold) rot_perm_launch(c, l, pr, np, perm.d, 1);
       Scratch prod(c, np * prod_bs), r(c, (size_t)np * 2 * N);
-      hoist_mac_launch(c, mt, tiles, dg.d, dg_bs, prod.d, prod_bs, l, fold);
+      const uint32_t launches = hoist_mac_launch(c, mt, tiles, dg.d, dg_bs, prod.d, prod_bs, l, fold);
+      if (debug) hoist_debug_chunk(note, "", np, tiles, launches);
       {
         ProfScope ps(c, KC_KSMAC);
         // the terms of recorded zero coefficients (returns at once when there are none)
@@ -106,12 +114,9 @@ static void rotation_set(evah_ctx *c, uint32_t l, const std::vector<RotPair> &pa
     if (c->tun.fb_persist) rot_fallback_launch(c, l, pairs.data() + ch.first, ch.count, ch.out, nullptr, 0, 0, 0, flag.bar(ci));
     else rot_chunk_plain(c, l, pairs.data() + ch.first, ch.count, ch.out);
   }
-  if (!c->capturing && c->tun.hoist_debug) { // diagnostics: how many zero coefficients did this set see?
-    uint32_t f = 0;
-    HIPCHK(hipMemcpyAsync(&f, flag.d, sizeof(f), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    std::fprintf(stderr, "rotation set: hoisted %zu rotations of %u sources, l = %u, zero coefficients = %u\n", pairs.size(), n_src, l, f);
-  }
+  if (debug) // diagnostics: what ran, and how many zero coefficients did this set see?
+    std::fprintf(stderr, "rotation set: hoisted=1 pairs=%zu sources=%u l=%u zeros=%u chunks=%zu%s\n", pairs.size(), n_src, l,
+                 hoist_debug_zeros(c, flag), chunks.size(), note.c_str());
 }
 
 // Several rotations of ONE ciphertext (the convolution pattern: image << i*w+j for a 3x3

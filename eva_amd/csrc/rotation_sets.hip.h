@@ -522,6 +522,8 @@ static void rot_fallback_launch(evah_ctx *c, uint32_t l, const RotPair *pr, uint
 struct HoistTiles {
   int TS = 1, TR = 1;
   uint32_t n_tiles = 0;
+  uint32_t n_src = 0, n_elt = 0; // the chunk's distinct sources and Galois elements
+  uint32_t n_full = 0;           // tiles whose TS x TR combinations are all pairs of the chunk (no padding)
   std::vector<std::array<uint32_t, 6>> tiles; // HT_TILES at a time go into HoistMacTab::tile
 };
 static HoistTiles hoist_tables(const RotPair *pr, uint32_t np, size_t N, HoistMacTab &mt, HoistFixTab &ft) {
@@ -552,6 +554,8 @@ static HoistTiles hoist_tables(const RotPair *pr, uint32_t np, size_t N, HoistMa
   // shape: as many sources as the chunk has (up to 4), then as many elements as 8 accumulator pairs allow
   HoistTiles ht;
   const size_t S = srcs.size(), R = elts.size();
+  ht.n_src = (uint32_t)S;
+  ht.n_elt = (uint32_t)R;
   // (8 x 1 for the instances of a batched handle reads every key once but every digit row eight times: 14.3 k against
   // 14.5 k DAGs/s with 4 x 2 on config 4; 1 x 8 needs 159 VGPRs; a 64-VGPR ceiling for 8 waves per SIMD spills: 9.8 k)
   ht.TS = S >= 4 ? 4 : (int)S;
@@ -584,6 +588,7 @@ static HoistTiles hoist_tables(const RotPair *pr, uint32_t np, size_t N, HoistMa
             taken[q] = 1;
             break;
           }
+    if (std::count(b + 16, b + 16 + ht.TS * ht.TR, (uint8_t)0xff) == 0) ht.n_full++;
     std::array<uint32_t, 6> w{};
     for (int i = 0; i < 6; i++) w[i] = b[4 * i] | (uint32_t)b[4 * i + 1] << 8 | (uint32_t)b[4 * i + 2] << 16 | (uint32_t)b[4 * i + 3] << 24;
     ht.tiles.push_back(w);
@@ -591,12 +596,14 @@ static HoistTiles hoist_tables(const RotPair *pr, uint32_t np, size_t N, HoistMa
   ht.n_tiles = (uint32_t)ht.tiles.size();
   return ht;
 }
-// the hoisted inner products of a chunk (k_hoist_mac), HT_TILES tiles per launch
-static void hoist_mac_launch(evah_ctx *c, HoistMacTab &mt, const HoistTiles &ht, const u64 *dg, size_t dg_bs, u64 *prod, size_t prod_bs, uint32_t l,
+// the hoisted inner products of a chunk (k_hoist_mac), HT_TILES tiles per launch; returns the number of launches
+static uint32_t hoist_mac_launch(evah_ctx *c, HoistMacTab &mt, const HoistTiles &ht, const u64 *dg, size_t dg_bs, u64 *prod, size_t prod_bs, uint32_t l,
                              bool fold) {
   ProfScope ps(c, KC_KSMAC);
+  uint32_t launches = 0;
   for (uint32_t t0 = 0; t0 < ht.n_tiles; t0 += HT_TILES) {
     const uint32_t n = std::min<uint32_t>(HT_TILES, ht.n_tiles - t0);
+    launches++;
     for (uint32_t t = 0; t < n; t++)
       for (int i = 0; i < 6; i++) mt.tile[t][i] = ht.tiles[t0 + t][i];
     // V = 2 (16-byte accesses) for the shapes with at most four accumulator pairs; MAP needs N / (256 V) >= 8 tiles
@@ -618,6 +625,25 @@ static void hoist_mac_launch(evah_ctx *c, HoistMacTab &mt, const HoistTiles &ht,
 #undef HM
     throw std::logic_error("hoisted inner product: no kernel for this tile shape");
   }
+  return launches;
+}
+// EVAH_HOIST_DEBUG: what a set did, one line per call on stderr (rotate.hip rotation_set, windows.hip).  The line is
+//   <head> | <chunk> | <chunk> ...      with key=value fields; a hoisted chunk reports
+//   pairs, sources and elts (distinct in the chunk), tile=TSxTR, tiles, full (tiles without padding), launches (of k_hoist_mac)
+// preceded for window sums by units, F and lin.  Nothing here runs with the knob unset.
+static bool hoist_debug_on(const evah_ctx *c) { return c->tun.hoist_debug && !c->capturing; }
+static void hoist_debug_chunk(std::string &line, const char *lead, uint32_t np, const HoistTiles &ht, uint32_t launches) {
+  char b[160];
+  std::snprintf(b, sizeof b, " | %spairs=%u sources=%u elts=%u tile=%dx%d tiles=%u full=%u launches=%u", lead, np, ht.n_src, ht.n_elt, ht.TS, ht.TR,
+                ht.n_tiles, ht.n_full, launches);
+  line += b;
+}
+// the zero-coefficient count of a hoisted set (a copy and a synchronisation: diagnostics only)
+static uint32_t hoist_debug_zeros(evah_ctx *c, const ZeroFlag &flag) {
+  uint32_t f = 0;
+  HIPCHK(hipMemcpyAsync(&f, flag.d, sizeof(f), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return f;
 }
 // digits of the unrotated c1 of every source, once: coefficient form (zeros recorded in flag_d), then the full
 // transforms under every output prime into dg_d[source][(l+1) l N]; t_d: n_src * l * N words of scratch

@@ -137,8 +137,11 @@ int evah_rotate_weighted_sums(evah_ctx *c, const evah_ct *const *cts, const int3
     std::vector<evah_ct *> v;
     ~Temps() { for (evah_ct *t : v) if (t) evah_ct_free(c, t); }
   } rotated{c, std::vector<evah_ct *>(n_terms, nullptr)};
+  const bool debug = hoist_debug_on(c);
   try {
     if (!fusable) {
+      if (debug) // (the rotation sets below report themselves)
+        std::fprintf(stderr, "window sums: fused=0 windows=%u rotated=%u sources=%zu B=%u l=%u\n", n_windows, n_rot, distinct.size(), B, l);
       // the general form: the rotations as launch sets (rotate_pairs / rotate_many), then one weighted sum per sum
       if (B == 1) {
         std::vector<uint32_t> idx;
@@ -253,6 +256,7 @@ int evah_rotate_weighted_sums(evah_ctx *c, const evah_ct *const *cts, const int3
       }
       ZeroFlag flag(c, chunks.size());
       const size_t dg_bs = (size_t)(l + 1) * l * N;
+      std::string note; // EVAH_HOIST_DEBUG: the chunks of this call
       {
         Scratch t(c, srcs.size() * l * N), dg(c, srcs.size() * dg_bs);
         hoist_digits(c, l, srcs, src_ps, flag, t.d, dg.d);
@@ -263,7 +267,12 @@ int evah_rotate_weighted_sums(evah_ctx *c, const evah_ct *const *cts, const int3
           HoistFixTab ft{};
           const HoistTiles tiles = hoist_tables(pr, np, N, mt, ft);
           Scratch prod(c, np * prod_bs), r(c, (size_t)np * 2 * N), mid(c, (ch.lin ? (size_t)ch.nu * ch.F : (size_t)np) * 2 * pps);
-          hoist_mac_launch(c, mt, tiles, dg.d, dg_bs, prod.d, prod_bs, l, true);
+          const uint32_t launches = hoist_mac_launch(c, mt, tiles, dg.d, dg_bs, prod.d, prod_bs, l, true);
+          if (debug) {
+            char lead[64];
+            std::snprintf(lead, sizeof lead, "units=%u F=%d lin=%d ", ch.nu, ch.F, ch.lin ? 1 : 0);
+            hoist_debug_chunk(note, lead, np, tiles, launches);
+          }
           {
             ProfScope ps(c, KC_KSMAC);
             hipLaunchKernelGGL(k_hoist_fix, dim3(c->N / 256, l + 1, np), dim3(256), 0, c->stream, c->dev, flag.d, ft, prod.d, prod_bs, l);
@@ -318,6 +327,9 @@ int evah_rotate_weighted_sums(evah_ctx *c, const evah_ct *const *cts, const int3
         else EW_LAUNCH((k_window_sums<2>), grid, dim3(256), 0, c->stream, c->dev, ch.wt, rot.d, pps, out_ps);
         HIPCHK(hipGetLastError());
       }
+      if (debug)
+        std::fprintf(stderr, "window sums: fused=1 pairs=%zu sources=%zu l=%u zeros=%u chunks=%zu%s\n", pairs.size(), srcs.size(), l,
+                     hoist_debug_zeros(c, flag), chunks.size(), note.c_str());
     }
   } catch (...) {
     for (evah_ct *t : made) evah_ct_free(c, t);
