@@ -144,6 +144,11 @@ _SIGS = {
     "evah_decrypt_decode_handles": [_vp, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.c_int, _vp],
     "evah_ct_slice": [_vp, _vp, C.c_uint32, C.c_uint32, _vpp],
     "evah_ctx_stack_stats": [_vp, _u64p],
+    # batched plaintexts
+    "evah_pt_encode_array": [_vp, C.c_uint32, _vp, C.c_int, C.c_uint32, C.c_uint32, C.c_double, _vpp],
+    "evah_pt_encode_array_async": [_vp, C.c_uint32, _vp, C.c_int, C.c_uint32, C.c_uint32, C.c_double, _vpp],
+    "evah_pt_batch": [_vp, C.POINTER(C.c_uint32)],
+    "evah_pt_download_instances": [_vp, _vp, _u64p],
     # seed-compressed evaluation keys
     "evah_key_upload_seeded": [_vp, C.c_int, C.c_uint32, C.c_uint32, _u64p, C.POINTER(C.c_uint8)],
     "evah_keygen_switch": [_vp, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_int8), C.POINTER(C.c_uint8), C.c_int, _u64p],
@@ -342,9 +347,9 @@ class Ciphertext:
 
 
 class Plaintext:
-    """Device-resident plaintext handle (evah_pt)."""
+    """Device-resident plaintext handle (evah_pt); a batched one holds an instance per instance of a batched ciphertext."""
 
-    __slots__ = ("ctx", "h")
+    __slots__ = ("ctx", "h", "staging")
 
     def __init__(self, ctx, h):
         self.ctx, self.h = ctx, h
@@ -357,10 +362,23 @@ class Plaintext:
     limbs = property(lambda self: self.info()[0])
     scale = property(lambda self: self.info()[1])
 
+    @property
+    def batch(self):
+        b = C.c_uint32()
+        _chk(_lib.evah_pt_batch(self.h, C.byref(b)))
+        return b.value
+
     def download(self):
         l, _ = self.info()
         out = np.empty((l, self.ctx.N), dtype=np.uint64)
         _chk(_lib.evah_pt_download(self.ctx.h, self.h, _p(out)))
+        return out
+
+    def download_instances(self):
+        """[batch][limbs][N]: every instance of a batched plaintext (evah_pt_download_instances)"""
+        l, _ = self.info()
+        out = np.empty((self.batch, l, self.ctx.N), dtype=np.uint64)
+        _chk(_lib.evah_pt_download_instances(self.ctx.h, self.h, _p(out)))
         return out
 
     def write(self, data):
@@ -848,6 +866,20 @@ class Context:
         h = C.c_void_p()
         _chk(_lib.evah_pt_encode(self.h, v.ctypes.data_as(C.POINTER(C.c_double)), v.shape[0], int(limbs), float(scale), C.byref(h)))
         return Plaintext(self, h)
+
+    def encode_pt_array(self, values, limbs, scale, wait=True):
+        """device CKKS encoder on the rows of values [batch, n] (uint8 / float32 / float64 cross in their own type): one
+        batched Plaintext whose instance b is encode_pt(values[b]) (evah_pt_encode_array).  wait=False is the
+        stream-ordered form: the array is kept on the handle until the caller has synchronised the queue."""
+        v, dt = array_dtype(values)
+        assert v.ndim == 2
+        h = C.c_void_p()
+        fn = _lib.evah_pt_encode_array if wait else _lib.evah_pt_encode_array_async
+        _chk(fn(self.h, v.shape[0], v.ctypes.data_as(C.c_void_p), dt, v.shape[1], int(limbs), float(scale), C.byref(h)))
+        pt = Plaintext(self, h)
+        if not wait:
+            pt.staging = v
+        return pt
 
     def uniform_pt(self, values, scale):
         values = np.ascontiguousarray(values, dtype=np.uint64)

@@ -541,7 +541,7 @@ static void decrypt_decode(evah_ctx *c, const evah_ct *const *cts, uint32_t n_ha
 // ---- the _many calls: values in, one batched handle out
 // the checks both encryption calls share, in the order evah_pt_encode and the encryptors make them
 static void encode_many_checks(evah_ctx *c, uint32_t batch, const void *values, int dtype, uint32_t n_values, uint32_t limbs, double scale,
-                               evah_ct **out) {
+                               const void *out) {
   if (c->capturing) throw std::logic_error("this call synchronises with the host and cannot be captured into a graph");
   if (batch < 1 || batch > (uint32_t)KS_BATCH_MAX) throw std::invalid_argument("batch must be 1..64");
   if (!values) throw std::invalid_argument("value pointer is null");
@@ -622,9 +622,47 @@ static void encode_encrypt_symmetric_many(evah_ctx *c, uint32_t batch, const voi
   count_client_h2d(c, dtype_size(dtype) * B * n_values + (ekeys ? 32 * B : B * N) + 32 * B);
 }
 
+// evah_pt_encode_array and its stream-ordered form: the encoder of the _many calls with the plaintexts
+// kept — instance b of the handle is evah_pt_encode of row b's float64 image, word for word.  The launches are
+// encode_many's, so their number does not depend on the batch.  wait: drain the queue (`values` is pageable host
+// memory); otherwise the copy stays in queue order and the caller keeps `values` until the queue is synchronised.
+static void pt_encode_array(evah_ctx *c, uint32_t batch, const void *values, int dtype, uint32_t n_values, uint32_t limbs, double scale, bool wait,
+                            evah_pt **out) {
+  use(c);
+  encode_many_checks(c, batch, values, dtype, n_values, limbs, scale, out);
+  const size_t N = c->N, B = batch;
+  Scratch vals(c, (dtype_size(dtype) * B * n_values + 7) / 8), cbuf(c, B * 2 * N);
+  evah_pt *t = pt_new(c, limbs, scale, batch);
+  try {
+    encode_many(c, batch, values, dtype, n_values, limbs, scale, vals.d, reinterpret_cast<double2 *>(cbuf.d), t->d);
+    if (wait) HIPCHK(hipStreamSynchronize(c->stream));
+  } catch (...) {
+    (void)hipStreamSynchronize(c->stream); // `values` is pageable host memory
+    evah_pt_free(c, t);
+    throw;
+  }
+  if (wait) t->buf->ready_everywhere = true;
+  count_client_h2d(c, dtype_size(dtype) * B * n_values);
+  *out = t;
+}
+
 } // namespace evah
 
 extern "C" {
+
+int evah_pt_encode_array(evah_ctx *c, uint32_t batch, const void *values, int dtype, uint32_t n_values, uint32_t limbs, double scale,
+                         evah_pt **out) {
+  API_BEGIN
+  pt_encode_array(c, batch, values, dtype, n_values, limbs, scale, true, out);
+  API_END
+}
+
+int evah_pt_encode_array_async(evah_ctx *c, uint32_t batch, const void *values, int dtype, uint32_t n_values, uint32_t limbs, double scale,
+                               evah_pt **out) {
+  API_BEGIN
+  pt_encode_array(c, batch, values, dtype, n_values, limbs, scale, false, out);
+  API_END
+}
 
 // the public key [2][k][N] / the secret key in NTT form [k][N] (client side), resident like the other keys
 int evah_client_key_upload(evah_ctx *c, int kind, const uint64_t *data) {
@@ -652,6 +690,7 @@ int evah_encrypt(evah_ctx *c, const evah_pt *pt, const int8_t *small, evah_ct **
   use(c);
   if (c->capturing) throw std::logic_error("this call synchronises with the host and cannot be captured into a graph");
   if (!c->sh->pk.d) throw std::invalid_argument("public key not present");
+  if (pt->batch != 1) throw std::invalid_argument("encrypt takes a single plaintext (a batch is encrypted by the evah_encode_encrypt_* calls)");
   acquire(c, pt->buf);
   if (pt->limbs + 1 > c->k) throw std::invalid_argument("plaintext level is not valid for encryption");
   *out = encrypt_public(c, 1, pt->limbs, pt->scale, pt->d, small, nullptr);
@@ -668,6 +707,7 @@ int evah_encrypt_symmetric(evah_ctx *c, const evah_pt *pt, const int8_t *e, cons
   if (!e || !seed32) throw std::invalid_argument("error polynomial and seed are required");
   if (c->N % 256) throw std::invalid_argument("encryption needs N divisible by 256");
   if (pt->limbs < 1 || pt->limbs > c->k - 1) throw std::invalid_argument("plaintext level is not valid for encryption"); // no special prime
+  if (pt->batch != 1) throw std::invalid_argument("encrypt takes a single plaintext (a batch is encrypted by the evah_encode_encrypt_* calls)");
   acquire(c, pt->buf);
   *out = encrypt_symmetric(c, 1, pt->limbs, pt->scale, pt->d, e, nullptr, seed32);
   API_END

@@ -118,6 +118,37 @@ k_weighted_sum(DevCtx cx, WsTab tab, uint32_t n, u64 *out, size_t o_ps) {
   st2(out + p * o_ps + off, r);
 }
 
+// K6b with per-instance weights (evah_pt::batch > 1): term j's weight of instance blockIdx.z / size
+// starts pt_bs[j] rows of N words behind the previous instance's (0: a plaintext all instances share).  The instance is
+// block-uniform, so the offset is scalar arithmetic and the loads stay 16 bytes per lane.  A kernel of its own: the
+// shared form above carries neither the table nor the divide.
+struct WsTabInst {
+  const u64 *ct[KS_BATCH_MAX], *pt[KS_BATCH_MAX];
+  uint32_t ct_ps[KS_BATCH_MAX]; // poly strides in units of N coefficients
+  uint32_t pt_bs[KS_BATCH_MAX]; // instance strides of the weights in units of N coefficients
+};
+__global__ void __launch_bounds__(256)
+k_weighted_sum_inst(DevCtx cx, WsTabInst tab, uint32_t n, uint32_t size, u64 *out, size_t o_ps) {
+  EW_SETUP
+  const uint32_t inst = p / size;
+  u128_t a0 = {0, 0}, a1 = {0, 0};
+  for (uint32_t j = 0; j < n; j++) {
+    const ulonglong2 x = ld2(tab.ct[j] + (size_t)p * tab.ct_ps[j] * cx.N + off);
+    if (tab.pt[j]) {
+      const ulonglong2 w = ld2(tab.pt[j] + (size_t)inst * tab.pt_bs[j] * cx.N + off);
+      acc128(a0, x.x, w.x);
+      acc128(a1, x.y, w.y);
+    } else {
+      acc128(a0, x.x, 1);
+      acc128(a1, x.y, 1);
+    }
+  }
+  ulonglong2 r;
+  r.x = barrett128(a0, pm);
+  r.y = barrett128(a1, pm);
+  st2(out + p * o_ps + off, r);
+}
+
 // K5: square 2 -> 3: (a0^2, 2 a0 a1, a1^2)
 __global__ void __launch_bounds__(256)
 k_square(DevCtx cx, const u64 *a, size_t a_ps, u64 *out, size_t o_ps) {
@@ -143,6 +174,19 @@ __global__ void __launch_bounds__(256)
 k_mul_plain(DevCtx cx, const u64 *a, size_t a_ps, const u64 *pt, u64 *out, size_t o_ps) {
   EW_SETUP
   ulonglong2 x = ld2(a + p * a_ps + off), y = ld2(pt + off), r;
+  r.x = mulmod(x.x, y.x, pm);
+  r.y = mulmod(x.y, y.y, pm);
+  st2(out + p * o_ps + off, r);
+}
+
+static_assert(sizeof(DevCtx) + sizeof(WsTabInst) + 64 <= 4096, "kernel arguments of k_weighted_sum_inst");
+
+// K6 with a per-instance plaintext: grid.z = instance * size + poly, instance b's plaintext at pt + b * pt_bs
+__global__ void __launch_bounds__(256)
+k_mul_plain_inst(DevCtx cx, const u64 *a, size_t a_ps, const u64 *pt, size_t pt_bs, uint32_t size, u64 *out, size_t o_ps) {
+  EW_SETUP
+  const uint32_t inst = p / size;
+  ulonglong2 x = ld2(a + p * a_ps + off), y = ld2(pt + inst * pt_bs + off), r;
   r.x = mulmod(x.x, y.x, pm);
   r.y = mulmod(x.y, y.y, pm);
   st2(out + p * o_ps + off, r);
@@ -495,9 +539,12 @@ static int addsub_plain_impl(evah_ctx *c, const evah_ct *a, const evah_pt *b, ev
   acquire(c, b->buf);
   if (a->limbs != b->limbs) throw std::invalid_argument("encrypted and plain parameter mismatch");
   if (!same_scale(a->scale, b->scale)) throw std::invalid_argument("scale mismatch");
+  check_pt_batch(a, b);
   evah_ct *o = ct_new(c, a->size, a->limbs, a->scale, a->batch);
+  // the plaintext is a one-polynomial operand: only polynomial 0 reads it, at instance * b_ps — 0 for a shared plaintext,
+  // the instance stride of a batched one
   EW_LAUNCH(k_addsub, ew_grid(c, a->limbs, a->size * a->batch), dim3(256), 0, c->stream, c->dev, a->d, a->ps,
-                     a->size, b->d, (size_t)0, 1u, o->d, o->ps, sub, a->size);
+                     a->size, b->d, b->batch > 1 ? b->bstride : (size_t)0, 1u, o->d, o->ps, sub, a->size);
   HIPCHK(hipGetLastError());
   *out = o;
   API_END
@@ -571,8 +618,13 @@ int evah_multiply_plain(evah_ctx *c, const evah_ct *a, const evah_pt *b, evah_ct
   if (a->limbs != b->limbs) throw std::invalid_argument("encrypted and plain parameter mismatch");
   const double ns = a->scale * b->scale;
   check_scale(c, ns, a->limbs);
+  check_pt_batch(a, b);
   evah_ct *o = ct_new(c, a->size, a->limbs, ns, a->batch);
-  EW_LAUNCH(k_mul_plain, ew_grid(c, a->limbs, a->size * a->batch), dim3(256), 0, c->stream, c->dev, a->d, a->ps, b->d, o->d, o->ps);
+  if (b->batch > 1)
+    EW_LAUNCH(k_mul_plain_inst, ew_grid(c, a->limbs, a->size * a->batch), dim3(256), 0, c->stream, c->dev, a->d, a->ps, b->d, b->bstride,
+              a->size, o->d, o->ps);
+  else
+    EW_LAUNCH(k_mul_plain, ew_grid(c, a->limbs, a->size * a->batch), dim3(256), 0, c->stream, c->dev, a->d, a->ps, b->d, o->d, o->ps);
   HIPCHK(hipGetLastError());
   *out = o;
   API_END
@@ -591,6 +643,7 @@ int evah_multiply_plain_many(evah_ctx *c, const evah_ct *const *cts, const evah_
     const evah_ct *a = cts[i];
     const evah_pt *b = pts[i];
     if (a->batch != 1) throw std::invalid_argument("multiply_plain_many takes single ciphertexts");
+    if (b->batch != 1) throw std::invalid_argument("multiply_plain_many takes single plaintexts (a batched plaintext goes with a batched ciphertext through evah_multiply_plain)");
     if (a->size != size || a->limbs != l) throw std::invalid_argument("encrypted parameter mismatch in batch");
     if (b->limbs != l) throw std::invalid_argument("encrypted and plain parameter mismatch");
     scales[i] = a->scale * b->scale;
@@ -617,6 +670,7 @@ int evah_weighted_sum(evah_ctx *c, const evah_ct *const *cts, const evah_pt *con
   const evah_ct *f = cts[0];
   const double scale = f->scale * (pts[0] ? pts[0]->scale : 1.0);
   WsTab tab{};
+  bool per_inst = false; // some weight differs per instance: the table with instance strides (k_weighted_sum_inst)
   for (uint32_t j = 0; j < n; j++) {
     const evah_ct *a = cts[j];
     if (a->limbs != f->limbs) throw std::invalid_argument("encrypted1 and encrypted2 parameter mismatch");
@@ -626,6 +680,8 @@ int evah_weighted_sum(evah_ctx *c, const evah_ct *const *cts, const evah_pt *con
     const double sj = a->scale * (pts[j] ? pts[j]->scale : 1.0);
     if (pts[j]) check_scale(c, sj, a->limbs);
     if (!same_scale(sj, scale)) throw std::invalid_argument("scale mismatch");
+    if (pts[j]) check_pt_batch(a, pts[j]);
+    per_inst = per_inst || (pts[j] && pts[j]->batch > 1);
     acquire(c, a->buf);
     if (pts[j]) acquire(c, pts[j]->buf);
     tab.ct[j] = a->d;
@@ -633,7 +689,18 @@ int evah_weighted_sum(evah_ctx *c, const evah_ct *const *cts, const evah_pt *con
     tab.ct_ps[j] = (uint32_t)(a->ps / c->N);
   }
   evah_ct *o = ct_new(c, f->size, f->limbs, scale, f->batch);
-  EW_LAUNCH(k_weighted_sum, ew_grid(c, f->limbs, f->size * f->batch), dim3(256), 0, c->stream, c->dev, tab, n, o->d, o->ps);
+  if (per_inst) {
+    WsTabInst ti{};
+    for (uint32_t j = 0; j < n; j++) {
+      ti.ct[j] = tab.ct[j];
+      ti.pt[j] = tab.pt[j];
+      ti.ct_ps[j] = tab.ct_ps[j];
+      ti.pt_bs[j] = pts[j] && pts[j]->batch > 1 ? (uint32_t)(pts[j]->bstride / c->N) : 0u;
+    }
+    EW_LAUNCH(k_weighted_sum_inst, ew_grid(c, f->limbs, f->size * f->batch), dim3(256), 0, c->stream, c->dev, ti, n, f->size, o->d, o->ps);
+  } else {
+    EW_LAUNCH(k_weighted_sum, ew_grid(c, f->limbs, f->size * f->batch), dim3(256), 0, c->stream, c->dev, tab, n, o->d, o->ps);
+  }
   HIPCHK(hipGetLastError());
   *out = o;
   API_END

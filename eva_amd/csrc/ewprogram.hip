@@ -165,7 +165,8 @@ int evah_elementwise_program(evah_ctx *c, const evah_val *in, uint32_t n_in, con
     if (x.preg[p] >= 0) return x.preg[p];
     if (!x.ct && !x.pt) throw std::logic_error("elementwise program: polynomial of a computed value is missing");
     u64 *base = x.ct ? x.ct->d + (size_t)p * x.ct->ps : x.pt->d;
-    const uint32_t bs = x.ct ? (uint32_t)((size_t)x.ct->size * x.ct->ps / N) : 0u;
+    // instances of a batched handle; a plaintext is shared (0) unless it is batched itself (its own instance stride)
+    const uint32_t bs = x.ct ? (uint32_t)((size_t)x.ct->size * x.ct->ps / N) : x.pt->batch > 1 ? (uint32_t)(x.pt->bstride / N) : 0u;
     pptr.push_back({base, bs});
     x.preg[p] = n_vreg++;
     pins.push_back({EW_LOAD, x.preg[p], (int)pptr.size() - 1, 0, 0, 0});
@@ -230,6 +231,7 @@ int evah_elementwise_program(evah_ctx *c, const evah_val *in, uint32_t n_in, con
         if (o.op == 13) {
           r.scale = a.scale * b.scale;
           check_scale(c, r.scale, a.limbs);
+          if (b.pt->batch != 1 && b.pt->batch != a.batch) throw std::invalid_argument("plaintext batch differs from the ciphertext's");
           if (b.pt->uniform && c->tun.ew_uniform) { // a scalar per limb: no load of the plaintext, Shoup products
             pptr.push_back({b.pt->d, 0u});
             const int ps = (int)pptr.size() - 1;
@@ -240,6 +242,7 @@ int evah_elementwise_program(evah_ctx *c, const evah_val *in, uint32_t n_in, con
           }
         } else {
           if (!same_scale(a.scale, b.scale)) throw std::invalid_argument("scale mismatch");
+          if (b.pt->batch != 1 && b.pt->batch != a.batch) throw std::invalid_argument("plaintext batch differs from the ciphertext's");
           r.scale = a.scale;
           r.preg[0] = emit(o.op == 11 ? EW_ADD : EW_SUB, poly(ia, 0), poly(ib, 0));
           for (uint32_t p = 1; p < a.size; p++) r.preg[p] = poly(ia, p);

@@ -160,8 +160,9 @@ struct evah_ct {
   double scale;
   // `batch` independent ciphertexts of identical shape in one handle: instance b starts at
   // d + b * size * ps, i.e. the handle is batch * size polynomials at a uniform stride.  Every
-  // evaluator entry point applies to all instances in one launch set (plaintext operands and keys
-  // are shared); this is how a batch of independent DAG instances is run (BASELINE config 4).
+  // evaluator entry point applies to all instances in one launch set (keys are shared; a plaintext
+  // operand is shared unless it is itself batched, evah_pt::batch); this is how a batch of independent
+  // DAG instances is run (BASELINE config 4).
   uint32_t batch = 1;
 };
 struct evah_pt {
@@ -169,6 +170,12 @@ struct evah_pt {
   u64 *d;
   uint32_t limbs;
   double scale;
+  // `batch` plaintexts of one shape in one handle (evah_pt_encode_array): instance b is [limbs][N] at d + b * bstride.
+  // The stride is the row of the handle the words were made for, so aliases and views with fewer limbs keep addressing
+  // their instances.  batch == 1 is the plaintext every instance of a batched ciphertext shares; a batched plaintext
+  // pairs instance b with instance b of a ciphertext of the same batch, and is never uniform.
+  uint32_t batch = 1;
+  size_t bstride = 0; // words between instances (limbs * N of the allocation)
   // every word of a limb's row is the same residue (evah_pt_uniform: the encoding of a uniform constant,
   // Program::makeUniformConstant).  Multiplying by such a plaintext is multiplying by a scalar of Z_q, which commutes with
   // the NTT: the convolution windows use it (ntt_window_lin.hip.h).  Cleared by anything that rewrites the words.
@@ -665,13 +672,19 @@ inline void ct_views(evah_ctx *c, FreshBuf &ob, uint32_t n, uint32_t size, uint3
   ob.b->refs = (int)n;
   ob.b = nullptr;
 }
-inline evah_pt *pt_new(evah_ctx *c, uint32_t limbs, double scale) {
+inline evah_pt *pt_new(evah_ctx *c, uint32_t limbs, double scale, uint32_t batch = 1) {
   evah_pt *t = new evah_pt;
-  t->buf = buf_new(c, (size_t)limbs * c->N);
+  t->buf = buf_new(c, (size_t)batch * limbs * c->N);
   t->d = t->buf->d;
   t->limbs = limbs;
   t->scale = scale;
+  t->batch = batch;
+  t->bstride = (size_t)limbs * c->N;
   return t;
+}
+// what every entry point that pairs a ciphertext with a plaintext operand checks: shared (batch 1), or one per instance
+inline void check_pt_batch(const evah_ct *a, const evah_pt *b) {
+  if (b->batch != 1 && b->batch != a->batch) throw std::invalid_argument("plaintext batch differs from the ciphertext's");
 }
 
 // rotate.hip: would evah_rotate_many hoist n rotations of one l-limb ciphertext of B instances?

@@ -658,8 +658,13 @@ int evah_pt_copy(evah_ctx *c, const evah_pt *src, evah_pt **out) {
   API_BEGIN
   use(c);
   acquire(c, src->buf);
-  evah_pt *o = pt_new(c, src->limbs, src->scale);
-  HIPCHK(hipMemcpyAsync(o->d, src->d, sizeof(u64) * (size_t)src->limbs * c->N, hipMemcpyDefault, c->stream));
+  evah_pt *o = pt_new(c, src->limbs, src->scale, src->batch);
+  const size_t row = sizeof(u64) * (size_t)src->limbs * c->N;
+  if (src->batch == 1 || src->bstride == (size_t)src->limbs * c->N)
+    HIPCHK(hipMemcpyAsync(o->d, src->d, row * src->batch, hipMemcpyDefault, c->stream));
+  else // a batched plaintext seen with fewer limbs than it was made with: one copy per instance
+    for (uint32_t b = 0; b < src->batch; b++)
+      HIPCHK(hipMemcpyAsync(o->d + b * o->bstride, src->d + b * src->bstride, row, hipMemcpyDefault, c->stream));
   o->uniform = src->uniform;
   *out = o;
   API_END
@@ -776,6 +781,7 @@ int evah_pt_write(evah_ctx *c, evah_pt *pt, const uint64_t *data) {
   API_BEGIN
   use(c);
   if (c->capturing) throw std::logic_error("evah_pt_write cannot be captured into a graph");
+  if (pt->batch != 1) throw std::invalid_argument("evah_pt_write takes a single plaintext");
   acquire(c, pt->buf);
   pt->uniform = false;
   HIPCHK(hipMemcpyAsync(pt->d, data, sizeof(u64) * (size_t)pt->limbs * c->N, hipMemcpyHostToDevice, c->stream));
@@ -917,10 +923,33 @@ int evah_pt_download(evah_ctx *c, const evah_pt *pt, uint64_t *out) {
   API_BEGIN
   use(c);
   if (c->capturing) throw std::logic_error("this call synchronises with the host and cannot be captured into a graph");
+  if (pt->batch != 1) throw std::invalid_argument("evah_pt_download takes a single plaintext (evah_pt_download_instances reads a batched one)");
   acquire(c, pt->buf);
   HIPCHK(hipMemcpyAsync(out, pt->d, sizeof(u64) * (size_t)pt->limbs * c->N, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   count_d2h(c, sizeof(u64) * (size_t)pt->limbs * c->N, true);
+  API_END
+}
+
+int evah_pt_batch(const evah_pt *pt, uint32_t *batch) {
+  API_BEGIN
+  *batch = pt->batch;
+  API_END
+}
+
+// every instance of a plaintext handle -> out [batch][limbs][N]: one linear copy per instance (a view with fewer limbs
+// than the handle was made with has its instances apart), then a drain
+int evah_pt_download_instances(evah_ctx *c, const evah_pt *pt, uint64_t *out) {
+  API_BEGIN
+  use(c);
+  if (c->capturing) throw std::logic_error("this call synchronises with the host and cannot be captured into a graph");
+  if (!out) throw std::invalid_argument("output pointer is null");
+  acquire(c, pt->buf);
+  const size_t row = (size_t)pt->limbs * c->N;
+  for (uint32_t b = 0; b < pt->batch; b++)
+    HIPCHK(hipMemcpyAsync(out + b * row, pt->d + b * pt->bstride, sizeof(u64) * row, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  count_d2h(c, sizeof(u64) * row * pt->batch, true);
   API_END
 }
 

@@ -126,11 +126,17 @@ int evah_execute(evah_ctx *c, const evah_op *ops, uint32_t n_ops, evah_val *tab,
       for (int32_t sstep : ls.steps) if (sstep != 0) return true;
       return false;
     };
+    auto per_instance = [&](const LazySum &ls) {
+      for (const evah_pt *w : ls.pts) if (w && w->batch > 1) return true;
+      return false;
+    };
     std::vector<std::vector<uint32_t>> groups; // windows: one or two sums over the same terms
     std::vector<uint32_t> plain;               // evaluated by evah_weighted_sum
     for (uint32_t v : vals) {
       LazySum &ls = st.sums.at(v);
-      if (!rotated(ls)) { plain.push_back(v); continue; }
+      // a weight that differs per instance (evah_pt::batch > 1) keeps the sum out of the fused windows, whose kernels
+      // read one weight for all instances: its rotations are materialised once below, then evah_weighted_sum
+      if (!rotated(ls) || per_instance(ls)) { plain.push_back(v); continue; }
       bool placed = false;
       for (auto &g : groups)
         if (g.size() < 2 && same_terms(st.sums.at(g[0]), ls)) { g.push_back(v); placed = true; break; }
@@ -461,6 +467,7 @@ int evah_execute(evah_ctx *c, const evah_op *ops, uint32_t n_ops, evah_val *tab,
       node->size = a.size; node->scale = a.scale;
     } else if (b.kind == 2) {
       if (a.limbs != b.limbs) return false;
+      if (b.pt->batch != 1 && b.pt->batch != a.batch) return false;
       node->size = a.size;
       if (o.op == 13) {
         node->scale = a.scale * b.scale;
@@ -690,7 +697,7 @@ int evah_execute(evah_ctx *c, const evah_op *ops, uint32_t n_ops, evah_val *tab,
         const uint32_t a = st.drots.count(o.src0) ? o.src0 : o.src1, b = a == o.src0 ? o.src1 : o.src0;
         const DRot &d = st.drots[a];
         evah_pt *w = static_cast<evah_pt *>(tab[b].h);
-        if (w->limbs != d.src->limbs) { single(o); continue; } // multiply_plain reports the mismatch
+        if (w->limbs != d.src->limbs || (w->batch != 1 && w->batch != d.src->batch)) { single(o); continue; } // multiply_plain reports the mismatch
         LazySum ls;
         ls.size = d.src->size; ls.limbs = d.src->limbs; ls.scale = d.src->scale * w->scale;
         ls.cts.push_back(alias_ct(d.src));
@@ -703,7 +710,7 @@ int evah_execute(evah_ctx *c, const evah_op *ops, uint32_t n_ops, evah_val *tab,
         const uint32_t a = is_plain_ct(o.src0) ? o.src0 : o.src1, b = a == o.src0 ? o.src1 : o.src0;
         evah_ct *x = static_cast<evah_ct *>(tab[a].h);
         evah_pt *w = static_cast<evah_pt *>(tab[b].h);
-        if (w->limbs != x->limbs) { single(o); continue; } // multiply_plain reports the mismatch
+        if (w->limbs != x->limbs || (w->batch != 1 && w->batch != x->batch)) { single(o); continue; } // multiply_plain reports the mismatch
         LazySum ls;
         ls.size = x->size; ls.limbs = x->limbs; ls.scale = x->scale * w->scale;
         ls.cts.push_back(alias_ct(x));

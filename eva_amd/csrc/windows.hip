@@ -95,6 +95,7 @@ int evah_rotate_weighted_sums(evah_ctx *c, const evah_ct *const *cts, const int3
         for (uint32_t j = 0; j < nt; j++) {
           const evah_pt *pt = pts[p0 + s * nt + j];
           if (pt && pt->limbs != l) throw std::invalid_argument("encrypted and plain parameter mismatch");
+          if (pt && pt->batch != 1) throw std::invalid_argument("rotate_weighted_sums takes weights that all instances share (a batched plaintext goes through evah_weighted_sum)");
           const double sj = cts[t0 + j]->scale * (pt ? pt->scale : 1.0);
           if (pt) {
             check_scale(c, sj, l);

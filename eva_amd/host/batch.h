@@ -84,6 +84,9 @@ inline void HipPublic::run_batch_groups(Program &program, size_t n_instances, bo
       sizes = std::move(split);
     }
   }
+  // host rows that the groups' stream-ordered encodes of per-instance raw values read (HipExecutor::staging,
+  // DESIGN.md 1.10): held until every queue has been synchronised
+  std::vector<std::shared_ptr<const void>> staged;
   const auto t_begin = std::chrono::steady_clock::now();
   try {
     for (size_t i0 = 0; g < sizes.size(); i0 += sizes[g], g++) {
@@ -101,6 +104,11 @@ inline void HipPublic::run_batch_groups(Program &program, size_t n_instances, bo
         for (TermId t = 0; t < program.size(); t++)
           if (done[t]) ex.set_value(t, consts[t]);
       }
+      struct TakeStaging { // also when the group fails half way: its copies may be in flight
+        std::vector<std::shared_ptr<const void>> &to;
+        HipExecutor &ex;
+        ~TakeStaging() { to.insert(to.end(), ex.staging.begin(), ex.staging.end()); }
+      } take{staged, ex};
       set_in(ex, i0, n);
       if (library_scheduler) ex.run_library(&done, true);
       else run_counted(program, ex, &done);
@@ -205,6 +213,7 @@ inline std::vector<HipValuation> HipPublic::execute_batch_multi(Program &program
   for (ConstCache &c1 : mc)
     if (c1.hash != prog_hash || c1.values.size() != program.size()) c1 = ConstCache{};
   std::vector<size_t> turn(G, 0);
+  std::vector<std::shared_ptr<const void>> staged; // rows the groups' stream-ordered encodes read, until the queues are synchronised
   auto sync_all = [&]() {
     int rc = 0;
     for (auto &f : batch_queues) rc |= evah_ctx_sync(f->h);
@@ -228,6 +237,11 @@ inline std::vector<HipValuation> HipPublic::execute_batch_multi(Program &program
         for (TermId t = 0; t < program.size(); t++)
           if (cm.done[t]) ex.set_value(t, cm.values[t]);
       }
+      struct TakeStaging {
+        std::vector<std::shared_ptr<const void>> &to;
+        HipExecutor &ex;
+        ~TakeStaging() { to.insert(to.end(), ex.staging.begin(), ex.staging.end()); }
+      } take{staged, ex};
       ex.set_inputs_batch(chunk, true);
       ex.run_library(&cm.done, true);
       ex.get_outputs_batch(all.data() + i0, n, true);

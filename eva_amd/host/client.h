@@ -179,8 +179,9 @@ struct ArrayInputs {
   std::vector<InputClass> cls;
   std::vector<const ArrayView *> arr;
 };
+// plains: unencrypted inputs of type Raw with a row per instance — copied into the batch in their own type
 inline ArrayInputs plan_array_inputs(const HostContext &hc, const std::map<std::string, ArrayView> &arrays, const Valuation &shared,
-                                     const CKKSSignature &sig, HipValuationBatch &out) {
+                                     const CKKSSignature &sig, HipValuationBatch &out, const std::map<std::string, ArrayView> &plains = {}) {
   check_vec_size(sig, hc.N / 2);
   if (arrays.empty()) throw std::invalid_argument("encrypt_array: no encrypted input array was given");
   ArrayInputs in;
@@ -220,6 +221,23 @@ inline ArrayInputs plan_array_inputs(const HostContext &hc, const std::map<std::
     in.cls.push_back(c);
     in.arr.push_back(it == arrays.end() ? nullptr : &it->second);
   }
+  for (auto &kv : plains) {
+    const std::string &name = kv.first;
+    const ArrayView &a = kv.second;
+    if (arrays.count(name) || shared.count(name)) throw std::invalid_argument("encrypt_array: input " + name + " is given twice");
+    const InputClass c = classify_input(hc, sig, name);
+    if (c.kind != Type::Raw) throw std::invalid_argument("encrypt_array: plain_arrays takes unencrypted inputs of type Raw, input " + name + " is not one");
+    if (a.n != (size_t)sig.vec_size) throw std::runtime_error("Input size does not match program vector size (input " + name + ")");
+    if (a.B != out.B)
+      throw std::invalid_argument("encrypt_array: input " + name + " has " + std::to_string(a.B) + " instances, " + arrays.begin()->first + " has " +
+                                  std::to_string(out.B));
+    PlainRows pr;
+    const uint8_t *src = static_cast<const uint8_t *>(a.data);
+    pr.bytes = std::make_shared<std::vector<uint8_t>>(src, src + a.B * a.n * a.itemsize());
+    pr.view = a;
+    pr.view.data = pr.bytes->data();
+    out.plains[name] = std::move(pr);
+  }
   return in;
 }
 inline void require_array_path(bool on_device, bool resident) {
@@ -238,6 +256,7 @@ inline HipValuation batch_instance(const HipValuationBatch &vb, size_t b) {
   HipValuation out;
   out.params = vb.params;
   out.values = vb.shared;
+  for (auto &kv : vb.plains) out.values[kv.first] = array_row_doubles(kv.second.view, b); // row b as an ordinary raw value
   for (auto &kv : vb.ciphers) {
     size_t first = 0;
     for (const BatchSegment &s : kv.second.segments) {
@@ -303,6 +322,31 @@ inline HipValuationBatch batch_of_list(const std::vector<const HipValuation *> &
   }
   for (auto &kv : vb.ciphers)
     if (kv.second.segments.size() != vb.B) throw std::runtime_error("value " + kv.first + " is not a ciphertext in every valuation of the list");
+  // a raw value that is not the same in every valuation keeps a row per instance
+  for (auto it = vb.shared.begin(); it != vb.shared.end();) {
+    const auto *r0 = std::get_if<std::vector<double>>(&it->second);
+    bool rows = false;
+    if (r0) {
+      bool everywhere = true; // (a list whose later valuations lack the value keeps instance 0's, as before)
+      for (size_t b = 1; b < list.size() && everywhere; b++) {
+        auto f = list[b]->values.find(it->first);
+        const auto *rb = f == list[b]->values.end() ? nullptr : std::get_if<std::vector<double>>(&f->second);
+        everywhere = rb && rb->size() == r0->size();
+        rows = rows || (everywhere && *rb != *r0);
+      }
+      rows = rows && everywhere;
+    }
+    if (!rows) { ++it; continue; }
+    PlainRows pr;
+    pr.bytes = std::make_shared<std::vector<uint8_t>>(list.size() * r0->size() * sizeof(double));
+    for (size_t b = 0; b < list.size(); b++) {
+      const auto &rb = std::get<std::vector<double>>(list[b]->values.at(it->first));
+      std::memcpy(pr.bytes->data() + b * rb.size() * sizeof(double), rb.data(), rb.size() * sizeof(double));
+    }
+    pr.view = ArrayView{pr.bytes->data(), EVAH_F64, list.size(), r0->size()};
+    vb.plains[it->first] = std::move(pr);
+    it = vb.shared.erase(it);
+  }
   return vb;
 }
 // u, e0, e1 of one public-key encryption from rng, in evahost::encrypt's order, as int8 [3][N] at small
@@ -492,11 +536,11 @@ inline std::vector<HostCipher> HipPublic::encrypt_group_sampled(const std::vecto
 // <= 64 as ONE evah_encode_encrypt_array each, in the array's type, and the batched handles are kept whole.  Device and
 // resident valuations only: there is no host path behind this call.
 inline HipValuationBatch HipPublic::encrypt_array(const std::map<std::string, ArrayView> &arrays, const Valuation &shared, const CKKSSignature &sig,
-                                                  uint64_t seed) {
+                                                  uint64_t seed, const std::map<std::string, ArrayView> &plains) {
   require_array_path(client_on_device(), resident);
   HipValuationBatch out;
   out.params = host;
-  const ArrayInputs in = plan_array_inputs(*host, arrays, shared, sig, out);
+  const ArrayInputs in = plan_array_inputs(*host, arrays, shared, sig, out, plains);
   ensure_public_key();
   out.root = dev;
   std::unique_ptr<SecureRng> stream = seed ? std::make_unique<SecureRng>(seed, 5) : std::make_unique<SecureRng>();
@@ -704,12 +748,12 @@ public:
   // so instance b is encrypt_batch's word for word.  Per name the rows leave in segments of <= 64 as ONE
   // evah_encode_encrypt_symmetric_array each; the handles are kept whole and the seeds stay with the batch.
   HipValuationBatch encrypt_array(const std::map<std::string, ArrayView> &arrays, const Valuation &shared, const CKKSSignature &sig,
-                                  uint64_t seed = 0) {
+                                  uint64_t seed = 0, const std::map<std::string, ArrayView> &plains = {}) {
     require_array_path(on_device(), resident);
     HipValuationBatch out;
     out.params = host;
     out.root = dev;
-    const ArrayInputs in = plan_array_inputs(*host, arrays, shared, sig, out);
+    const ArrayInputs in = plan_array_inputs(*host, arrays, shared, sig, out, plains);
     std::unique_ptr<SecureRng> seeds = seed ? std::make_unique<SecureRng>(seed, 4) : std::make_unique<SecureRng>();
     std::unique_ptr<SecureRng> errors = seed ? std::make_unique<SecureRng>(seed, 3) : std::make_unique<SecureRng>();
     std::vector<std::vector<std::array<uint8_t, 32>>> ek(in.names.size()); // per name, per instance

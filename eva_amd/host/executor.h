@@ -39,7 +39,21 @@ public:
   struct LazyRelin {
     TermId src;
   };
-  using RuntimeValue = std::variant<std::monostate, std::shared_ptr<CtHandle>, std::shared_ptr<PtHandle>, std::vector<double>, LazyPlain, LazyRelin>;
+  // A raw (unencrypted) value that differs between the instances of a batched run, row b for instance b:
+  // doubles [B][vec_size], or — an input that came as an array and that no raw op has touched — the caller's typed rows
+  // [B][view.n], which an Encode sends to the device in their own type.
+  struct RawRows {
+    uint32_t B = 0;
+    std::shared_ptr<const std::vector<double>> rows; // [B][vec_size]; null while only `view` holds the value
+    ArrayView view;                                   // the caller's typed rows (data == nullptr: none)
+    std::shared_ptr<const void> keep;                 // what keeps view.data alive
+    std::string origin;                               // the input the rows come from (messages)
+  };
+  using RowsPtr = std::shared_ptr<RawRows>; // (held by pointer: the variant every term carries keeps its size)
+  using RuntimeValue = std::variant<std::monostate, std::shared_ptr<CtHandle>, std::shared_ptr<PtHandle>, std::vector<double>, LazyPlain, LazyRelin, RowsPtr>;
+  // host arrays that stream-ordered encodes of this executor still read (evah_pt_encode_array_async): the caller of a
+  // batched run takes them over and keeps them until its queues are synchronised
+  std::vector<std::shared_ptr<const void>> staging;
 
   // queues: issue queues (HIP streams) of one device — queues[0] is the root context, the rest
   // are its forks.  Independent DAG nodes are spread over them (the GPU counterpart of the
@@ -140,8 +154,9 @@ public:
 
   // A batch of independent input valuations for ONE program (BASELINE config 4): every encrypted
   // input becomes one batched device handle ([B][size][limbs][N]); from there each node is a
-  // single backend call that covers all B instances.  Plaintext / raw inputs are shared by the
-  // batch, so they have to be identical across the instances.
+  // single backend call that covers all B instances.  A pre-encoded plaintext input is shared by the
+  // batch, so it has to be identical across the instances; a raw input that differs becomes a
+  // per-instance value (RawRows), one that is the same everywhere the shared vector it always was.
   // async: the uploads are only enqueued (evah_ct_upload_instances_async); the caller keeps the
   // valuations alive and synchronises the queue before touching them
   void set_inputs_batch(const std::vector<const HipValuation *> &batch, bool async = false) {
@@ -200,12 +215,28 @@ public:
         objects[t] = std::make_shared<PtHandle>(ctx, h);
       } else {
         const auto &raw = std::get<std::vector<double>>(kv.second);
-        for (const HipValuation *v : batch)
-          if (std::get<std::vector<double>>(v->values.at(kv.first)) != raw)
-            throw std::runtime_error("execute_batch: unencrypted input " + kv.first + " must be the same for every instance");
-        std::vector<double> v;
-        ConstantValue{raw}.expand_to(v, program.vec_size());
-        objects[t] = std::move(v);
+        bool same = true;
+        for (const HipValuation *v : batch) same = same && std::get<std::vector<double>>(v->values.at(kv.first)) == raw;
+        if (same) { // one value for every instance: the shared operand
+          std::vector<double> v;
+          ConstantValue{raw}.expand_to(v, program.vec_size());
+          objects[t] = std::move(v);
+          continue;
+        }
+        // rows that differ: a per-instance raw value
+        const size_t n = program.vec_size();
+        auto rows = std::make_shared<std::vector<double>>();
+        rows->reserve((size_t)B * n);
+        std::vector<double> one;
+        for (const HipValuation *v : batch) {
+          ConstantValue{std::get<std::vector<double>>(v->values.at(kv.first))}.expand_to(one, n);
+          rows->insert(rows->end(), one.begin(), one.end());
+        }
+        RawRows rr;
+        rr.B = B;
+        rr.rows = std::move(rows);
+        rr.origin = kv.first;
+        objects[t] = std::make_shared<RawRows>(std::move(rr));
       }
     }
   }
@@ -243,6 +274,7 @@ public:
         chk((async ? evah_ct_download_instances_async : evah_ct_download_instances)(ctx, (*c)->h, ptrs.data()));
       } else {
         if (auto *p = std::get_if<std::shared_ptr<PtHandle>>(&o)) {
+          refuse_batched_plain_output(kv.first, (*p)->h);
           HostPlain hp;
           chk(evah_pt_info((*p)->h, &hp.limbs, &hp.scale));
           hp.data.resize((size_t)hp.limbs * host.N);
@@ -250,6 +282,11 @@ public:
           for (size_t b = 0; b < n_outs; b++) outs[b].values[kv.first] = hp;
         } else if (auto *r = std::get_if<std::vector<double>>(&o)) {
           for (size_t b = 0; b < n_outs; b++) outs[b].values[kv.first] = *r;
+        } else if (std::holds_alternative<RowsPtr>(o)) { // row b to instance b's valuation
+          const std::vector<double> &rows = rows_of(kv.second);
+          const size_t n = program.vec_size();
+          if (std::get<RowsPtr>(o)->B != n_outs) throw std::runtime_error("Output " + kv.first + ": its rows are not one per instance");
+          for (size_t b = 0; b < n_outs; b++) outs[b].values[kv.first] = std::vector<double>(rows.begin() + b * n, rows.begin() + (b + 1) * n);
         } else {
           throw std::runtime_error("Output " + kv.first + " was not computed");
         }
@@ -292,6 +329,31 @@ public:
         throw std::runtime_error("execute_batch: shared input " + kv.first + " is a ciphertext");
       }
     }
+    // rows i0 .. i0 + n - 1 of every per-instance raw input, in their own type and without conversion;
+    // an input whose rows are all equal over the whole batch takes the shared path in every group
+    for (auto &kv : vb.plains) {
+      const TermId t = program.input(kv.first);
+      const ArrayView &a = kv.second.view;
+      if (a.B != vb.B || i0 + n > a.B) throw std::runtime_error("execute_batch: input " + kv.first + " does not hold a row for every instance");
+      if (a.n < 1 || program.vec_size() % a.n) throw std::runtime_error("Input size does not match program vector size (input " + kv.first + ")");
+      const size_t row_bytes = a.n * a.itemsize();
+      bool same = true;
+      for (size_t b = 1; b < a.B && same; b++) same = std::memcmp(a.row(0), a.row(b), row_bytes) == 0;
+      if (same) {
+        std::vector<double> v;
+        ConstantValue{array_row_doubles(a, i0)}.expand_to(v, program.vec_size());
+        objects[t] = std::move(v);
+        continue;
+      }
+      RawRows rr;
+      rr.B = (uint32_t)n;
+      rr.view = a;
+      rr.view.data = a.row(i0);
+      rr.view.B = n;
+      rr.keep = kv.second.bytes;
+      rr.origin = kv.first;
+      objects[t] = std::make_shared<RawRows>(std::move(rr));
+    }
   }
   // get_outputs_batch for a batch of batched handles: the group's batched output handle is one more segment of `out`, as it
   // is (no evah_ct_unstack, no per-instance values); queue: the fork the group ran on (null: the root's own queue)
@@ -306,8 +368,20 @@ public:
         chk(evah_ct_batch((*c)->h, &s.n));
         if (s.n != n_outs) throw std::runtime_error("Output " + kv.first + " does not depend on an encrypted input of the batch");
         out.ciphers[kv.first].segments.push_back(std::move(s));
+      } else if (std::holds_alternative<RowsPtr>(o)) { // the group's rows behind those of the groups before it
+        const std::vector<double> &rows = rows_of(kv.second);
+        if (std::get<RowsPtr>(o)->B != n_outs) throw std::runtime_error("Output " + kv.first + ": its rows are not one per instance");
+        PlainRows &pr = out.plains[kv.first];
+        if (!pr.bytes) pr.bytes = std::make_shared<std::vector<uint8_t>>();
+        const uint8_t *src = reinterpret_cast<const uint8_t *>(rows.data());
+        pr.bytes->insert(pr.bytes->end(), src, src + rows.size() * sizeof(double));
+        pr.view.dtype = EVAH_F64;
+        pr.view.n = program.vec_size();
+        pr.view.B = pr.bytes->size() / (pr.view.n * sizeof(double));
+        pr.view.data = pr.bytes->data();
       } else if (!out.shared.count(kv.first)) {
         if (auto *p = std::get_if<std::shared_ptr<PtHandle>>(&o)) {
+          refuse_batched_plain_output(kv.first, (*p)->h);
           HostPlain hp;
           chk(evah_pt_info((*p)->h, &hp.limbs, &hp.scale));
           hp.data.resize((size_t)hp.limbs * host.N);
@@ -343,13 +417,27 @@ public:
       objects[t] = std::move(v);
     } break;
     case Op::Encode:
-      if (!is_raw(a[0])) throw std::runtime_error("Encode expects a raw operand");
+      if (!is_raw(a[0]) && !is_rows(a[0])) throw std::runtime_error("Encode expects a raw operand");
       objects[t] = LazyPlain{a[0], x.encode_scale, x.encode_level};
       break;
     case Op::Add:
     case Op::Sub:
     case Op::Mul:
-      if (is_raw(a[0]) && is_raw(a[1])) {
+      if ((is_rows(a[0]) || is_rows(a[1])) && (is_raw(a[0]) || is_rows(a[0])) && (is_raw(a[1]) || is_rows(a[1]))) {
+        // raw arithmetic row by row; a shared raw operand broadcasts over the instances
+        const uint32_t B = is_rows(a[0]) ? std::get<RowsPtr>(objects[a[0]])->B : std::get<RowsPtr>(objects[a[1]])->B;
+        const size_t n = program.vec_size();
+        if (is_rows(a[0]) && is_rows(a[1]) && std::get<RowsPtr>(objects[a[1]])->B != B) throw std::runtime_error("per-instance raw operands of different batch sizes");
+        const std::vector<double> &u = is_rows(a[0]) ? rows_of(a[0]) : raw(a[0]), &v = is_rows(a[1]) ? rows_of(a[1]) : raw(a[1]);
+        const size_t su = is_rows(a[0]) ? n : 0, sv = is_rows(a[1]) ? n : 0;
+        auto o = std::make_shared<std::vector<double>>((size_t)B * n);
+        for (uint32_t b = 0; b < B; b++)
+          for (size_t i = 0; i < n; i++) {
+            const double p = u[b * su + i], q = v[b * sv + i];
+            (*o)[b * n + i] = x.op == Op::Add ? p + q : x.op == Op::Sub ? p - q : p * q;
+          }
+        objects[t] = derived_rows(is_rows(a[0]) ? a[0] : a[1], std::move(o));
+      } else if (is_raw(a[0]) && is_raw(a[1])) {
         const auto &u = raw(a[0]), &v = raw(a[1]);
         std::vector<double> o(u.size());
         for (size_t i = 0; i < u.size(); i++) o[i] = x.op == Op::Add ? u[i] + v[i] : x.op == Op::Sub ? u[i] - v[i] : u[i] * v[i];
@@ -360,7 +448,20 @@ public:
       break;
     case Op::RotateLeftConst:
     case Op::RotateRightConst:
-      if (is_raw(a[0])) {
+      if (is_rows(a[0])) {
+        const std::vector<double> &u = rows_of(a[0]);
+        const size_t n = program.vec_size();
+        auto o = std::make_shared<std::vector<double>>();
+        o->reserve(u.size());
+        std::vector<double> in, out;
+        for (size_t b = 0; b * n < u.size(); b++) {
+          in.assign(u.begin() + b * n, u.begin() + (b + 1) * n);
+          if (x.op == Op::RotateLeftConst) rotate_left(in, x.rotation, out);
+          else rotate_right(in, x.rotation, out);
+          o->insert(o->end(), out.begin(), out.end());
+        }
+        objects[t] = derived_rows(a[0], std::move(o));
+      } else if (is_raw(a[0])) {
         std::vector<double> o;
         if (x.op == Op::RotateLeftConst) rotate_left(raw(a[0]), x.rotation, o);
         else rotate_right(raw(a[0]), x.rotation, o);
@@ -398,7 +499,11 @@ public:
       }
       break;
     case Op::Negate:
-      if (is_raw(a[0])) {
+      if (is_rows(a[0])) {
+        auto o = std::make_shared<std::vector<double>>(rows_of(a[0]));
+        for (auto &v : *o) v = -v;
+        objects[t] = derived_rows(a[0], std::move(o));
+      } else if (is_raw(a[0])) {
         auto o = raw(a[0]);
         for (auto &v : o) v = -v;
         objects[t] = std::move(o);
@@ -417,6 +522,10 @@ public:
         // throw std::bad_variant_access here (seal_executor.h:197-215 take a Ciphertext); its
         // semantic executor copies (reference_executor.cpp) — which is what the value means.
         objects[t] = raw(a[0]);
+        break;
+      }
+      if (is_rows(a[0])) { // the same for a per-instance raw value
+        objects[t] = objects[a[0]];
         break;
       }
       if (x.op == Op::Relinearize) {
@@ -543,7 +652,7 @@ public:
   // feed a not-yet-materialised Encode stay until that Encode is dropped.
   void free(TermId t) {
     if (program.at(t).op == Op::Output) return;
-    if (is_raw(t))
+    if (is_raw(t) || is_rows(t))
       for (TermId u : program.at(t).uses)
         if (std::holds_alternative<LazyPlain>(objects[u])) return;
     if (is_cipher(t))
@@ -592,6 +701,13 @@ public:
         throw std::runtime_error("Output " + kv.first + " was not computed");
       }
     }
+  }
+
+  // an output that is a per-instance plaintext has no host form (HostPlain is one plaintext)
+  void refuse_batched_plain_output(const std::string &name, const evah_pt *h) const {
+    uint32_t pb = 1;
+    chk(evah_pt_batch(h, &pb));
+    if (pb != 1) throw std::runtime_error("Output " + name + " is a plaintext that differs per instance: execute_batch returns raw or encrypted outputs only");
   }
 
 private:
@@ -656,6 +772,31 @@ private:
     return std::holds_alternative<std::shared_ptr<PtHandle>>(objects[t]) || std::holds_alternative<LazyPlain>(objects[t]);
   }
   bool is_raw(TermId t) const { return std::holds_alternative<std::vector<double>>(objects[t]); }
+  bool is_rows(TermId t) const { return std::holds_alternative<RowsPtr>(objects[t]); }
+  // the doubles [B][vec_size] of a per-instance raw value; typed rows are converted (and replicated to vec_size) once
+  const std::vector<double> &rows_of(TermId t) {
+    RawRows &r = *std::get<RowsPtr>(objects[t]);
+    if (!r.rows) {
+      const size_t n = program.vec_size();
+      auto rows = std::make_shared<std::vector<double>>();
+      rows->reserve((size_t)r.B * n);
+      std::vector<double> wide;
+      for (size_t b = 0; b < r.B; b++) {
+        ConstantValue{array_row_doubles(r.view, b)}.expand_to(wide, n);
+        rows->insert(rows->end(), wide.begin(), wide.end());
+      }
+      r.rows = std::move(rows);
+    }
+    return *r.rows;
+  }
+  RowsPtr derived_rows(TermId from, std::shared_ptr<const std::vector<double>> rows) const {
+    const RawRows &f = *std::get<RowsPtr>(objects[from]);
+    RawRows r;
+    r.B = f.B;
+    r.rows = std::move(rows);
+    r.origin = f.origin;
+    return std::make_shared<RawRows>(std::move(r));
+  }
   const std::vector<double> &raw(TermId t) const { return std::get<std::vector<double>>(objects[t]); }
   evah_ct *ct(TermId t) {
     auto *p = std::get_if<std::shared_ptr<CtHandle>>(&objects[t]);
@@ -663,7 +804,8 @@ private:
     return (*p)->h;
   }
   evah_pt *pt(TermId t) {
-    if (auto *lz = std::get_if<LazyPlain>(&objects[t])) objects[t] = encode_raw(lz->src, lz->scale_bits, lz->level);
+    if (auto *lz = std::get_if<LazyPlain>(&objects[t]))
+      objects[t] = is_rows(lz->src) ? encode_rows(lz->src, lz->scale_bits, lz->level) : encode_raw(lz->src, lz->scale_bits, lz->level);
     return std::get<std::shared_ptr<PtHandle>>(objects[t])->h;
   }
 
@@ -699,6 +841,33 @@ private:
     } else if (is_plain(b)) chk(evah_multiply_plain(ctx, ct(a), pt(b), &h));
     else throw std::runtime_error("Unsupported operation encountered");
     return wrap(h);
+  }
+
+  // Encode of a per-instance raw value: ONE evah_pt_encode_array_async for the B rows at the node's
+  // level and scale, stream-ordered so the groups of a batched run keep flowing; the rows it reads are handed to
+  // `staging`.  Typed rows cross in their own type.  There is no host path: a row the device encoder cannot take raises.
+  RuntimeValue encode_rows(TermId src, uint32_t scale_bits, uint32_t level) {
+    RawRows &r = *std::get<RowsPtr>(objects[src]);
+    if (level >= host.k - 1) throw std::runtime_error("Encode level exceeds the modulus chain");
+    const uint32_t limbs = host.k - 1 - level;
+    const double scale = std::pow(2.0, (double)scale_bits);
+    const bool typed = !r.rows && r.view.data;
+    const size_t n = typed ? r.view.n : program.vec_size();
+    for (size_t b = 0; b < r.B; b++) {
+      const std::vector<double> row = typed ? array_row_doubles(r.view, b) : std::vector<double>(r.rows->begin() + b * n, r.rows->begin() + (b + 1) * n);
+      if (!device_encode || !device_encodable(row, scale, limbs))
+        throw std::runtime_error("execute_batch: unencrypted input " + r.origin + ", instance " + std::to_string(b) +
+                                 ": its encoding at scale 2^" + std::to_string(scale_bits) + " is too large for the device encoder");
+    }
+    evah_pt *h = nullptr;
+    if (typed) {
+      chk(evah_pt_encode_array_async(ctx, r.B, r.view.data, r.view.dtype, (uint32_t)n, limbs, scale, &h));
+      staging.push_back(r.keep);
+    } else {
+      chk(evah_pt_encode_array_async(ctx, r.B, r.rows->data(), EVAH_F64, (uint32_t)n, limbs, scale, &h));
+      staging.push_back(r.rows);
+    }
+    return std::make_shared<PtHandle>(ctx, h);
   }
 
   // seal_executor.h:217-243: replicate vec_size -> N/2 slots, encode at 2^scale, level -> limbs.

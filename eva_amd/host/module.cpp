@@ -367,8 +367,20 @@ PYBIND11_MODULE(_eva, m) {
         std::vector<std::string> n;
         for (auto &kv : v.ciphers) n.push_back(kv.first);
         for (auto &kv : v.shared) n.push_back(kv.first);
+        for (auto &kv : v.plains) n.push_back(kv.first);
         return n;
       })
+      .def("plain_arrays", [](const HipValuationBatch &v) {
+        py::dict d;
+        for (auto &kv : v.plains) {
+          const ArrayView &a = kv.second.view;
+          const py::dtype dt = a.dtype == EVAH_F64 ? py::dtype::of<double>() : a.dtype == EVAH_F32 ? py::dtype::of<float>() : py::dtype::of<uint8_t>();
+          py::array arr(dt, std::vector<py::ssize_t>{(py::ssize_t)a.B, (py::ssize_t)a.n});
+          std::memcpy(arr.mutable_data(), a.data, a.B * a.n * a.itemsize());
+          d[py::str(kv.first)] = arr;
+        }
+        return d;
+      }, "the unencrypted values that differ per instance (DESIGN.md 1.10): {name: ndarray [B, n]} in the type they are held in")
       .def("segments", [](const HipValuationBatch &v, const std::string &name) {
         auto it = v.ciphers.find(name);
         if (it == v.ciphers.end()) throw std::out_of_range("No encrypted value named " + name);
@@ -388,8 +400,10 @@ PYBIND11_MODULE(_eva, m) {
       }, "every instance as a SEALValuation (views; a symmetric value keeps its seed, so save() still writes it compressed)");
   py::class_<HipPublic, std::shared_ptr<HipPublic>>(mseal, "SEALPublic", "Public context: encryption and execution on the MI355X")
       .def("_encrypt_array", [](HipPublic &p, const std::map<std::string, py::array> &arrays, const Valuation &shared, const CKKSSignature &sig,
-                                uint64_t seed) { return p.encrypt_array(array_views(arrays), shared, sig, seed); },
-           py::arg("arrays"), py::arg("shared"), py::arg("signature"), py::arg("seed") = 0,
+                                uint64_t seed, const std::map<std::string, py::array> &plains) {
+             return p.encrypt_array(array_views(arrays), shared, sig, seed, array_views(plains));
+           },
+           py::arg("arrays"), py::arg("shared"), py::arg("signature"), py::arg("seed") = 0, py::arg("plain_arrays") = std::map<std::string, py::array>{},
            "encrypt_array on normalised arguments (eva_amd.seal.normalise_arrays): C-contiguous [B, n] arrays of float64, float32 or uint8")
       .def("execute_batch", [](HipPublic &p, Program &program, const HipValuationBatch &inputs) { return p.execute_batch(program, inputs); },
            py::arg("program"), py::arg("inputs"),
@@ -571,8 +585,10 @@ PYBIND11_MODULE(_eva, m) {
          "order and names sorted within an instance, so instance 0 of a seeded call equals encrypt() and no two values share a seed. "
          "device_sampling: each error polynomial is expanded from a 32-byte key of the secret stream, on the device in the grouped calls (DESIGN.md 1.7)")
       .def("_encrypt_array", [](HipSecret &s, const std::map<std::string, py::array> &arrays, const Valuation &shared, const CKKSSignature &sig,
-                                uint64_t seed) { return s.encrypt_array(array_views(arrays), shared, sig, seed); },
-           py::arg("arrays"), py::arg("shared"), py::arg("signature"), py::arg("seed") = 0,
+                                uint64_t seed, const std::map<std::string, py::array> &plains) {
+             return s.encrypt_array(array_views(arrays), shared, sig, seed, array_views(plains));
+           },
+           py::arg("arrays"), py::arg("shared"), py::arg("signature"), py::arg("seed") = 0, py::arg("plain_arrays") = std::map<std::string, py::array>{},
            "encrypt_array on normalised arguments (eva_amd.seal.normalise_arrays); every ciphertext is seeded")
       .def("decrypt_array", [](HipSecret &s, py::object enc, const CKKSSignature &sig, py::object dtype) {
         const py::dtype dt = py::dtype::from_args(dtype);
@@ -603,6 +619,16 @@ PYBIND11_MODULE(_eva, m) {
           py::array_t<double> a({(py::ssize_t)vb->B, (py::ssize_t)sig.vec_size});
           for (size_t b = 0; b < vb->B; b++) std::copy(v.begin(), v.end(), a.mutable_data() + b * v.size());
           out[py::str(kv.first)] = code == EVAH_F32 ? py::array(a.attr("astype")(dt)) : py::array(a);
+        }
+        for (auto &kv : vb->plains) { // an unencrypted output with a row per instance: [B, vec_size] float64
+          const ArrayView &pv = kv.second.view;
+          if (pv.n < 1 || (size_t)sig.vec_size % pv.n) throw std::runtime_error("Output " + kv.first + " does not match the signature's vector size");
+          py::array_t<double> a({(py::ssize_t)vb->B, (py::ssize_t)sig.vec_size});
+          for (size_t b = 0; b < vb->B; b++) {
+            const std::vector<double> row = array_row_doubles(pv, b);
+            for (size_t r = 0; r < (size_t)sig.vec_size / pv.n; r++) std::copy(row.begin(), row.end(), a.mutable_data() + b * sig.vec_size + r * pv.n);
+          }
+          out[py::str(kv.first)] = py::array(a);
         }
         return out;
       }, py::arg("enc_outputs"), py::arg("signature"), py::arg("dtype") = py::module_::import("numpy").attr("float64"),

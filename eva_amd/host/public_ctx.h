@@ -104,8 +104,9 @@ public:
                                           uint64_t seed = 0);
   // encrypt_batch(..., device_sampling = true, seed) for arrays [B][n] in their own type, one per encrypted input, kept as
   // batched handles (client.h); `shared`: the plain and raw inputs, one value for all instances
+  // `plains`: raw inputs with a row per instance, kept in their own type
   HipValuationBatch encrypt_array(const std::map<std::string, ArrayView> &arrays, const Valuation &shared, const CKKSSignature &sig,
-                                  uint64_t seed = 0);
+                                  uint64_t seed = 0, const std::map<std::string, ArrayView> &plains = {});
 
   // SEALPublic::execute (seal.cpp:104-122) — THE hot path.  First call for a program: upload
   // inputs, walk the DAG issuing HIP work over the queues, download outputs.  From the second call

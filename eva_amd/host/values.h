@@ -166,13 +166,6 @@ struct BatchCipher {
   std::vector<BatchSegment> segments;
   std::vector<std::array<uint8_t, 32>> seeds; // symmetric encryptions: the seed of c1 per instance, else empty
 };
-struct HipValuationBatch {
-  size_t B = 0;
-  std::map<std::string, BatchCipher> ciphers;
-  std::unordered_map<std::string, SchemeValue> shared; // plaintexts and raw vectors: one value for all instances
-  std::shared_ptr<DeviceCtx> root;                     // the device state every segment lives on
-  std::shared_ptr<const HostContext> params;
-};
 // an array [B][n] of the caller's, in its own type (EVAH_F64 / EVAH_F32 / EVAH_U8), C-contiguous
 struct ArrayView {
   const void *data = nullptr;
@@ -180,6 +173,28 @@ struct ArrayView {
   size_t B = 0, n = 0;
   size_t itemsize() const { return dtype == EVAH_F64 ? 8 : dtype == EVAH_F32 ? 4 : 1; }
   const void *row(size_t b) const { return static_cast<const char *>(data) + b * n * itemsize(); }
+};
+// row b as the doubles its values convert to exactly
+inline std::vector<double> array_row_doubles(const ArrayView &a, size_t b) {
+  std::vector<double> v(a.n);
+  for (size_t i = 0; i < a.n; i++)
+    v[i] = a.dtype == EVAH_F64   ? static_cast<const double *>(a.row(b))[i]
+           : a.dtype == EVAH_F32 ? (double)static_cast<const float *>(a.row(b))[i]
+                                 : (double)static_cast<const uint8_t *>(a.row(b))[i];
+  return v;
+}
+// an unencrypted value that differs per instance: typed rows [B][n] the batch owns, row b for instance b
+struct PlainRows {
+  ArrayView view;                               // into *bytes
+  std::shared_ptr<std::vector<uint8_t>> bytes;  // the rows in their own type
+};
+struct HipValuationBatch {
+  size_t B = 0;
+  std::map<std::string, BatchCipher> ciphers;
+  std::unordered_map<std::string, SchemeValue> shared; // plaintexts and raw vectors: one value for all instances
+  std::map<std::string, PlainRows> plains;             // raw values with a row per instance
+  std::shared_ptr<DeviceCtx> root;                     // the device state every segment lives on
+  std::shared_ptr<const HostContext> params;
 };
 
 // host words of a ciphertext value, downloaded on first use (waits for the value to be computed) or expanded

@@ -49,15 +49,45 @@ def normalise_arrays(arrays, signature):
     return enc, shared, B
 
 
-def _encrypt_array(self, arrays, signature, seed=0):
+def normalise_plain_arrays(plain_arrays, signature, B):
+    """The plain_arrays of encrypt_array as the library takes them: {name: C-contiguous [B, n] array} for
+    unencrypted (Raw) inputs of the signature, one row per instance, with n the signature's vector size and B the
+    encrypted arrays' B; dtypes as normalise_arrays treats them (uint8, float32, float64 kept, anything else float64)."""
+    n = signature.vec_size
+    out = {}
+    for name in sorted(plain_arrays or {}):
+        if name not in signature.inputs:
+            raise KeyError(f"No input named {name} in the signature")
+        if signature.inputs[name].input_type != _Type.Raw:
+            raise ValueError(f"plain_arrays takes unencrypted inputs of type Raw: input {name} is not one")
+        a = _np.asarray(plain_arrays[name])
+        if a.dtype not in ARRAY_DTYPES or not a.flags["C_CONTIGUOUS"]:
+            a = _np.ascontiguousarray(a, dtype=_np.float64)
+        if a.ndim != 2:
+            raise ValueError(f"unencrypted input {name} in plain_arrays needs an array [B, n], one row per instance, not shape {a.shape}")
+        if a.shape[1] != n:
+            raise ValueError(f"Input size does not match program vector size (input {name}: rows of {a.shape[1]} values, vector size {n})")
+        if a.shape[0] != B:
+            raise ValueError(f"input {name} has {a.shape[0]} instances, the encrypted inputs have {B}")
+        out[name] = a
+    return out
+
+
+def _encrypt_array(self, arrays, signature, seed=0, plain_arrays=None):
     """encrypt_batch(rows, signature, device_sampling=True, seed=seed) for arrays: `arrays` maps every
     encrypted input to an array [B, n] — uint8, float32 and float64 cross PCIe in their own type and are converted on
     the GPU — and every other input to the one value all instances share.  Returns a SEALValuationBatch whose instance b
     is encrypt_batch's instance b word for word; per name the instances stay in batched handles of at most 64.
     Raises without a HIP device, with EVA_DEVICE_CLIENT=0, with resident = False and for a value the device encoder
-    cannot take: there is no host path behind this call."""
-    enc, shared, _ = normalise_arrays(arrays, signature)
-    return self._encrypt_array(enc, shared, signature, seed)
+    cannot take: there is no host path behind this call.
+    plain_arrays: {name: array [B, n]} for unencrypted (Raw) inputs that differ per instance, kept in
+    their own type; execute_batch encodes a group's rows on the device where the program encodes the input."""
+    enc, shared, B = normalise_arrays(arrays, signature)
+    plains = normalise_plain_arrays(plain_arrays, signature, B)
+    for name in plains:
+        if name in shared:
+            raise ValueError(f"input {name} is given twice: in arrays and in plain_arrays")
+    return self._encrypt_array(enc, shared, signature, seed, plains)
 
 
 _SEALPublic.encrypt_array = _encrypt_array

@@ -130,8 +130,9 @@ void evah_host_free(void *p);
 
 /* ---- batched handles: `batch` (<= 64) independent ciphertexts of one shape in ONE handle
  * ([batch][size][limbs][N]).  Every evaluator entry point above/below accepts them and applies the
- * SEAL call to each instance in one launch set (plaintext operands and keys are shared by the
- * instances; two ciphertext operands must have the same batch).  This is the unit a batch of
+ * SEAL call to each instance in one launch set (keys are shared by the instances; a plaintext operand is
+ * shared too unless it is a batched plaintext of the same batch, evah_pt_encode_array below; two ciphertext
+ * operands must have the same batch).  This is the unit a batch of
  * independent program instances runs on (BASELINE config 4: 256 Sobel DAGs) — the reference runs
  * such a batch as `batch` separate SEALPublic::execute calls (seal.cpp:104-122). */
 int evah_ct_upload_batch(evah_ctx *ctx, uint32_t batch, uint32_t size, uint32_t limbs, double scale,
@@ -233,6 +234,29 @@ int evah_pt_uniform(evah_ctx *ctx, uint32_t limbs, double scale, const uint64_t 
 int evah_pt_info(const evah_pt *pt, uint32_t *limbs, double *scale);
 int evah_pt_download(evah_ctx *ctx, const evah_pt *pt, uint64_t *out /* [limbs][N] */);
 void evah_pt_free(evah_ctx *ctx, evah_pt *pt);
+/* ---- batched plaintexts: `batch` (<= 64) plaintexts of one level and scale in ONE handle, instance b
+ * for instance b of a batched ciphertext of the same batch — the unencrypted input of seal_executor.h:264-277 that
+ * differs between the program instances of a batch (a mask, a query, a per-request gain).  evah_add_plain,
+ * evah_sub_plain, evah_multiply_plain, evah_weighted_sum (per term), evah_elementwise_program and evah_execute take one
+ * wherever they take a plaintext: instance b of the result is the same call on evah_ct_slice(ct, b, 1) and plaintext b.
+ * A batch that is neither 1 nor the ciphertext's is refused ("plaintext batch differs from the ciphertext's").
+ * evah_rotate_weighted_sums, evah_multiply_plain_many, evah_encrypt, evah_encrypt_symmetric, evah_pt_write and
+ * evah_pt_download refuse a batched handle; evah_pt_copy, evah_pt_info and evah_pt_free handle it. */
+/* encoder.encode (seal_executor.h:242) of every row of values [batch][n_values] (EVAH_F64 / EVAH_F32 / EVAH_U8, crossing
+ * PCIe in that type): instance b = evah_pt_encode of row b converted to double, word for word.  The launches are those
+ * of the evah_encode_encrypt_* calls' encoder, their number independent of the batch; checks and messages are theirs
+ * (batch 1..64, null pointers, the limb count, n_values dividing the slots, "encoded values are too large" per row, an
+ * unknown dtype, a capturing context).  batch = 1 gives an ordinary plaintext.  Bytes sent count in
+ * evah_ctx_transfer_stats out[4]. */
+int evah_pt_encode_array(evah_ctx *ctx, uint32_t batch, const void *values, int dtype /* EVAH_F64 | EVAH_F32 | EVAH_U8 */,
+                         uint32_t n_values, uint32_t limbs, double scale, evah_pt **out);
+/* the same, stream-ordered like evah_ct_upload_instances_async: the host -> device copy stays in ctx's queue order and
+ * the call returns; `values` must stay valid and untouched until evah_ctx_sync(ctx) */
+int evah_pt_encode_array_async(evah_ctx *ctx, uint32_t batch, const void *values, int dtype, uint32_t n_values, uint32_t limbs,
+                               double scale, evah_pt **out);
+int evah_pt_batch(const evah_pt *pt, uint32_t *batch);
+/* every instance of a plaintext handle (batched or single) */
+int evah_pt_download_instances(evah_ctx *ctx, const evah_pt *pt, uint64_t *out /* [batch][limbs][N] */);
 
 /* ---- evaluator ops: one per SEAL call made by SEALExecutor::operator() ---------------------- */
 /* evaluator.add (seal_executor.h:124); sizes may differ (2/3), limbs and scale must match */
