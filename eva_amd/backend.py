@@ -142,6 +142,13 @@ _SIGS = {
     "evah_encode_encrypt_symmetric_array": [_vp, C.c_uint32, _vp, C.c_int, C.c_uint32, C.c_uint32, C.c_double, C.POINTER(C.c_uint8),
                                             C.POINTER(C.c_uint8), _vpp],
     "evah_decrypt_decode_handles": [_vp, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.c_int, _vp],
+    # the array calls on device memory
+    "evah_rows_abs_sum_dev": [_vp, C.c_uint32, _vp, C.c_int, C.c_size_t, _vp, C.c_uint32, C.POINTER(C.c_double)],
+    "evah_encode_encrypt_array_dev": [_vp, C.c_uint32, _vp, C.c_int, C.c_size_t, _vp, C.POINTER(C.c_double), C.c_uint32, C.c_uint32,
+                                      C.c_double, C.POINTER(C.c_uint8), _vpp],
+    "evah_encode_encrypt_symmetric_array_dev": [_vp, C.c_uint32, _vp, C.c_int, C.c_size_t, _vp, C.POINTER(C.c_double), C.c_uint32,
+                                                C.c_uint32, C.c_double, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _vpp],
+    "evah_decrypt_decode_rows": [_vp, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.c_int, _vp, C.c_size_t, C.c_int, C.c_int],
     "evah_ct_slice": [_vp, _vp, C.c_uint32, C.c_uint32, _vpp],
     "evah_ctx_stack_stats": [_vp, _u64p],
     # batched plaintexts
@@ -162,6 +169,7 @@ _SIGS = {
     "evah_ctx_set_shard": [_vp, C.c_uint32, C.c_uint32],
     "evah_ctx_shard_info": [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
     "evah_buf_alloc": [_vp, C.c_size_t, _vpp],
+    "evah_buf_wipe": [_vp, _vp],
     "evah_buf_copy": [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t],
     "evah_buf_gather": [_vp, _vp, C.c_uint32, _vpp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_size_t],
     "evah_ctx_enable_peer": [_vp, _vp],
@@ -442,6 +450,22 @@ class DeviceBuffer:
         data = np.ascontiguousarray(data, dtype=np.uint64).reshape(-1)
         _chk(_lib.evah_buf_upload(self.ctx.h, self.h, int(off), data.size, _p(data)))
 
+    def upload_bytes(self, data):
+        """the bytes of `data` (any array) to the start of the buffer, padded with zeros to whole words"""
+        raw = np.ascontiguousarray(data).reshape(-1).view(np.uint8)
+        words = np.zeros((raw.size + 7) // 8, dtype=np.uint64)
+        words.view(np.uint8)[:raw.size] = raw
+        self.upload(words)
+
+    def download_bytes(self):
+        """the whole buffer as uint8"""
+        return self.download().view(np.uint8)
+
+    def view(self, shape, dtype, offset=0, pitch=None):
+        """rows [B, n] of `dtype` inside this buffer, row b at byte offset + b * pitch (default: contiguous), as an object
+        with __cuda_array_interface__: what the device-array calls take"""
+        return DeviceView(self, shape, dtype, offset, pitch)
+
     def free(self):
         if self.h and self.ctx.h:
             _lib.evah_buf_free(self.ctx.h, self.h)
@@ -452,6 +476,33 @@ class DeviceBuffer:
             self.free()
         except Exception:
             pass
+
+
+class DeviceView:
+    """A [B, n] array of uint8 / float32 / float64 inside a DeviceBuffer (which it keeps alive)."""
+
+    def __init__(self, buf, shape, dtype, offset=0, pitch=None):
+        self.buf, self.shape, self.dtype, self.offset = buf, tuple(int(x) for x in shape), np.dtype(dtype), int(offset)
+        B, n = self.shape
+        self.pitch = n * self.dtype.itemsize if pitch is None else int(pitch)
+        assert self.offset + (B - 1) * self.pitch + n * self.dtype.itemsize <= 8 * buf.words
+
+    @property
+    def ptr(self):
+        return self.buf.ptr + self.offset
+
+    @property
+    def __cuda_array_interface__(self):
+        contiguous = self.pitch == self.shape[1] * self.dtype.itemsize
+        return {"shape": self.shape, "typestr": self.dtype.str, "data": (self.ptr, False), "version": 3,
+                "strides": None if contiguous else (self.pitch, self.dtype.itemsize)}
+
+    def to_numpy(self):
+        """the rows on the host (a synchronising download of the whole buffer)"""
+        raw = self.buf.download_bytes()
+        B, n = self.shape
+        rows = [raw[self.offset + b * self.pitch: self.offset + b * self.pitch + n * self.dtype.itemsize] for b in range(B)]
+        return np.stack(rows).view(self.dtype).reshape(B, n) if B else np.empty((0, n), self.dtype)
 
 
 class Context:
@@ -650,6 +701,54 @@ class Context:
         ptrs = (C.c_void_p * max(len(cts), 1))(*[ct.h for ct in cts])
         _chk(_lib.evah_decrypt_decode_handles(self.h, ptrs, len(cts), int(n_out), _DTYPES[dt] if dtype_code is None else int(dtype_code),
                                               out.ctypes.data_as(_vp)))
+        return out
+
+    # ---- the array calls on device memory: rows = a DeviceView, or anything with .ptr, .shape, .dtype, .pitch
+    @staticmethod
+    def _rows_args(rows, dtype_code, pitch):
+        B, n = rows.shape
+        code = _DTYPES.get(np.dtype(rows.dtype), -1) if dtype_code is None else int(dtype_code)
+        return int(B), int(n), C.c_void_p(rows.ptr), code, int(rows.pitch if pitch is None else pitch)
+
+    def rows_abs_sum_dev(self, rows, producer=None, dtype_code=None, pitch=None):
+        """float64 [B]: sum_i |rows[b][i]| computed on the device (evah_rows_abs_sum_dev)"""
+        B, n, ptr, code, pitch = self._rows_args(rows, dtype_code, pitch)
+        out = np.empty(max(B, 1), dtype=np.float64)
+        _chk(_lib.evah_rows_abs_sum_dev(self.h, B, ptr, code, pitch, C.c_void_p(producer), n, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out[:B]
+
+    def encode_encrypt_array_dev(self, rows, limbs, scale, rkeys, row_sums=None, producer=None, dtype_code=None, pitch=None):
+        """encode_encrypt_array on rows in device memory (evah_encode_encrypt_array_dev); does not drain the queue"""
+        B, n, ptr, code, pitch = self._rows_args(rows, dtype_code, pitch)
+        sums = None if row_sums is None else np.ascontiguousarray(row_sums, dtype=np.float64)
+        h = C.c_void_p()
+        _chk(_lib.evah_encode_encrypt_array_dev(self.h, B, ptr, code, pitch, C.c_void_p(producer),
+                                                None if sums is None else sums.ctypes.data_as(C.POINTER(C.c_double)), n, int(limbs),
+                                                float(scale), _keys32(rkeys, B), C.byref(h)))
+        return Ciphertext(self, h)
+
+    def encode_encrypt_symmetric_array_dev(self, rows, limbs, scale, ekeys, seeds, row_sums=None, producer=None, dtype_code=None, pitch=None):
+        """encode_encrypt_symmetric_array on rows in device memory (evah_encode_encrypt_symmetric_array_dev)"""
+        B, n, ptr, code, pitch = self._rows_args(rows, dtype_code, pitch)
+        sums = None if row_sums is None else np.ascontiguousarray(row_sums, dtype=np.float64)
+        h = C.c_void_p()
+        _chk(_lib.evah_encode_encrypt_symmetric_array_dev(self.h, B, ptr, code, pitch, C.c_void_p(producer),
+                                                          None if sums is None else sums.ctypes.data_as(C.POINTER(C.c_double)), n,
+                                                          int(limbs), float(scale), _keys32(ekeys, B), _keys32(seeds, B), C.byref(h)))
+        return Ciphertext(self, h)
+
+    def decrypt_decode_rows(self, cts, n_out, out, wait=True, dtype_code=None, pitch=None):
+        """decrypt_decode_handles into rows with a pitch (evah_decrypt_decode_rows).  out: a DeviceView (device rows, written
+        in place; wait=False leaves the call in queue order), or a 2-d numpy array whose rows may be pitched (host rows)"""
+        ptrs = (C.c_void_p * max(len(cts), 1))(*[ct.h for ct in cts])
+        if isinstance(out, np.ndarray):
+            assert out.ndim == 2 and out.strides[1] == out.itemsize
+            ptr, row_pitch, on_device, dt = C.c_void_p(out.ctypes.data), out.strides[0], 0, out.dtype
+        else:
+            ptr, row_pitch, on_device, dt = C.c_void_p(out.ptr), out.pitch, 1, out.dtype
+        code = _DTYPES.get(np.dtype(dt), -1) if dtype_code is None else int(dtype_code)
+        _chk(_lib.evah_decrypt_decode_rows(self.h, ptrs, len(cts), int(n_out), code, ptr, int(row_pitch if pitch is None else pitch),
+                                           on_device, 1 if wait else 0))
         return out
 
     def stack_stats(self):

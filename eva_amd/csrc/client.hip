@@ -411,12 +411,61 @@ k_dec_gather(const double2 *c, const uint32_t *slot_map, uint32_t n_out, uint32_
   if (i < n_out) out[(size_t)blockIdx.y * n_out + i] = (T)c[(size_t)blockIdx.y * N + slot_map[i]].x;
 }
 
+// ---- the kernels of the device-array calls: rows that live in the caller's device memory, row b at
+// byte b * pitch of the base (a torch slice t[:, :n] is pitched; a uint8_t row may start at any byte)
+// what check_encodable adds up, where the rows are: sums[b] = sum_i |rows[b][i]| as doubles (every T converts exactly).
+// One workgroup per row, thread t adds the elements t, t + 256, ... in that order, then a fixed tree through LDS: no
+// atomics, so a row gives the same sum on every run.  A NaN or an infinity in the row makes its sum non-finite.
+template <class T>
+__global__ void __launch_bounds__(256)
+k_rows_abs_sum(const unsigned char *rows, size_t pitch, uint32_t n_values, double *sums) {
+#pragma clang fp contract(off)
+  __shared__ double part[256];
+  const uint32_t tid = threadIdx.x;
+  const T *row = reinterpret_cast<const T *>(rows + (size_t)blockIdx.x * pitch);
+  double s = 0.0;
+  for (uint32_t i = tid; i < n_values; i += 256) s += fabs((double)row[i]);
+  part[tid] = s;
+  __syncthreads();
+  for (uint32_t h = 128; h; h >>= 1) {
+    if (tid < h) part[tid] += part[tid + h];
+    __syncthreads();
+  }
+  if (!tid) sums[blockIdx.x] = part[0];
+}
+// k_enc_scatter_many with a row pitch in bytes; one scalar load per thread, as there
+template <class T>
+__global__ void __launch_bounds__(256)
+k_enc_scatter_rows(const unsigned char *vals, size_t pitch, uint32_t n_vals, const uint32_t *slot_map, double2 *c, uint32_t slots) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= slots) return;
+  const double v = (double)reinterpret_cast<const T *>(vals + (size_t)blockIdx.y * pitch)[i % n_vals];
+  c += (size_t)blockIdx.y * 2 * slots;
+  c[slot_map[i]] = make_double2(v, 0.0);
+  c[slot_map[slots + i]] = make_double2(v, -0.0); // conjugate of a real value
+}
+// the slot value as the row's type: double and float as k_dec_gather casts them; uint8_t = the nearest integer, ties to
+// even, clamped to [0, 255], NaN -> 0 (np.clip(np.rint(np.nan_to_num(d, nan=0)), 0, 255))
+template <class T> __device__ __forceinline__ T dec_value(double x) { return (T)x; }
+template <> __device__ __forceinline__ uint8_t dec_value<uint8_t>(double x) {
+  const double r = rint(x);
+  return r != r ? (uint8_t)0 : (uint8_t)fmin(fmax(r, 0.0), 255.0);
+}
+// k_dec_gather with a destination pitch in bytes (rows in the caller's device memory, or the call's scratch)
+template <class T>
+__global__ void __launch_bounds__(256)
+k_dec_gather_rows(const double2 *c, const uint32_t *slot_map, uint32_t n_out, uint32_t N, unsigned char *out, size_t pitch) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n_out) reinterpret_cast<T *>(out + (size_t)blockIdx.y * pitch)[i] = dec_value<T>(c[(size_t)blockIdx.y * N + slot_map[i]].x);
+}
+
 // ---- one body per operation: no argument checks inside, every entry point below makes its own
 // SEAL Encryptor::encrypt of `batch` NTT-form plaintexts pt [batch][l][N] (a handle's words, or the call's scratch) into
 // one handle [batch][2][l][N].  Randomness: small = the host's (u ternary, e0, e1 error polynomials) as int8 [batch][3][N], or
-// (rkeys) drawn here from a 32-byte key per instance.  Drains the queue: `small` / `rkeys` are pageable host memory.
+// (rkeys) drawn here from a 32-byte key per instance.  Drains the queue: `small` / `rkeys` are pageable host memory —
+// unless drain is false (the device-array calls: rkeys is one of the queue's pinned key slots).
 static evah_ct *encrypt_public(evah_ctx *c, uint32_t batch, uint32_t l, double scale, const u64 *pt, const int8_t *small,
-                               const uint8_t *rkeys) {
+                               const uint8_t *rkeys, bool drain = true) {
   const uint32_t up = l + 1;
   const size_t N = c->N, B = batch;
   Scratch sm8(c, rkeys ? 4 * B : (3 * B * N + 7) / 8), sm(c, 3 * B * up * N), ct(c, 2 * B * up * N), r(c, 2 * B * N);
@@ -441,7 +490,7 @@ static evah_ct *encrypt_public(evah_ctx *c, uint32_t batch, uint32_t l, double s
     ntt_forward<OpModDown>(c, mp, 2 * batch * l);
     w_keys.now();
     w_sm.now();
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if (drain) HIPCHK(hipStreamSynchronize(c->stream));
   } catch (...) {
     (void)hipStreamSynchronize(c->stream);
     evah_ct_free(c, o);
@@ -452,9 +501,10 @@ static evah_ct *encrypt_public(evah_ctx *c, uint32_t batch, uint32_t l, double s
 
 // Encryptor::encrypt_symmetric of `batch` NTT-form plaintexts m [batch][l][N] into one handle: c1 = a from seeds[b],
 // c0 = m - (a s + NTT(e)).  e = the host's error polynomials as int8 [batch][N], or (ekeys) drawn here from a 32-byte
-// key per instance.  Drains the queue: `e` / `ekeys` and `seeds` are pageable host memory.
+// key per instance.  Drains the queue: `e` / `ekeys` and `seeds` are pageable host memory — unless drain is false (the
+// device-array calls: ekeys and seeds lie in one of the queue's pinned key slots).
 static evah_ct *encrypt_symmetric(evah_ctx *c, uint32_t batch, uint32_t l, double scale, const u64 *m, const int8_t *e,
-                                  const uint8_t *ekeys, const uint8_t *seeds) {
+                                  const uint8_t *ekeys, const uint8_t *seeds, bool drain = true) {
   const size_t N = c->N, B = batch;
   Scratch e8(c, ekeys ? 4 * B : (B * N + 7) / 8), en(c, B * l * N);
   std::unique_ptr<Scratch> seed_dev; // more than 8 instances: the seeds as a device buffer, returned to the pool after the drain
@@ -482,7 +532,7 @@ static evah_ct *encrypt_symmetric(evah_ctx *c, uint32_t batch, uint32_t l, doubl
     HIPCHK(hipGetLastError());
     w_en.now();
     w_e8.now();
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if (drain) HIPCHK(hipStreamSynchronize(c->stream));
   } catch (...) {
     (void)hipStreamSynchronize(c->stream);
     evah_ct_free(c, o);
@@ -497,8 +547,18 @@ static size_t dtype_size(int dtype) { return dtype == EVAH_F64 ? 8 : dtype == EV
 // SEAL Decryptor::decrypt + CKKSEncoder::decode of the n instances that n_handles handles of one size, limb count and
 // scale hold together (a single ciphertext is one instance; instance j of a batched handle is d + j * size * ps), read in
 // place: the first n_out slot values of each into out [n][n_out] (host) as double (EVAH_F64) or float (EVAH_F32), rows
-// in list order, then instance order
-static void decrypt_decode(evah_ctx *c, const evah_ct *const *cts, uint32_t n_handles, uint32_t n, uint32_t n_out, int dtype_out, void *out) {
+// in list order, then instance order.
+// rows (evah_decrypt_decode_rows): `out` has a row pitch in bytes, may be device memory — the gather then
+// writes the caller's rows and nothing crosses to the host — and dtype_out may be EVAH_U8; wait = false (device rows
+// only) leaves the call in queue order.
+struct RowsDst { size_t pitch; bool on_device, wait; };
+template <class T>
+static void dec_gather_rows(evah_ctx *c, const double2 *cd, uint32_t n, uint32_t n_out, void *out, size_t pitch) {
+  EW_LAUNCH(k_dec_gather_rows<T>, dim3((n_out + 255) / 256, n), dim3(256), 0, c->stream, cd, c->sh->enc_slot_map, n_out, c->N,
+            static_cast<unsigned char *>(out), pitch);
+}
+static void decrypt_decode(evah_ctx *c, const evah_ct *const *cts, uint32_t n_handles, uint32_t n, uint32_t n_out, int dtype_out, void *out,
+                           const RowsDst *rows = nullptr) {
   const uint32_t l = cts[0]->limbs, N = c->N;
   enc_tables(c);
   dec_tables(c);
@@ -511,11 +571,12 @@ static void decrypt_decode(evah_ctx *c, const evah_ct *const *cts, uint32_t n_ha
       tab.ct_ps[r] = (uint32_t)(cts[i]->ps / N);
     }
   }
-  const size_t B = n, out_bytes = dtype_size(dtype_out) * B * n_out;
-  Scratch m(c, B * l * N), cbuf(c, B * 2 * N), outd(c, (out_bytes + 7) / 8);
+  const size_t B = n, row_bytes = dtype_size(dtype_out) * n_out, out_bytes = row_bytes * B;
+  const bool to_dev = rows && rows->on_device;
+  Scratch m(c, B * l * N), cbuf(c, B * 2 * N), outd(c, to_dev ? 1 : (out_bytes + 7) / 8);
   {
     // the decrypted messages, their FP images and the slot values do not stay behind in pool memory the next call reuses
-    Wipe w_m{c, m.d, sizeof(u64) * B * l * N}, w_c{c, cbuf.d, sizeof(double2) * B * N}, w_o{c, outd.d, out_bytes};
+    Wipe w_m{c, m.d, sizeof(u64) * B * l * N}, w_c{c, cbuf.d, sizeof(double2) * B * N}, w_o{c, outd.d, out_bytes, to_dev};
     EW_LAUNCH(k_decrypt_dot, dim3(N / 256, l, n), dim3(256), 0, c->stream, c->dev, tab, cts[0]->size, l, c->sh->sk.d, m.d);
     OpPlain::Params ip{m.d, m.d, (size_t)l * N, (size_t)l * N, l, 0, 0, {}};
     ntt_inverse<OpPlain>(c, ip, n * l);
@@ -523,25 +584,34 @@ static void decrypt_decode(evah_ctx *c, const evah_ct *const *cts, uint32_t n_ha
     EW_LAUNCH(k_crt_to_double, dim3(N / 256, n), dim3(256), 0, c->stream, c->dev, t, l, m.d, 1.0 / cts[0]->scale, cd);
     HIPCHK(hipGetLastError());
     fft_batched<false>(c, cd, c->sh->dec_roots, n, make_double2(0.0, 0.0), 0.0);
-    if (dtype_out == EVAH_F32)
+    if (rows) { // the caller's rows, or (host rows) the scratch at its own pitch
+      void *dst = to_dev ? out : outd.d;
+      const size_t pitch = to_dev ? rows->pitch : row_bytes;
+      if (dtype_out == EVAH_F32) dec_gather_rows<float>(c, cd, n, n_out, dst, pitch);
+      else if (dtype_out == EVAH_U8) dec_gather_rows<uint8_t>(c, cd, n, n_out, dst, pitch);
+      else dec_gather_rows<double>(c, cd, n, n_out, dst, pitch);
+    } else if (dtype_out == EVAH_F32)
       EW_LAUNCH(k_dec_gather<float>, dim3((n_out + 255) / 256, n), dim3(256), 0, c->stream, cd, c->sh->enc_slot_map, n_out, N,
                 reinterpret_cast<float *>(outd.d));
     else
       EW_LAUNCH(k_dec_gather<double>, dim3((n_out + 255) / 256, n), dim3(256), 0, c->stream, cd, c->sh->enc_slot_map, n_out, N,
                 reinterpret_cast<double *>(outd.d));
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, outd.d, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (rows && !to_dev && rows->pitch != row_bytes)
+      HIPCHK(hipMemcpy2DAsync(out, rows->pitch, outd.d, row_bytes, row_bytes, B, hipMemcpyDeviceToHost, c->stream));
+    else if (!to_dev)
+      HIPCHK(hipMemcpyAsync(out, outd.d, out_bytes, hipMemcpyDeviceToHost, c->stream));
     w_m.now();
     w_c.now();
     w_o.now();
   }
-  HIPCHK(hipStreamSynchronize(c->stream));
+  if (!to_dev || rows->wait) HIPCHK(hipStreamSynchronize(c->stream));
+  if (rows && !to_dev) c->sh->xfer[5] += out_bytes; // evah_decrypt_decode_rows counts what it brings to the host: device rows, nothing
 }
 
 // ---- the _many calls: values in, one batched handle out
 // the checks both encryption calls share, in the order evah_pt_encode and the encryptors make them
-static void encode_many_checks(evah_ctx *c, uint32_t batch, const void *values, int dtype, uint32_t n_values, uint32_t limbs, double scale,
-                               const void *out) {
+static void encode_shape_checks(evah_ctx *c, uint32_t batch, const void *values, uint32_t n_values, uint32_t limbs, const void *out) {
   if (c->capturing) throw std::logic_error("this call synchronises with the host and cannot be captured into a graph");
   if (batch < 1 || batch > (uint32_t)KS_BATCH_MAX) throw std::invalid_argument("batch must be 1..64");
   if (!values) throw std::invalid_argument("value pointer is null");
@@ -550,6 +620,10 @@ static void encode_many_checks(evah_ctx *c, uint32_t batch, const void *values, 
   const uint32_t slots = c->N >> 1;
   if (n_values < 1 || n_values > slots || slots % n_values) throw std::invalid_argument("value count must divide the slot count");
   if (c->N % 256) throw std::invalid_argument("encryption needs N divisible by 256");
+}
+static void encode_many_checks(evah_ctx *c, uint32_t batch, const void *values, int dtype, uint32_t n_values, uint32_t limbs, double scale,
+                               const void *out) {
+  encode_shape_checks(c, batch, values, n_values, limbs, out);
   // evah_pt_encode's: "encoded values are too large", on the values in the type they came in (the verdict on their
   // float64 image: the conversion is exact, and a float NaN or infinity is a double NaN or infinity)
   if (dtype == EVAH_F64) check_encodable(c, static_cast<const double *>(values), batch, n_values, scale);
@@ -559,13 +633,34 @@ static void encode_many_checks(evah_ctx *c, uint32_t batch, const void *values, 
 }
 // values [batch][n_values] of `dtype` (host) -> NTT-form plaintexts pt [batch][limbs][N] on the queue; vals, cbuf: the
 // call's scratch.  The values cross in their own type and become doubles in the scatter.
+// dev (the device-array calls): `values` is the caller's device memory with dev->pitch bytes between rows —
+// nothing is copied, the scatter reads it in place, and dev->release(), right behind the scatter, hands the array back to
+// the stream that produced it.
+struct DevSrc {
+  size_t pitch;
+  void *producer;         // the stream that wrote the array, as the ABI names it; NULL: the caller synchronised beforehand
+  bool host_wait = false; // set by release(): no producer stream to hand back to, the call waits for dev_out on the host
+  void release(evah_ctx *c);
+};
+template <class T>
+static void enc_scatter_rows(evah_ctx *c, uint32_t batch, const void *values, size_t pitch, uint32_t n_values, double2 *cd) {
+  const uint32_t slots = c->N >> 1;
+  EW_LAUNCH(k_enc_scatter_rows<T>, dim3((slots + 255) / 256, batch), dim3(256), 0, c->stream, static_cast<const unsigned char *>(values), pitch,
+            n_values, c->sh->enc_slot_map, cd, slots);
+}
 static void encode_many(evah_ctx *c, uint32_t batch, const void *values, int dtype, uint32_t n_values, uint32_t limbs, double scale, u64 *vals,
-                        double2 *cd, u64 *pt) {
+                        double2 *cd, u64 *pt, DevSrc *dev = nullptr) {
   const uint32_t N = c->N, slots = N >> 1;
   enc_tables(c);
-  HIPCHK(hipMemcpyAsync(vals, values, dtype_size(dtype) * (size_t)batch * n_values, hipMemcpyHostToDevice, c->stream));
+  if (!dev) HIPCHK(hipMemcpyAsync(vals, values, dtype_size(dtype) * (size_t)batch * n_values, hipMemcpyHostToDevice, c->stream));
   const dim3 grid((slots + 255) / 256, batch);
-  if (dtype == EVAH_F32)
+  if (dev) {
+    if (dtype == EVAH_F32) enc_scatter_rows<float>(c, batch, values, dev->pitch, n_values, cd);
+    else if (dtype == EVAH_U8) enc_scatter_rows<uint8_t>(c, batch, values, dev->pitch, n_values, cd);
+    else enc_scatter_rows<double>(c, batch, values, dev->pitch, n_values, cd);
+    HIPCHK(hipGetLastError());
+    dev->release(c);
+  } else if (dtype == EVAH_F32)
     EW_LAUNCH(k_enc_scatter_many<float>, grid, dim3(256), 0, c->stream, reinterpret_cast<const float *>(vals), n_values, c->sh->enc_slot_map, cd, slots);
   else if (dtype == EVAH_U8)
     EW_LAUNCH(k_enc_scatter_many<uint8_t>, grid, dim3(256), 0, c->stream, reinterpret_cast<const uint8_t *>(vals), n_values, c->sh->enc_slot_map, cd, slots);
@@ -644,6 +739,155 @@ static void pt_encode_array(evah_ctx *c, uint32_t batch, const void *values, int
   if (wait) t->buf->ready_everywhere = true;
   count_client_h2d(c, dtype_size(dtype) * B * n_values);
   *out = t;
+}
+
+// ---- the device-array calls: the same bodies with the rows in the caller's device memory
+// an event of the queue, made at first use (never while capturing: these calls refuse a capturing context first)
+static hipEvent_t cached_event(hipEvent_t &e) {
+  if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  return e;
+}
+// the stream the ABI names: hipStreamLegacy is the null stream
+static hipStream_t producer_stream(void *producer) { return (hipStream_t)producer == hipStreamLegacy ? nullptr : (hipStream_t)producer; }
+// before the first read of the caller's array: the queue waits for what its producer has enqueued so far
+static void wait_for_producer(evah_ctx *c, void *producer) {
+  if (!producer) return;
+  hipEvent_t e = cached_event(c->dev_in);
+  HIPCHK(hipEventRecord(e, producer_stream(producer)));
+  HIPCHK(hipStreamWaitEvent(c->stream, e, 0));
+}
+// behind the last kernel that reads it: whatever the producer enqueues next (an overwrite, a free and reuse) waits for the read
+void DevSrc::release(evah_ctx *c) {
+  hipEvent_t e = cached_event(c->dev_out);
+  HIPCHK(hipEventRecord(e, c->stream));
+  if (producer) HIPCHK(hipStreamWaitEvent(producer_stream(producer), e, 0));
+  else host_wait = true;
+}
+// `p` .. `p + span` must be device memory of the context's GPU: asked of the runtime, before anything is launched
+static void check_device_rows(evah_ctx *c, const void *p, size_t span, const std::string &what) {
+  hipPointerAttribute_t at{};
+  const hipError_t e = hipPointerGetAttributes(&at, p);
+  if (e != hipSuccess) (void)hipGetLastError(); // (a pointer the runtime has never seen: plain host memory)
+  if (e != hipSuccess || at.type == hipMemoryTypeUnregistered || at.type == hipMemoryTypeHost)
+    throw std::invalid_argument(what + " is host memory: this call takes device memory (use the host-array call, or copy the array to the GPU)");
+  if (at.type == hipMemoryTypeManaged || at.isManaged)
+    throw std::invalid_argument(what + " is managed memory: this call takes device memory (hipMalloc, or a torch tensor on the GPU)");
+  if (at.type != hipMemoryTypeDevice) throw std::invalid_argument(what + " is not device memory");
+  if (at.device != c->device)
+    throw std::invalid_argument(what + " is memory of GPU " + std::to_string(at.device) + ", this context runs on GPU " + std::to_string(c->device));
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, const_cast<void *>(p)) != hipSuccess) {
+    (void)hipGetLastError(); // (an allocator the runtime keeps no range for: the caller's shape is taken as given)
+    return;
+  }
+  const uintptr_t lo = (uintptr_t)base, at_p = (uintptr_t)p;
+  if (at_p < lo || span > size || at_p - lo > size - span) throw std::invalid_argument(what + ": the rows run past the end of their allocation");
+}
+// the shape of rows in device memory: item size of `dtype`, pitch, alignment, and where the memory lives
+static void check_rows_shape(evah_ctx *c, const void *p, int dtype, const char *dtype_msg, size_t n_rows, size_t n_cols, size_t pitch, bool on_device,
+                             const std::string &what) {
+  const size_t item = dtype_size(dtype);
+  if (!item) throw std::invalid_argument(dtype_msg);
+  if (pitch < item * n_cols) throw std::invalid_argument("row pitch is smaller than a row");
+  if (pitch % item) throw std::invalid_argument("row pitch is not a multiple of the item size");
+  if ((uintptr_t)p % item) throw std::invalid_argument(what + " is not aligned to its item size");
+  if (on_device) check_device_rows(c, p, (n_rows - 1) * pitch + item * n_cols, what);
+}
+static const char *const VALUE_DTYPE_MSG = "unknown value dtype (EVAH_F64, EVAH_F32 or EVAH_U8)";
+
+// sums[b] = k_rows_abs_sum of row b, brought to the host: one launch, one copy of 8 * rows bytes, one wait
+static void rows_abs_sum(evah_ctx *c, uint32_t rows, const void *values, int dtype, size_t pitch, uint32_t n_values, double *sums) {
+  Scratch sd(c, rows);
+  const unsigned char *v = static_cast<const unsigned char *>(values);
+  double *d = reinterpret_cast<double *>(sd.d);
+  if (dtype == EVAH_F32) EW_LAUNCH(k_rows_abs_sum<float>, dim3(rows), dim3(256), 0, c->stream, v, pitch, n_values, d);
+  else if (dtype == EVAH_U8) EW_LAUNCH(k_rows_abs_sum<uint8_t>, dim3(rows), dim3(256), 0, c->stream, v, pitch, n_values, d);
+  else EW_LAUNCH(k_rows_abs_sum<double>, dim3(rows), dim3(256), 0, c->stream, v, pitch, n_values, d);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(sums, d, sizeof(double) * rows, hipMemcpyDeviceToHost, c->stream);
+  const hipError_t s = hipStreamSynchronize(c->stream); // also on an error: the scratch returns to the pool behind the launch
+  HIPCHK(e);
+  HIPCHK(s);
+  c->sh->xfer[5] += sizeof(double) * rows;
+}
+// check_encodable's rule on a row's sum of absolute values; a NaN or an infinity in the row left the sum non-finite
+static void check_row_sums(const evah_ctx *c, const double *sums, uint32_t batch, uint32_t n_values, double scale) {
+  const uint32_t slots = c->N >> 1;
+  for (uint32_t b = 0; b < batch; b++) {
+    const double bound = 2.0 * sums[b] * (double)(slots / n_values) * scale / (double)c->N;
+    if (!std::isfinite(sums[b]) || !(bound < 4611686018427387904.0)) throw std::invalid_argument("encoded values are too large"); // 2^62
+  }
+}
+
+// a pinned block for the randomness keys (and seeds) of one call: the copies that read it are asynchronous, and the slot
+// is taken again only after the event recorded behind them.  Slots whose copies have finished are zeroed as soon as a
+// later call looks: the keys are secrets.
+static evah_ctx::KeySlot &key_slot(evah_ctx *c) {
+  for (auto &s : c->key_slots)
+    if (s.busy && hipEventQuery(s.done) == hipSuccess) {
+      std::memset(s.host, 0, evah_ctx::KEY_SLOT_BYTES);
+      s.busy = false;
+    }
+  (void)hipGetLastError(); // (hipErrorNotReady of a query is not an error)
+  evah_ctx::KeySlot &s = c->key_slots[c->key_slot_next];
+  c->key_slot_next = (c->key_slot_next + 1) % evah_ctx::KEY_SLOTS;
+  if (!s.host) HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&s.host), evah_ctx::KEY_SLOT_BYTES, hipHostMallocDefault));
+  if (s.busy) {
+    HIPCHK(hipEventSynchronize(s.done));
+    s.busy = false;
+  }
+  cached_event(s.done);
+  return s;
+}
+
+// evah_encode_encrypt_array_dev (rkeys) and evah_encode_encrypt_symmetric_array_dev (ekeys, seeds): the bodies of
+// encode_encrypt_many / encode_encrypt_symmetric_many with the rows read where they are.  No drain: the handle is valid
+// in queue order.  On an error the queue is drained, so no read of `values` is pending when the call returns.
+static void encode_encrypt_dev(evah_ctx *c, bool symmetric, uint32_t batch, const void *values, int dtype, size_t pitch, void *producer,
+                               const double *row_sums, uint32_t n_values, uint32_t limbs, double scale, const uint8_t *keys, const uint8_t *seeds,
+                               evah_ct **out) {
+  use(c);
+  encode_shape_checks(c, batch, values, n_values, limbs, out);
+  check_rows_shape(c, values, dtype, VALUE_DTYPE_MSG, batch, n_values, pitch, true, "values");
+  if (symmetric) {
+    if (!c->sh->sk.d) throw std::invalid_argument("secret key not present");
+    if (!keys || !seeds) throw std::invalid_argument("error polynomial and seed are required");
+  } else {
+    if (!keys) throw std::invalid_argument("randomness pointer is null");
+    if (!c->sh->pk.d) throw std::invalid_argument("public key not present");
+    if (limbs + 1 > c->k) throw std::invalid_argument("plaintext level is not valid for encryption");
+  }
+  *out = nullptr;
+  wait_for_producer(c, producer);
+  std::vector<double> own;
+  if (!row_sums) {
+    own.resize(batch);
+    rows_abs_sum(c, batch, values, dtype, pitch, n_values, own.data());
+    row_sums = own.data();
+  }
+  check_row_sums(c, row_sums, batch, n_values, scale);
+  const size_t N = c->N, B = batch;
+  evah_ctx::KeySlot &slot = key_slot(c);
+  std::memcpy(slot.host, keys, 32 * B);
+  if (symmetric) std::memcpy(slot.host + 32 * KS_BATCH_MAX, seeds, 32 * B);
+  slot.busy = true; // from here on the slot holds keys: zeroed behind its event, whatever happens
+  DevSrc src{pitch, producer};
+  try {
+    Scratch cbuf(c, B * 2 * N), pt(c, B * limbs * N);
+    encode_many(c, batch, values, dtype, n_values, limbs, scale, nullptr, reinterpret_cast<double2 *>(cbuf.d), pt.d, &src);
+    *out = symmetric ? encrypt_symmetric(c, batch, limbs, scale, pt.d, nullptr, slot.host, slot.host + 32 * KS_BATCH_MAX, false)
+                     : encrypt_public(c, batch, limbs, scale, pt.d, nullptr, slot.host, false);
+    HIPCHK(hipEventRecord(slot.done, c->stream));
+    if (src.host_wait) HIPCHK(hipEventSynchronize(c->dev_out));
+  } catch (...) {
+    (void)hipStreamSynchronize(c->stream);
+    std::memset(slot.host, 0, evah_ctx::KEY_SLOT_BYTES);
+    slot.busy = false;
+    if (*out) { evah_ct_free(c, *out); *out = nullptr; }
+    throw;
+  }
+  count_client_h2d(c, (symmetric ? 64 : 32) * B);
 }
 
 } // namespace evah
@@ -796,9 +1040,8 @@ int evah_decrypt_decode_many(evah_ctx *c, const evah_ct *const *cts, uint32_t n,
 
 // evah_decrypt_decode_many over handles that may be batched: the same checks in the same order, the
 // instances counted over the whole list
-int evah_decrypt_decode_handles(evah_ctx *c, const evah_ct *const *cts, uint32_t n_handles, uint32_t n_out, int dtype_out, void *out) {
-  API_BEGIN
-  use(c);
+// the checks of evah_decrypt_decode_handles before and behind its dtype check (evah_decrypt_decode_rows makes the same)
+static uint32_t handles_checks_list(evah_ctx *c, const evah_ct *const *cts, uint32_t n_handles, const void *out) {
   if (c->capturing) throw std::logic_error("this call synchronises with the host and cannot be captured into a graph");
   if (!c->sh->sk.d) throw std::invalid_argument("secret key not present");
   if (n_handles < 1) throw std::invalid_argument("batch must be 1..64");
@@ -813,13 +1056,67 @@ int evah_decrypt_decode_handles(evah_ctx *c, const evah_ct *const *cts, uint32_t
     n += cts[i]->batch;
   }
   if (n > (uint64_t)KS_BATCH_MAX) throw std::invalid_argument("the handles hold more than 64 instances in total");
-  if (dtype_out != EVAH_F64 && dtype_out != EVAH_F32) throw std::invalid_argument("unknown output dtype (EVAH_F64 or EVAH_F32)");
+  return (uint32_t)n;
+}
+static void handles_checks_shape(evah_ctx *c, const evah_ct *const *cts, uint32_t n_out) {
   if (cts[0]->size < 1 || cts[0]->size > 3) throw std::invalid_argument("ciphertext size out of range");
   if (n_out < 1 || n_out > c->N >> 1) throw std::invalid_argument("slot count out of range");
   if (cts[0]->limbs > 61) throw std::invalid_argument("too many limbs");
   if (c->N % 256) throw std::invalid_argument("decryption needs N divisible by 256");
   check_scale(c, cts[0]->scale, cts[0]->limbs); // decode_internal: "scale out of bounds"
-  decrypt_decode(c, cts, n_handles, (uint32_t)n, n_out, dtype_out, out);
+}
+
+int evah_decrypt_decode_handles(evah_ctx *c, const evah_ct *const *cts, uint32_t n_handles, uint32_t n_out, int dtype_out, void *out) {
+  API_BEGIN
+  use(c);
+  const uint32_t n = handles_checks_list(c, cts, n_handles, out);
+  if (dtype_out != EVAH_F64 && dtype_out != EVAH_F32) throw std::invalid_argument("unknown output dtype (EVAH_F64 or EVAH_F32)");
+  handles_checks_shape(c, cts, n_out);
+  decrypt_decode(c, cts, n_handles, n, n_out, dtype_out, out);
+  API_END
+}
+
+// ---- the device-array calls
+int evah_rows_abs_sum_dev(evah_ctx *c, uint32_t rows, const void *values, int dtype, size_t row_pitch, void *producer, uint32_t n_values,
+                          double *sums_out) {
+  API_BEGIN
+  use(c);
+  if (c->capturing) throw std::logic_error("this call synchronises with the host and cannot be captured into a graph");
+  if (rows < 1) throw std::invalid_argument("row count must be at least 1");
+  if (!values) throw std::invalid_argument("value pointer is null");
+  if (!sums_out) throw std::invalid_argument("output pointer is null");
+  if (n_values < 1) throw std::invalid_argument("value count must be at least 1");
+  check_rows_shape(c, values, dtype, VALUE_DTYPE_MSG, rows, n_values, row_pitch, true, "values");
+  wait_for_producer(c, producer);
+  rows_abs_sum(c, rows, values, dtype, row_pitch, n_values, sums_out); // (waits: the read is over, nothing to hand back)
+  API_END
+}
+
+int evah_encode_encrypt_array_dev(evah_ctx *c, uint32_t batch, const void *values, int dtype, size_t row_pitch, void *producer,
+                                  const double *row_sums, uint32_t n_values, uint32_t limbs, double scale, const uint8_t *rkeys, evah_ct **out) {
+  API_BEGIN
+  encode_encrypt_dev(c, false, batch, values, dtype, row_pitch, producer, row_sums, n_values, limbs, scale, rkeys, nullptr, out);
+  API_END
+}
+
+int evah_encode_encrypt_symmetric_array_dev(evah_ctx *c, uint32_t batch, const void *values, int dtype, size_t row_pitch, void *producer,
+                                            const double *row_sums, uint32_t n_values, uint32_t limbs, double scale, const uint8_t *ekeys,
+                                            const uint8_t *seeds, evah_ct **out) {
+  API_BEGIN
+  encode_encrypt_dev(c, true, batch, values, dtype, row_pitch, producer, row_sums, n_values, limbs, scale, ekeys, seeds, out);
+  API_END
+}
+
+int evah_decrypt_decode_rows(evah_ctx *c, const evah_ct *const *cts, uint32_t n_handles, uint32_t n_out, int dtype_out, void *out,
+                             size_t row_pitch, int out_on_device, int wait) {
+  API_BEGIN
+  use(c);
+  const uint32_t n = handles_checks_list(c, cts, n_handles, out);
+  if (!dtype_size(dtype_out)) throw std::invalid_argument("unknown output dtype (EVAH_F64, EVAH_F32 or EVAH_U8)");
+  handles_checks_shape(c, cts, n_out);
+  check_rows_shape(c, out, dtype_out, "unknown output dtype (EVAH_F64, EVAH_F32 or EVAH_U8)", n, n_out, row_pitch, out_on_device != 0, "out");
+  const RowsDst rows{row_pitch, out_on_device != 0, wait != 0};
+  decrypt_decode(c, cts, n_handles, n, n_out, dtype_out, out, &rows);
   API_END
 }
 

@@ -422,6 +422,15 @@ struct evah_ctx {
   bool capturing = false;              // inside evah_capture_begin/end: no syncs, no profiling events
   std::vector<hipEvent_t> capture_events; // events consumed by the capture in progress
   std::vector<hipEvent_t> sync_events; // recycled events for cross-queue ordering
+  // the device-array client calls (client.hip), all made at first use and kept for the queue's lifetime:
+  // dev_in / dev_out order the queue against the stream that produced the caller's array (record on one, wait on the
+  // other); key_slots are pinned host blocks the randomness keys and seeds of a call are staged in, so that their copies
+  // are asynchronous and the call need not drain — a slot is reused once the event recorded behind its copies has passed
+  struct KeySlot { unsigned char *host = nullptr; hipEvent_t done = nullptr; bool busy = false; };
+  static constexpr uint32_t KEY_SLOTS = 8, KEY_SLOT_BYTES = 2 * 32 * KS_BATCH_MAX;
+  hipEvent_t dev_in = nullptr, dev_out = nullptr;
+  KeySlot key_slots[KEY_SLOTS];
+  uint32_t key_slot_next = 0;
   Tunables tun; // launch-shape decisions, read from the environment once when the context is created
   bool all_tb = false; // every prime is 2^b - c with b > 32, c < 2^32 (DevPrime::tb_c != 0) or below 2^54: ks_inner_kernel<MAC3> applies
   // what ntt_modup_kernel may assume of this context's primes (modup_variant below): every prime has the top-bit

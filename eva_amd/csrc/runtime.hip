@@ -241,6 +241,12 @@ void evah_ctx_destroy(evah_ctx *c) {
   for (auto e : c->prof_free) (void)hipEventDestroy(e);
   for (auto e : c->sync_events) (void)hipEventDestroy(e);
   for (auto e : c->capture_events) (void)hipEventDestroy(e);
+  for (auto &s : c->key_slots) { // (the queue was synchronised above: no copy still reads a slot)
+    if (s.host) { std::memset(s.host, 0, evah_ctx::KEY_SLOT_BYTES); (void)hipHostFree(s.host); }
+    if (s.done) (void)hipEventDestroy(s.done);
+  }
+  if (c->dev_in) (void)hipEventDestroy(c->dev_in);
+  if (c->dev_out) (void)hipEventDestroy(c->dev_out);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   if (c->own) (void)hipStreamDestroy(c->own);

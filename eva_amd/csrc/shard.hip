@@ -94,6 +94,15 @@ void evah_buf_free(evah_ctx *c, evah_buf *b) {
   buf_unref(c, b->buf);
   delete b;
 }
+int evah_buf_wipe(evah_ctx *c, evah_buf *b) {
+  API_BEGIN
+  use(c);
+  if (!b) throw std::invalid_argument("buffer is null");
+  if (c->capturing) throw std::logic_error("evah_buf_wipe cannot be captured into a graph");
+  acquire(c, b->buf);
+  HIPCHK(hipMemsetAsync(b->buf->d, 0, sizeof(u64) * b->words, c->stream));
+  API_END
+}
 void *evah_buf_ptr(evah_buf *b) { return b ? b->buf->d : nullptr; }
 size_t evah_buf_words(const evah_buf *b) { return b ? b->words : 0; }
 

@@ -105,6 +105,16 @@ template <class T> inline bool device_encodable(const HostContext &hc, const T *
 inline bool device_encodable(const HostContext &hc, const std::vector<double> &in, double scale, uint32_t limbs) {
   return device_encodable(hc, in.data(), in.size(), scale, limbs);
 }
+// the same rule on a row's sum of absolute values, for rows the host does not hold (evah_rows_abs_sum_dev, DESIGN.md
+// 1.11): a NaN or an infinity in the row left the sum non-finite
+inline bool device_encodable_sum(const HostContext &hc, double sum, size_t n, double scale, uint32_t limbs) {
+  const size_t slots = hc.N / 2;
+  if (std::getenv("EVA_DEVICE_ENCODE") && !std::atoi(std::getenv("EVA_DEVICE_ENCODE"))) return false;
+  if (n == 0 || n > slots || slots % n || !std::isfinite(sum)) return false;
+  const double bound = 2.0 * sum * (double)(slots / n) * scale / (double)hc.N;
+  const int bits = (int)std::ceil(std::log2(std::max(bound, 1.0))) + 1;
+  return bits < 62 && bits < hc.total_bits[limbs];
+}
 
 // A device handle as a value: resident (it stays in HBM, host words on demand) or downloaded.  seed: the value is
 // seeded — the seed stays with it, so that save() can still write the value compressed, and only c0
@@ -180,8 +190,10 @@ struct ArrayInputs {
   std::vector<const ArrayView *> arr;
 };
 // plains: unencrypted inputs of type Raw with a row per instance — copied into the batch in their own type
-inline ArrayInputs plan_array_inputs(const HostContext &hc, const std::map<std::string, ArrayView> &arrays, const Valuation &shared,
-                                     const CKKSSignature &sig, HipValuationBatch &out, const std::map<std::string, ArrayView> &plains = {}) {
+// devctx: the device state a device array's rows are summed on (one evah_rows_abs_sum_dev per such array, over all B rows)
+inline ArrayInputs plan_array_inputs(const HostContext &hc, std::map<std::string, ArrayView> &arrays, const Valuation &shared,
+                                     const CKKSSignature &sig, HipValuationBatch &out, const std::map<std::string, ArrayView> &plains = {},
+                                     evah_ctx *devctx = nullptr) {
   check_vec_size(sig, hc.N / 2);
   if (arrays.empty()) throw std::invalid_argument("encrypt_array: no encrypted input array was given");
   ArrayInputs in;
@@ -202,14 +214,21 @@ inline ArrayInputs plan_array_inputs(const HostContext &hc, const std::map<std::
       check_input_size(v, sig);
       unencrypted_value(hc, c, v, out.shared[name]);
     } else {
-      const ArrayView &a = it->second;
+      ArrayView &a = it->second;
       if (c.kind != Type::Cipher) throw std::invalid_argument("encrypt_array: input " + name + " is not encrypted: it is one value shared by all instances");
       if (a.n != (size_t)sig.vec_size) throw std::runtime_error("Input size does not match program vector size (input " + name + ")");
       if (a.B != out.B)
         throw std::invalid_argument("encrypt_array: input " + name + " has " + std::to_string(a.B) + " instances, " + arrays.begin()->first + " has " +
                                     std::to_string(out.B));
+      if (a.on_device) { // the rows stay where they are: their sums come to the host, 8 bytes a row
+        if (!devctx) throw std::logic_error("encrypt_array: a device array needs the device state");
+        if (a.B > 0xffffffffull) throw std::invalid_argument("encrypt_array: input " + name + " has too many instances");
+        a.sums = std::make_shared<std::vector<double>>(a.B);
+        chk(evah_rows_abs_sum_dev(devctx, (uint32_t)a.B, a.data, a.dtype, a.row_pitch(), a.producer, (uint32_t)a.n, a.sums->data()));
+      }
       for (size_t b = 0; b < a.B; b++) {
-        const bool ok = a.dtype == EVAH_F64   ? device_encodable(hc, static_cast<const double *>(a.row(b)), a.n, c.scale, c.limbs)
+        const bool ok = a.on_device           ? device_encodable_sum(hc, (*a.sums)[b], a.n, c.scale, c.limbs)
+                        : a.dtype == EVAH_F64 ? device_encodable(hc, static_cast<const double *>(a.row(b)), a.n, c.scale, c.limbs)
                         : a.dtype == EVAH_F32 ? device_encodable(hc, static_cast<const float *>(a.row(b)), a.n, c.scale, c.limbs)
                                               : device_encodable(hc, static_cast<const uint8_t *>(a.row(b)), a.n, c.scale, c.limbs);
         if (!ok)
@@ -231,6 +250,7 @@ inline ArrayInputs plan_array_inputs(const HostContext &hc, const std::map<std::
     if (a.B != out.B)
       throw std::invalid_argument("encrypt_array: input " + name + " has " + std::to_string(a.B) + " instances, " + arrays.begin()->first + " has " +
                                   std::to_string(out.B));
+    if (a.on_device) throw std::invalid_argument("encrypt_array: plain_arrays stays on the host, input " + name + " is a device array");
     PlainRows pr;
     const uint8_t *src = static_cast<const uint8_t *>(a.data);
     pr.bytes = std::make_shared<std::vector<uint8_t>>(src, src + a.B * a.n * a.itemsize());
@@ -535,13 +555,14 @@ inline std::vector<HostCipher> HipPublic::encrypt_group_sampled(const std::vecto
 // encrypted input — so instance b is encrypt_batch's instance b word for word.  Per name the rows leave in segments of
 // <= 64 as ONE evah_encode_encrypt_array each, in the array's type, and the batched handles are kept whole.  Device and
 // resident valuations only: there is no host path behind this call.
-inline HipValuationBatch HipPublic::encrypt_array(const std::map<std::string, ArrayView> &arrays, const Valuation &shared, const CKKSSignature &sig,
+inline HipValuationBatch HipPublic::encrypt_array(const std::map<std::string, ArrayView> &arrays_in, const Valuation &shared, const CKKSSignature &sig,
                                                   uint64_t seed, const std::map<std::string, ArrayView> &plains) {
   require_array_path(client_on_device(), resident);
   HipValuationBatch out;
   out.params = host;
-  const ArrayInputs in = plan_array_inputs(*host, arrays, shared, sig, out, plains);
-  ensure_public_key();
+  std::map<std::string, ArrayView> arrays = arrays_in; // (plan_array_inputs attaches the sums of a device array to its view)
+  ensure_public_key(); // (before the checks: a device array's rows are summed on the device state)
+  const ArrayInputs in = plan_array_inputs(*host, arrays, shared, sig, out, plains, dev->h);
   out.root = dev;
   std::unique_ptr<SecureRng> stream = seed ? std::make_unique<SecureRng>(seed, 5) : std::make_unique<SecureRng>();
   std::vector<std::vector<std::array<uint8_t, 32>>> rkeys(in.names.size()); // per name, per instance
@@ -560,7 +581,10 @@ inline HipValuationBatch HipPublic::encrypt_array(const std::map<std::string, Ar
       const size_t n = std::min<size_t>(CLIENT_BATCH_MAX, out.B - b0);
       std::vector<uint8_t> keys = keys_flat(rkeys[i].data() + b0, n);
       evah_ct *c = nullptr;
-      const int rc = evah_encode_encrypt_array(dev->h, (uint32_t)n, a.row(b0), a.dtype, (uint32_t)a.n, in.cls[i].limbs, in.cls[i].scale, keys.data(), &c);
+      const int rc = a.on_device ? evah_encode_encrypt_array_dev(dev->h, (uint32_t)n, a.row(b0), a.dtype, a.row_pitch(), a.producer, a.sums->data() + b0,
+                                                                 (uint32_t)a.n, in.cls[i].limbs, in.cls[i].scale, keys.data(), &c)
+                                 : evah_encode_encrypt_array(dev->h, (uint32_t)n, a.row(b0), a.dtype, (uint32_t)a.n, in.cls[i].limbs, in.cls[i].scale,
+                                                             keys.data(), &c);
       wipe_bytes(keys.data(), keys.size());
       chk(rc);
       bc.segments.push_back(BatchSegment{std::make_shared<CtHandle>(dev->h, c), (uint32_t)n, nullptr, 2, in.cls[i].limbs, in.cls[i].scale});
@@ -747,13 +771,14 @@ public:
   // streams and the same draws — per instance, names sorted, 4 seed words and a 4-word error key per encrypted input —
   // so instance b is encrypt_batch's word for word.  Per name the rows leave in segments of <= 64 as ONE
   // evah_encode_encrypt_symmetric_array each; the handles are kept whole and the seeds stay with the batch.
-  HipValuationBatch encrypt_array(const std::map<std::string, ArrayView> &arrays, const Valuation &shared, const CKKSSignature &sig,
+  HipValuationBatch encrypt_array(const std::map<std::string, ArrayView> &arrays_in, const Valuation &shared, const CKKSSignature &sig,
                                   uint64_t seed = 0, const std::map<std::string, ArrayView> &plains = {}) {
     require_array_path(on_device(), resident);
     HipValuationBatch out;
     out.params = host;
     out.root = dev;
-    const ArrayInputs in = plan_array_inputs(*host, arrays, shared, sig, out, plains);
+    std::map<std::string, ArrayView> arrays = arrays_in; // (plan_array_inputs attaches the sums of a device array to its view)
+    const ArrayInputs in = plan_array_inputs(*host, arrays, shared, sig, out, plains, dev->h);
     std::unique_ptr<SecureRng> seeds = seed ? std::make_unique<SecureRng>(seed, 4) : std::make_unique<SecureRng>();
     std::unique_ptr<SecureRng> errors = seed ? std::make_unique<SecureRng>(seed, 3) : std::make_unique<SecureRng>();
     std::vector<std::vector<std::array<uint8_t, 32>>> ek(in.names.size()); // per name, per instance
@@ -776,8 +801,11 @@ public:
         std::vector<uint8_t> ekeys = keys_flat(ek[i].data() + b0, n);
         const std::vector<uint8_t> sd = keys_flat(bc.seeds.data() + b0, n);
         evah_ct *c = nullptr;
-        const int rc = evah_encode_encrypt_symmetric_array(dev->h, (uint32_t)n, a.row(b0), a.dtype, (uint32_t)a.n, in.cls[i].limbs, in.cls[i].scale,
-                                                           ekeys.data(), sd.data(), &c);
+        const int rc = a.on_device ? evah_encode_encrypt_symmetric_array_dev(dev->h, (uint32_t)n, a.row(b0), a.dtype, a.row_pitch(), a.producer,
+                                                                             a.sums->data() + b0, (uint32_t)a.n, in.cls[i].limbs, in.cls[i].scale,
+                                                                             ekeys.data(), sd.data(), &c)
+                                   : evah_encode_encrypt_symmetric_array(dev->h, (uint32_t)n, a.row(b0), a.dtype, (uint32_t)a.n, in.cls[i].limbs,
+                                                                         in.cls[i].scale, ekeys.data(), sd.data(), &c);
         wipe_bytes(ekeys.data(), ekeys.size());
         chk(rc);
         bc.segments.push_back(BatchSegment{std::make_shared<CtHandle>(dev->h, c), (uint32_t)n, nullptr, 2, in.cls[i].limbs, in.cls[i].scale});
@@ -789,12 +817,15 @@ public:
   // and scale are packed into calls of <= 64 instances of evah_decrypt_decode_handles, each writing straight into the rows
   // rows[name] + first instance * vec_size * itemsize of the caller's array [B][vec_size] (dtype_out: EVAH_F64, the doubles
   // of decrypt_batch bit for bit, or EVAH_F32).  Needs the device; the batch lives on this key pair's device state.
-  void decrypt_array(const HipValuationBatch &vb, const CKKSSignature &sig, int dtype_out, const std::map<std::string, void *> &rows) {
+  // rows_on_device: the rows are device memory of this key pair's state, written group by group by
+  // evah_decrypt_decode_rows in queue order, with one wait at the end of the call; EVAH_U8 takes that entry point too
+  void decrypt_array(const HipValuationBatch &vb, const CKKSSignature &sig, int dtype_out, const std::map<std::string, void *> &rows,
+                     bool rows_on_device = false) {
     if (!on_device()) throw std::runtime_error("decrypt_array needs a HIP device: none is visible, or EVA_DEVICE_CLIENT=0 keeps the client on the host");
     if (sig.vec_size <= 0) throw std::runtime_error("Signature vector size must be positive");
     if (vb.root != dev) throw std::runtime_error("decrypt_array: the batch lives on the device state of another key pair");
     const uint32_t n_out = (uint32_t)sig.vec_size;
-    const size_t row_bytes = (size_t)n_out * (dtype_out == EVAH_F32 ? 4 : 8);
+    const size_t row_bytes = (size_t)n_out * (dtype_out == EVAH_F32 ? 4 : dtype_out == EVAH_U8 ? 1 : 8);
     for (auto &kv : vb.ciphers) {
       char *out = static_cast<char *>(rows.at(kv.first));
       const auto &segs = kv.second.segments;
@@ -808,12 +839,16 @@ public:
           n += segs[s1++].n;
         }
         if (s1 == s0) throw std::runtime_error("output " + kv.first + ": a segment holds more than 64 instances");
-        chk(evah_decrypt_decode_handles(dev->h, hs.data(), (uint32_t)hs.size(), n_out, dtype_out, out + row * row_bytes));
+        if (rows_on_device || dtype_out == EVAH_U8)
+          chk(evah_decrypt_decode_rows(dev->h, hs.data(), (uint32_t)hs.size(), n_out, dtype_out, out + row * row_bytes, row_bytes, rows_on_device ? 1 : 0, 0));
+        else
+          chk(evah_decrypt_decode_handles(dev->h, hs.data(), (uint32_t)hs.size(), n_out, dtype_out, out + row * row_bytes));
         row += n;
         s0 = s1;
       }
       if (row != vb.B) throw std::runtime_error("output " + kv.first + ": the segments do not hold every instance");
     }
+    if (rows_on_device) chk(evah_ctx_sync(dev->h));
   }
   // the shape check of a ciphertext that is decrypted on the device
   void check_device_shape(const std::string &name, const HostCipher &c) const {

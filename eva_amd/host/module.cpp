@@ -56,6 +56,31 @@ std::map<std::string, ArrayView> array_views(const std::map<std::string, py::arr
   return out;
 }
 
+// the device arrays of encrypt_array as eva_amd.seal.normalise_device_arrays hands them over:
+// {name: (device pointer, EVAH_* code, B, n, row pitch in bytes, producer stream or 0)}, added to the host views
+using DevArrayArgs = std::map<std::string, std::tuple<uintptr_t, int, size_t, size_t, size_t, uintptr_t>>;
+std::map<std::string, ArrayView> with_device_arrays(std::map<std::string, ArrayView> views, const DevArrayArgs &dev) {
+  for (auto &kv : dev) {
+    if (views.count(kv.first)) throw std::invalid_argument("encrypt_array: input " + kv.first + " is given twice");
+    ArrayView v;
+    v.data = reinterpret_cast<const void *>(std::get<0>(kv.second));
+    v.dtype = std::get<1>(kv.second);
+    if (v.dtype != EVAH_F64 && v.dtype != EVAH_F32 && v.dtype != EVAH_U8) throw std::invalid_argument("input " + kv.first + ": the array must be float64, float32 or uint8");
+    v.B = std::get<2>(kv.second);
+    v.n = std::get<3>(kv.second);
+    v.pitch = std::get<4>(kv.second);
+    v.on_device = true;
+    v.producer = reinterpret_cast<void *>(std::get<5>(kv.second));
+    views.emplace(kv.first, v);
+  }
+  return views;
+}
+// decrypt_array's rule for uint8 on values the host holds: np.clip(np.rint(np.nan_to_num(a, nan=0)), 0, 255).astype(uint8)
+py::array as_uint8(const py::array &a) {
+  py::module_ np = py::module_::import("numpy");
+  return py::array(np.attr("clip")(np.attr("rint")(np.attr("nan_to_num")(a, py::arg("nan") = 0.0)), 0, 255).attr("astype")(np.attr("uint8")));
+}
+
 } // namespace
 
 PYBIND11_MODULE(_eva, m) {
@@ -400,11 +425,13 @@ PYBIND11_MODULE(_eva, m) {
       }, "every instance as a SEALValuation (views; a symmetric value keeps its seed, so save() still writes it compressed)");
   py::class_<HipPublic, std::shared_ptr<HipPublic>>(mseal, "SEALPublic", "Public context: encryption and execution on the MI355X")
       .def("_encrypt_array", [](HipPublic &p, const std::map<std::string, py::array> &arrays, const Valuation &shared, const CKKSSignature &sig,
-                                uint64_t seed, const std::map<std::string, py::array> &plains) {
-             return p.encrypt_array(array_views(arrays), shared, sig, seed, array_views(plains));
+                                uint64_t seed, const std::map<std::string, py::array> &plains, const DevArrayArgs &dev_arrays) {
+             return p.encrypt_array(with_device_arrays(array_views(arrays), dev_arrays), shared, sig, seed, array_views(plains));
            },
            py::arg("arrays"), py::arg("shared"), py::arg("signature"), py::arg("seed") = 0, py::arg("plain_arrays") = std::map<std::string, py::array>{},
-           "encrypt_array on normalised arguments (eva_amd.seal.normalise_arrays): C-contiguous [B, n] arrays of float64, float32 or uint8")
+           py::arg("device_arrays") = DevArrayArgs{},
+           "encrypt_array on normalised arguments (eva_amd.seal.normalise_arrays): C-contiguous [B, n] arrays of float64, float32 or uint8; "
+           "device_arrays: rows in device memory (eva_amd.seal.normalise_device_arrays)")
       .def("execute_batch", [](HipPublic &p, Program &program, const HipValuationBatch &inputs) { return p.execute_batch(program, inputs); },
            py::arg("program"), py::arg("inputs"),
            "execute_batch on a SEALValuationBatch: each group's inputs are slices of the batch's handles and its batched outputs are the "
@@ -568,6 +595,32 @@ PYBIND11_MODULE(_eva, m) {
           d[py::int_(kv.first)] = to_numpy(kv.second.words(*p.host, tmp), {(py::ssize_t)kv.second.n_digits, 2, (py::ssize_t)p.host->k, (py::ssize_t)p.host->N});
         return d;
       });
+  py::class_<DeviceArray, std::shared_ptr<DeviceArray>>(mseal, "DeviceArray",
+                                                        "decrypted rows [B, vec_size] in the key pair's device state (decrypt_array(device=True), DESIGN.md 1.11); "
+                                                        "the memory is zeroed on the queue before it returns to the pool")
+      .def_property_readonly("shape", [](const DeviceArray &a) { return py::make_tuple(a.B, a.n); })
+      .def_property_readonly("dtype", [](const DeviceArray &a) {
+        return py::dtype(a.dtype == EVAH_F64 ? "float64" : a.dtype == EVAH_F32 ? "float32" : "uint8");
+      })
+      .def_property_readonly("ptr", [](const DeviceArray &a) { return (uintptr_t)a.ptr(); })
+      .def_property_readonly("__cuda_array_interface__", [](const DeviceArray &a) {
+        py::dict d;
+        d["shape"] = py::make_tuple(a.B, a.n);
+        d["typestr"] = a.dtype == EVAH_F64 ? "<f8" : a.dtype == EVAH_F32 ? "<f4" : "|u1";
+        d["data"] = py::make_tuple((uintptr_t)a.ptr(), false);
+        d["strides"] = py::none();
+        d["version"] = 3;
+        return d;
+      })
+      .def("to_numpy", [](const DeviceArray &a) {
+        const size_t words = (a.bytes() + 7) / 8;
+        std::vector<uint64_t> w(words);
+        chk(evah_buf_download(a.dev->h, a.buf, 0, words, w.data()));
+        py::array out(py::dtype(a.dtype == EVAH_F64 ? "float64" : a.dtype == EVAH_F32 ? "float32" : "uint8"),
+                      std::vector<py::ssize_t>{(py::ssize_t)a.B, (py::ssize_t)a.n});
+        std::memcpy(out.mutable_data(), w.data(), a.bytes());
+        return out;
+      }, "the rows on the host (a synchronising download)");
   py::class_<HipSecret, std::shared_ptr<HipSecret>>(mseal, "SEALSecret", "Secret context: decryption. Holds the secret key.")
       .def("encrypt", [](HipSecret &s, const Valuation &inputs, const CKKSSignature &sig, uint64_t seed) {
         HipValuation v = s.encrypt(inputs, sig, seed);
@@ -585,17 +638,19 @@ PYBIND11_MODULE(_eva, m) {
          "order and names sorted within an instance, so instance 0 of a seeded call equals encrypt() and no two values share a seed. "
          "device_sampling: each error polynomial is expanded from a 32-byte key of the secret stream, on the device in the grouped calls (DESIGN.md 1.7)")
       .def("_encrypt_array", [](HipSecret &s, const std::map<std::string, py::array> &arrays, const Valuation &shared, const CKKSSignature &sig,
-                                uint64_t seed, const std::map<std::string, py::array> &plains) {
-             return s.encrypt_array(array_views(arrays), shared, sig, seed, array_views(plains));
+                                uint64_t seed, const std::map<std::string, py::array> &plains, const DevArrayArgs &dev_arrays) {
+             return s.encrypt_array(with_device_arrays(array_views(arrays), dev_arrays), shared, sig, seed, array_views(plains));
            },
            py::arg("arrays"), py::arg("shared"), py::arg("signature"), py::arg("seed") = 0, py::arg("plain_arrays") = std::map<std::string, py::array>{},
+           py::arg("device_arrays") = DevArrayArgs{},
            "encrypt_array on normalised arguments (eva_amd.seal.normalise_arrays); every ciphertext is seeded")
-      .def("decrypt_array", [](HipSecret &s, py::object enc, const CKKSSignature &sig, py::object dtype) {
+      .def("decrypt_array", [](HipSecret &s, py::object enc, const CKKSSignature &sig, py::object dtype, bool device) {
         const py::dtype dt = py::dtype::from_args(dtype);
         int code;
         if (dt.kind() == 'f' && dt.itemsize() == 8) code = EVAH_F64;
         else if (dt.kind() == 'f' && dt.itemsize() == 4) code = EVAH_F32;
-        else throw std::invalid_argument("decrypt_array: dtype must be float64 or float32");
+        else if (dt.kind() == 'u' && dt.itemsize() == 1) code = EVAH_U8;
+        else throw std::invalid_argument("decrypt_array: dtype must be float64, float32 or uint8");
         if (sig.vec_size <= 0) throw std::runtime_error("Signature vector size must be positive");
         HipValuationBatch from_list;
         const HipValuationBatch *vb;
@@ -608,17 +663,26 @@ PYBIND11_MODULE(_eva, m) {
         }
         py::dict out;
         std::map<std::string, void *> rows;
-        for (auto &kv : vb->ciphers) {
-          py::array a(dt, std::vector<py::ssize_t>{(py::ssize_t)vb->B, (py::ssize_t)sig.vec_size});
-          rows[kv.first] = a.mutable_data();
-          out[py::str(kv.first)] = a;
+        if (device) { // the rows stay in the key pair's device state; unencrypted outputs below stay numpy arrays
+          if (!s.on_device()) throw std::runtime_error("decrypt_array needs a HIP device: none is visible, or EVA_DEVICE_CLIENT=0 keeps the client on the host");
+          for (auto &kv : vb->ciphers) {
+            auto a = std::make_shared<DeviceArray>(s.dev, code, vb->B, (size_t)sig.vec_size);
+            rows[kv.first] = a->ptr();
+            out[py::str(kv.first)] = a;
+          }
+        } else {
+          for (auto &kv : vb->ciphers) {
+            py::array a(dt, std::vector<py::ssize_t>{(py::ssize_t)vb->B, (py::ssize_t)sig.vec_size});
+            rows[kv.first] = a.mutable_data();
+            out[py::str(kv.first)] = a;
+          }
         }
-        s.decrypt_array(*vb, sig, code, rows);
+        s.decrypt_array(*vb, sig, code, rows, device);
         for (auto &kv : vb->shared) { // one value for all instances: decrypt()'s doubles in every row
           const std::vector<double> v = s.decrypt_value(kv.first, kv.second, sig);
           py::array_t<double> a({(py::ssize_t)vb->B, (py::ssize_t)sig.vec_size});
           for (size_t b = 0; b < vb->B; b++) std::copy(v.begin(), v.end(), a.mutable_data() + b * v.size());
-          out[py::str(kv.first)] = code == EVAH_F32 ? py::array(a.attr("astype")(dt)) : py::array(a);
+          out[py::str(kv.first)] = code == EVAH_U8 ? as_uint8(a) : code == EVAH_F32 ? py::array(a.attr("astype")(dt)) : py::array(a);
         }
         for (auto &kv : vb->plains) { // an unencrypted output with a row per instance: [B, vec_size] float64
           const ArrayView &pv = kv.second.view;
@@ -631,10 +695,18 @@ PYBIND11_MODULE(_eva, m) {
           out[py::str(kv.first)] = py::array(a);
         }
         return out;
-      }, py::arg("enc_outputs"), py::arg("signature"), py::arg("dtype") = py::module_::import("numpy").attr("float64"),
+      }, py::arg("enc_outputs"), py::arg("signature"), py::arg("dtype") = py::module_::import("numpy").attr("float64"), py::arg("device") = false,
            "decrypt a SEALValuationBatch (or a list of SEALValuations) into {name: ndarray[B, vec_size]}: up to 64 instances of one name per "
            "device call, written straight into the array's rows; float64 rows are decrypt_batch's doubles bit for bit, float32 rows are those "
-           "doubles rounded to nearest-even on the device")
+           "doubles rounded to nearest-even on the device, uint8 rows the nearest integer (ties to even) clamped to [0, 255], NaN -> 0. "
+           "device=True: every decrypted name is a DeviceArray [B, vec_size] in the key pair's device state instead (no device -> host copy, "
+           "one wait at the end of the call); unencrypted outputs stay numpy arrays")
+      // test hook: an unwritten DeviceArray [B, n] from the pool of the key pair's device state — what the pool hands out next
+      .def("_device_array", [](HipSecret &s, size_t B, size_t n, py::object dtype) {
+        const py::dtype dt = py::dtype::from_args(dtype);
+        if (!s.on_device()) throw std::runtime_error("decrypt_array needs a HIP device: none is visible, or EVA_DEVICE_CLIENT=0 keeps the client on the host");
+        return std::make_shared<DeviceArray>(s.dev, dt.itemsize() == 8 ? EVAH_F64 : dt.itemsize() == 4 ? EVAH_F32 : EVAH_U8, B, n);
+      }, py::arg("B"), py::arg("n"), py::arg("dtype"))
       .def("decrypt", &HipSecret::decrypt, py::arg("enc_outputs"), py::arg("signature"))
       .def("decrypt_batch", &HipSecret::decrypt_batch, py::arg("enc_outputs"), py::arg("signature"),
            "decrypt() of every valuation of a list, bit for bit; on the device up to 64 outputs of one name are decrypted and decoded in one call")

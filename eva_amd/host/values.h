@@ -167,12 +167,41 @@ struct BatchCipher {
   std::vector<std::array<uint8_t, 32>> seeds; // symmetric encryptions: the seed of c1 per instance, else empty
 };
 // an array [B][n] of the caller's, in its own type (EVAH_F64 / EVAH_F32 / EVAH_U8), C-contiguous
+// — or rows in device memory, possibly pitched, which the host never dereferences: on_device, with the
+// stream that produced them (null: the caller synchronised) and, once plan_array_inputs has asked the device for them,
+// the rows' sums of absolute values
 struct ArrayView {
   const void *data = nullptr;
   int dtype = EVAH_F64;
   size_t B = 0, n = 0;
+  size_t pitch = 0; // bytes between rows; 0: contiguous
+  bool on_device = false;
+  void *producer = nullptr;
+  std::shared_ptr<std::vector<double>> sums;
   size_t itemsize() const { return dtype == EVAH_F64 ? 8 : dtype == EVAH_F32 ? 4 : 1; }
-  const void *row(size_t b) const { return static_cast<const char *>(data) + b * n * itemsize(); }
+  size_t row_pitch() const { return pitch ? pitch : n * itemsize(); }
+  const void *row(size_t b) const { return static_cast<const char *>(data) + b * row_pitch(); }
+};
+// memory of a key pair's device state that holds decrypted rows [B][n] (decrypt_array(device=True)):
+// zeroed on the queue before it returns to the pool
+struct DeviceArray {
+  std::shared_ptr<DeviceCtx> dev;
+  evah_buf *buf = nullptr;
+  int dtype = EVAH_F64;
+  size_t B = 0, n = 0;
+  DeviceArray(std::shared_ptr<DeviceCtx> d, int dt, size_t B_, size_t n_) : dev(std::move(d)), dtype(dt), B(B_), n(n_) {
+    chk(evah_buf_alloc(dev->h, (bytes() + 7) / 8, &buf));
+  }
+  DeviceArray(const DeviceArray &) = delete;
+  DeviceArray &operator=(const DeviceArray &) = delete;
+  ~DeviceArray() {
+    if (!buf) return;
+    (void)evah_buf_wipe(dev->h, buf);
+    evah_buf_free(dev->h, buf);
+  }
+  size_t itemsize() const { return dtype == EVAH_F64 ? 8 : dtype == EVAH_F32 ? 4 : 1; }
+  size_t bytes() const { return B * n * itemsize(); }
+  void *ptr() const { return evah_buf_ptr(buf); }
 };
 // row b as the doubles its values convert to exactly
 inline std::vector<double> array_row_doubles(const ArrayView &a, size_t b) {

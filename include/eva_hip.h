@@ -457,6 +457,55 @@ int evah_encode_encrypt_symmetric_array(evah_ctx *ctx, uint32_t batch, const voi
 int evah_decrypt_decode_handles(evah_ctx *ctx, const evah_ct *const *cts, uint32_t n_handles, uint32_t n_out, int dtype_out,
                                 void *out);
 
+/* ---- the array calls on device memory ----------------------------------------------------------
+ * The inputs of seal.cpp:24-102 and the outputs of seal.cpp:124-146 as rows that already live in HBM (a torch tensor, an
+ * evah_buf): in place of the host -> device copy of evah_encode_encrypt_array and the device -> host copy of
+ * evah_decrypt_decode_handles, the encoder's scatter reads and the decoder's gather writes the caller's memory.  Row b
+ * starts at byte b * row_pitch of the base; row_pitch is at least a row and a multiple of the item size (a slice
+ * t[:, :n] is pitched), the base is aligned to the item size and nothing more.
+ * values / out must be device memory of ctx's GPU (hipPointerGetAttributes; host and managed memory are refused by
+ * name), and where the runtime knows the allocation the rows must lie inside it.
+ * Ordering: ctx's queue is a non-blocking stream and is ordered against nobody else's.  `producer` is the hipStream_t on
+ * which the caller's array was written (hipStreamLegacy = (hipStream_t)1 for the null stream), or NULL.  Given, the queue
+ * waits for an event recorded on it before its first read, and an event recorded on the queue behind the last kernel
+ * that reads `values` is made a dependency of `producer` (hipStreamWaitEvent): a later overwrite, or a free and reuse, on
+ * that stream cannot overtake the read.  NULL: the caller has synchronised beforehand, and the call waits on the host
+ * for that second event before it returns.  The events are kept by the queue, not created per call.
+ * All refusals — a capturing context, memory that is not device memory of this GPU, a pitch smaller than a row or not a
+ * multiple of the item size, an unknown dtype, and those of the host-array calls — come before anything is launched. */
+/* sums_out[b] (host, `rows` doubles) = sum_i |values[b][i]| in FP64, every value read as the double it converts to
+ * exactly: what check_encodable adds up, computed where the rows are.  One launch, one copy of 8 * rows bytes, one wait.
+ * A row's sum is the same on every run (fixed order, no atomics) and may differ from a serial sum in its last bits; a
+ * NaN or an infinity in a row leaves its sum non-finite.  rows is not limited to 64. */
+int evah_rows_abs_sum_dev(evah_ctx *ctx, uint32_t rows, const void *values, int dtype, size_t row_pitch, void *producer,
+                          uint32_t n_values, double *sums_out);
+/* evah_encode_encrypt_array / evah_encode_encrypt_symmetric_array (seal.cpp:24-102) on rows in device memory: instance b
+ * is word for word what those calls give for the same rows brought to the host.  No value byte crosses PCIe; the
+ * randomness keys (and seeds) go up as before, through pinned blocks of the queue, and evah_ctx_transfer_stats out[4]
+ * grows by 32 * batch (64 * batch).  THE CALL DOES NOT DRAIN THE QUEUE: the handle is valid in queue order, like every
+ * evaluator result.
+ * row_sums: NULL, and the call computes evah_rows_abs_sum_dev itself (one more launch and one wait); or the sums that
+ * evah_rows_abs_sum_dev returned for exactly these rows, to which check_encodable's rule (bound below 2^62, finite) is
+ * applied without a launch.  The library TRUSTS such sums: it cannot tell whether the rows were rewritten in between.
+ * Sums that understate the rows give wrong words in the affected instances (a coefficient beyond the 63 bits the
+ * rounding keeps) — never an access out of bounds: every index the kernels form comes from batch, n_values and
+ * row_pitch, not from a value. */
+int evah_encode_encrypt_array_dev(evah_ctx *ctx, uint32_t batch, const void *values, int dtype, size_t row_pitch, void *producer,
+                                  const double *row_sums, uint32_t n_values, uint32_t limbs, double scale, const uint8_t *rkeys,
+                                  evah_ct **out);
+int evah_encode_encrypt_symmetric_array_dev(evah_ctx *ctx, uint32_t batch, const void *values, int dtype, size_t row_pitch,
+                                            void *producer, const double *row_sums, uint32_t n_values, uint32_t limbs, double scale,
+                                            const uint8_t *ekeys, const uint8_t *seeds, evah_ct **out);
+/* evah_decrypt_decode_handles (seal.cpp:124-146: the same checks, messages, launches and scratch wipes) into rows of
+ * row_pitch bytes.  out_on_device = 0: host memory, and the call waits whatever `wait` says; out_on_device = 1: device
+ * memory of ctx's GPU, written by the gather — no device -> host copy — and wait = 0 leaves the call in queue order
+ * (evah_ctx_sync, or evah_ctx_wait from the consumer's queue, before the rows are read).  dtype_out: EVAH_F64 and
+ * EVAH_F32 rows carry evah_decrypt_decode_handles' bit patterns; EVAH_U8 is the double rounded to the nearest integer,
+ * ties to even, clamped to [0, 255], NaN -> 0.  The bytes between rows are not touched.  Host rows count in
+ * evah_ctx_transfer_stats out[5], device rows do not. */
+int evah_decrypt_decode_rows(evah_ctx *ctx, const evah_ct *const *cts, uint32_t n_handles, uint32_t n_out, int dtype_out, void *out,
+                             size_t row_pitch, int out_on_device, int wait);
+
 /* ---- whole-DAG submit: a topologically sorted flat op list over a value table.
  * One call replaces the per-node loop ProgramTraversal::forwardPass + SEALExecutor::operator()
  * (program_traversal.h:36-93, seal_executor.h:279-404) for the encrypted part of a program.
@@ -533,6 +582,9 @@ int evah_ctx_set_shard(evah_ctx *ctx, uint32_t shard, uint32_t n_shards);
 int evah_ctx_shard_info(evah_ctx *ctx, uint32_t *shard, uint32_t *n_shards);
 int evah_buf_alloc(evah_ctx *ctx, size_t words, evah_buf **out);
 void evah_buf_free(evah_ctx *ctx, evah_buf *buf);
+/* zero the buffer on ctx's queue (the queue it was allocated from): what a holder of decrypted values does before
+ * evah_buf_free returns the memory to the pool */
+int evah_buf_wipe(evah_ctx *ctx, evah_buf *buf);
 void *evah_buf_ptr(evah_buf *buf);
 size_t evah_buf_words(const evah_buf *buf);
 int evah_buf_copy(evah_ctx *dst_ctx, evah_buf *dst, size_t dst_off, const evah_buf *src, size_t src_off, size_t words);
