@@ -56,6 +56,7 @@ _SIGS = {
     "evah_ctx_transfer_stats": [_vp, _u64p],
     "evah_ctx_modup_variant": [_vp, C.POINTER(C.c_uint32)],
     "evah_ctx_tail_variant": [_vp, C.POINTER(C.c_uint32)],
+    "evah_ctx_ks_tail": [_vp, C.POINTER(C.c_uint32)],
     "evah_ctx_key_bytes": [_vp, _u64p],
     "evah_ctx_key_bytes_detail": [_vp, _u64p],
     "evah_ctx_key_upload_stats": [_vp, _u64p],
@@ -798,6 +799,13 @@ class Context:
         out = (C.c_uint32 * 3)()
         _chk(_lib.evah_ctx_tail_variant(self.h, out))
         return bool(out[0]), bool(out[1]), bool(out[2])
+
+    def ks_tail(self):
+        """(the tail's contiguous passes run inside the key-switch kernel, fewest workgroups of the first key-switch slice
+        for which they do; 0 = every eligible launch set) of this context's relinearize + rescale (EVAH_KS_TAIL)"""
+        out = (C.c_uint32 * 2)()
+        _chk(_lib.evah_ctx_ks_tail(self.h, out))
+        return bool(out[0]), int(out[1])
 
     def key_bytes(self):
         """bytes of HBM the evaluation keys of this device state occupy (a limb shard holds its prime rows only)"""

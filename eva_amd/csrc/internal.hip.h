@@ -350,6 +350,17 @@ struct Tunables {
   // forward transform reading both once per output prime).  Same words either way.  EVAH_MODUP_SPEC=0 selects the
   // generic tail kernel as it does the generic mod-up (tail_variant below)
   bool tail_fuse = true;
+  // EVAH_KS_TAIL (unset = by size): where the three-launch tail above applies, the key switch is the one-wave radix-2^30
+  // kernel and every prime has the top-bit shape, the two contiguous launches of that tail run inside the key-switch
+  // kernel instead (ks_inner_kernel TAIL, ntt_ks_inner.hip.h): it is launched as two row slices around ntt_tail_kernel —
+  // rows l - 1 and l leave as the contiguous inverse pass's intermediates r and t, rows 0 .. l - 2 take the correction
+  // tile in, transform it and store the output words — five launches, and prod never reaches memory.  Same words.
+  // 1 = wherever that holds; 0 = never (the six launches at throughput size, for A/B runs within one library);
+  // unset = where slice A alone fills the chip: its 2 n N / 256 one-wave workgroups each walk a whole digit loop, so a
+  // launch set with fewer than EVAH_KS_TAIL_MIN_WGS (4096 = 256 CUs x 4 SIMDs x the kernel's 4 waves) of them would run
+  // that loop twice in a row on a part of the chip where one launch walks it once on all of it
+  int ks_tail = -1;
+  uint32_t ks_tail_min_wgs = 4096;
   // EVAH_LDS_EXTRA (0): bytes of dynamic LDS added to every ntt_pass_kernel launch — an occupancy probe for the
   // tuning notes (fewer workgroups per CU), never set in production
   uint32_t lds_extra = 0;
@@ -399,6 +410,8 @@ struct Tunables {
     if (const char *e = std::getenv("EVAH_MODUP_LR")) t.modup_lr = std::atoi(e) == 2 ? 2 : 3;
     flag("EVAH_MODUP_SPEC", t.modup_spec);
     flag("EVAH_TAIL_FUSE", t.tail_fuse);
+    if (const char *e = std::getenv("EVAH_KS_TAIL")) t.ks_tail = std::atoi(e) != 0 ? 1 : 0;
+    count("EVAH_KS_TAIL_MIN_WGS", t.ks_tail_min_wgs);
     if (const char *e = std::getenv("EVAH_KS_GROUPS")) t.ks_groups = std::max(1, std::atoi(e));
     if (const char *e = std::getenv("EVAH_KS_THREADS")) {
       const int n = std::atoi(e);
@@ -467,6 +480,18 @@ struct TailVariant { bool fused, tbonly, lazyonly; };
 inline TailVariant tail_variant(const evah_ctx *c) {
   const bool tb = c->tun.modup_spec && EVAH_TOPBIT && c->modup_tb;
   return {c->tun.tail_fuse, tb, tb && c->tail_lazy};
+}
+
+// whether a context's relinearize + rescale launch sets run the tail's contiguous passes inside the key-switch kernel
+// (Tunables::ks_tail) once the launch set itself qualifies — the mod-up kernel's size, a level of 2 .. 15 limbs, whole keys
+// in the split layout (relin_rescale_core) — and the smallest slice A it does so for (0: every size)
+struct KsTailVariant { bool on; uint32_t min_wgs; };
+inline KsTailVariant ks_tail_variant(const evah_ctx *c) {
+  const bool one_wave = (std::min<uint32_t>(c->N, (uint32_t)c->tun.ks_threads << 2) >> 2) <= 64;
+  const bool modup = c->tun.modup && std::max(1, c->tun.ks_groups) == 1 && c->N >= 2048 && (c->logN + 1) / 2 <= 9;
+  const bool on = c->tun.ks_tail != 0 && c->tun.fold_pa && c->tun.fuse_mac && c->tun.tail_fuse && modup && EVAH_TOPBIT &&
+                  c->modup_tb && c->tun.mac3 && c->all_tb && one_wave;
+  return {on, on && c->tun.ks_tail < 0 ? c->tun.ks_tail_min_wgs : 0};
 }
 
 inline void use(evah_ctx *c) { HIPCHK(hipSetDevice(c->device)); }

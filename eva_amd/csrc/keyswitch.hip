@@ -78,19 +78,30 @@ static void launch_ks_inner_p(evah_ctx *c, const u64 *target, const u64 *scratch
   const uint32_t n_tiles = c->N / tile;
   // the one-wave workgroup (the default) is compiled with its own launch bound: the register
   // allocator is not held to the 256-thread budget
-  auto go = [&](auto kernel, const auto &mt, const auto &at) {
+  auto go_tail = [&](auto kernel, const auto &mt, const auto &at, const auto &tl) {
     hipLaunchKernelGGL(kernel, dim3(n_tiles * kb.n, kb.ni), dim3(tile >> LR), lds, c->stream, c->dev, target, kb.target_bs, scratch,
                        kb.scratch_bs, kb.keys, prod, kb.prod_bs, l, kb.i0, logC, n_tiles, kb.n, kb.targets, mt, kb.istep,
-                       kb.nout ? kb.nout : l + 1, kb.r_out, at, (kb.lazy_out ? 1 : 0) | (kb.diag ? 2 : 0), kb.fold_row);
+                       kb.nout ? kb.nout : l + 1, kb.r_out, at, (kb.lazy_out ? 1 : 0) | (kb.diag ? 2 : 0), kb.fold_row, tl);
   };
-  if (kb.r_out && (!one_wave || kb.istep != 1)) throw std::logic_error("fused special-row inverse pass needs the one-wave key-switch kernel");
+  auto go = [&](auto kernel, const auto &mt, const auto &at) { go_tail(kernel, mt, at, NoMul{}); };
+  if (kb.r_out && !kb.tail && (!one_wave || kb.istep != 1)) throw std::logic_error("fused special-row inverse pass needs the one-wave key-switch kernel");
   if (kb.fold && kb.istep != 1) throw std::logic_error("the folded key-switch forms are not used on limb shards");
   if (kb.fold && !kb.mul && !kb.adds) throw std::logic_error("folded key switch without polynomials to fold");
+  if (kb.tail) {
+    // the slices' rows are fixed: the kernel tells the special row from the last one, and a data row from both, by them
+    const bool rows_ok = kb.tail == KS_TAIL_A ? (kb.i0 + 1 == l && kb.ni == 2 && kb.tail_out.t) : (kb.i0 == 0 && kb.ni + 1 == l && kb.tail_out.dst_ps);
+    if (P < 6 || !kb.mac3 || !one_wave || !kb.fold || kb.istep != 1 || kb.diag || kb.fold_row != ~0u || !kb.r_out || l < 2 || !rows_ok)
+      throw std::logic_error("key-switch tail epilogue outside its form");
+  }
   const int mode = kb.mul ? (kb.fold ? KS_FOLDMUL : KS_MUL) : (kb.fold ? KS_FOLDADD : KS_PLAIN);
   auto with_mode = [&](auto mode_tag) {
     constexpr int M = decltype(mode_tag)::value;
     const KsMulArg<M> mt = [&] { if constexpr (M == KS_MUL || M == KS_FOLDMUL) return *kb.mul; else return NoMul{}; }();
     const KsAddArg<M> at = [&] { if constexpr (M == KS_FOLDADD) return *kb.adds; else return NoMul{}; }();
+    if constexpr ((M == KS_FOLDMUL || M == KS_FOLDADD) && P >= 6) { // (the mod-up these slices follow needs N >= 2048)
+      if (kb.tail == KS_TAIL_A) { go_tail(ks_inner_kernel<P, LR, 64, M, false, true, KS_TAIL_A>, mt, at, kb.tail_out); return; }
+      if (kb.tail == KS_TAIL_B) { go_tail(ks_inner_kernel<P, LR, 64, M, false, true, KS_TAIL_B>, mt, at, kb.tail_out); return; }
+    }
     if constexpr (M != KS_MUL) { // radix-2^30 accumulation: the one-wave kernels of the current forms
       if (kb.mac3 && one_wave) {
         if (kb.r_out) go(ks_inner_kernel<P, LR, 64, M, true, true>, mt, at);
@@ -130,6 +141,16 @@ static bool ks_takes_modup(evah_ctx *c, uint32_t l, uint32_t n) {
   return !ks_small(c, l, n) && c->tun.modup && c->tun.fuse_mac && std::max(1, c->tun.ks_groups) == 1 && modup_fits(c);
 }
 
+// relinearize + rescale of n instances at level l with the tail's contiguous passes inside the key-switch kernel
+// (Tunables::ks_tail): where the three-launch tail applies (relin_rescale_core), the key switch is the one-wave radix-2^30
+// kernel on the split relinearization key, and — unless the knob is set — slice A's workgroups fill the chip
+static bool ks_tail_applies(evah_ctx *c, uint32_t l, uint32_t n) {
+  const KsTailVariant v = ks_tail_variant(c);
+  if (!v.on || l < 2 || !ks_takes_modup(c, l, n) || !ks_mac3(c, l)) return false;
+  if (!c->sh->relin.d_split || c->sh->relin.rows != c->k || c->sh->relin.n_digits < l) return false;
+  return (uint64_t)2 * n * (c->N / 256) >= v.min_wgs;
+}
+
 // SEAL Evaluator::switch_key_inplace, device version.
 //   out[K] = (add && K < add_polys ? add[K] : 0) + keyswitch(target)[K],  K in {0,1}
 // steps 1-2 of switch_key for a batch of n (target, key) pairs in one set of launches:
@@ -140,9 +161,10 @@ static bool ks_takes_modup(evah_ctx *c, uint32_t l, uint32_t n) {
 // here (fused into the key-switch kernel) — the special rows of prod are then NOT written.
 bool switch_key_products(evah_ctx *c, uint32_t l, const u64 *target, size_t target_bs, const KeyDev *const *keys,
                          uint32_t n, u64 *prod_d, const PtrTab *target_tab, const MulTab *mul, u64 *r_small, bool fold,
-                         const PtrTab *adds, bool lazy_out) {
+                         const PtrTab *adds, bool lazy_out, const KsTailPlan *tail) {
   const size_t N = c->N;
   KsBatch kb = ks_batch(c, l, keys, n, /*mac3_ok=*/!(mul && !fold)); // (not the r03 fused-multiply form)
+  if (tail && !(kb.mac3 && fold && ks_takes_modup(c, l, n))) throw std::logic_error("key-switch tail epilogue outside its form");
   kb.target_bs = target_bs;
   if (target_tab) kb.targets = *target_tab; // target == nullptr: separately allocated targets
   kb.mul = mul;
@@ -193,6 +215,29 @@ bool switch_key_products(evah_ctx *c, uint32_t l, const u64 *target, size_t targ
     // (relinearize_many of Harris' three products: 3456 digit tiles, 768 mod-down tiles): the special rows' first inverse
     // pass then rides the key-switch kernel here as well (one launch of ~6 us less)
     if (r_small && groups == 1 && c->tun.fuse_special_inv && ks_one_wave(c)) kb.r_out = r_small;
+    if (tail) { // (groups == 1 and the mod-up: checked above)
+      dp.i0 = 0;
+      dp.ni = l + 1;
+      launch_modup<OpKsDigit>(c, dp, n);
+      // slice A: the last and the special rows, leaving as the contiguous inverse pass's intermediates in t and r
+      kb.tail = KS_TAIL_A;
+      kb.i0 = l - 1;
+      kb.ni = 2;
+      kb.r_out = const_cast<u64 *>(tail->lp.r);
+      kb.tail_out = KsTailOut{tail->lp.t, 0};
+      launch_ks_inner(c, b, target, sc.d, kb, nullptr, l);
+      // both strided inverse passes and the correction's strided forward pass under every output prime, first-pass words
+      // to the output buffer
+      launch_tail(c, tail->lp, tail->rp, 2 * n);
+      // slice B: the data rows below the last, each workgroup finishing the output words of its tile in place
+      kb.tail = KS_TAIL_B;
+      kb.i0 = 0;
+      kb.ni = l - 1;
+      kb.r_out = tail->rp.dst;
+      kb.tail_out = KsTailOut{nullptr, tail->rp.dst_ps};
+      launch_ks_inner(c, b, target, sc.d, kb, nullptr, l);
+      return false;
+    }
     for (uint32_t g = 0; g < groups; g++) {
       const uint32_t i0 = (uint32_t)((uint64_t)(l + 1) * g / groups), i1 = (uint32_t)((uint64_t)(l + 1) * (g + 1) / groups);
       if (i1 == i0) continue;
@@ -306,11 +351,26 @@ static void relin_rescale_core(evah_ctx *c, uint32_t l, uint32_t n, const Size3T
     a_polys = in->c01;
     for (uint32_t i = 0; i < 2 * n; i++) a_last.p[i] = a_polys.p[i] + (size_t)last * N;
   }
-  Scratch prod(c, (size_t)n * 2 * pps);
   std::vector<const KeyDev *> keys(n, &c->sh->relin);
   // r04: P * (the polynomials the key-switch result is added to) goes into the inner products themselves, so the
   // combine passes below read prod only (Tunables::fold_pa; the r03 forms stay for A/B runs)
   const bool fold = c->tun.fold_pa && c->tun.fuse_mac; // EVAH_FUSE_MAC=0 (the unfused reference path): the OpRR / OpRRLast forms below
+  if (ks_tail_applies(c, l, n)) {
+    // r10: five launches — the key-switch kernel runs the tail's two contiguous passes on the tiles it holds, as two
+    // row slices around ntt_tail_kernel; prod is not allocated.  The contiguous forward rounds of slice B are the
+    // digits' (input < 9q from a top-bit strided pass, < 16q from the compare-and-subtract one): the tail
+    // kernel ends its rows with the RoundSeq the mod-up ends its own with, and ks_tail_applies admits only contexts
+    // whose primes all have the top-bit shape, so the < 9q holds for each tail variant that can get here (TBONLY,
+    // LAZYONLY, and the generic kernel under EVAH_MODUP_SPEC=0, whose forward_rounds then pick the top-bit rounds
+    // row by row).  A prime of another shape below 2^54, which MAC3 alone admits, would ride the kernel's rounds
+    // unreduced to (16 + 4 P) q, past the 16q OpRRT::combine takes: such a context keeps the launches below.
+    Scratch r(c, (size_t)n * 2 * N), t(c, (size_t)n * 2 * N);
+    KsTailPlan plan{OpRRLastFolded::Params{nullptr, 0, nullptr, pps, r.d, N, t.d, N, last, sp, {}},
+                    OpRRFolded::Params{r.d, N, t.d, N, nullptr, 0, nullptr, pps, out_d, ops, sp, last, l - 1, {}}};
+    switch_key_products(c, l, nullptr, 0, keys.data(), n, nullptr, &c2, mul, nullptr, fold, mul ? nullptr : &a_polys, /*lazy_out=*/true, &plan);
+    return;
+  }
+  Scratch prod(c, (size_t)n * 2 * pps);
   switch_key_products(c, l, nullptr, 0, keys.data(), n, prod.d, &c2, mul, nullptr, fold, mul ? nullptr : &a_polys, /*lazy_out=*/fold);
   Scratch r(c, (size_t)n * 2 * N), t(c, (size_t)n * 2 * N);
   if (fold && tail_variant(c).fused && ks_takes_modup(c, l, n)) {

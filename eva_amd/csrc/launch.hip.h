@@ -147,6 +147,17 @@ struct KsBatch { // one launch worth of key-switches: regular strides, irregular
   u64 *r_out = nullptr; // != nullptr: the special row leaves as the first inverse pass of the mod-down (INVSP)
   bool diag = false;    // the diagonal digit comes from scratch too (no NTT-form target: the chain step, ntt_chain.hip.h)
   uint32_t fold_row = ~0u; // KS_FOLDMUL: != ~0u adds (P q_a^-1) d_K, a = fold_row, instead of P d_K
+  // a slice of the relinearize + rescale key switch that runs the tail's contiguous passes itself (ks_inner_kernel TAIL;
+  // prod is not written).  KS_TAIL_A: i0 = l - 1, ni = 2, r_out = r, tail_out.t = t; KS_TAIL_B: i0 = 0, ni = l - 1,
+  // r_out = the output buffer, tail_out.dst_ps = its polynomial stride
+  int tail = KS_TAIL_NONE;
+  KsTailOut tail_out{};
+};
+// What relin_rescale_core hands switch_key_products when the key switch runs the tail's contiguous passes (EVAH_KS_TAIL):
+// the launch set is mod-up, slice A, ntt_tail_kernel (lp, rp), slice B, and prod is never touched
+struct KsTailPlan {
+  OpRRLastFolded::Params lp; // r, t, last, sp (prod is not read)
+  OpRRFolded::Params rp;     // dst = the output buffer, which slice B finishes in place (r, t, prod are not read)
 };
 // The operand table of pairs x B products of size-2 ciphertexts at level l — entry i * B + x is instance x of pair i —
 // with the checks every call that multiplies makes of its operands (batch_msg: its text for a handle that does not hold
@@ -335,7 +346,7 @@ static void inverse_then_forward(evah_ctx *c, const typename InvOp::Params &ip, 
 // steps 1-2 of SEAL's switch_key_inplace for a batch of n (target, key) pairs (see the definition)
 bool switch_key_products(evah_ctx *c, uint32_t l, const u64 *target, size_t target_bs, const KeyDev *const *keys, uint32_t n,
                          u64 *prod_d, const PtrTab *target_tab = nullptr, const MulTab *mul = nullptr, u64 *r_small = nullptr,
-                         bool fold = false, const PtrTab *adds = nullptr, bool lazy_out = false);
+                         bool fold = false, const PtrTab *adds = nullptr, bool lazy_out = false, const KsTailPlan *tail = nullptr);
 void switch_key(evah_ctx *c, uint32_t l, const u64 *target, const KeyDev &key, const u64 *add, size_t add_ps, uint32_t add_polys,
                 u64 *out, size_t out_ps);
 // ---- defined in elementwise.hip: dst[i] = (src[i] mod 2^30) | (src[i] >> 30) << 32 (KeyDev::d_split)

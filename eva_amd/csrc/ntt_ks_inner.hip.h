@@ -131,12 +131,45 @@ __device__ __forceinline__ u128_t mac3_recombine(u64 s0, u64 s1, u64 s2) {
 // where the 128-bit accumulation takes 28.  A1 holds 7 digits (14 products < 16 x 2^60), so the sums are normalised
 // (carry words moved up) every 7 digits; after the loop they are recombined into the 128-bit accumulators the
 // epilogue works on.  6 registers per accumulator instead of 4.
-template <int P, int LR, int MAXT, int MODE, bool INVSP = false, bool MAC3 = false>
+// TAIL (relinearize + rescale at throughput size, the one-wave MAC3 kernel in a fold mode; EVAH_KS_TAIL): the two
+// contiguous passes of the tail run here, on the tile whose inner product the workgroup holds in registers, and prod is
+// never written.  The key switch is launched as two row slices around ntt_tail_kernel:
+//   KS_TAIL_A  rows l - 1 and l.  After the fold the workgroup restages its twiddle heaps from the inverse table and runs
+//              the contiguous inverse pass of its tile for K = 0, 1 — what OpTailIntt does from prod: the special row
+//              canonical (as INVSP), lazy intermediate to r_out[2 inst + K]; the last row times P^-1 mod q_last
+//              (OpRRLastT<RR_FOLDED>::load; the exact Shoup product takes the lazy word reduce128_lazy leaves), lazy
+//              intermediate to tail.t[2 inst + K].
+//   KS_TAIL_B  rows 0 .. l - 2, after ntt_tail_kernel left the lazy first-pass words of the correction in the output
+//              buffer (r_out = out[0], polynomial 2 inst + K at tail.dst_ps words).  For K = 0, 1 the workgroup brings the
+//              correction tile of its row into `lin` by LDS-DMA, runs the contiguous forward rounds of the digits on it
+//              (the forward heaps are still staged), combines the transformed word with its accumulator
+//              (OpRRT<RR_FOLDED>::combine) and stores the output word where the correction was read.  Only this wave
+//              touches that tile.  Bounds: the correction arrives < 9q — every prime has the top-bit shape on this path
+//              (the host gates on evah_ctx::modup_tb), so the tail kernel's strided rounds are the top-bit ones in each
+//              of its variants — and the top-bit contiguous rounds leave < 13q, inside the < 16q the combine takes.
+// Both run after the digit loop, where the radix-2^30 sums and the key prefetch are dead, like the fold.
+constexpr int KS_TAIL_NONE = 0, KS_TAIL_A = 1, KS_TAIL_B = 2;
+struct KsTailOut {
+  u64 *t;        // KS_TAIL_A: [2 n_inst][N], the last rows' intermediate
+  size_t dst_ps; // KS_TAIL_B: words between the polynomials of the output buffer
+};
+template <int TAIL> struct KsTailArgs { using Out = KsTailOut; };
+template <> struct KsTailArgs<KS_TAIL_NONE> { using Out = NoMul; };
+template <int TAIL> using KsTailArg = typename KsTailArgs<TAIL>::Out;
+// the combine of relinearize + rescale lives with its op (ntt_ops.hip.h, which needs the tables above and therefore
+// follows this header): the kernel names it through its template parameter, so it is looked up at instantiation
+template <int AM> struct OpRRT;
+template <int TAIL> struct KsTailOps { using RR = OpRRT<2>; }; // RR_FOLDED
+
+template <int P, int LR, int MAXT, int MODE, bool INVSP = false, bool MAC3 = false, int TAIL = KS_TAIL_NONE>
 __global__ void __launch_bounds__(MAXT)
 ks_inner_kernel(DevCtx cx, const u64 *__restrict__ target_b, size_t target_bs, const u64 *__restrict__ scratch_b,
                 size_t scratch_bs, KsKeys keys, u64 *__restrict__ prod_b, size_t prod_bs, uint32_t l, uint32_t i0,
                 int logC, uint32_t n_tiles, uint32_t n_inst, PtrTab targets, KsMulArg<MODE> mul, uint32_t istep,
-                uint32_t nout, u64 *__restrict__ r_out, KsAddArg<MODE> adds, int flags, uint32_t fold_row) {
+                uint32_t nout, u64 *__restrict__ r_out, KsAddArg<MODE> adds, int flags, uint32_t fold_row,
+                KsTailArg<TAIL> tail) {
+  static_assert(TAIL == KS_TAIL_NONE || (MAC3 && !INVSP && MAXT == 64 && (MODE == KS_FOLDMUL || MODE == KS_FOLDADD)),
+                "the tail epilogues belong to the one-wave radix-2^30 kernel in a fold mode");
   // flags: bit 0 = lazy_out; bit 1 = diag — the diagonal digit I == J comes from scratch like every other (first-pass
   // intermediate of its forward transform) instead of an NTT-form target (the chain step, ntt_chain.hip.h).
   // fold_row (KS_FOLDMUL / KS_FOLDADD): ~0u adds P d_K; a = fold_row adds (P q_a^-1) d_K (DevCtx::plinv — the chain step's folded rescale)
@@ -370,6 +403,21 @@ ks_inner_kernel(DevCtx cx, const u64 *__restrict__ target_b, size_t target_bs, c
       acc1[i] = mac3_recombine(s0[1][i], s1[1][i], s2[1][i]);
     }
   }
+  // KS_TAIL_B: the correction tile of (inst, K, I), where the output word goes as well; K = 0's tile is requested before
+  // the fold, whose operand loads it then travels with (`lin` is free: the last digit's reads of it are waited for)
+  u64 *tail_row = nullptr; // (block-uniform: K = 0's tile)
+  size_t tail_ps = 0;
+  auto dma_corr = [&](int K) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // reads of `lin` issued so far have returned
+#pragma unroll
+    for (int it = 0; it < NPAIR; it++)
+      __builtin_amdgcn_global_load_lds(tail_row + (size_t)K * tail_ps + 2 * (threadIdx.x + it * T), lin + 2 * it * T, 16, 0, 0);
+  };
+  if constexpr (TAIL == KS_TAIL_B) {
+    tail_ps = tail.dst_ps;
+    tail_row = r_out + (size_t)2 * inst * tail_ps + (size_t)I * N + gbase;
+    dma_corr(0);
+  }
   if constexpr (MODE == KS_FOLDMUL || MODE == KS_FOLDADD) {
     { // after the digit loop, where its prefetch registers are free (as a prologue the block cost 32 VGPRs: 147, 3 waves
       // per SIMD).  No branch: the special row multiplies by modq[P][P] = (0, 0) — P = 0 mod P — and reads a row that exists
@@ -440,6 +488,99 @@ ks_inner_kernel(DevCtx cx, const u64 *__restrict__ target_b, size_t target_bs, c
       }
       return;
     }
+  }
+  if constexpr (TAIL == KS_TAIL_A) {
+    const bool special = I == l; // block-uniform; the other row of the slice is I == l - 1
+    const ulonglong2 *twi = cx.tw_inv + (size_t)kap * cx.N;
+    const ulonglong2 pinv = cx.invq[(size_t)(cx.k - 1) * cx.k + kap]; // P^-1 mod q_last ((0, 0) on the special row: not used)
+    __syncthreads(); // the forward heaps have been consumed: the same nodes of the inverse table take their place
+    for (int idx = threadIdx.x; idx < (C << P); idx += T) {
+      const int sb = idx >> P, n = idx & (S - 1);
+      if (n) {
+        const int d = 31 - __clz(n);
+        twl[idx] = twi[((size_t)((1u << pre) + sub0 + sb) << d) + (n - (1 << d))];
+      }
+    }
+#pragma unroll
+    for (int K = 0; K < 2; K++) {
+      __syncthreads(); // the tile in LDS has been consumed
+#pragma unroll
+      for (int it = 0; it < NPAIR; it++) {
+        const int idx = 2 * (threadIdx.x + it * T);
+        const int sb = idx >> P, e = idx & (S - 1);
+        const u128_t ax = K ? acc1[2 * it] : acc0[2 * it], ay = K ? acc1[2 * it + 1] : acc0[2 * it + 1];
+        u64 vx, vy;
+        if (special) {
+          vx = barrett128(ax, pm);
+          vy = barrett128(ay, pm);
+        } else {
+          vx = mul_shoup(reduce128_lazy(ax, pm), pinv.x, pinv.y, pm.q);
+          vy = mul_shoup(reduce128_lazy(ay, pm), pinv.x, pinv.y, pm.q);
+        }
+        lds[sb * SP + lds_pad<P>(e)] = vx;
+        lds[sb * SP + lds_pad<P>(e + 1)] = vy;
+      }
+      __syncthreads();
+      // as ntt_loop_kernel's inverse pass: local heaps, N^-1 left to the strided pass (ntt_tail_kernel)
+      RoundSeq<P, LR, 0, true, true, true, false>::run(lds + sub * SP, tid, 0, 0, twl + (sub << P), pm);
+      __syncthreads();
+      u64 *r = (special ? r_out : tail.t) + ((size_t)2 * inst + K) * N + gbase;
+#pragma unroll
+      for (int it = 0; it < NPAIR; it++) {
+        const int idx = 2 * (threadIdx.x + it * T);
+        const int sb = idx >> P, e = idx & (S - 1);
+        ulonglong2 v;
+        v.x = lds[sb * SP + lds_pad<P>(e)];
+        v.y = lds[sb * SP + lds_pad<P>(e + 1)];
+        *reinterpret_cast<ulonglong2 *>(r + idx) = v; // lazy intermediate of the inverse transform
+      }
+    }
+    return;
+  }
+  if constexpr (TAIL == KS_TAIL_B) {
+    using RR = typename KsTailOps<TAIL>::RR;
+    using RS = Rounds<P, LR>;
+    const ulonglong2 pinv = cx.invq[(size_t)(cx.k - 1) * cx.k + kap], linv = cx.invq[(size_t)(l - 1) * cx.k + kap];
+    // the words prod would have held (lazy_out), one register pair each where the accumulators took two
+    u64 red[2][NTT_R];
+#pragma unroll
+    for (int i = 0; i < NTT_R; i++) {
+      red[0][i] = reduce128_lazy(acc0[i], pm);
+      red[1][i] = reduce128_lazy(acc1[i], pm);
+    }
+#pragma unroll
+    for (int K = 0; K < 2; K++) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the correction tile has landed in `lin`
+      __builtin_amdgcn_wave_barrier();
+      // the digits' rounds: first round from `lin` into the padded tile, K = 1's tile requested behind its reads
+      auto next_tile = [&]() { if (K == 0) dma_corr(1); };
+      ntt_round<P, LR, RS::bits(0), RS::lo(0), false, true, true, true, true>(lds + sub * SP, tid, 0, 0, twl + (sub << P), pm,
+                                                                            lin + sub * S, next_tile);
+      if constexpr (RS::NR > 1) {
+        __builtin_amdgcn_wave_barrier();
+        RoundSeq<P, LR, 1, false, true, true, true, true, true>::run(lds + sub * SP, tid, 0, 0, twl + (sub << P), pm);
+      }
+      __builtin_amdgcn_wave_barrier();
+      // (one descriptor per tile and the lane offset the key loads use: no 64-bit address per store)
+      const __amdgpu_buffer_rsrc_t out = __builtin_amdgcn_make_buffer_rsrc(tail_row + (size_t)K * tail_ps, 0, 0x7fffffff, 0x00020000);
+#pragma unroll
+      for (int it = 0; it < NPAIR; it++) {
+        const int idx = 2 * (threadIdx.x + it * T);
+        const int sb = idx >> P, e = idx & (S - 1);
+        const u64 wx = lds[sb * SP + lds_pad<P>(e)], wy = lds[sb * SP + lds_pad<P>(e + 1)];
+        ulonglong2 v;
+        v.x = RR::combine(pm, pinv, linv, 0, red[K][2 * it], wx);
+        v.y = RR::combine(pm, pinv, linv, 0, red[K][2 * it + 1], wy);
+        typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+        u32x4 w;
+        w.x = (uint32_t)v.x;
+        w.y = (uint32_t)(v.x >> 32);
+        w.z = (uint32_t)v.y;
+        w.w = (uint32_t)(v.y >> 32);
+        __builtin_amdgcn_raw_buffer_store_b128(w, out, 16u * threadIdx.x + 16u * (uint32_t)(it * T), 0, 0);
+      }
+    }
+    return;
   }
   u64 *p0 = prod + (size_t)Irow * N + gbase, *p1 = prod + ((size_t)nout + Irow) * N + gbase;
   // lazy_out: the data rows go to combine passes that take any 64-bit representative (OpRRT / OpRRLastT multiply prod by

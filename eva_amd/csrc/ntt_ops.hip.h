@@ -514,12 +514,19 @@ template <int AM> struct OpRRT {
   static __device__ __forceinline__ u64 load(const DevCtx &, const Job &j, const DevPrime &pm, uint32_t n) {
     return conv<LZ>(j, pm, j.r[n], j.t[n]);
   }
+  // The output word from the transformed correction W (lazy, < 16q: what the contiguous forward rounds leave), the
+  // key-switch word `prod` (any 64-bit representative) and a = av (canonical; 0 in the folded form).  One body for
+  // store_fwd, store_fwd_loop and the key-switch kernel's tail epilogue (ks_inner_kernel KS_TAIL_B), so the bounds hold
+  // for all three
+  static __device__ __forceinline__ u64 combine(const DevPrime &pm, ulonglong2 pinv, ulonglong2 linv, u64 av, u64 prod, u64 W) {
+    W += (W >= pm.q8 ? pm.nq8 : 0);                                          // [0,16q) -> [0,8q)
+    const u64 x = av + mul_tw_lazy5(prod, pinv.x, pinv.y, pm.nq) + pm.q8 - W; // < q + 4q + 8q < 14q < 2^64
+    return mul_shoup(x, linv.x, linv.y, pm.q);                               // exact for any 64-bit operand
+  }
   static __device__ __forceinline__ void store_fwd(const DevCtx &cx, const Job &j, const DevPrime &pm, uint32_t n, u64 W) {
-    W += (W >= pm.q8 ? pm.nq8 : 0);                                                  // [0,16q) -> [0,8q)
     u64 av = 0;
     if constexpr (AM != RR_FOLDED) av = MUL ? product_poly(j.mul, j.K, j.off + n, pm) : j.a[n];
-    const u64 x = av + mul_tw_lazy5(j.prod[n], j.pinv.x, j.pinv.y, pm.nq) + pm.q8 - W; // < 14q < 2^64
-    j.dst[n] = mul_shoup(x, j.linv.x, j.linv.y, pm.q);                               // exact for any 64-bit operand
+    j.dst[n] = combine(pm, j.pinv, j.linv, av, j.prod[n], W);
   }
   // (no Pre here: requesting prod ahead of the tile measured 2 % slower on this pass — 372 against 364 us per
   // 32-triple launch — its on-the-fly products already keep four loads per word in flight)
@@ -533,9 +540,7 @@ template <int AM> struct OpRRT {
     if constexpr (AM == RR_MUL) {
       store_fwd(cx, j, pm, n, W);
     } else {
-      W += (W >= pm.q8 ? pm.nq8 : 0);
-      const u64 x = p.a + mul_tw_lazy5(p.prod, j.pinv.x, j.pinv.y, pm.nq) + pm.q8 - W;
-      j.dst[n] = mul_shoup(x, j.linv.x, j.linv.y, pm.q);
+      j.dst[n] = combine(pm, j.pinv, j.linv, p.a, p.prod, W);
     }
   }
 };

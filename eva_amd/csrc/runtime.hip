@@ -724,6 +724,14 @@ int evah_ctx_tail_variant(evah_ctx *c, uint32_t out[3]) {
   API_END
 }
 
+int evah_ctx_ks_tail(evah_ctx *c, uint32_t out[2]) {
+  API_BEGIN
+  const KsTailVariant v = ks_tail_variant(c);
+  out[0] = v.on;
+  out[1] = v.min_wgs;
+  API_END
+}
+
 int evah_ctx_transfer_stats(evah_ctx *c, uint64_t out[6]) {
   API_BEGIN
   for (int i = 0; i < 6; i++) out[i] = c->sh->xfer[i];

@@ -190,6 +190,12 @@ int evah_ctx_modup_variant(evah_ctx *ctx, uint32_t out[3]);
  * when that kernel has only the top-bit butterflies compiled in, out[2] = 1 when only the lazy conversion is
  * (q_last <= 4 q_i and P <= 8 q_i for every pair i < last of data primes).  All of them compute the same words. */
 int evah_ctx_tail_variant(evah_ctx *ctx, uint32_t out[3]);
+/* whether the contiguous passes of that tail run inside the key-switch kernel (EVAH_KS_TAIL: five launches, the key-switch
+ * products never stored): out[0] = 1 when this context's relinearize + rescale launch sets take that path — the three-launch
+ * tail, the radix-2^30 key switch, every prime of the top-bit shape — at the mod-up kernel's size, on levels of 2 .. 15
+ * limbs; out[1] = the fewest workgroups the first key-switch slice (2 n N / 256 for n instances) must have for it, 0 when
+ * EVAH_KS_TAIL=1 asks for every such launch set.  Same words either way. */
+int evah_ctx_ks_tail(evah_ctx *ctx, uint32_t out[2]);
 /* bytes of HBM the evaluation keys (relinearization + Galois) of this context's device state occupy.  After
  * evah_ctx_set_shard(ctx, s, G) an upload keeps only shard s's prime rows of a key (its data limbs and the
  * special prime): (ceil((k-1)/G) + 1) / k of the whole key. */
