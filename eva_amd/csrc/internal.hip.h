@@ -330,10 +330,9 @@ struct Tunables {
   // a handle become entries of the fused call's launch set); 0 = the three batched calls
   bool chain_step = true, chain_batched = true;
   uint32_t chain_fuse_blocks = 256;
-  // EVAH_MODUP (1): a key switch too large for the fused small-launch form, in one output-limb slice (EVAH_KS_GROUPS 1),
-  // runs the digits' strided inverse pass and their conversion + first forward pass under every output prime as ONE
-  // launch, a workgroup per digit tile (ntt_modup_kernel, ntt_modup.hip.h); 0 = the strided inverse pass storing the
-  // canonical digits, then the OpKsDigit strided pass reading each digit tile once per output prime
+  // EVAH_MODUP (1): a key switch in the form KS_DIGITS_MODUP (KsCaps::modup below) runs the digits' strided inverse pass and
+  // their conversion + first forward pass under every output prime as ONE launch, a workgroup per digit tile
+  // (ntt_modup_kernel, ntt_modup.hip.h); 0 = KS_DIGITS_SLICED, each digit tile read once per output prime
   bool modup = true;
   // EVAH_MODUP_LR (3): log2 coefficients per thread of ntt_modup_kernel on its 2048-coefficient tile — 3 = 256 threads
   // (84 VGPRs, 5 waves per SIMD at P = 8: headline +2.6 % over the r07 kernel), 2 = 512 threads (62 VGPRs, 8 waves per
@@ -342,19 +341,16 @@ struct Tunables {
   // (evah_ctx::modup_tb / modup_lazy: top-bit butterflies only, lazy digit conversion only); 0 = the generic kernel
   int modup_lr = 3;
   bool modup_spec = true;
-  // EVAH_TAIL_FUSE (1): where the key switch of a relinearize + rescale (stored or fused with the multiply) takes the
-  // mod-up kernel and the combine is the folded form (EVAH_FOLD_PA), its tail runs as three launches — one contiguous
-  // inverse launch for the special and the last rows together (OpTailIntt), ntt_tail_kernel (ntt_tail.hip.h: both strided
-  // inverse passes, r_K and t_K in registers, the strided forward pass under every output prime), OpRRT's contiguous
-  // pass; 0 = the six launches (inverse transform of the special rows storing r, of the last rows storing t, OpRRT's
-  // forward transform reading both once per output prime).  Same words either way.  EVAH_MODUP_SPEC=0 selects the
-  // generic tail kernel as it does the generic mod-up (tail_variant below)
+  // EVAH_TAIL_FUSE (1): the tail of a relinearize + rescale in the form TAIL_THREE (ks_form, launch.hip.h) runs as three
+  // launches — one contiguous inverse launch for the special and the last rows together (OpTailIntt), ntt_tail_kernel
+  // (ntt_tail.hip.h: both strided inverse passes, r_K and t_K in registers, the strided forward pass under every output
+  // prime), OpRRT's contiguous pass; 0 = the six launches.  Same words either way.  EVAH_MODUP_SPEC=0 selects the generic
+  // tail kernel as it does the generic mod-up (tail_variant below)
   bool tail_fuse = true;
-  // EVAH_KS_TAIL (unset = by size): where the three-launch tail above applies, the key switch is the one-wave radix-2^30
-  // kernel and every prime has the top-bit shape, the two contiguous launches of that tail run inside the key-switch
-  // kernel instead (ks_inner_kernel TAIL, ntt_ks_inner.hip.h): it is launched as two row slices around ntt_tail_kernel —
-  // rows l - 1 and l leave as the contiguous inverse pass's intermediates r and t, rows 0 .. l - 2 take the correction
-  // tile in, transform it and store the output words — five launches, and prod never reaches memory.  Same words.
+  // EVAH_KS_TAIL (unset = by size): where KsCaps::ks_tail_on holds (below), the two contiguous launches of the three-launch
+  // tail run inside the key-switch kernel instead (ks_inner_kernel TAIL, ntt_ks_inner.hip.h): two row slices around
+  // ntt_tail_kernel — rows l - 1 and l leave as the contiguous inverse pass's intermediates r and t, rows 0 .. l - 2 take
+  // the correction tile in, transform it and store the output words — five launches, prod never reaches memory.  Same words.
   // 1 = wherever that holds; 0 = never (the six launches at throughput size, for A/B runs within one library);
   // unset = where slice A alone fills the chip: its 2 n N / 256 one-wave workgroups each walk a whole digit loop, so a
   // launch set with fewer than EVAH_KS_TAIL_MIN_WGS (4096 = 256 CUs x 4 SIMDs x the kernel's 4 waves) of them would run
@@ -482,17 +478,46 @@ inline TailVariant tail_variant(const evah_ctx *c) {
   return {c->tun.tail_fuse, tb, tb && c->tail_lazy};
 }
 
-// whether a context's relinearize + rescale launch sets run the tail's contiguous passes inside the key-switch kernel
-// (Tunables::ks_tail) once the launch set itself qualifies — the mod-up kernel's size, a level of 2 .. 15 limbs, whole keys
-// in the split layout (relin_rescale_core) — and the smallest slice A it does so for (0: every size)
-struct KsTailVariant { bool on; uint32_t min_wgs; };
-inline KsTailVariant ks_tail_variant(const evah_ctx *c) {
-  const bool one_wave = (std::min<uint32_t>(c->N, (uint32_t)c->tun.ks_threads << 2) >> 2) <= 64;
-  const bool modup = c->tun.modup && std::max(1, c->tun.ks_groups) == 1 && c->N >= 2048 && (c->logN + 1) / 2 <= 9;
-  const bool on = c->tun.ks_tail != 0 && c->tun.fold_pa && c->tun.fuse_mac && c->tun.tail_fuse && modup && EVAH_TOPBIT &&
-                  c->modup_tb && c->tun.mac3 && c->all_tb && one_wave;
-  return {on, on && c->tun.ks_tail < 0 ? c->tun.ks_tail_min_wgs : 0};
+// ---- the key switch: its launch geometry, and which of its launch forms a context's knobs, degree and primes admit.
+// Each fact is stated here once; ks_form (launch.hip.h) adds what depends on the level, the batch and the keys.
+constexpr int KS_LR = 2;                // ks_inner_kernel works on 4 coefficients per thread (32 accumulator VGPRs)
+constexpr uint32_t KS_WAVE = 64;        // a workgroup of at most one wave: the one-wave key-switch kernel (the default)
+constexpr uint32_t WIDE_TILE = 2048;    // coefficients per tile of the mod-up, tail and small-launch kernels (NTT_THREADS << 3)
+constexpr int WIDE_TILE_MAX_P = 9;      // the largest strided sub-transform (2^P points) those kernels are instantiated for
+constexpr uint32_t MAC3_MAX_LIMBS = 15; // radix-2^30 accumulation: the top sum holds 15 digits
+struct KsCaps {
+  uint32_t wg_threads, groups, ks_tail_min_wgs;
+  bool one_wave, wide_tile, modup, mac3, special_inv, fold, tail3, ks_tail_on;
+};
+inline KsCaps ks_caps(const evah_ctx *c) {
+  const Tunables &t = c->tun;
+  KsCaps k{};
+  // threads per workgroup of ks_inner_kernel, over a tile of wg_threads << KS_LR coefficients; one wave is what the
+  // radix-2^30 accumulation, the fused special-row inverse pass and the tail slices need
+  k.wg_threads = std::min<uint32_t>(c->N, (uint32_t)t.ks_threads << KS_LR) >> KS_LR;
+  k.one_wave = k.wg_threads <= KS_WAVE;
+  k.groups = (uint32_t)std::max(1, t.ks_groups); // output-limb slices per key switch (a level clamps it to l + 1 again)
+  k.wide_tile = c->N >= WIDE_TILE && (int)(c->logN + 1) / 2 <= WIDE_TILE_MAX_P; // the shapes of ntt_modup_kernel, ntt_tail_kernel
+  k.modup = t.modup && t.fuse_mac && k.groups == 1 && k.wide_tile; // past the small-launch form: the mod-up kernel
+  k.mac3 = t.mac3 && t.fuse_mac && c->all_tb && k.one_wave;        // ks_inner_kernel<MAC3>, at levels of <= MAC3_MAX_LIMBS limbs
+  k.special_inv = t.fuse_special_inv && k.one_wave; // the special row's first inverse pass may ride the key-switch kernel (INVSP)
+  k.fold = t.fold_pa && t.fuse_mac; // P * (what the result is added to) joins the inner products (KS_FOLDMUL / KS_FOLDADD)
+  k.tail3 = t.tail_fuse;            // relinearize + rescale after the mod-up: the three-launch tail
+  // ... or the tail's contiguous passes inside two slices of the key-switch kernel (Tunables::ks_tail), for launch sets
+  // whose slice A has at least ks_tail_min_wgs workgroups.  The contiguous forward rounds of slice B are the digits'
+  // (input < 9q from a top-bit strided pass, < 16q from the compare-and-subtract one): the tail kernel ends
+  // its rows with the RoundSeq the mod-up ends its own with, and modup_tb admits only contexts whose primes all have the
+  // top-bit shape, so the < 9q holds for each tail variant that can get here (TBONLY, LAZYONLY, and the generic kernel
+  // under EVAH_MODUP_SPEC=0, whose forward_rounds then pick the top-bit rounds row by row).  A prime of another shape below
+  // 2^54, which mac3 alone admits, would ride the kernel's rounds unreduced to (16 + 4 P) q, past the 16q OpRRT::combine
+  // takes: such a context keeps the other tails.
+  k.ks_tail_on = t.ks_tail != 0 && k.fold && k.tail3 && k.modup && k.mac3 && EVAH_TOPBIT && c->modup_tb;
+  k.ks_tail_min_wgs = k.ks_tail_on && t.ks_tail < 0 ? t.ks_tail_min_wgs : 0;
+  return k;
 }
+// what evah_ctx_ks_tail reports
+struct KsTailVariant { bool on; uint32_t min_wgs; };
+inline KsTailVariant ks_tail_variant(const evah_ctx *c) { return {ks_caps(c).ks_tail_on, ks_caps(c).ks_tail_min_wgs}; }
 
 inline void use(evah_ctx *c) { HIPCHK(hipSetDevice(c->device)); }
 inline void count_h2d(evah_ctx *c, size_t bytes, bool plain = false) { c->sh->xfer[plain ? 2 : 0]++; c->sh->xfer[4] += bytes; }

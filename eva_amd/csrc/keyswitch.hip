@@ -36,29 +36,12 @@ k_ks_mac(DevCtx cx, const u64 *target, const u64 *scratch, const u64 *key, u64 *
   st2(prod + ((size_t)(l + 1) + I) * N + n, r1);
 }
 
-// ks_inner_kernel works on 4 coefficients per thread (32 accumulator VGPRs): a workgroup of ks_wg_threads over a tile
-// of four times as many coefficients
-constexpr int KS_LR = 2;
-static uint32_t ks_wg_threads(const evah_ctx *c) { return std::min<uint32_t>(c->N, (uint32_t)c->tun.ks_threads << KS_LR) >> KS_LR; }
-// the one-wave key-switch kernel (the default): what the radix-2^30 accumulation and the fused special-row inverse pass need
-static bool ks_one_wave(const evah_ctx *c) { return ks_wg_threads(c) <= 64; }
-// radix-2^30 accumulation (ks_inner_kernel<MAC3>) at level l: every prime of the top-bit shape, at most 15 limbs (the top
-// sum holds 15 digits), the one-wave kernel; the caller adds what it knows of the keys (split copies) and of the mode
-static bool ks_mac3(const evah_ctx *c, uint32_t l) { return c->tun.mac3 && c->tun.fuse_mac && c->all_tb && l <= 15 && ks_one_wave(c); }
-// the header of a launch set of n key switches at level l, instance b with keys[b]: strides of the converted digits and of
-// prod, the key pointers — the split copies when mac3_ok, ks_mac3 and every key allow the radix-2^30 accumulation
-static KsBatch ks_batch(evah_ctx *c, uint32_t l, const KeyDev *const *keys, uint32_t n, bool mac3_ok) {
-  if (n < 1 || n > (uint32_t)KS_BATCH_MAX) throw std::runtime_error("key-switch batch out of range");
+// the header of a launch set of n key switches at level l in the form f, instance b with keys[b] (ks_form saw them): strides
+// of the converted digits and of prod, the key pointers — the split copies under f.mac3
+static KsBatch ks_batch(evah_ctx *c, uint32_t l, const KeyDev *const *keys, uint32_t n, const KsForm &f) {
   KsBatch kb;
-  kb.n = n;
-  kb.scratch_bs = (size_t)(l + 1) * l * c->N;
-  kb.prod_bs = (size_t)2 * (l + 1) * c->N;
-  kb.mac3 = mac3_ok && ks_mac3(c, l);
-  for (uint32_t b = 0; b < n; b++) {
-    if (keys[b]->n_digits < l) throw std::runtime_error("key switching key has too few digits");
-    if (keys[b]->rows != c->k) throw std::logic_error("this context holds a limb shard's key rows: use the evah_shard_* entry points");
-    kb.mac3 = kb.mac3 && keys[b]->d_split;
-  }
+  kb.n = n, kb.mac3 = f.mac3;
+  kb.scratch_bs = (size_t)(l + 1) * l * c->N, kb.prod_bs = (size_t)2 * (l + 1) * c->N;
   for (uint32_t b = 0; b < n; b++) kb.keys.key[b] = kb.mac3 ? keys[b]->d_split : keys[b]->d;
   return kb;
 }
@@ -67,8 +50,9 @@ template <int P>
 static void launch_ks_inner_p(evah_ctx *c, const u64 *target, const u64 *scratch, const KsBatch &kb, u64 *prod, uint32_t l) {
   constexpr int LR = KS_LR;
   ProfScope ps(c, KC_KSMAC);
-  const uint32_t tile = ks_wg_threads(c) << LR;
-  const bool one_wave = ks_one_wave(c);
+  const KsCaps caps = ks_caps(c);
+  const uint32_t tile = caps.wg_threads << LR;
+  const bool one_wave = caps.one_wave;
   const int logC = (int)ilog2(tile) - P;
   if (logC < 0) throw std::runtime_error("ks_inner tile smaller than one sub-transform");
   // coefficients tile + per-sub twiddle heaps (16 B per node)
@@ -132,90 +116,59 @@ void launch_ks_inner(evah_ctx *c, int P, const u64 *target, const u64 *scratch, 
   }
 }
 
-// the launch form of a batch of n key switches at level l (switch_key_products below): the latency-bound one, whose
-// digit passes run as ntt_inv_fwd_kernel, or the throughput-sized one with the mod-up kernel
-static bool ks_small(evah_ctx *c, uint32_t l, uint32_t n) {
-  return c->tun.fuse_mac && std::max(1, c->tun.ks_groups) == 1 && fuse_small_launch(c, n * (l + 1) * l);
-}
-static bool ks_takes_modup(evah_ctx *c, uint32_t l, uint32_t n) {
-  return !ks_small(c, l, n) && c->tun.modup && c->tun.fuse_mac && std::max(1, c->tun.ks_groups) == 1 && modup_fits(c);
-}
-
-// relinearize + rescale of n instances at level l with the tail's contiguous passes inside the key-switch kernel
-// (Tunables::ks_tail): where the three-launch tail applies (relin_rescale_core), the key switch is the one-wave radix-2^30
-// kernel on the split relinearization key, and — unless the knob is set — slice A's workgroups fill the chip
-static bool ks_tail_applies(evah_ctx *c, uint32_t l, uint32_t n) {
-  const KsTailVariant v = ks_tail_variant(c);
-  if (!v.on || l < 2 || !ks_takes_modup(c, l, n) || !ks_mac3(c, l)) return false;
-  if (!c->sh->relin.d_split || c->sh->relin.rows != c->k || c->sh->relin.n_digits < l) return false;
-  return (uint64_t)2 * n * (c->N / 256) >= v.min_wgs;
-}
-
 // SEAL Evaluator::switch_key_inplace, device version.
 //   out[K] = (add && K < add_polys ? add[K] : 0) + keyswitch(target)[K],  K in {0,1}
-// steps 1-2 of switch_key for a batch of n (target, key) pairs in one set of launches:
-// prod[b][K][I] (I <= l, slot l = special prime) = sum_J op_b(I,J) * key_b[J][K].
-// target_b = target + b * target_bs; prod_b = prod_d + b * 2 (l+1) N.
-// r_small != nullptr: the caller will mod-down through the latency-bound launch form and offers
-// r_small[2 n][N] for the special rows' first inverse pass; returns true when that pass was done
-// here (fused into the key-switch kernel) — the special rows of prod are then NOT written.
-bool switch_key_products(evah_ctx *c, uint32_t l, const u64 *target, size_t target_bs, const KeyDev *const *keys,
-                         uint32_t n, u64 *prod_d, const PtrTab *target_tab, const MulTab *mul, u64 *r_small, bool fold,
-                         const PtrTab *adds, bool lazy_out, const KsTailPlan *tail) {
+// steps 1-2 of switch_key for a batch of q.n (target, key) pairs in one set of launches, in the form f = ks_form(...) of
+// the caller: prod[b][K][I] (I <= l, slot l = special prime) = sum_J op_b(I,J) * key_b[J][K].
+// target_b = q.target + b * q.target_bs (or q.targets.p[b]); prod_b = q.prod + b * 2 (l+1) N.
+// f.special_inv: the special rows' first inverse pass leaves in q.r[2 n][N] and the special rows of prod are NOT written.
+void switch_key_products(evah_ctx *c, uint32_t l, const KsCall &q, const KsForm &f) {
   const size_t N = c->N;
-  KsBatch kb = ks_batch(c, l, keys, n, /*mac3_ok=*/!(mul && !fold)); // (not the r03 fused-multiply form)
-  if (tail && !(kb.mac3 && fold && ks_takes_modup(c, l, n))) throw std::logic_error("key-switch tail epilogue outside its form");
-  kb.target_bs = target_bs;
-  if (target_tab) kb.targets = *target_tab; // target == nullptr: separately allocated targets
-  kb.mul = mul;
-  kb.fold = fold;
-  kb.adds = adds;
-  kb.lazy_out = lazy_out;
+  const uint32_t n = q.n;
+  const MulTab *const mul = q.mul;
+  const bool fold = q.fold;
+  KsBatch kb = ks_batch(c, l, q.keys, n, f);
+  static_cast<KsOperands &>(kb) = q;
   if ((mul || fold) && !c->tun.fuse_mac) throw std::logic_error("the fused multiply / folded forms need the fused key-switch kernel");
+  if ((q.tail ? f.tail != TAIL_KS_SLICES : f.tail == TAIL_KS_SLICES || !q.prod) || (f.special_inv && !q.r))
+    throw std::logic_error("key-switch request lacks what its form writes");
   Scratch t(c, (size_t)n * l * N);        // coefficient-form digits
   Scratch sc(c, n * kb.scratch_bs);       // converted digits, NTT form per output limb
   // folded fused multiply: d2 is stored by the inverse transform that forms it and is the target from memory
   Scratch d2(c, mul && fold ? (size_t)n * l * N : 1);
+  const u64 *target = q.target;
   if (mul && fold) {
     target = d2.d;
-    kb.target_bs = target_bs = (size_t)l * N;
+    kb.target_bs = (size_t)l * N;
   }
   // 1. digits to coefficient form (job -> (b, J))
   OpKsDigit::Params dp{t.d, sc.d, l, (size_t)l * N, kb.scratch_bs, 0, l + 1};
-  // a small key switch is latency-bound: the digits' strided inverse pass and the first pass of the
-  // digit conversion then run as one launch
-  const bool small = ks_small(c, l, n);
-  // a throughput-sized one: the strided inverse pass of each digit tile runs once, in the workgroup that converts it for
-  // every output prime (ntt_modup_kernel) — t is then the contiguous pass's intermediate, never the canonical digits
-  const bool modup = ks_takes_modup(c, l, n);
+  // KS_DIGITS_SMALL: the digits' strided inverse pass and the first pass of the digit conversion run as one launch;
+  // KS_DIGITS_MODUP: the strided inverse pass of each digit tile runs once, in the workgroup that converts it for every
+  // output prime — either way t is the contiguous pass's intermediate, never the canonical digits
+  const bool pass1_only = f.digits == KS_DIGITS_SMALL || f.digits == KS_DIGITS_MODUP;
   if (mul) { // the target is the product's d2, formed on load
     OpMulIntt::Params ip{*mul, t.d, (size_t)l * N, l, fold ? d2.d : nullptr};
-    if (small || modup) launch_pass_p<false, true, OpMulIntt>(c, c->logN / 2, ip, n * l);
+    if (pass1_only) launch_pass_p<false, true, OpMulIntt>(c, c->logN / 2, ip, n * l);
     else ntt_inverse<OpMulIntt>(c, ip, n * l);
   } else {
-    OpPlain::Params ip{target, t.d, target_bs, (size_t)l * N, l, 0, 0, {}};
-    if (target_tab) ip.src_tab = *target_tab;
-    if (small || modup) launch_pass_p<false, true, OpPlain>(c, c->logN / 2, ip, n * l);
+    OpPlain::Params ip{target, t.d, kb.target_bs, (size_t)l * N, l, 0, 0, q.targets};
+    if (pass1_only) launch_pass_p<false, true, OpPlain>(c, c->logN / 2, ip, n * l);
     else ntt_inverse<OpPlain>(c, ip, n * l);
   }
-  if (small) {
+  if (f.special_inv) kb.r_out = q.r;
+  if (f.digits == KS_DIGITS_SMALL) {
     dp.i0 = kb.i0 = 0;
     dp.ni = kb.ni = l + 1;
     launch_inv_fwd<OpKsDigit>(c, dp, n * (l + 1) * l);
-    if (r_small && c->tun.fuse_special_inv && ks_one_wave(c)) kb.r_out = r_small;
-    launch_ks_inner(c, c->logN / 2, target, sc.d, kb, prod_d, l);
-    return kb.r_out != nullptr;
+    launch_ks_inner(c, c->logN / 2, target, sc.d, kb, q.prod, l);
+    return;
   }
-  if (c->tun.fuse_mac) { // 128-bit accumulation of lazy (<16q) products, folded every 16 digits
+  if (f.digits != KS_DIGITS_UNFUSED) { // 128-bit accumulation of lazy (<16q) products, folded every 16 digits
     // Output limbs are processed in slices so that a slice's converted digits (ni * l * N words)
     // are still in L2 / Infinity Cache when the fused second pass consumes them.
     const int a = (c->logN + 1) / 2, b = c->logN / 2;
-    const uint32_t groups = std::min<uint32_t>(std::max(1, c->tun.ks_groups), l + 1);
-    // r5: the digit transforms may be throughput-sized while the mod-down that follows is still a small launch
-    // (relinearize_many of Harris' three products: 3456 digit tiles, 768 mod-down tiles): the special rows' first inverse
-    // pass then rides the key-switch kernel here as well (one launch of ~6 us less)
-    if (r_small && groups == 1 && c->tun.fuse_special_inv && ks_one_wave(c)) kb.r_out = r_small;
-    if (tail) { // (groups == 1 and the mod-up: checked above)
+    if (const KsTailPlan *tail = q.tail) { // (the mod-up in one slice: ks_form)
       dp.i0 = 0;
       dp.ni = l + 1;
       launch_modup<OpKsDigit>(c, dp, n);
@@ -236,53 +189,44 @@ bool switch_key_products(evah_ctx *c, uint32_t l, const u64 *target, size_t targ
       kb.r_out = tail->rp.dst;
       kb.tail_out = KsTailOut{nullptr, tail->rp.dst_ps};
       launch_ks_inner(c, b, target, sc.d, kb, nullptr, l);
-      return false;
+      return;
     }
-    for (uint32_t g = 0; g < groups; g++) {
-      const uint32_t i0 = (uint32_t)((uint64_t)(l + 1) * g / groups), i1 = (uint32_t)((uint64_t)(l + 1) * (g + 1) / groups);
+    for (uint32_t g = 0; g < f.groups; g++) {
+      const uint32_t i0 = (uint32_t)((uint64_t)(l + 1) * g / f.groups), i1 = (uint32_t)((uint64_t)(l + 1) * (g + 1) / f.groups);
       if (i1 == i0) continue;
       dp.i0 = kb.i0 = i0;
       dp.ni = kb.ni = i1 - i0;
-      // 2a. base-convert + first (strided) NTT pass of every digit under the slice's output primes (modup: with the
+      // 2a. base-convert + first (strided) NTT pass of every digit under the slice's output primes (the mod-up: with the
       // digits' strided inverse pass in front, all output primes in one slice)
-      if (modup) launch_modup<OpKsDigit>(c, dp, n);
+      if (f.digits == KS_DIGITS_MODUP) launch_modup<OpKsDigit>(c, dp, n);
       else launch_pass_p<true, false, OpKsDigit>(c, a, dp, n * (i1 - i0) * l);
       // 2b. second (contiguous) pass fused with the inner product with the key
-      launch_ks_inner(c, b, target, sc.d, kb, prod_d, l);
+      launch_ks_inner(c, b, target, sc.d, kb, q.prod, l);
     }
-    return kb.r_out != nullptr;
   } else {
     // unfused reference path (EVAH_FUSE_MAC=0): full digit NTTs, then a separate MAC kernel
     ntt_forward<OpKsDigit>(c, dp, n * (l + 1) * l);
     for (uint32_t b = 0; b < n; b++) {
       ProfScope ps(c, KC_KSMAC);
       hipLaunchKernelGGL(k_ks_mac, dim3(c->N / 512, l + 1), dim3(256), 0, c->stream, c->dev,
-                         target ? target + b * target_bs : target_tab->p[b], sc.d + b * kb.scratch_bs, keys[b]->d,
-                         prod_d + b * kb.prod_bs, l);
+                         target ? target + b * kb.target_bs : q.targets.p[b], sc.d + b * kb.scratch_bs, q.keys[b]->d,
+                         q.prod + b * kb.prod_bs, l);
       HIPCHK(hipGetLastError());
     }
   }
-  return false;
 }
 
 void switch_key(evah_ctx *c, uint32_t l, const u64 *target, const KeyDev &key, const u64 *add,
                        size_t add_ps, uint32_t add_polys, u64 *out, size_t out_ps) {
-  const size_t N = c->N;
-  Scratch prod(c, (size_t)2 * (l + 1) * N);    // [K][l+1][N]
-  Scratch r(c, 2 * N);
   const KeyDev *kp = &key;
+  KsCall q;
+  q.target = target, q.keys = &kp;
   // fold_pa: P * add[K] goes into the inner products (KS_FOLDADD), the combine pass then adds nothing
-  const bool fold = c->tun.fold_pa && c->tun.fuse_mac && add && add_polys >= 1 && add_polys <= 2;
+  q.fold = ks_caps(c).fold && add && add_polys >= 1 && add_polys <= 2;
   PtrTab adds{};
-  if (fold)
-    for (uint32_t K = 0; K < add_polys; K++) adds.p[K] = add + K * add_ps;
-  const bool inv1 = switch_key_products(c, l, target, 0, &kp, 1, prod.d, nullptr, nullptr, fuse_small_launch(c, 2 * l) ? r.d : nullptr,
-                                        fold, fold ? &adds : nullptr);
-  if (fold) add = nullptr;
-  // 3. mod-down by the special prime: INTT(special limb) + P/2, then per-limb NTT + combine
-  OpPlain::Params sp{prod.d + (size_t)l * N, r.d, (size_t)(l + 1) * N, N, 1, c->k - 1, 1, {}};
-  OpModDown::Params mp{r.d, N, prod.d, (size_t)(l + 1) * N, add, add_ps, add_polys, out, out_ps, c->k - 1, l};
-  inverse_then_forward<OpPlain, OpModDown>(c, sp, 2, mp, 2 * l, inv1);
+  for (uint32_t K = 0; K < add_polys && q.fold; K++) adds.p[K] = add + K * add_ps;
+  q.adds = q.fold ? &adds : nullptr;
+  switch_key_mod_down(c, l, q, md_combine(q.fold ? nullptr : add, add_ps, add_polys, out, out_ps));
 }
 
 // ---- the size-3 entry points: checks, instance tables, one body per operation
@@ -322,19 +266,16 @@ template <class Body> static void size3_chunks(const evah_ct *a, Body body) {
 
 // relinearize: n (<= KS_BATCH_MAX) size-3 ciphertexts of l limbs in one launch set -> out_d[n][2][l N]
 static void relin_core(evah_ctx *c, uint32_t l, uint32_t n, const Size3Tab &in, u64 *out_d) {
-  const size_t N = c->N, pps = (size_t)(l + 1) * N;
-  Scratch prod(c, (size_t)n * 2 * pps), r(c, (size_t)n * 2 * N);
   std::vector<const KeyDev *> keys(n, &c->sh->relin);
+  KsCall q;
+  q.targets = in.c2, q.keys = keys.data(), q.n = n;
   // fold_pa: P * c_K goes into the inner products (KS_FOLDADD), the combine pass then adds nothing
-  const bool fold = c->tun.fold_pa && c->tun.fuse_mac;
-  const bool inv1 = switch_key_products(c, l, nullptr, 0, keys.data(), n, prod.d, &in.c2, nullptr, fuse_small_launch(c, 2 * n * l) ? r.d : nullptr,
-                                        fold, fold ? &in.c01 : nullptr);
-  // mod-down by the special prime: INTT(special limb) + P/2, then per-limb NTT + combine
-  OpPlain::Params sp{prod.d + (size_t)l * N, r.d, pps, N, 1, c->k - 1, 1, {}};
-  OpModDown::Params mp{r.d, N, prod.d, pps, nullptr, 0, 0, out_d, (size_t)l * N, c->k - 1, l};
-  mp.use_add_tab = !fold;
+  q.fold = ks_caps(c).fold;
+  q.adds = q.fold ? &in.c01 : nullptr;
+  OpModDown::Params mp = md_combine(nullptr, 0, 0, out_d, (size_t)l * c->N);
+  mp.use_add_tab = !q.fold;
   mp.add_tab = in.c01;
-  inverse_then_forward<OpPlain, OpModDown>(c, sp, 2 * n, mp, 2 * n * l, inv1);
+  switch_key_mod_down(c, l, q, mp);
 }
 
 // relinearize + rescale_to_next: n (<= KS_BATCH_MAX) size-3 ciphertexts of l limbs -> out_d[n][2][(l-1) N], one set of
@@ -352,47 +293,48 @@ static void relin_rescale_core(evah_ctx *c, uint32_t l, uint32_t n, const Size3T
     for (uint32_t i = 0; i < 2 * n; i++) a_last.p[i] = a_polys.p[i] + (size_t)last * N;
   }
   std::vector<const KeyDev *> keys(n, &c->sh->relin);
+  const KsForm f = ks_form(c, l, keys.data(), n, /*rescale=*/true, mul != nullptr);
+  KsCall q;
+  q.targets = c2, q.keys = keys.data(), q.n = n, q.mul = mul;
   // r04: P * (the polynomials the key-switch result is added to) goes into the inner products themselves, so the
-  // combine passes below read prod only (Tunables::fold_pa; the r03 forms stay for A/B runs)
-  const bool fold = c->tun.fold_pa && c->tun.fuse_mac; // EVAH_FUSE_MAC=0 (the unfused reference path): the OpRR / OpRRLast forms below
-  if (ks_tail_applies(c, l, n)) {
+  // combine passes below read prod only (Tunables::fold_pa; the r03 forms stay for A/B runs, and for EVAH_FUSE_MAC=0)
+  const bool fold = q.fold = f.tail != TAIL_R03;
+  q.adds = mul ? nullptr : &a_polys;
+  q.lazy_out = fold;
+  // the folded tail's two ops on prod (null: the key-switch slices, which never store it), r and t
+  auto folded = [&](const u64 *prod_d, u64 *r_d, u64 *t_d) {
+    return KsTailPlan{OpRRLastFolded::Params{nullptr, 0, prod_d ? prod_d + (size_t)last * N : nullptr, pps, r_d, N, t_d, N, last, sp, {}},
+                      OpRRFolded::Params{r_d, N, t_d, N, nullptr, 0, prod_d, pps, out_d, ops, sp, last, l - 1, {}}};
+  };
+  if (f.tail == TAIL_KS_SLICES) {
     // r10: five launches — the key-switch kernel runs the tail's two contiguous passes on the tiles it holds, as two
-    // row slices around ntt_tail_kernel; prod is not allocated.  The contiguous forward rounds of slice B are the
-    // digits' (input < 9q from a top-bit strided pass, < 16q from the compare-and-subtract one): the tail
-    // kernel ends its rows with the RoundSeq the mod-up ends its own with, and ks_tail_applies admits only contexts
-    // whose primes all have the top-bit shape, so the < 9q holds for each tail variant that can get here (TBONLY,
-    // LAZYONLY, and the generic kernel under EVAH_MODUP_SPEC=0, whose forward_rounds then pick the top-bit rounds
-    // row by row).  A prime of another shape below 2^54, which MAC3 alone admits, would ride the kernel's rounds
-    // unreduced to (16 + 4 P) q, past the 16q OpRRT::combine takes: such a context keeps the launches below.
+    // row slices around ntt_tail_kernel; prod is not allocated (KsCaps::ks_tail_on: which contexts, and why)
     Scratch r(c, (size_t)n * 2 * N), t(c, (size_t)n * 2 * N);
-    KsTailPlan plan{OpRRLastFolded::Params{nullptr, 0, nullptr, pps, r.d, N, t.d, N, last, sp, {}},
-                    OpRRFolded::Params{r.d, N, t.d, N, nullptr, 0, nullptr, pps, out_d, ops, sp, last, l - 1, {}}};
-    switch_key_products(c, l, nullptr, 0, keys.data(), n, nullptr, &c2, mul, nullptr, fold, mul ? nullptr : &a_polys, /*lazy_out=*/true, &plan);
+    const KsTailPlan plan = folded(nullptr, r.d, t.d);
+    q.tail = &plan;
+    switch_key_products(c, l, q, f);
     return;
   }
   Scratch prod(c, (size_t)n * 2 * pps);
-  switch_key_products(c, l, nullptr, 0, keys.data(), n, prod.d, &c2, mul, nullptr, fold, mul ? nullptr : &a_polys, /*lazy_out=*/fold);
+  q.prod = prod.d;
+  switch_key_products(c, l, q, f);
   Scratch r(c, (size_t)n * 2 * N), t(c, (size_t)n * 2 * N);
-  if (fold && tail_variant(c).fused && ks_takes_modup(c, l, n)) {
+  const KsTailPlan p = folded(prod.d, r.d, t.d);
+  if (f.tail == TAIL_THREE) {
     // the tail in three launches where the key switch above took the mod-up kernel (the RR_MEM / RR_MUL forms keep the
     // six below): contiguous inverse pass of the special and the last rows together; both strided inverse passes, r_K
     // and t_K in registers, and OpRRFolded's strided pass under every output prime (ntt_tail_kernel); its contiguous pass
-    OpRRLastFolded::Params lp{nullptr, 0, prod.d + (size_t)last * N, pps, r.d, N, t.d, N, last, sp, {}};
-    OpTailIntt::Params ip{lp, prod.d + (size_t)l * N, pps, r.d};
+    OpTailIntt::Params ip{p.lp, prod.d + (size_t)l * N, pps, r.d};
     launch_pass_p<false, true, OpTailIntt>(c, c->logN / 2, ip, 4 * n);
-    OpRRFolded::Params rp{r.d, N, t.d, N, nullptr, 0, prod.d, pps, out_d, ops, sp, last, l - 1, {}};
-    launch_tail(c, lp, rp, 2 * n);
-    launch_pass_p<false, false, OpRRFolded>(c, c->logN / 2, rp, 2 * n * (l - 1));
+    launch_tail(c, p.lp, p.rp, 2 * n);
+    launch_pass_p<false, false, OpRRFolded>(c, c->logN / 2, p.rp, 2 * n * (l - 1));
     return;
   }
   // r_K = INTT_P(prod[K][special]) + P/2
-  OpPlain::Params spp{prod.d + (size_t)l * N, r.d, pps, N, 1, sp, 1, {}};
-  ntt_inverse<OpPlain>(c, spp, 2 * n);
+  ntt_inverse<OpPlain>(c, special_rows_intt(c, l, prod.d, r.d), 2 * n);
   if (fold) { // prod already carries P a[K]
-    OpRRLastFolded::Params lp{nullptr, 0, prod.d + (size_t)last * N, pps, r.d, N, t.d, N, last, sp, {}};
-    ntt_inverse<OpRRLastFolded>(c, lp, 2 * n);
-    OpRRFolded::Params rp{r.d, N, t.d, N, nullptr, 0, prod.d, pps, out_d, ops, sp, last, l - 1, {}};
-    ntt_forward<OpRRFolded>(c, rp, 2 * n * (l - 1));
+    ntt_inverse<OpRRLastFolded>(c, p.lp, 2 * n);
+    ntt_forward<OpRRFolded>(c, p.rp, 2 * n * (l - 1));
   } else if (mul) {
     OpRRLastMul::Params lp{nullptr, 0, prod.d + (size_t)last * N, pps, r.d, N, t.d, N, last, sp, a_last, *mul};
     ntt_inverse<OpRRLastMul>(c, lp, 2 * n);
@@ -445,8 +387,9 @@ static void mul_relin_rescale(evah_ctx *c, const evah_ct *const *as, const evah_
 // wants it; the rescale of d0 / d1 and the mod-down sharing one forward transform through (P L^-1) d_K folded into the inner
 // products).  For ordinary contexts with whole keys and full transform tiles; anything else keeps the forms below.
 static bool chain_step_applies(evah_ctx *c) {
-  return c->tun.chain_step && c->tun.fuse_mac && c->tun.fold_pa && std::max(1, c->tun.ks_groups) == 1 && c->dev.pstep == 1 &&
-         c->dev.p0 == 0 && !c->dev.guard && c->N >= ((uint32_t)NTT_THREADS << 3) && c->sh->relin.rows == c->k;
+  const KsCaps k = ks_caps(c);
+  return c->tun.chain_step && k.fold && k.groups == 1 && c->dev.pstep == 1 && c->dev.p0 == 0 && !c->dev.guard && c->N >= WIDE_TILE &&
+         c->sh->relin.rows == c->k;
 }
 // stored: instance b is a STORED size-3 ciphertext at tab.a[b] (polynomial stride tab.a_ps[b], tab.b[b] == nullptr) instead of
 // the product tab.a[b] x tab.b[b] — Rescale -> Relinearize of a sum of products (evah_rescale_relinearize)
@@ -454,7 +397,8 @@ static void chain_step(evah_ctx *c, const MulTab &tab, uint32_t n, uint32_t l, u
   const uint32_t lp = l - 1, last = l - 1, sp = c->k - 1;
   const size_t N = c->N, ops = (size_t)lp * N, pps = (size_t)(lp + 1) * N;
   const std::vector<const KeyDev *> keys(n, &c->sh->relin);
-  KsBatch kb = ks_batch(c, lp, keys.data(), n, /*mac3_ok=*/true);
+  const KsForm f = ks_form(c, lp, keys.data(), n); // (of its fields the chain step takes mac3, md_small and special_inv)
+  KsBatch kb = ks_batch(c, lp, keys.data(), n, f);
   Scratch t2(c, (size_t)n * l * N), r01(c, (size_t)n * 2 * N);
   // 1. products + contiguous inverse pass: every limb of d2, limb L of d0 and d1
   OpChainIntt::Params ip{tab, t2.d, r01.d, l};
@@ -490,20 +434,16 @@ static void chain_step(evah_ctx *c, const MulTab &tab, uint32_t n, uint32_t l, u
   // 3. contiguous forward pass + key inner product + (P L^-1) d_K; the special limb's contiguous inverse pass when the
   //    mod-down is a small launch
   Scratch prod(c, (size_t)n * 2 * pps), r(c, (size_t)n * 2 * N);
-  const bool small_md = fuse_small_launch(c, 2 * n * lp);
-  if (small_md && c->tun.fuse_special_inv && ks_one_wave(c)) kb.r_out = r.d;
+  if (f.special_inv) kb.r_out = r.d;
   launch_ks_inner(c, c->logN / 2, nullptr, sc.d, kb, prod.d, lp);
   // 4. / 5. one forward transform per (K, i) for the rescale of d_K and the mod-down of prod_K
   OpRsMd::Params fp{r01.d, r.d, out_d, ops, last, sp, lp};
   OpModDown::Params mp{r.d, N, prod.d, pps, nullptr, 0, 0, out_d, ops, sp, lp};
-  if (small_md) {
-    if (!kb.r_out) {
-      OpPlain::Params spp{prod.d + (size_t)lp * N, r.d, pps, N, 1, sp, 1, {}};
-      launch_pass_p<false, true, OpPlain>(c, c->logN / 2, spp, 2 * n);
-    }
+  const OpPlain::Params spp = special_rows_intt(c, lp, prod.d, r.d);
+  if (f.md_small) {
+    if (!f.special_inv) launch_pass_p<false, true, OpPlain>(c, c->logN / 2, spp, 2 * n);
     launch_inv2<OpRsMd, true>(c, fp, 2 * n * lp);
   } else {
-    OpPlain::Params spp{prod.d + (size_t)lp * N, r.d, pps, N, 1, sp, 1, {}};
     ntt_inverse<OpPlain>(c, spp, 2 * n);
     OpPlain::Params lpp{r01.d, r01.d, N, N, 1, last, 1, {}}; // second (strided) pass of limb L of d0 / d1, in place
     launch_pass_p<true, true, OpPlain>(c, (c->logN + 1) / 2, lpp, 2 * n);
@@ -522,7 +462,7 @@ static void mul_rescale_relin(evah_ctx *c, const evah_ct *const *as, const evah_
   if (!c->sh->relin.d) throw std::invalid_argument("relinearization key not present");
   const uint32_t l = as[0]->limbs;
   if (l < 2) throw std::invalid_argument("end of modulus switching chain reached");
-  const uint32_t lp = l - 1, last = l - 1, sp = c->k - 1;
+  const uint32_t lp = l - 1, last = l - 1;
   const size_t N = c->N, ops = (size_t)lp * N, pps = (size_t)(lp + 1) * N;
   MulTab tab{};
   const std::vector<double> scales = fill_mul_tab(c, as, bs, pairs, B, l, "multiply_rescale_relinearize_many: operands of one call hold the same number of instances", tab);
@@ -560,12 +500,15 @@ static void mul_rescale_relin(evah_ctx *c, const evah_ct *const *as, const evah_
     // key switch of d2' (the products only; d0', d1' join in the combine)
     Scratch prod(c, (size_t)n * 2 * pps), r(c, (size_t)n * 2 * N);
     std::vector<const KeyDev *> keys(n, &c->sh->relin);
-    const bool inv1 = switch_key_products(c, lp, dp2.d, ops, keys.data(), n, prod.d, nullptr, nullptr, fuse_small_launch(c, 2 * n * lp) ? r.d : nullptr);
+    const KsForm f = ks_form(c, lp, keys.data(), n);
+    KsCall q;
+    q.target = dp2.d, q.target_bs = ops, q.keys = keys.data(), q.n = n;
+    q.prod = prod.d, q.r = r.d;
+    switch_key_products(c, lp, q, f);
     side.join();
-    OpPlain::Params spp{prod.d + (size_t)lp * N, r.d, pps, N, 1, sp, 1, {}};
-    OpModDown::Params mp{r.d, N, prod.d, pps, dp01.d, ops, 2, ob.d(), ops, sp, lp};
+    OpModDown::Params mp = md_combine(dp01.d, ops, 2, ob.d(), ops);
     mp.add_bs = 2 * ops;
-    inverse_then_forward<OpPlain, OpModDown>(c, spp, 2 * n, mp, 2 * n * lp, inv1);
+    ks_mod_down(c, lp, n, f, prod.d, r.d, mp);
   }
   ct_views(c, ob, pairs, 2, lp, B, [&](uint32_t i) { return scales[i] / pow2(divisor_bits); }, outs);
 }

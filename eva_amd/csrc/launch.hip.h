@@ -131,18 +131,24 @@ static void launch_pass_p(evah_ctx *c, int P, const typename Op::Params &prm, ui
   launch_pass_lr<3, STRIDED, INVERSE, Op>(c, P, prm, jobs);
 }
 
-struct KsBatch { // one launch worth of key-switches: regular strides, irregular keys
-  uint32_t n = 1;
-  uint32_t i0 = 0, ni = 0; // output-limb slice
-  size_t target_bs = 0, scratch_bs = 0, prod_bs = 0;
-  KsKeys keys{};
-  PtrTab targets{}; // used when the targets are separate allocations (target == nullptr)
+static_assert(WIDE_TILE == (uint32_t)NTT_THREADS << 3, "the mod-up, tail and small-launch kernels work on 8 coefficients per thread");
+
+// what a batch of key switches reads beside the digits: the same in a caller's request (KsCall) and in a launch's header
+struct KsOperands {
+  size_t target_bs = 0;        // target of instance b = target + b * target_bs, or
+  PtrTab targets{};            // targets.p[b] when the targets are separate allocations (target == nullptr)
   const MulTab *mul = nullptr; // fused multiply: the target of instance b is d2 = a1 b1 of product b
   bool fold = false;           // fused multiply: P * d0, P * d1 are added to the products here (KS_FOLDMUL; the target is then
                                // read from memory); without mul: P * adds.p[2b + K] is (KS_FOLDADD)
   const PtrTab *adds = nullptr;
-  bool mac3 = false;           // keys point at the split layout: ks_inner_kernel<MAC3> (radix-2^30 accumulation)
   bool lazy_out = false;       // the data rows of prod may be any 64-bit representative (consumer: the relinearize + rescale combine)
+};
+struct KsBatch : KsOperands { // one launch worth of key-switches: regular strides, irregular keys
+  uint32_t n = 1;
+  uint32_t i0 = 0, ni = 0; // output-limb slice
+  size_t scratch_bs = 0, prod_bs = 0;
+  KsKeys keys{};
+  bool mac3 = false;           // keys point at the split layout: ks_inner_kernel<MAC3> (radix-2^30 accumulation)
   uint32_t istep = 1, nout = 0; // output limbs I = i0 + y * istep; nout = rows per polynomial of prod (0: l + 1)
   u64 *r_out = nullptr; // != nullptr: the special row leaves as the first inverse pass of the mod-down (INVSP)
   bool diag = false;    // the diagonal digit comes from scratch too (no NTT-form target: the chain step, ntt_chain.hip.h)
@@ -153,11 +159,20 @@ struct KsBatch { // one launch worth of key-switches: regular strides, irregular
   int tail = KS_TAIL_NONE;
   KsTailOut tail_out{};
 };
-// What relin_rescale_core hands switch_key_products when the key switch runs the tail's contiguous passes (EVAH_KS_TAIL):
+// What relin_rescale_core hands switch_key_products when the key switch runs the tail's contiguous passes (TAIL_KS_SLICES):
 // the launch set is mod-up, slice A, ntt_tail_kernel (lp, rp), slice B, and prod is never touched
 struct KsTailPlan {
   OpRRLastFolded::Params lp; // r, t, last, sp (prod is not read)
   OpRRFolded::Params rp;     // dst = the output buffer, which slice B finishes in place (r, t, prod are not read)
+};
+// a caller's request to switch_key_products: n (target, key) pairs at one level
+struct KsCall : KsOperands {
+  const u64 *target = nullptr;         // targets at stride target_bs; nullptr: the table `targets`
+  const KeyDev *const *keys = nullptr; // keys[b] switches instance b
+  uint32_t n = 1;
+  u64 *prod = nullptr;                 // [n][2][l + 1][N]; not written under a tail plan
+  u64 *r = nullptr;                    // [2 n][N]: takes the special rows' first inverse pass where KsForm::special_inv
+  const KsTailPlan *tail = nullptr;    // TAIL_KS_SLICES
 };
 // The operand table of pairs x B products of size-2 ciphertexts at level l — entry i * B + x is instance x of pair i —
 // with the checks every call that multiplies makes of its operands (batch_msg: its text for a handle that does not hold
@@ -205,6 +220,49 @@ static inline bool fuse_small_launch(evah_ctx *c, uint32_t fwd_jobs) {
   if (c->dev.guard) return true; // a guarded (normally skipped) launch set: the fewest launches, whatever the size
   return (uint64_t)fwd_jobs * (c->N / tile) <= c->tun.fuse_small_blocks;
 }
+
+// ---- the launch form of a batch of n key switches at level l with keys[b]: chosen here, once per launch set, from ks_caps
+// and the sizes; whoever launches takes it as given (DESIGN.md 4.6 lists form, condition and launches)
+enum KsDigits { KS_DIGITS_SMALL, KS_DIGITS_MODUP, KS_DIGITS_SLICED, KS_DIGITS_UNFUSED }; // (the last: EVAH_FUSE_MAC=0)
+// what follows the products: the mod-down, or one of the four relinearize + rescale tails
+enum RelinTail { TAIL_MOD_DOWN, TAIL_KS_SLICES, TAIL_THREE, TAIL_FOLDED, TAIL_R03 };
+struct KsForm {
+  KsDigits digits;
+  uint32_t groups;  // output-limb slices of KS_DIGITS_SLICED
+  bool mac3;        // radix-2^30 accumulation: the context and the level admit it and every key has its split copy
+  bool md_small;    // the mod-down that follows is a small launch
+  bool special_inv; // the special rows' first inverse pass leaves the key-switch kernel in KsCall::r; prod's special rows are NOT written
+  RelinTail tail;
+};
+// rescale: relinearize + rescale (a tail follows, not the mod-down); mul: the target is a product formed on load
+static inline KsForm ks_form(evah_ctx *c, uint32_t l, const KeyDev *const *keys, uint32_t n, bool rescale = false, bool mul = false) {
+  if (n < 1 || n > (uint32_t)KS_BATCH_MAX) throw std::runtime_error("key-switch batch out of range");
+  const KsCaps k = ks_caps(c);
+  KsForm f{};
+  if (!c->tun.fuse_mac) f.digits = KS_DIGITS_UNFUSED;
+  else if (k.groups == 1 && fuse_small_launch(c, n * (l + 1) * l)) f.digits = KS_DIGITS_SMALL;
+  else f.digits = k.modup ? KS_DIGITS_MODUP : KS_DIGITS_SLICED;
+  f.groups = std::min<uint32_t>(k.groups, l + 1);
+  // (the r03 fused-multiply form, KS_MUL, has no radix-2^30 kernel)
+  f.mac3 = k.mac3 && l <= MAC3_MAX_LIMBS && !(mul && !k.fold);
+  for (uint32_t b = 0; b < n; b++) { // the keys: present for the level, whole, and in the split layout for mac3
+    if (keys[b]->n_digits < l) throw std::runtime_error("key switching key has too few digits");
+    if (keys[b]->rows != c->k) throw std::logic_error("this context holds a limb shard's key rows: use the evah_shard_* entry points");
+    f.mac3 = f.mac3 && keys[b]->d_split;
+  }
+  // r5: the digit transforms may be throughput-sized while the mod-down that follows is still a small launch
+  // (relinearize_many of Harris' three products: 3456 digit tiles, 768 mod-down tiles): the special rows' first inverse
+  // pass then rides the key-switch kernel as it does in the small form (one launch of ~6 us less)
+  f.md_small = !rescale && fuse_small_launch(c, 2 * n * l);
+  f.special_inv = f.md_small && k.special_inv && f.digits != KS_DIGITS_UNFUSED && k.groups == 1;
+  if (!rescale) f.tail = TAIL_MOD_DOWN;
+  // slice A's 2 n N / 256 one-wave workgroups fill the chip (Tunables::ks_tail)
+  else if (k.ks_tail_on && l >= 2 && f.digits == KS_DIGITS_MODUP && f.mac3 &&
+           (uint64_t)2 * n * (c->N / (KS_WAVE << KS_LR)) >= k.ks_tail_min_wgs) f.tail = TAIL_KS_SLICES;
+  else if (k.fold && k.tail3 && f.digits == KS_DIGITS_MODUP) f.tail = TAIL_THREE;
+  else f.tail = k.fold ? TAIL_FOLDED : TAIL_R03;
+  return f;
+}
 template <int P, class Op, int LR> static void launch_inv_fwd_plr(evah_ctx *c, const typename Op::Params &prm, uint32_t jobs) {
   ProfScope ps(c, OpClass<Op>::fwd_a);
   const uint32_t tile = (uint32_t)NTT_THREADS << LR, n_tiles = c->N / tile;
@@ -231,8 +289,7 @@ template <class Op> static void launch_inv_fwd(evah_ctx *c, const typename Op::P
 // ---- the key switch's mod-up at throughput size: strided inverse pass of each digit, then its conversion and forward
 // strided pass under every output prime of prm (i0 = 0, istep = 1), one workgroup per (column tile, digit, instance) —
 // ntt_modup_kernel (ntt_modup.hip.h).  n = instances; the digits' contiguous inverse pass left its intermediate in prm.t
-// Both shapes (Tunables::modup_lr) work on 2048-coefficient tiles: N >= 2048 and P <= 9.
-static inline bool modup_fits(evah_ctx *c) { return c->N >= ((uint32_t)NTT_THREADS << 3) && (c->logN + 1) / 2 <= 9; }
+// Both shapes (Tunables::modup_lr) work on 2048-coefficient tiles: KsCaps::wide_tile.
 template <int P, int LR, class Op, bool TBONLY, bool LAZYONLY>
 static void launch_modup_v(evah_ctx *c, const typename Op::Params &prm, uint32_t n) {
   ProfScope ps(c, OpClass<Op>::fwd_a);
@@ -259,7 +316,7 @@ template <int P, class Op> static void launch_modup_p(evah_ctx *c, const typenam
   else go(std::integral_constant<int, 3>{});
 }
 template <class Op> static void launch_modup(evah_ctx *c, const typename Op::Params &prm, uint32_t n) {
-  if (!modup_fits(c) || prm.i0 != 0 || prm.istep != 1) throw std::logic_error("mod-up kernel outside its shapes");
+  if (!ks_caps(c).wide_tile || prm.i0 != 0 || prm.istep != 1) throw std::logic_error("mod-up kernel outside its shapes");
   switch ((c->logN + 1) / 2) {
   case 6: launch_modup_p<6, Op>(c, prm, n); break;
   case 7: launch_modup_p<7, Op>(c, prm, n); break;
@@ -270,7 +327,7 @@ template <class Op> static void launch_modup(evah_ctx *c, const typename Op::Par
 }
 // ---- the strided passes of the relinearize + rescale tail at throughput size, one workgroup per (column tile, polynomial):
 // ntt_tail_kernel (ntt_tail.hip.h).  The contiguous inverse pass (OpTailIntt) left the special rows' intermediate in lp.r and
-// the last rows' in lp.t; the lazy first-pass words of OpRRFolded go to rp.dst.  Same shapes as the mod-up (modup_fits).
+// the last rows' in lp.t; the lazy first-pass words of OpRRFolded go to rp.dst.  Same shapes as the mod-up (KsCaps::wide_tile).
 template <int P, bool TBONLY, bool LAZYONLY>
 static void launch_tail_v(evah_ctx *c, const OpRRLastFolded::Params &lp, const OpRRFolded::Params &rp, uint32_t polys) {
   ProfScope ps(c, KC_MODDOWN_A);
@@ -283,7 +340,7 @@ static void launch_tail_v(evah_ctx *c, const OpRRLastFolded::Params &lp, const O
 // (a template so that only the translation unit that calls it instantiates the kernels)
 template <class RR = OpRRFolded>
 static void launch_tail(evah_ctx *c, const OpRRLastFolded::Params &lp, const typename RR::Params &rp, uint32_t polys) {
-  if (!modup_fits(c) || rp.jl < 1) throw std::logic_error("tail kernel outside its shapes");
+  if (!ks_caps(c).wide_tile || rp.jl < 1) throw std::logic_error("tail kernel outside its shapes");
   const TailVariant v = tail_variant(c);
   auto go = [&](auto ptag) {
     constexpr int P = decltype(ptag)::value;
@@ -343,10 +400,38 @@ static void inverse_then_forward(evah_ctx *c, const typename InvOp::Params &ip, 
 }
 
 // ---- defined in keyswitch.hip
-// steps 1-2 of SEAL's switch_key_inplace for a batch of n (target, key) pairs (see the definition)
-bool switch_key_products(evah_ctx *c, uint32_t l, const u64 *target, size_t target_bs, const KeyDev *const *keys, uint32_t n,
-                         u64 *prod_d, const PtrTab *target_tab = nullptr, const MulTab *mul = nullptr, u64 *r_small = nullptr,
-                         bool fold = false, const PtrTab *adds = nullptr, bool lazy_out = false, const KsTailPlan *tail = nullptr);
+// steps 1-2 of SEAL's switch_key_inplace for a batch of n (target, key) pairs in the form f (see the definition)
+void switch_key_products(evah_ctx *c, uint32_t l, const KsCall &q, const KsForm &f);
+
+// ---- key switch + mod-down (steps 1-3)
+// the special rows of prod[polys][l + 1][N] through the inverse transform into r[polys][N], + P/2: what every mod-down starts with
+inline OpPlain::Params special_rows_intt(const evah_ctx *c, uint32_t l, const u64 *prod, u64 *r) {
+  return OpPlain::Params{prod + (size_t)l * c->N, r, (size_t)(l + 1) * c->N, c->N, 1, c->k - 1, 1, {}};
+}
+// the caller's side of a mod-down's combine pass: add[K] (stride add_ps; K < add_polys, ~0u: even polys only) joins, the result
+// goes to dst; add_tab / use_add_tab or add_bs are set on the result where they apply
+inline OpModDown::Params md_combine(const u64 *add, size_t add_ps, uint32_t add_polys, u64 *dst, size_t dst_ps) {
+  return OpModDown::Params{nullptr, 0, nullptr, 0, add, add_ps, add_polys, dst, dst_ps, 0, 0};
+}
+// step 3 for the products of n key switches in the form f: INTT(special rows) + P/2, then per-limb NTT + combine (mp: md_combine).
+// f.special_inv: switch_key_products left the first inverse pass in r and did not write the special rows.
+// (templates so that only the translation units that call them instantiate the kernels)
+template <class MD = OpModDown>
+static void ks_mod_down(evah_ctx *c, uint32_t l, uint32_t n, const KsForm &f, const u64 *prod, u64 *r, typename MD::Params mp) {
+  mp.r = r, mp.r_ps = c->N;
+  mp.c = prod, mp.c_ps = (size_t)(l + 1) * c->N;
+  mp.a = c->k - 1, mp.jl = l;
+  inverse_then_forward<OpPlain, MD>(c, special_rows_intt(c, l, prod, r), 2 * n, mp, 2 * n * l, f.special_inv);
+}
+// steps 1-3: out[b][K] = (the combine side of mp) + keyswitch(target_b)[K]; q.prod and q.r are supplied here
+template <class MD = OpModDown>
+static void switch_key_mod_down(evah_ctx *c, uint32_t l, KsCall q, const typename MD::Params &mp) {
+  Scratch prod(c, (size_t)q.n * 2 * (l + 1) * c->N), r(c, (size_t)q.n * 2 * c->N);
+  const KsForm f = ks_form(c, l, q.keys, q.n);
+  q.prod = prod.d, q.r = r.d;
+  switch_key_products(c, l, q, f);
+  ks_mod_down<MD>(c, l, q.n, f, prod.d, r.d, mp);
+}
 void switch_key(evah_ctx *c, uint32_t l, const u64 *target, const KeyDev &key, const u64 *add, size_t add_ps, uint32_t add_polys,
                 u64 *out, size_t out_ps);
 // ---- defined in elementwise.hip: dst[i] = (src[i] mod 2^30) | (src[i] >> 30) << 32 (KeyDev::d_split)

@@ -103,7 +103,7 @@ static void rotation_set(evah_ctx *c, uint32_t l, const std::vector<RotPair> &pa
       }
       PermTab gt{};
       for (uint32_t q = 0; q < np; q++) gt.p[q] = pr[q].perm;
-      rot_mod_down(c, l, np, prod.d, fold ? nullptr : perm.d, ch.out, r.d, false, &gt);
+      rot_mod_down(c, l, np, prod.d, fold ? nullptr : perm.d, ch.out, r.d, gt);
     }
   }
   // exact fallback: the same outputs through the unhoisted launches, each a no-op unless there

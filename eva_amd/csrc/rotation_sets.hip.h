@@ -428,40 +428,32 @@ static void rot_perm_launch(evah_ctx *c, uint32_t l, const RotPair *pr, uint32_t
                      polys);
   HIPCHK(hipGetLastError());
 }
-// mod-down of a chunk's products (step 3 of switch_key); c0' = perm_d[2r] is added to the even polys
+// mod-down of a hoisted chunk's products (step 3 of switch_key); c0' = perm_d[2r] is added to the even polys
 // perm_d == nullptr: P c0' was added to the products already (KS_FOLDADD)
-// gather != nullptr: prod is indexed in each pair's SOURCE space (k_hoist_mac), read through gather->p[pair]
-static void rot_mod_down(evah_ctx *c, uint32_t l, uint32_t np, u64 *prod_d, const u64 *perm_d, u64 *out_d, u64 *r_d, bool inv1,
-                         const PermTab *gather = nullptr) {
+// prod is indexed in each pair's SOURCE space (k_hoist_mac), read through gather.p[pair]
+static void rot_mod_down(evah_ctx *c, uint32_t l, uint32_t np, u64 *prod_d, const u64 *perm_d, u64 *out_d, u64 *r_d, const PermTab &gather) {
   const size_t N = c->N, pps = (size_t)l * N;
-  if (gather) {
-    OpPlainG::Params sp{prod_d + (size_t)l * N, r_d, (size_t)(l + 1) * N, N, 1, c->k - 1, 1, {}};
-    sp.perm_tab = *gather;
-    OpModDownG::Params mp{r_d, N, prod_d, (size_t)(l + 1) * N, perm_d, pps, ~0u, out_d, pps, c->k - 1, l};
-    mp.perm_tab = *gather;
-    inverse_then_forward<OpPlainG, OpModDownG>(c, sp, 2 * np, mp, 2 * np * l, inv1);
-    return;
-  }
-  // INTT of the special limbs, job = r*2 + K
-  OpPlain::Params sp{prod_d + (size_t)l * N, r_d, (size_t)(l + 1) * N, N, 1, c->k - 1, 1, {}};
-  // mod-down + combine, poly index pp = r*2 + K; c0' (even pp) is added, odd pp start from 0
-  OpModDown::Params mp{r_d, N, prod_d, (size_t)(l + 1) * N, perm_d, pps, ~0u, out_d, pps, c->k - 1, l};
-  inverse_then_forward<OpPlain, OpModDown>(c, sp, 2 * np, mp, 2 * np * l, inv1);
+  OpPlainG::Params sp{prod_d + (size_t)l * N, r_d, (size_t)(l + 1) * N, N, 1, c->k - 1, 1, {}};
+  sp.perm_tab = gather;
+  OpModDownG::Params mp{r_d, N, prod_d, (size_t)(l + 1) * N, perm_d, pps, ~0u, out_d, pps, c->k - 1, l};
+  mp.perm_tab = gather;
+  inverse_then_forward<OpPlainG, OpModDownG>(c, sp, 2 * np, mp, 2 * np * l);
 }
 // SEAL's order — rotate, then decompose the rotated c1 (every launch honours c->dev.guard)
 static void rot_chunk_plain(evah_ctx *c, uint32_t l, const RotPair *pr, uint32_t np, u64 *out_d) {
-  const size_t N = c->N, pps = (size_t)l * N, prod_bs = (size_t)2 * (l + 1) * N;
+  const size_t pps = (size_t)l * c->N;
   std::vector<const KeyDev *> keys(np);
   for (uint32_t r = 0; r < np; r++) keys[r] = pr[r].key;
   Scratch perm(c, (size_t)np * 2 * pps); // [r][c0 permuted | c1 permuted = key-switch target]
   rot_perm_launch(c, l, pr, np, perm.d, 2);
-  Scratch prod(c, np * prod_bs), r(c, (size_t)np * 2 * N);
-  const bool fold = c->tun.fold_pa && c->tun.fuse_mac;
+  KsCall q;
+  q.target = perm.d + pps, q.target_bs = 2 * pps, q.keys = keys.data(), q.n = np;
+  q.fold = ks_caps(c).fold;
   PtrTab adds{}; // P * (permuted c0) joins the inner product of K = 0; nothing is added to K = 1
-  for (uint32_t rr = 0; rr < np && fold; rr++) adds.p[2 * rr] = perm.d + (size_t)rr * 2 * pps;
-  const bool inv1 = switch_key_products(c, l, perm.d + pps, 2 * pps, keys.data(), np, prod.d, nullptr, nullptr,
-                                        fuse_small_launch(c, 2 * np * l) ? r.d : nullptr, fold, fold ? &adds : nullptr);
-  rot_mod_down(c, l, np, prod.d, fold ? nullptr : perm.d, out_d, r.d, inv1);
+  for (uint32_t rr = 0; rr < np && q.fold; rr++) adds.p[2 * rr] = perm.d + (size_t)rr * 2 * pps;
+  q.adds = q.fold ? &adds : nullptr;
+  // mod-down + combine, poly index pp = r*2 + K; c0' (even pp) is added unless folded, odd pp start from 0
+  switch_key_mod_down(c, l, q, md_combine(q.fold ? nullptr : perm.d, pps, ~0u, out_d, pps));
 }
 // the zero-coefficient record of a hoisted set: d[0] = count, d[1..] = positions (OpPlainZ, k_hoist_fix), preceded in the
 // same allocation by one word per chunk for the persistent fallback (its ticket and finished-chunk counters); everything
