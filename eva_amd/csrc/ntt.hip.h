@@ -93,17 +93,32 @@ __device__ __forceinline__ u64 mad64(uint32_t a, uint32_t b, u64 c) {
   asm("v_mad_u64_u32 %0, vcc, %1, %2, %3" : "=&v"(d) : "v"(a), "v"(b), "v"(c) : "vcc");
   return d;
 }
+// the same instruction with its second factor in a scalar register: a VALU instruction of gfx950 takes one scalar
+// source, and every multiply of the twiddle product uses exactly one twiddle word — a workgroup-uniform twiddle
+// (UTw below) is used where it is, with no copy into vector registers
+__device__ __forceinline__ u64 mad64s(uint32_t a, uint32_t bs, u64 c) {
+  u64 d;
+  asm("v_mad_u64_u32 %0, vcc, %1, %2, %3" : "=&v"(d) : "v"(a), "s"(bs), "v"(c) : "vcc");
+  return d;
+}
+// SW: the twiddle words are workgroup-uniform (scalar registers)
+template <bool SW> __device__ __forceinline__ u64 mad64w(uint32_t a, uint32_t b, u64 c) {
+  if constexpr (SW) return mad64s(a, b, c);
+  else return mad64(a, b, c);
+}
+// SM: so are the words of the modulus (a kernel that read its DevPrime with prime_uniform, below)
+template <bool SW = false, bool SM = false>
 __device__ __forceinline__ u64 mul_tw_lazy5_add_mad(u64 x, u64 w, u64 ws, u64 nq, u64 a) {
   const uint32_t x0 = (uint32_t)x, x1 = (uint32_t)(x >> 32), s0 = (uint32_t)ws, s1 = (uint32_t)(ws >> 32);
   const u64 t = (u64)x1 * s1 + (u64)__umulhi(x1, s0) + (u64)__umulhi(x0, s1);
   const uint32_t w0 = (uint32_t)w, w1 = (uint32_t)(w >> 32);
   const uint32_t t0 = (uint32_t)t, t1 = (uint32_t)(t >> 32), n0 = (uint32_t)nq, n1 = (uint32_t)(nq >> 32);
-  u64 r = mad64(x0, w0, a);
-  r = mad64(t0, n0, r);
-  u64 h = mad64(x0, w1, r >> 32); // from here on only the low word of h matters: its upper word is never read
-  h = mad64(x1, w0, h);
-  h = mad64(t0, n1, h);
-  h = mad64(t1, n0, h);
+  u64 r = mad64w<SW>(x0, w0, a);
+  r = mad64w<SM>(t0, n0, r);
+  u64 h = mad64w<SW>(x0, w1, r >> 32); // from here on only the low word of h matters: its upper word is never read
+  h = mad64w<SW>(x1, w0, h);
+  h = mad64w<SM>(t0, n1, h);
+  h = mad64w<SM>(t1, n0, h);
   return (h << 32) | (uint32_t)r;
 }
 #ifndef EVAH_MADLO
@@ -122,15 +137,16 @@ __device__ __forceinline__ u64 mul_tw_tb_add(u64 x, u64 w, u64 ws, uint32_t c, u
   const u64 t = (u64)x1 * s1 + (u64)__umulhi(x1, s0) + (u64)__umulhi(x0, s1);
   return ((a + x * w) + t * (u64)c) - ((u64)((uint32_t)t << sh) << 32);
 }
+template <bool SW = false, bool SM = false>
 __device__ __forceinline__ u64 mul_tw_tb_add_mad(u64 x, u64 w, u64 ws, uint32_t c, uint32_t sh, u64 a) {
   const uint32_t x0 = (uint32_t)x, x1 = (uint32_t)(x >> 32), s0 = (uint32_t)ws, s1 = (uint32_t)(ws >> 32);
   const u64 t = (u64)x1 * s1 + (u64)__umulhi(x1, s0) + (u64)__umulhi(x0, s1);
   const uint32_t w0 = (uint32_t)w, w1 = (uint32_t)(w >> 32), t0 = (uint32_t)t, t1 = (uint32_t)(t >> 32);
-  u64 r = mad64(x0, w0, a);
-  r = mad64(t0, c, r);
-  u64 h = mad64(x0, w1, r >> 32); // from here on only the low word of h matters
-  h = mad64(x1, w0, h);
-  h = mad64(t1, c, h);
+  u64 r = mad64w<SW>(x0, w0, a);
+  r = mad64w<SM>(t0, c, r);
+  u64 h = mad64w<SW>(x0, w1, r >> 32); // from here on only the low word of h matters
+  h = mad64w<SW>(x1, w0, h);
+  h = mad64w<SM>(t1, c, h);
   return ((u64)((uint32_t)h - (t0 << sh)) << 32) | (uint32_t)r;
 }
 // forward Cooley-Tukey butterfly.  The twiddle product is in [0,4q), so each stage grows the
@@ -148,18 +164,18 @@ __device__ __forceinline__ u64 mul_tw_tb_add_mad(u64 x, u64 w, u64 ws, uint32_t 
 // instructions to get below 8q.  Starting from ~q instead of 8q, THREE stages fit before the next reduction (5q, 9q,
 // 13q) instead of two, so a pass reduces on every third stage (ntt_round).  Primes of another shape (DevPrime::tb_c
 // == 0) take the compare-and-subtract butterflies; the choice is block-uniform, made once per transform.
-template <bool REDUCE, bool MAD = false, bool TB = false>
+template <bool REDUCE, bool MAD = false, bool TB = false, bool SW = false, bool SM = false>
 __device__ __forceinline__ void bfly_fwd(u64 &X, u64 &Y, ulonglong2 w, u64 nq, u64 q4, u64 q8, u64 nq8, uint32_t tbc = 0,
                                          uint32_t tbs = 0, uint32_t tbm = 0) {
   u64 x = X;
   if constexpr (REDUCE && TB) {
     const uint32_t hi = (uint32_t)(X >> 32);
-    x = mad64(hi >> tbs, tbc, ((u64)(hi & tbm) << 32) | (uint32_t)X); // < q + 16c
+    x = mad64w<SM>(hi >> tbs, tbc, ((u64)(hi & tbm) << 32) | (uint32_t)X); // < q + 16c
   } else if constexpr (REDUCE) {
     x = X + (X >= q8 ? nq8 : 0);
   }
-  if constexpr (TB && EVAH_TBMUL) X = MAD ? mul_tw_tb_add_mad(Y, w.x, w.y, tbc, tbs, x) : mul_tw_tb_add(Y, w.x, w.y, tbc, tbs, x);
-  else X = MAD ? mul_tw_lazy5_add_mad(Y, w.x, w.y, nq, x) : mul_tw_lazy5_add(Y, w.x, w.y, nq, x);
+  if constexpr (TB && EVAH_TBMUL) X = MAD ? mul_tw_tb_add_mad<SW, SM>(Y, w.x, w.y, tbc, tbs, x) : mul_tw_tb_add(Y, w.x, w.y, tbc, tbs, x);
+  else X = MAD ? mul_tw_lazy5_add_mad<SW, SM>(Y, w.x, w.y, nq, x) : mul_tw_lazy5_add(Y, w.x, w.y, nq, x);
   Y = ((x << 1) + q4) - X;
 }
 // inverse Gentleman-Sande butterfly, X,Y in [0,5q) -> [0,5q)
@@ -168,6 +184,76 @@ __device__ __forceinline__ void bfly_inv(u64 &X, u64 &Y, ulonglong2 w, u64 nq, u
   u64 d = X + q5 - Y;
   X = s + (s >= q5 ? nq5 : 0);
   Y = mul_tw_lazy5(d, w.x, w.y, nq);
+}
+
+// The uniform round of a strided pass.  Its first forward round (stages 0 .. RB-1, S0 == 0 in ntt_round) uses heap
+// nodes 1 .. 2^RB - 1 whatever the thread and the column, and so does the last round of its inverse: 7 twiddles at
+// RB = 3, which every thread used to read from the staged copy in LDS into up to 28 vector registers.  UTw holds them
+// as workgroup-uniform values: loaded from the global table through a constant-address-space pointer on a uniform
+// address (s_load_dwordx4 — the kernels store to global memory, so alias analysis is not asked to prove the table
+// read-only), they stay in scalar registers and each multiply of the twiddle product names its twiddle word as its one
+// scalar source.  Same words, same butterflies: every lazy value is what the LDS form computes.
+#ifndef EVAH_TW_SGPR
+#define EVAH_TW_SGPR 1 // 0: every round's twiddles from LDS (A/B switch of the build)
+#endif
+struct NoUTw {};
+template <int NU> struct UTw { ulonglong2 w[NU]; }; // w[k]: heap node k, 1 <= k < NU
+template <class UT> struct IsUTw : std::false_type {};
+template <int NU> struct IsUTw<UTw<NU>> : std::bool_constant<EVAH_TW_SGPR != 0> {};
+// the uniform round's twiddles of a P-point strided pass at 2^LR coefficients per thread (NoUTw when the switch is off)
+template <int P, int LR> using UTwOf = std::conditional_t<EVAH_TW_SGPR != 0, UTw<(1 << Rounds<P, LR>::bits(0))>, NoUTw>;
+// table = cx.tw_fwd / cx.tw_inv; FROM = 1, or 2 for an inverse pass that folds N^-1 into its last stage (node 1 unused)
+template <class UT> __device__ __forceinline__ void utw_load(UT &, const ulonglong2 *, uint32_t, uint32_t, int = 1) {}
+template <int NU> __device__ __forceinline__ void utw_load(UTw<NU> &ut, const ulonglong2 *table, uint32_t prime, uint32_t N, int from = 1) {
+  typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+  typedef const __attribute__((address_space(4))) u64x2 *ConstTw;
+  const ConstTw p = (ConstTw)(table + (size_t)__builtin_amdgcn_readfirstlane(prime) * N);
+#pragma unroll
+  for (int k = 1; k < NU; k++) {
+    if (k < from) continue;
+    const u64x2 v = p[k];
+    ut.w[k].x = v.x;
+    ut.w[k].y = v.y;
+  }
+}
+// A workgroup's prime read the same way.  cx.primes[prime] after the kernel's first global store is a vector load of
+// workgroup-uniform words (the compiler cannot prove the table unclobbered), and nq, 4q and the top-bit constants then
+// occupy vector registers across every round of a row loop; through the constant address space they are scalar
+// loads, and the butterflies of a pass that is given a UTw name them as scalar sources (SM).
+__device__ __forceinline__ DevPrime prime_uniform(const DevPrime *primes, uint32_t prime) {
+  typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+  typedef const __attribute__((address_space(4))) u64x2 *ConstVec;
+  static_assert(sizeof(DevPrime) % sizeof(u64x2) == 0, "DevPrime: whole 16-byte words");
+  constexpr int NW = sizeof(DevPrime) / sizeof(u64x2);
+  const ConstVec p = (ConstVec)(primes + __builtin_amdgcn_readfirstlane(prime));
+  u64x2 raw[NW];
+#pragma unroll
+  for (int i = 0; i < NW; i++) raw[i] = p[i];
+  DevPrime pm;
+  __builtin_memcpy(&pm, raw, sizeof(DevPrime));
+  return pm;
+}
+// one entry of a context table (halfmod, invq, ...) at a workgroup-uniform index, the same way
+__device__ __forceinline__ u64 uniform_entry(const u64 *table, uint32_t idx) {
+  typedef const __attribute__((address_space(4))) u64 *ConstWord;
+  return ((ConstWord)table)[__builtin_amdgcn_readfirstlane(idx)];
+}
+__device__ __forceinline__ ulonglong2 uniform_entry(const ulonglong2 *table, uint32_t idx) {
+  typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+  typedef const __attribute__((address_space(4))) u64x2 *ConstVec;
+  const u64x2 v = ((ConstVec)table)[__builtin_amdgcn_readfirstlane(idx)];
+  ulonglong2 r;
+  r.x = v.x;
+  r.y = v.y;
+  return r;
+}
+// the prime of a pass that takes a UTw (the plain table read when the switch is off)
+__device__ __forceinline__ DevPrime pass_prime(const DevCtx &cx, uint32_t prime) {
+#if EVAH_TW_SGPR
+  return prime_uniform(cx.primes, prime);
+#else
+  return cx.primes[prime];
+#endif
 }
 
 // One register round: RB stages over bit range [LO, LO+RB) of the P-bit local index.
@@ -186,10 +272,11 @@ template <int P, bool RED_EVEN> constexpr bool tb_reduce_stage(int s) {
 // lin_in != nullptr: this round's inputs are read from an UNPADDED copy of the sub-transform (element e at lin_in[e] —
 // where an LDS-DMA load put the tile, ks_inner_kernel<MAC3>), its outputs go to the padded tile as usual
 struct NoHook { __device__ __forceinline__ void operator()() const {} };
-template <int P, int LR, int RB, int LO, bool INVERSE, bool STRIDED, bool RED_EVEN, bool LASTFOLD = STRIDED, bool TB = false, class AfterLoad = NoHook>
+// ut: a UTw with the uniform round's twiddles (strided passes; used by the round with S0 == 0 only), or NoUTw
+template <int P, int LR, int RB, int LO, bool INVERSE, bool STRIDED, bool RED_EVEN, bool LASTFOLD = STRIDED, bool TB = false, class AfterLoad = NoHook, class UT = NoUTw>
 __device__ __forceinline__ void ntt_round(u64 *sub_lds, int tid, uint32_t h, uint32_t pre,
                                           const ulonglong2 *__restrict__ tw, const DevPrime &pm, const u64 *lin_in = nullptr,
-                                          AfterLoad after_load = AfterLoad()) {
+                                          AfterLoad after_load = AfterLoad(), const UT &ut = UT()) {
   constexpr int NTT_R = 1 << LR;
   constexpr int S = 1 << P, TPS = S / NTT_R, G = NTT_R >> RB, NU = 1 << RB;
   constexpr int S0 = P - LO - RB; // local stages above this round
@@ -199,6 +286,8 @@ __device__ __forceinline__ void ntt_round(u64 *sub_lds, int tid, uint32_t h, uin
   // -4.4 %, mod-down pass 1 -2.5 %); the contiguous passes (combine epilogue: +8 %), the one-wave
   // key-switch kernel (LR = 2: +1.5 %) and the inverse butterflies keep the compiler's form
   constexpr bool MAD = EVAH_MADLO && !INVERSE && STRIDED && LR == 3;
+  constexpr bool UNI = IsUTw<UT>::value && STRIDED && S0 == 0; // node == 1 for every thread: twiddle (1 << s) + v of ut
+  constexpr bool SM = IsUTw<UT>::value; // a pass that is given a UTw read pm with prime_uniform: scalar registers
   u64 x[NTT_R];
 #pragma unroll
   for (int g = 0; g < G; g++) {
@@ -226,10 +315,12 @@ __device__ __forceinline__ void ntt_round(u64 *sub_lds, int tid, uint32_t h, uin
         for (int u = 0; u < NU; u++) {
           if (u & half) continue;
           const int v = u >> (RB - s);
-          const ulonglong2 w = tw[((size_t)node << s) + v];
+          ulonglong2 w;
+          if constexpr (UNI) w = ut.w[(1 << s) + v];
+          else w = tw[((size_t)node << s) + v];
           const bool red = TB ? tb_reduce_stage<P, RED_EVEN>(S0 + s) : ((((S0 + s) & 1) == 0) == RED_EVEN);
-          if (red) bfly_fwd<true, MAD, TB>(x[g * NU + u], x[g * NU + u + half], w, nq, q4, q8, nq8, pm.tb_c, pm.tb_sh, pm.tb_mask);
-          else bfly_fwd<false, MAD, TB>(x[g * NU + u], x[g * NU + u + half], w, nq, q4, q8, nq8, pm.tb_c, pm.tb_sh, pm.tb_mask);
+          if (red) bfly_fwd<true, MAD, TB, UNI, SM>(x[g * NU + u], x[g * NU + u + half], w, nq, q4, q8, nq8, pm.tb_c, pm.tb_sh, pm.tb_mask);
+          else bfly_fwd<false, MAD, TB, UNI, SM>(x[g * NU + u], x[g * NU + u + half], w, nq, q4, q8, nq8, pm.tb_c, pm.tb_sh, pm.tb_mask);
         }
       }
     } else {
@@ -248,7 +339,9 @@ __device__ __forceinline__ void ntt_round(u64 *sub_lds, int tid, uint32_t h, uin
             Y = mul_shoup(d, pm.w0ninv, pm.w0ninv_s, q);
           } else {
             const int v = u >> (RB - s);
-            const ulonglong2 w = tw[((size_t)node << s) + v];
+            ulonglong2 w;
+            if constexpr (UNI) w = ut.w[(1 << s) + v];
+            else w = tw[((size_t)node << s) + v];
             bfly_inv(X, Y, w, nq, q5, nq5);
           }
         }
@@ -264,25 +357,27 @@ __device__ __forceinline__ void ntt_round(u64 *sub_lds, int tid, uint32_t h, uin
 // for the very loads that are meant to overlap the transform
 template <int P, int LR, int I, bool INVERSE, bool STRIDED, bool RED_EVEN, bool LASTFOLD = STRIDED, bool TB = false, bool WAVESYNC = false> struct RoundSeq {
   // forward: rounds 0..NR-1 (top bits first); inverse: NR-1..0 (low bits first)
+  template <class UT = NoUTw>
   static __device__ __forceinline__ void run(u64 *sub_lds, int tid, uint32_t h, uint32_t pre,
-                                             const ulonglong2 *tw, const DevPrime &pm) {
+                                             const ulonglong2 *tw, const DevPrime &pm, const UT &ut = UT()) {
     using RS = Rounds<P, LR>;
     constexpr int idx = INVERSE ? (RS::NR - 1 - I) : I;
-    ntt_round<P, LR, RS::bits(idx), RS::lo(idx), INVERSE, STRIDED, RED_EVEN, LASTFOLD, TB>(sub_lds, tid, h, pre, tw, pm);
+    ntt_round<P, LR, RS::bits(idx), RS::lo(idx), INVERSE, STRIDED, RED_EVEN, LASTFOLD, TB, NoHook, UT>(sub_lds, tid, h, pre, tw, pm, nullptr, NoHook(), ut);
     if constexpr (I + 1 < RS::NR) {
       // a sub-transform of <= 64 threads lives in one wave: its LDS exchange is ordered by the wave's own DS queue
       if constexpr (WAVESYNC || (!EVAH_ROUND_BARRIER && ((1 << P) >> LR) <= 64)) __builtin_amdgcn_wave_barrier();
       else __syncthreads();
-      RoundSeq<P, LR, I + 1, INVERSE, STRIDED, RED_EVEN, LASTFOLD, TB, WAVESYNC>::run(sub_lds, tid, h, pre, tw, pm);
+      RoundSeq<P, LR, I + 1, INVERSE, STRIDED, RED_EVEN, LASTFOLD, TB, WAVESYNC>::run(sub_lds, tid, h, pre, tw, pm, ut);
     }
   }
 };
 // forward rounds of one pass: the top-bit butterflies when the prime has the shape, else compare-and-subtract
 // (block-uniform: pm is the workgroup's prime)
-template <int P, int LR, bool STRIDED, bool RED_EVEN>
-__device__ __forceinline__ void forward_rounds(u64 *sub_lds, int tid, uint32_t h, uint32_t pre, const ulonglong2 *tw, const DevPrime &pm) {
-  if (EVAH_TOPBIT && pm.tb_c) RoundSeq<P, LR, 0, false, STRIDED, RED_EVEN, STRIDED, true>::run(sub_lds, tid, h, pre, tw, pm);
-  else RoundSeq<P, LR, 0, false, STRIDED, RED_EVEN, STRIDED, false>::run(sub_lds, tid, h, pre, tw, pm);
+template <int P, int LR, bool STRIDED, bool RED_EVEN, class UT = NoUTw>
+__device__ __forceinline__ void forward_rounds(u64 *sub_lds, int tid, uint32_t h, uint32_t pre, const ulonglong2 *tw, const DevPrime &pm,
+                                               const UT &ut = UT()) {
+  if (EVAH_TOPBIT && pm.tb_c) RoundSeq<P, LR, 0, false, STRIDED, RED_EVEN, STRIDED, true>::run(sub_lds, tid, h, pre, tw, pm, ut);
+  else RoundSeq<P, LR, 0, false, STRIDED, RED_EVEN, STRIDED, false>::run(sub_lds, tid, h, pre, tw, pm, ut);
 }
 
 // One pass.  grid.x = (N / tile) * jx-count (tile index in the low log_tiles bits), grid.y / grid.z

@@ -73,9 +73,13 @@ ntt_modup_kernel(DevCtx cx, typename Op::Params prm, int log_tiles) {
       if (S >= T || (int)threadIdx.x + r * T < S) twn[r] = tw[threadIdx.x + r * T];
   };
   tw_request(jb.prime);
+  // the uniform round's twiddles (UTw, ntt.hip.h) go to scalar registers straight from the tables: here the inverse
+  // pass's last round; each row's first forward round in the row loop
+  UTwOf<P, LR> utA;
+  utw_load(utA, cx.tw_inv, pa, cx.N, 2);
   __syncthreads();
   const int sub = threadIdx.x / TPS, tid = threadIdx.x % TPS;
-  RoundSeq<P, LR, 0, true, true, false>::run(lds + sub * SP, tid, 0, 0, twl, pmA); // canonical mod q_J (N^-1 folded in)
+  RoundSeq<P, LR, 0, true, true, false>::run(lds + sub * SP, tid, 0, 0, twl, pmA, utA); // canonical mod q_J (N^-1 folded in)
   __syncthreads();
   u64 t[NTT_R]; // this thread's words of t_J: every output row converts them from here
 #pragma unroll
@@ -89,7 +93,12 @@ ntt_modup_kernel(DevCtx cx, typename Op::Params prm, int log_tiles) {
 #pragma unroll
     for (int r = 0; r < TWR; r++)
       if (S >= T || (int)threadIdx.x + r * T < S) twl[threadIdx.x + r * T] = twn[r];
-    const DevPrime pm = cx.primes[jb.prime];
+    // the row's prime and its uniform twiddles: scalar loads, waited for once, before the conversion.  (Requested a row
+    // ahead, beside tw_request below, two sets of 28 scalar registers are live across the butterflies and the kernels
+    // spill scalar registers: profiles/r11_tw_sgpr_notes.md)
+    const DevPrime pm = pass_prime(cx, jb.prime);
+    UTwOf<P, LR> ut;
+    utw_load(ut, cx.tw_fwd, jb.prime, cx.N);
     auto convert = [&](auto lazy_tag) {
       constexpr bool LZ = decltype(lazy_tag)::value;
 #pragma unroll
@@ -104,8 +113,8 @@ ntt_modup_kernel(DevCtx cx, typename Op::Params prm, int log_tiles) {
     const bool more = in < prm.ni;
     if (more) tw_request(jn.prime);
     __syncthreads();
-    if constexpr (TBONLY) RoundSeq<P, LR, 0, false, true, false, true, true>::run(lds + sub * SP, tid, 0, 0, twl, pm);
-    else forward_rounds<P, LR, true, false>(lds + sub * SP, tid, 0, 0, twl, pm);
+    if constexpr (TBONLY) RoundSeq<P, LR, 0, false, true, false, true, true>::run(lds + sub * SP, tid, 0, 0, twl, pm, ut);
+    else forward_rounds<P, LR, true, false>(lds + sub * SP, tid, 0, 0, twl, pm, ut);
     __syncthreads();
     const __amdgpu_buffer_rsrc_t row = __builtin_amdgcn_make_buffer_rsrc(jb.dst, 0, 0x7fffffff, 0x00020000);
 #pragma unroll

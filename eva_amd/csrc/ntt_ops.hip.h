@@ -503,6 +503,15 @@ template <int AM> struct OpRRT {
     j.lazy = cx.primes[p.last].q <= cx.primes[i].q4 && cx.primes[p.sp].q <= cx.primes[i].q8;
     return true;
   }
+  // conv's constants of job j once more, as scalar loads (uniform_entry, ntt.hip.h).  ntt_tail_kernel sets a row's job
+  // up a row ahead, after its first global store: setup's table reads are vector loads there, and their eight words
+  // would occupy vector registers across the row's butterflies.  Read again at the row's start they replace those
+  // loads, which the compiler then drops.  Same table entries as setup.
+  static __device__ __forceinline__ void conv_consts_uniform(const DevCtx &cx, const Params &p, Job &j) {
+    j.halfP = uniform_entry(cx.halfmod, p.sp * cx.k + j.prime);
+    j.halfL = uniform_entry(cx.halfmod, p.last * cx.k + j.prime);
+    j.pinv = uniform_entry(cx.invq, p.sp * cx.k + j.prime);
+  }
   // u P^-1 + v at one coefficient from r_K and t_K there (ntt_tail_kernel converts from registers)
   template <bool LZ> static __device__ __forceinline__ u64 conv(const Job &j, const DevPrime &pm, u64 r, u64 t) {
     if (LZ) return mul_tw_lazy5(r + (pm.q - j.halfP), j.pinv.x, j.pinv.y, pm.nq) + (t + (pm.q - j.halfL));

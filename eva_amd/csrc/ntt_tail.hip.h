@@ -66,11 +66,16 @@ ntt_tail_kernel(DevCtx cx, OpRRLastFolded::Params lp, OpRRFolded::Params rp) {
   };
   const int sub = threadIdx.x / TPS, tid = threadIdx.x % TPS;
   u64 r[NTT_R], t[NTT_R]; // this thread's words of r_K and t_K: every output row converts them from here
+  // the uniform round's twiddles (UTw, ntt.hip.h) of the transform at hand, in scalar registers straight from the
+  // tables: requested before the barrier in front of its rounds (a transform ahead, two sets are live across the
+  // butterflies and the kernel spills scalar registers: profiles/r11_tw_sgpr_notes.md)
+  UTwOf<P, LR> ut;
   {
     // ---- 1. the special-row tile modulo P
     const DevPrime pmP = cx.primes[lp.sp];
     const u64 *srcP = jl.r, *srcL = jl.dst;
     tw_request(cx.tw_inv, lp.sp);
+    utw_load(ut, cx.tw_inv, lp.sp, cx.N, 2);
 #pragma unroll
     for (int it = 0; it < NTT_R; it++) lds[lds_at(it)] = srcP[n0 + it * nstep];
     tw_stage();
@@ -78,7 +83,7 @@ ntt_tail_kernel(DevCtx cx, OpRRLastFolded::Params lp, OpRRFolded::Params rp) {
     for (int it = 0; it < NTT_R; it++) t[it] = srcL[n0 + it * nstep]; // the last-row tile, in flight during the rounds below
     tw_request(cx.tw_inv, jl.prime);
     __syncthreads();
-    RoundSeq<P, LR, 0, true, true, false>::run(lds + sub * SP, tid, 0, 0, twl, pmP); // canonical mod P (N^-1 folded in)
+    RoundSeq<P, LR, 0, true, true, false>::run(lds + sub * SP, tid, 0, 0, twl, pmP, ut); // canonical mod P (N^-1 folded in)
     __syncthreads();
     // every thread is past the rounds: the twiddle buffer and the tile may be rewritten; each thread rewrites only the
     // tile slots it reads here
@@ -93,11 +98,12 @@ ntt_tail_kernel(DevCtx cx, OpRRLastFolded::Params lp, OpRRFolded::Params rp) {
   uint32_t iy = 0;
   OpRRFolded::setup(cx, rp, 0, iy, poly, jb);
   tw_request(cx.tw_fwd, jb.prime);
+  utw_load(ut, cx.tw_inv, jl.prime, cx.N, 2);
   __syncthreads();
   {
     // ---- 2. the last-row tile modulo q_last, t_K
     const DevPrime pmL = cx.primes[jl.prime];
-    RoundSeq<P, LR, 0, true, true, false>::run(lds + sub * SP, tid, 0, 0, twl, pmL); // canonical mod q_last
+    RoundSeq<P, LR, 0, true, true, false>::run(lds + sub * SP, tid, 0, 0, twl, pmL, ut); // canonical mod q_last
     __syncthreads();
 #pragma unroll
     for (int it = 0; it < NTT_R; it++) t[it] = OpRRLastFolded::combine(jl, pmL, lds[lds_at(it)], r[it]);
@@ -106,7 +112,12 @@ ntt_tail_kernel(DevCtx cx, OpRRLastFolded::Params lp, OpRRFolded::Params rp) {
   while (true) {
     // every thread is past the previous rounds (barrier above / below)
     tw_stage();
-    const DevPrime pm = cx.primes[jb.prime];
+    // the row's prime, its uniform twiddles and the conversion's constants: scalar loads, waited for once
+    const DevPrime pm = pass_prime(cx, jb.prime);
+    utw_load(ut, cx.tw_fwd, jb.prime, cx.N);
+#if EVAH_TW_SGPR
+    OpRRFolded::conv_consts_uniform(cx, rp, jb);
+#endif
     auto convert = [&](auto lazy_tag) {
       constexpr bool LZ = decltype(lazy_tag)::value;
 #pragma unroll
@@ -122,8 +133,8 @@ ntt_tail_kernel(DevCtx cx, OpRRLastFolded::Params lp, OpRRFolded::Params rp) {
       tw_request(cx.tw_fwd, jn.prime);
     }
     __syncthreads();
-    if constexpr (TBONLY) RoundSeq<P, LR, 0, false, true, false, true, true>::run(lds + sub * SP, tid, 0, 0, twl, pm);
-    else forward_rounds<P, LR, true, false>(lds + sub * SP, tid, 0, 0, twl, pm);
+    if constexpr (TBONLY) RoundSeq<P, LR, 0, false, true, false, true, true>::run(lds + sub * SP, tid, 0, 0, twl, pm, ut);
+    else forward_rounds<P, LR, true, false>(lds + sub * SP, tid, 0, 0, twl, pm, ut);
     __syncthreads();
     // a row is at most 2^17 * 8 bytes: offsets fit 32 bits
     const __amdgpu_buffer_rsrc_t row = __builtin_amdgcn_make_buffer_rsrc(jb.dst, 0, 0x7fffffff, 0x00020000);
