@@ -150,6 +150,8 @@ _SIGS = {
     "evah_encode_encrypt_symmetric_array_dev": [_vp, C.c_uint32, _vp, C.c_int, C.c_size_t, _vp, C.POINTER(C.c_double), C.c_uint32,
                                                 C.c_uint32, C.c_double, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _vpp],
     "evah_decrypt_decode_rows": [_vp, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.c_int, _vp, C.c_size_t, C.c_int, C.c_int],
+    # the refresh
+    "evah_refresh_handles": [_vp, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.c_double, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _vpp],
     "evah_ct_slice": [_vp, _vp, C.c_uint32, C.c_uint32, _vpp],
     "evah_ctx_stack_stats": [_vp, _u64p],
     # batched plaintexts
@@ -703,6 +705,18 @@ class Context:
         _chk(_lib.evah_decrypt_decode_handles(self.h, ptrs, len(cts), int(n_out), _DTYPES[dt] if dtype_code is None else int(dtype_code),
                                               out.ctypes.data_as(_vp)))
         return out
+
+    def refresh_handles(self, cts, limbs_out, scale_out, ekeys, seeds):
+        """decrypt, divide by 2^t = scale / scale_out (ties towards +infinity) and encrypt again every instance of the
+        handles of `cts` (as decrypt_decode_handles takes them) at limbs_out limbs and scale_out -> one batched handle
+        [instances][2][limbs_out][N] (evah_refresh_handles); ekeys, seeds: one 32-byte string per instance
+        each, or None (the null pointer, which the call refuses)"""
+        rows = sum(ct.batch for ct in cts)
+        ptrs = (C.c_void_p * max(len(cts), 1))(*[ct.h for ct in cts])
+        h = C.c_void_p()
+        _chk(_lib.evah_refresh_handles(self.h, ptrs, len(cts), int(limbs_out), float(scale_out), _keys32(ekeys, rows), _keys32(seeds, rows),
+                                       C.byref(h)))
+        return Ciphertext(self, h)
 
     # ---- the array calls on device memory (DESIGN.md 1.11): rows = a DeviceView, or anything with .ptr, .shape, .dtype, .pitch
     @staticmethod

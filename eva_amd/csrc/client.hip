@@ -403,6 +403,82 @@ k_crt_to_double(DevCtx cx, CrtTab t, uint32_t l, const u64 *coeff, double inv_sc
   const size_t n = (size_t)blockIdx.x * blockDim.x + threadIdx.x, inst = blockIdx.y;
   out[inst * cx.N + n] = make_double2(crt_to_double(cx, t, l, coeff + inst * l * cx.N, n, inv_scale), 0.0);
 }
+// ---- the refresh: the decrypted integer M of a coefficient, divided by 2^t, under the target's primes
+// the lift table of (l, L, t) (hostmath.h lift_table_build) as the kernel reads it
+struct LiftTab {
+  const u64 *half, *wpre, *qmod, *inv2t, *premod;
+  u64 qw;
+};
+// One thread per coefficient n of instance blockIdx.y: coeff [inst][l][N] (the decrypted message, coefficient form) ->
+// out [inst][L][N], the canonical residues of M' = floor((M + 2^(t-1)) / 2^t) (t = 0: M), M = U for U <= floor(Q_l / 2),
+// else U - Q_l.  Everything is read off the mixed-radix digits v_i of U (garner): the sign by comparing digits with those
+// of floor(Q_l / 2) from the top, U mod q_j for a prime j >= l as sum_i v_i (q_0..q_{i-1} mod q_j), and the remainder
+// rho = (M + 2^(t-1)) mod 2^t from M mod 2^64 = sum_i v_i (q_0..q_{i-1} mod 2^64) - [neg] (Q_l mod 2^64), wrapping.
+// Then M' = (M + 2^(t-1) - rho) / 2^t exactly, i.e. (M_j + (2^(t-1) - rho)) (2^t)^-1 mod q_j: rescale's exact division
+// with 2^t in place of a prime.  No multi-word integer is formed.
+// LB bounds l.  Up to 16 every loop over the digits is unrolled with the bound as its trip count and the level as a
+// uniform predicate, so r[] and v[] are indexed by constants and stay in registers; the LB = 62 form keeps the loops and
+// the arrays go to scratch memory, as crt_to_double's do.
+template <int LB>
+__global__ void __launch_bounds__(256)
+k_refresh_lift(DevCtx cx, CrtTab g, LiftTab t, uint32_t l, uint32_t L, uint32_t sh, const u64 *coeff, u64 *out) {
+  constexpr int UNR = LB <= 16 ? LB : 1;
+  const size_t n = (size_t)blockIdx.x * blockDim.x + threadIdx.x, inst = blockIdx.y;
+  coeff += inst * l * cx.N + n;
+  out += inst * L * cx.N + n;
+  u64 r[LB], v[LB];
+#pragma unroll UNR
+  for (int i = 0; i < LB; i++) r[i] = i < (int)l ? coeff[(size_t)i * cx.N] : 0;
+#pragma unroll UNR
+  for (int i = 0; i < LB; i++) { // garner(), with constant indices
+    v[i] = 0;
+    if (i < (int)l) {
+      const DevPrime pm = cx.primes[i];
+      u128_t acc = {0, 0};
+#pragma unroll UNR
+      for (int j = 0; j < i; j++) acc128(acc, v[j] >= pm.q ? barrett64(v[j], pm.q, pm.brt) : v[j], g.pre_mod[i * l + j]);
+      v[i] = i ? mulmod(submod(r[i], barrett128(acc, pm), pm.q), g.inv_prefix[i], pm) : r[0];
+    }
+  }
+  bool neg = false, decided = false; // U > floor(Q_l / 2): mixed radix is positional, the first differing digit from the top decides
+#pragma unroll UNR
+  for (int i = LB - 1; i >= 0; i--)
+    if (i < (int)l && !decided && v[i] != t.half[i]) {
+      neg = v[i] > t.half[i];
+      decided = true;
+    }
+  int64_t d = 0; // 2^(t-1) - rho, |d| <= 2^61
+  if (sh) {
+    u64 w = neg ? 0 - t.qw : 0; // M mod 2^64
+#pragma unroll UNR
+    for (int i = 0; i < LB; i++)
+      if (i < (int)l) w += v[i] * t.wpre[i];
+    const u64 hb = (u64)1 << (sh - 1), rho = (w + hb) & (((u64)1 << sh) - 1);
+    d = (int64_t)hb - (int64_t)rho;
+  }
+  auto emit = [&](uint32_t j, u64 m) {
+    const DevPrime pm = cx.primes[j];
+    if (neg) m = submod(m, t.qmod[j], pm.q);
+    if (sh) {
+      const u64 a = barrett64(d < 0 ? (u64)(-d) : (u64)d, pm.q, pm.brt); // a 30-bit prime is far below |d|
+      m = mulmod(addmod(m, d < 0 ? negmod(a, pm.q) : a, pm.q), t.inv2t[j], pm);
+    }
+    out[(size_t)j * cx.N] = m;
+  };
+#pragma unroll UNR
+  for (int j = 0; j < LB; j++) // a prime the value has a residue of: U mod q_j = r_j
+    if (j < (int)l && j < (int)L) emit(j, r[j]);
+  for (uint32_t j = l; j < L; j++) {
+    const DevPrime pm = cx.primes[j];
+    const u64 *pre = t.premod + (size_t)(j - l) * l;
+    u128_t acc = {0, 0};
+#pragma unroll UNR
+    for (int i = 0; i < LB; i++)
+      if (i < (int)l) acc128(acc, v[i] >= pm.q ? barrett64(v[i], pm.q, pm.brt) : v[i], pre[i]);
+    emit(j, barrett128(acc, pm));
+  }
+}
+
 // T = double, or float: the double rounded to nearest-even here, so that half the bytes cross to the host
 template <class T>
 __global__ void __launch_bounds__(256)
@@ -557,29 +633,39 @@ static void dec_gather_rows(evah_ctx *c, const double2 *cd, uint32_t n, uint32_t
   EW_LAUNCH(k_dec_gather_rows<T>, dim3((n_out + 255) / 256, n), dim3(256), 0, c->stream, cd, c->sh->enc_slot_map, n_out, c->N,
             static_cast<unsigned char *>(out), pitch);
 }
+// the instances of a call's handles, acquired, in list order, then instance order
+static DotTab dot_tab_of(evah_ctx *c, const evah_ct *const *cts, uint32_t n_handles) {
+  DotTab tab{};
+  for (uint32_t i = 0, r = 0; i < n_handles; i++) {
+    acquire(c, cts[i]->buf);
+    for (uint32_t j = 0; j < cts[i]->batch; j++, r++) {
+      tab.ct[r] = cts[i]->d + (size_t)j * cts[i]->size * cts[i]->ps;
+      tab.ct_ps[r] = (uint32_t)(cts[i]->ps / c->N);
+    }
+  }
+  return tab;
+}
+// the decrypted messages of n instances in coefficient form, m [n][l][N]: the dot product with s and the inverse
+// transforms (decrypt_decode and refresh)
+static void decrypt_to_coeff(evah_ctx *c, const DotTab &tab, uint32_t size, uint32_t l, uint32_t n, u64 *m) {
+  EW_LAUNCH(k_decrypt_dot, dim3(c->N / 256, l, n), dim3(256), 0, c->stream, c->dev, tab, size, l, c->sh->sk.d, m);
+  OpPlain::Params ip{m, m, (size_t)l * c->N, (size_t)l * c->N, l, 0, 0, {}};
+  ntt_inverse<OpPlain>(c, ip, n * l);
+}
 static void decrypt_decode(evah_ctx *c, const evah_ct *const *cts, uint32_t n_handles, uint32_t n, uint32_t n_out, int dtype_out, void *out,
                            const RowsDst *rows = nullptr) {
   const uint32_t l = cts[0]->limbs, N = c->N;
   enc_tables(c);
   dec_tables(c);
   const CrtTab t = crt_tab_cached(c, l);
-  DotTab tab{};
-  for (uint32_t i = 0, r = 0; i < n_handles; i++) {
-    acquire(c, cts[i]->buf);
-    for (uint32_t j = 0; j < cts[i]->batch; j++, r++) {
-      tab.ct[r] = cts[i]->d + (size_t)j * cts[i]->size * cts[i]->ps;
-      tab.ct_ps[r] = (uint32_t)(cts[i]->ps / N);
-    }
-  }
+  const DotTab tab = dot_tab_of(c, cts, n_handles);
   const size_t B = n, row_bytes = dtype_size(dtype_out) * n_out, out_bytes = row_bytes * B;
   const bool to_dev = rows && rows->on_device;
   Scratch m(c, B * l * N), cbuf(c, B * 2 * N), outd(c, to_dev ? 1 : (out_bytes + 7) / 8);
   {
     // the decrypted messages, their FP images and the slot values do not stay behind in pool memory the next call reuses
     Wipe w_m{c, m.d, sizeof(u64) * B * l * N}, w_c{c, cbuf.d, sizeof(double2) * B * N}, w_o{c, outd.d, out_bytes, to_dev};
-    EW_LAUNCH(k_decrypt_dot, dim3(N / 256, l, n), dim3(256), 0, c->stream, c->dev, tab, cts[0]->size, l, c->sh->sk.d, m.d);
-    OpPlain::Params ip{m.d, m.d, (size_t)l * N, (size_t)l * N, l, 0, 0, {}};
-    ntt_inverse<OpPlain>(c, ip, n * l);
+    decrypt_to_coeff(c, tab, cts[0]->size, l, n, m.d);
     double2 *cd = reinterpret_cast<double2 *>(cbuf.d);
     EW_LAUNCH(k_crt_to_double, dim3(N / 256, n), dim3(256), 0, c->stream, c->dev, t, l, m.d, 1.0 / cts[0]->scale, cd);
     HIPCHK(hipGetLastError());
@@ -890,6 +976,73 @@ static void encode_encrypt_dev(evah_ctx *c, bool symmetric, uint32_t batch, cons
   count_client_h2d(c, (symmetric ? 64 : 32) * B);
 }
 
+// ---- the refresh
+// the lift table of (l, L, t) on the device, built once per context family (freed with it)
+static LiftTab lift_tab_cached(evah_ctx *c, uint32_t l, uint32_t L, uint32_t t) {
+  const uint32_t key = l | L << 8 | t << 16;
+  auto it = c->sh->lift_tabs.find(key);
+  if (it == c->sh->lift_tabs.end()) {
+    const std::vector<u64> tab = lift_table_build(c->primes, l, L, t);
+    u64 *d = nullptr;
+    HIPCHK(hipMalloc(&d, sizeof(u64) * tab.size()));
+    try {
+      h2d_now(c, d, tab.data(), sizeof(u64) * tab.size());
+    } catch (...) {
+      (void)hipFree(d);
+      throw;
+    }
+    it = c->sh->lift_tabs.emplace(key, d).first;
+  }
+  const LiftLayout at{l, L};
+  const u64 *d = it->second;
+  // (Q_l mod 2^64 travels as an argument: wrapping products of the chain primes, as the builder forms them)
+  u64 qw = 1;
+  for (uint32_t i = 0; i < l; i++) qw *= c->primes[i];
+  return LiftTab{d + at.half(), d + at.wpre(), d + at.qmod(), d + at.inv2t(), d + at.premod(), qw};
+}
+template <int LB>
+static void launch_refresh_lift(evah_ctx *c, const CrtTab &g, const LiftTab &t, uint32_t l, uint32_t L, uint32_t sh, uint32_t n, const u64 *m,
+                                u64 *out) {
+  EW_LAUNCH(k_refresh_lift<LB>, dim3(c->N / 256, n), dim3(256), 0, c->stream, c->dev, g, t, l, L, sh, m, out);
+}
+// evah_refresh_handles: the n instances of the handles (one size, l limbs, scale 2^a) decrypted, their integer messages
+// divided by 2^sh and encrypted again at L limbs and scale_out into one handle [n][2][L][N].  The launches are those of
+// decrypt_decode up to the inverse transforms, k_refresh_lift, one forward transform of the n L rows, and the tail of
+// encrypt_symmetric: their number does not depend on n.  One drain of the queue, at the end.
+static evah_ct *refresh(evah_ctx *c, const evah_ct *const *cts, uint32_t n_handles, uint32_t n, uint32_t L, uint32_t sh, double scale_out,
+                        const uint8_t *ekeys, const uint8_t *seeds) {
+  const uint32_t l = cts[0]->limbs;
+  const size_t N = c->N, B = n;
+  const CrtTab g = crt_tab_cached(c, l);
+  const LiftTab t = lift_tab_cached(c, l, L, sh);
+  const DotTab tab = dot_tab_of(c, cts, n_handles);
+  Scratch m(c, B * l * N), mo(c, B * L * N);
+  evah_ct *o = nullptr;
+  try {
+    // the decrypted messages, at both levels, do not stay behind in pool memory the next call reuses
+    Wipe w_m{c, m.d, sizeof(u64) * B * l * N}, w_mo{c, mo.d, sizeof(u64) * B * L * N};
+    decrypt_to_coeff(c, tab, cts[0]->size, l, n, m.d);
+    if (l <= 2) launch_refresh_lift<2>(c, g, t, l, L, sh, n, m.d, mo.d);
+    else if (l <= 4) launch_refresh_lift<4>(c, g, t, l, L, sh, n, m.d, mo.d);
+    else if (l <= 8) launch_refresh_lift<8>(c, g, t, l, L, sh, n, m.d, mo.d);
+    else if (l <= 16) launch_refresh_lift<16>(c, g, t, l, L, sh, n, m.d, mo.d);
+    else launch_refresh_lift<62>(c, g, t, l, L, sh, n, m.d, mo.d);
+    HIPCHK(hipGetLastError());
+    w_m.now();
+    OpPlain::Params fp{mo.d, mo.d, (size_t)L * N, (size_t)L * N, L, 0, 0, {}};
+    ntt_forward<OpPlain>(c, fp, n * L);
+    o = encrypt_symmetric(c, n, L, scale_out, mo.d, nullptr, ekeys, seeds, false);
+    w_mo.now();
+    HIPCHK(hipStreamSynchronize(c->stream)); // `ekeys` and `seeds` are pageable host memory
+  } catch (...) {
+    (void)hipStreamSynchronize(c->stream);
+    if (o) evah_ct_free(c, o);
+    throw;
+  }
+  count_client_h2d(c, 64 * B);
+  return o;
+}
+
 } // namespace evah
 
 extern "C" {
@@ -1117,6 +1270,34 @@ int evah_decrypt_decode_rows(evah_ctx *c, const evah_ct *const *cts, uint32_t n_
   check_rows_shape(c, out, dtype_out, "unknown output dtype (EVAH_F64, EVAH_F32 or EVAH_U8)", n, n_out, row_pitch, out_on_device != 0, "out");
   const RowsDst rows{row_pitch, out_on_device != 0, wait != 0};
   decrypt_decode(c, cts, n_handles, n, n_out, dtype_out, out, &rows);
+  API_END
+}
+
+// ---- the refresh
+// the exponent of a scale 2^a, a an integer
+static int pow2_exponent(double scale) {
+  int e = 0;
+  if (!(scale > 0) || !std::isfinite(scale) || std::frexp(scale, &e) != 0.5)
+    throw std::invalid_argument("scale is not a power of two: refresh takes scales 2^a with a an integer");
+  return e - 1;
+}
+
+int evah_refresh_handles(evah_ctx *c, const evah_ct *const *cts, uint32_t n_handles, uint32_t limbs_out, double scale_out, const uint8_t *ekeys,
+                         const uint8_t *seeds, evah_ct **out) {
+  API_BEGIN
+  use(c);
+  if (c->dev.pstep > 1) throw std::invalid_argument("a limb shard holds no whole secret key");
+  const uint32_t n = handles_checks_list(c, cts, n_handles, out);
+  if (!ekeys || !seeds) throw std::invalid_argument("error polynomial and seed are required");
+  if (cts[0]->size < 1 || cts[0]->size > 3) throw std::invalid_argument("ciphertext size out of range");
+  if (cts[0]->limbs > 61) throw std::invalid_argument("too many limbs");
+  if (limbs_out < 1 || limbs_out > c->k - 1 || cts[0]->limbs < 1 || cts[0]->limbs > c->k - 1)
+    throw std::invalid_argument("invalid limb count for this context");
+  const int t = pow2_exponent(cts[0]->scale) - pow2_exponent(scale_out);
+  if (t < 0) throw std::invalid_argument("the target scale is above the value's: refresh divides, it does not multiply");
+  if (t > 62) throw std::invalid_argument("the scale ratio exceeds 2^62");
+  if (c->N % 256) throw std::invalid_argument("refresh needs N divisible by 256");
+  *out = refresh(c, cts, n_handles, n, limbs_out, (uint32_t)t, scale_out, ekeys, seeds);
   API_END
 }
 

@@ -123,6 +123,61 @@ inline std::vector<u64> root_power_table(uint32_t N, u64 q, u64 psi) {
   return rp;
 }
 
+// ---- the refresh's lift table: what turns the mixed-radix digits v_i of a decrypted coefficient
+// U = sum_i v_i q_0..q_{i-1} in [0, Q_l) into the residues of floor((M + 2^(t-1)) / 2^t) under the first L chain primes,
+// M = U or U - Q_l.  One array of words() words, the same for the device kernel and the host twin:
+//   half   [l]          mixed-radix digits of floor(Q_l / 2): comparing digits from the top is comparing the integers
+//   wpre   [l]          q_0..q_{i-1} mod 2^64 (wrapping)
+//   qmod   [L]          Q_l mod q_j (0 for j < l)
+//   inv2t  [L]          (2^t)^-1 mod q_j (every prime is odd)
+//   premod [L - l][l]   q_0..q_{i-1} mod q_j for the primes j >= l the value has no residue of (none when L <= l)
+//   qw     [1]          Q_l mod 2^64
+struct LiftLayout {
+  uint32_t l, L;
+  size_t half() const { return 0; }
+  size_t wpre() const { return l; }
+  size_t qmod() const { return 2 * (size_t)l; }
+  size_t inv2t() const { return 2 * (size_t)l + L; }
+  size_t premod() const { return 2 * (size_t)l + 2 * (size_t)L; }
+  size_t qw() const { return premod() + (size_t)(L > l ? L - l : 0) * l; }
+  size_t words() const { return qw() + 1; }
+};
+inline std::vector<u64> lift_table_build(const std::vector<u64> &primes, uint32_t l, uint32_t L, uint32_t t) {
+  const LiftLayout at{l, L};
+  std::vector<u64> tab(at.words(), 0);
+  std::vector<u64> w{1}; // Q_l, little-endian words
+  u64 wp = 1;
+  for (uint32_t i = 0; i < l; i++) {
+    tab[at.wpre() + i] = wp;
+    wp *= primes[i];
+    u64 carry = 0;
+    for (auto &x : w) { u128 p = (u128)x * primes[i] + carry; x = (u64)p; carry = (u64)(p >> 64); }
+    if (carry) w.push_back(carry);
+  }
+  tab[at.qw()] = wp;
+  for (size_t s = 0; s < w.size(); s++) w[s] = (w[s] >> 1) | (s + 1 < w.size() ? w[s + 1] << 63 : 0); // floor(Q_l / 2)
+  for (uint32_t i = 0; i < l; i++) { // its digits: the remainder of dividing by q_i, the quotient carried on
+    u64 rem = 0;
+    for (size_t s = w.size(); s-- > 0;) {
+      const u128 cur = ((u128)rem << 64) | w[s];
+      w[s] = (u64)(cur / primes[i]);
+      rem = (u64)(cur % primes[i]);
+    }
+    tab[at.half() + i] = rem;
+  }
+  for (uint32_t j = 0; j < L; j++) {
+    const u64 qj = primes[j];
+    u64 acc = 1 % qj;
+    for (uint32_t i = 0; i < l; i++) {
+      if (j >= l) tab[at.premod() + (size_t)(j - l) * l + i] = acc;
+      acc = mulmod(acc, primes[i] % qj, qj);
+    }
+    tab[at.qmod() + j] = acc;
+    tab[at.inv2t() + j] = invmod(powmod(2, t, qj), qj);
+  }
+  return tab;
+}
+
 // ---- complex roots of the CKKS encoder (FP64).  The encoder's bits depend on the exact doubles
 // used as roots, so they are produced the way SEAL 3.6's util::ComplexRoots produces them: the
 // first octant of the 2N-th roots from cos/sin(2*pi*i/2N), all others through the 8-fold

@@ -199,6 +199,7 @@ struct SharedDev {
   KeyDev pk, sk; // client side (client.hip): public key [2][k][N], secret key in NTT form [k][N]
   double2 *dec_roots = nullptr; // CKKS decoder: zeta^br(j) (forward special FFT, heap order)
   std::map<uint32_t, u64 *> crt_tabs; // decoder (client.hip): the Garner tables of a level, built at its first use
+  std::map<uint32_t, u64 *> lift_tabs; // refresh (client.hip): the lift table of (l, L, t), key l | L << 8 | t << 16
   std::map<uint32_t, KeyDev> galois;
   std::map<uint32_t, uint32_t *> perms;
   std::map<uint32_t, uint32_t *> perms_inv; // the inverse tables (hoisted rotation sets)
@@ -223,6 +224,7 @@ struct SharedDev {
     if (sk.d) { (void)hipMemset(sk.d, 0, sk.bytes); (void)hipFree(sk.d); } // key material does not stay behind in freed HBM
     if (dec_roots) (void)hipFree(dec_roots);
     for (auto &kv : crt_tabs) (void)hipFree(kv.second);
+    for (auto &kv : lift_tabs) (void)hipFree(kv.second);
     for (auto &kv : galois) {
       (void)hipFree(kv.second.d);
       if (kv.second.d_split) (void)hipFree(kv.second.d_split);

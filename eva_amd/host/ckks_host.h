@@ -827,4 +827,103 @@ inline std::vector<u64> decrypt_to_coeff(const HostContext &cx, const SecretKey 
   return m;
 }
 
+// The exponent a of a scale 2^a with a an integer; anything else is refused (the refresh's scales)
+inline int pow2_exponent(double scale) {
+  int e = 0;
+  if (!(scale > 0) || !std::isfinite(scale) || std::frexp(scale, &e) != 0.5)
+    throw std::invalid_argument("scale is not a power of two: refresh takes scales 2^a with a an integer");
+  return e - 1;
+}
+// the shift t = a - b of a refresh from scale 2^a to scale 2^b: 0 <= t <= 62
+inline uint32_t refresh_shift(double scale_in, double scale_out) {
+  const int t = pow2_exponent(scale_in) - pow2_exponent(scale_out);
+  if (t < 0) throw std::invalid_argument("the target scale is above the value's: refresh divides, it does not multiply");
+  if (t > 62) throw std::invalid_argument("the scale ratio exceeds 2^62");
+  return (uint32_t)t;
+}
+// Garner's constants of a level: inv_prefix[i] = (q_0..q_{i-1})^-1 mod q_i, pre_mod[i * l + j] = q_0..q_{j-1} mod q_i
+struct GarnerTab {
+  std::vector<u64> inv_prefix, pre_mod;
+  GarnerTab(const std::vector<u64> &primes, uint32_t l) : inv_prefix(l), pre_mod((size_t)l * l) {
+    for (uint32_t i = 0; i < l; i++) {
+      const u64 qi = primes[i];
+      u64 acc = 1 % qi;
+      for (uint32_t j = 0; j < i; j++) {
+        pre_mod[(size_t)i * l + j] = acc;
+        acc = evah::mulmod(acc, primes[j] % qi, qi);
+      }
+      inv_prefix[i] = evah::invmod(acc, qi);
+    }
+  }
+};
+// One coefficient of the refresh: residues r[i] (i < l) of U in [0, Q_l) -> out[j] (j < L), the residues
+// of floor((M + 2^(t-1)) / 2^t) with M = U for U <= floor(Q_l / 2), else U - Q_l (ties towards +infinity).  The steps, the
+// table (hostmath.h lift_table_build) and so the words are the device kernel's (client.hip k_refresh_lift).
+inline void refresh_lift_coeff(const std::vector<u64> &primes, const std::vector<u64> &tab, uint32_t l, uint32_t L, uint32_t t, const u64 *r,
+                               const GarnerTab &g, u64 *v, u64 *out) {
+  const evah::LiftLayout at{l, L};
+  for (uint32_t i = 0; i < l; i++) { // Garner: U = sum_i v_i q_0..q_{i-1}
+    const u64 qi = primes[i];
+    u64 acc = 0;
+    for (uint32_t j = 0; j < i; j++) acc = evah::addmod(acc, evah::mulmod(v[j] % qi, g.pre_mod[(size_t)i * l + j], qi), qi);
+    v[i] = i ? evah::mulmod(evah::submod(r[i], acc, qi), g.inv_prefix[i], qi) : r[0];
+  }
+  bool neg = false;
+  for (uint32_t i = l; i-- > 0;)
+    if (v[i] != tab[at.half() + i]) { neg = v[i] > tab[at.half() + i]; break; }
+  u64 w = 0;
+  for (uint32_t i = 0; i < l; i++) w += v[i] * tab[at.wpre() + i];
+  if (neg) w -= tab[at.qw()];
+  const u64 hb = t ? (u64)1 << (t - 1) : 0, rho = t ? (w + hb) & (((u64)1 << t) - 1) : 0;
+  const int64_t d = (int64_t)hb - (int64_t)rho; // |d| <= 2^61
+  for (uint32_t j = 0; j < L; j++) {
+    const u64 qj = primes[j];
+    u64 m;
+    if (j < l) {
+      m = r[j];
+    } else {
+      m = 0;
+      for (uint32_t i = 0; i < l; i++) m = evah::addmod(m, evah::mulmod(v[i] % qj, tab[at.premod() + (size_t)(j - l) * l + i], qj), qj);
+    }
+    if (neg) m = evah::submod(m, tab[at.qmod() + j], qj);
+    if (t) {
+      const u64 dm = d < 0 ? evah::negmod((u64)(-d) % qj, qj) : (u64)d % qj;
+      m = evah::mulmod(evah::addmod(m, dm, qj), tab[at.inv2t() + j], qj);
+    }
+    out[j] = m;
+  }
+}
+// The refresh on the host: decrypt ct (size 2 or 3, l limbs, scale 2^a), divide the integer message by
+// 2^t with the rule above, and encrypt it again under sk at L limbs and scale 2^(a - t): error = sampled_small(ek, 1), c1
+// from `seed`.  No decode, no floating point.  Word for word what evah_refresh_handles gives.
+inline HostCipher refresh_host(const HostContext &cx, const SecretKey &sk, const HostCipher &ct, uint32_t L, uint32_t t,
+                               const std::array<uint8_t, 32> &ek, const std::array<uint8_t, 32> &seed) {
+  const uint32_t N = cx.N, l = ct.limbs;
+  if (ct.size < 1 || ct.size > 3) throw std::invalid_argument("ciphertext size out of range");
+  if (l < 1 || l > cx.k - 1 || L < 1 || L > cx.k - 1) throw std::invalid_argument("invalid limb count for this context");
+  if (t > 62) throw std::invalid_argument("the scale ratio exceeds 2^62");
+  if (ct.data.size() != (size_t)ct.size * l * N) throw std::invalid_argument("ciphertext words do not match its shape");
+  std::vector<u64> m = decrypt_to_coeff(cx, sk, ct);
+  const std::vector<u64> tab = evah::lift_table_build(cx.primes, l, L, t);
+  const GarnerTab g(cx.primes, l);
+  HostPlain pt;
+  pt.limbs = L;
+  pt.scale = std::ldexp(ct.scale, -(int)t);
+  pt.data.resize((size_t)L * N);
+  std::vector<u64> r(l), v(l), o(L);
+  for (uint32_t n = 0; n < N; n++) {
+    for (uint32_t i = 0; i < l; i++) r[i] = m[(size_t)i * N + n];
+    refresh_lift_coeff(cx.primes, tab, l, L, t, r.data(), g, v.data(), o.data());
+    for (uint32_t j = 0; j < L; j++) pt.data[(size_t)j * N + n] = o[j];
+  }
+  for (uint32_t j = 0; j < L; j++) cx.ntt(j, pt.data.data() + (size_t)j * N);
+  std::vector<int8_t> e(N);
+  sampled_small(ek.data(), 1, N, e.data());
+  HostCipher out = encrypt_symmetric(cx, sk, pt, e, seed);
+  wipe(e);
+  wipe_bytes(m.data(), m.size() * sizeof(u64));
+  wipe_bytes(pt.data.data(), pt.data.size() * sizeof(u64));
+  return out;
+}
+
 } // namespace evahost

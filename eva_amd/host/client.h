@@ -260,9 +260,9 @@ inline ArrayInputs plan_array_inputs(const HostContext &hc, std::map<std::string
   }
   return in;
 }
-inline void require_array_path(bool on_device, bool resident) {
-  if (!on_device) throw std::runtime_error("encrypt_array needs a HIP device: none is visible, or EVA_DEVICE_CLIENT=0 keeps the client on the host");
-  if (!resident) throw std::runtime_error("encrypt_array needs resident valuations: resident = False (EVA_RESIDENT=0) keeps them on the host");
+inline void require_array_path(bool on_device, bool resident, const std::string &call = "encrypt_array") {
+  if (!on_device) throw std::runtime_error(call + " needs a HIP device: none is visible, or EVA_DEVICE_CLIENT=0 keeps the client on the host");
+  if (!resident) throw std::runtime_error(call + " needs resident valuations: resident = False (EVA_RESIDENT=0) keeps them on the host");
 }
 inline std::vector<uint8_t> keys_flat(const std::array<uint8_t, 32> *keys, size_t n) {
   std::vector<uint8_t> flat(n * 32);
@@ -939,6 +939,150 @@ public:
         std::fill(flat.begin(), flat.end(), 0.0);
         i0 = i1;
       }
+    }
+    return out;
+  }
+
+  // ---- the refresh: decrypt, divide by a power of two and encrypt again under this key pair, without
+  // decoding, so that a result becomes a valid input of the program `sig` belongs to — at that input's level and scale.
+  // For every encrypted input `name` of sig the source is the value (rename[name], else name) of the valuation; the
+  // consumer's unencrypted inputs are encoded as encrypt() encodes them.  Randomness: encrypt_batch(..., device_sampling =
+  // true)'s contract — one pair of streams per call, instances in order, names sorted within an instance, 4 seed words and
+  // a 4-word error key per encrypted input, all drawn before the first device call, the keys wiped afterwards.
+  struct RefreshInput {
+    std::string name, source;
+    InputClass cls;
+  };
+  std::vector<RefreshInput> refresh_plan(const CKKSSignature &sig, const std::map<std::string, std::string> &rename) const {
+    check_vec_size(sig, host->N / 2);
+    std::vector<RefreshInput> plan;
+    for (auto &kv : sig.inputs)
+      if (kv.second.input_type == Type::Cipher) {
+        auto r = rename.find(kv.first);
+        plan.push_back(RefreshInput{kv.first, r == rename.end() ? kv.first : r->second, classify_input(*host, sig, kv.first)});
+      }
+    std::sort(plan.begin(), plan.end(), [](const RefreshInput &a, const RefreshInput &b) { return a.name < b.name; });
+    return plan;
+  }
+  void refresh_unencrypted(const Valuation &inputs, const CKKSSignature &sig, std::unordered_map<std::string, SchemeValue> &out) const {
+    for (auto &kv : inputs) {
+      check_input_size(kv.second, sig);
+      if (!unencrypted_value(*host, classify_input(*host, sig, kv.first), kv.second, out[kv.first]))
+        throw std::invalid_argument("refresh: input " + kv.first + " is encrypted: its value comes from the valuation, not from inputs");
+    }
+  }
+  struct WipeKeyRows {
+    std::vector<std::vector<std::array<uint8_t, 32>>> &k;
+    ~WipeKeyRows() { for (auto &n : k) for (auto &x : n) wipe_bytes(x.data(), 32); }
+  };
+  // one value: on the device when one is present (a value resident on this key pair's state is read in place, any other
+  // uploaded first, as decrypt_value does), else the host twin — the same words
+  HostCipher refresh_value(const std::string &name, const HostCipher &c, uint32_t limbs, double scale, uint32_t shift,
+                           const std::array<uint8_t, 32> &ek, const std::array<uint8_t, 32> &sd) {
+    if (on_device()) {
+      check_device_shape(name, c);
+      CtHandle uploaded;
+      const evah_ct *h = nullptr;
+      if (c.dev && c.dev->root == dev) {
+        h = c.dev->h->h;
+      } else {
+        evah_ct *up = nullptr;
+        chk(evah_ct_upload(dev->h, c.size, c.limbs, c.scale, (const uint64_t *)words(c).data(), &up));
+        uploaded = CtHandle(dev->h, up);
+        h = up;
+      }
+      evah_ct *o = nullptr;
+      chk(evah_refresh_handles(dev->h, &h, 1, limbs, scale, ek.data(), sd.data(), &o));
+      return cipher_of_handle(dev, *host, o, limbs, scale, resident, &sd);
+    }
+    if (c.size < 1 || c.size > 3 || c.limbs < 1 || c.limbs > host->k - 1 || words(c).size() != (size_t)c.size * c.limbs * host->N)
+      throw std::runtime_error("output " + name + ": ciphertext shape does not match its data or the encryption parameters");
+    return refresh_host(*host, sk, c, limbs, shift, ek, sd);
+  }
+  HipValuation refresh(const HipValuation &enc, const CKKSSignature &sig, const std::map<std::string, std::string> &rename = {},
+                       const Valuation &inputs = {}, uint64_t seed = 0) {
+    const std::vector<RefreshInput> plan = refresh_plan(sig, rename);
+    HipValuation out;
+    out.params = host;
+    refresh_unencrypted(inputs, sig, out.values);
+    std::vector<const HostCipher *> src(plan.size());
+    std::vector<uint32_t> shift(plan.size());
+    for (size_t i = 0; i < plan.size(); i++) {
+      auto it = enc.values.find(plan[i].source);
+      if (it == enc.values.end()) throw std::out_of_range("refresh: no value named " + plan[i].source + " in the valuation (input " + plan[i].name + ")");
+      src[i] = std::get_if<HostCipher>(&it->second);
+      if (!src[i]) throw std::invalid_argument("refresh: value " + plan[i].source + " is not a ciphertext");
+      shift[i] = refresh_shift(src[i]->scale, plan[i].cls.scale);
+    }
+    std::unique_ptr<SecureRng> seeds = seed ? std::make_unique<SecureRng>(seed, 4) : std::make_unique<SecureRng>();
+    std::unique_ptr<SecureRng> errors = seed ? std::make_unique<SecureRng>(seed, 3) : std::make_unique<SecureRng>();
+    std::vector<std::array<uint8_t, 32>> sd(plan.size());
+    std::vector<std::vector<std::array<uint8_t, 32>>> ek(1);
+    WipeKeyRows wipe_keys{ek};
+    for (size_t i = 0; i < plan.size(); i++) {
+      sd[i] = draw_key32(*seeds);
+      ek[0].push_back(draw_key32(*errors));
+    }
+    for (size_t i = 0; i < plan.size(); i++)
+      out.values[plan[i].name] = refresh_value(plan[i].source, *src[i], plan[i].cls.limbs, plan[i].cls.scale, shift[i], ek[0][i], sd[i]);
+    return out;
+  }
+  // the same for a batch of batched handles: per name, consecutive segments of one shape are packed into calls of <= 64
+  // instances of evah_refresh_handles, as decrypt_array packs them; the results stay whole batched handles with their seeds.
+  // Needs the device and resident valuations; the batch lives on this key pair's device state.
+  HipValuationBatch refresh_batch(const HipValuationBatch &vb, const CKKSSignature &sig, const std::map<std::string, std::string> &rename = {},
+                                  const Valuation &inputs = {}, uint64_t seed = 0) {
+    require_array_path(on_device(), resident, "refresh");
+    if (vb.root != dev) throw std::runtime_error("refresh: the batch lives on the device state of another key pair");
+    const std::vector<RefreshInput> plan = refresh_plan(sig, rename);
+    HipValuationBatch out;
+    out.B = vb.B;
+    out.params = host;
+    out.root = dev;
+    refresh_unencrypted(inputs, sig, out.shared);
+    std::vector<const BatchCipher *> src(plan.size());
+    for (size_t i = 0; i < plan.size(); i++) {
+      auto it = vb.ciphers.find(plan[i].source);
+      if (it == vb.ciphers.end())
+        throw std::out_of_range("refresh: no encrypted value named " + plan[i].source + " in the batch (input " + plan[i].name + ")");
+      src[i] = &it->second;
+    }
+    std::unique_ptr<SecureRng> seeds = seed ? std::make_unique<SecureRng>(seed, 4) : std::make_unique<SecureRng>();
+    std::unique_ptr<SecureRng> errors = seed ? std::make_unique<SecureRng>(seed, 3) : std::make_unique<SecureRng>();
+    std::vector<std::vector<std::array<uint8_t, 32>>> ek(plan.size()); // per name, per instance
+    WipeKeyRows wipe_keys{ek};
+    for (size_t b = 0; b < out.B; b++)
+      for (size_t i = 0; i < plan.size(); i++) {
+        out.ciphers[plan[i].name].seeds.push_back(draw_key32(*seeds));
+        ek[i].push_back(draw_key32(*errors));
+      }
+    for (size_t i = 0; i < plan.size(); i++) {
+      const auto &segs = src[i]->segments;
+      const InputClass &cls = plan[i].cls;
+      BatchCipher &bc = out.ciphers[plan[i].name];
+      size_t row = 0;
+      for (size_t s0 = 0; s0 < segs.size();) {
+        std::vector<const evah_ct *> hs;
+        size_t n = 0, s1 = s0;
+        while (s1 < segs.size() && n + segs[s1].n <= CLIENT_BATCH_MAX && segs[s1].size == segs[s0].size && segs[s1].limbs == segs[s0].limbs &&
+               segs[s1].scale == segs[s0].scale) {
+          hs.push_back(segs[s1].h->h);
+          n += segs[s1++].n;
+        }
+        if (s1 == s0) throw std::runtime_error("value " + plan[i].source + ": a segment holds more than 64 instances");
+        if (row + n > out.B) throw std::runtime_error("value " + plan[i].source + ": the segments hold more instances than the batch");
+        (void)refresh_shift(segs[s0].scale, cls.scale); // the scale rules, with the host's messages, before anything is launched
+        std::vector<uint8_t> ekeys = keys_flat(ek[i].data() + row, n);
+        const std::vector<uint8_t> sd = keys_flat(bc.seeds.data() + row, n);
+        evah_ct *c = nullptr;
+        const int rc = evah_refresh_handles(dev->h, hs.data(), (uint32_t)hs.size(), cls.limbs, cls.scale, ekeys.data(), sd.data(), &c);
+        wipe_bytes(ekeys.data(), ekeys.size());
+        chk(rc);
+        bc.segments.push_back(BatchSegment{std::make_shared<CtHandle>(dev->h, c), (uint32_t)n, nullptr, 2, cls.limbs, cls.scale});
+        row += n;
+        s0 = s1;
+      }
+      if (row != vb.B) throw std::runtime_error("value " + plan[i].source + ": the segments do not hold every instance");
     }
     return out;
   }

@@ -283,11 +283,21 @@ PYBIND11_MODULE(_eva, m) {
       .def_readwrite("prime_bits", &CKKSParameters::prime_bits)
       .def_readwrite("rotations", &CKKSParameters::rotations)
       .def_readwrite("poly_modulus_degree", &CKKSParameters::poly_modulus_degree);
+  // (both can be made by hand: a refresh may target any level and scale of the chain, not only what a compiled program
+  // on this machine asks for)
   py::class_<CKKSEncodingInfo>(mckks, "CKKSEncodingInfo")
+      .def(py::init([](Type t, int scale, int level) { return CKKSEncodingInfo{t, scale, level}; }), py::arg("input_type"), py::arg("scale"),
+           py::arg("level"))
       .def_readonly("input_type", &CKKSEncodingInfo::input_type)
       .def_readonly("scale", &CKKSEncodingInfo::scale)
       .def_readonly("level", &CKKSEncodingInfo::level);
   py::class_<CKKSSignature>(mckks, "CKKSSignature")
+      .def(py::init([](int vec_size, std::unordered_map<std::string, CKKSEncodingInfo> inputs) {
+             CKKSSignature s;
+             s.vec_size = vec_size;
+             s.inputs = std::move(inputs);
+             return s;
+           }), py::arg("vec_size"), py::arg("inputs"))
       .def_readonly("vec_size", &CKKSSignature::vec_size)
       .def_readonly("inputs", &CKKSSignature::inputs);
 
@@ -707,6 +717,18 @@ PYBIND11_MODULE(_eva, m) {
         if (!s.on_device()) throw std::runtime_error("decrypt_array needs a HIP device: none is visible, or EVA_DEVICE_CLIENT=0 keeps the client on the host");
         return std::make_shared<DeviceArray>(s.dev, dt.itemsize() == 8 ? EVAH_F64 : dt.itemsize() == 4 ? EVAH_F32 : EVAH_U8, B, n);
       }, py::arg("B"), py::arg("n"), py::arg("dtype"))
+      .def("refresh", [](HipSecret &s, py::object enc, const CKKSSignature &sig, py::object rename, py::object inputs, uint64_t seed) -> py::object {
+        const auto rn = rename.is_none() ? std::map<std::string, std::string>{} : rename.cast<std::map<std::string, std::string>>();
+        const Valuation in = inputs.is_none() ? Valuation{} : inputs.cast<Valuation>();
+        if (py::isinstance<HipValuationBatch>(enc)) return py::cast(s.refresh_batch(enc.cast<const HipValuationBatch &>(), sig, rn, in, seed));
+        return py::cast(s.refresh(enc.cast<const HipValuation &>(), sig, rn, in, seed));
+      }, py::arg("enc"), py::arg("signature"), py::arg("rename") = py::none(), py::arg("inputs") = py::none(), py::arg("seed") = 0,
+           "Refresh (DESIGN.md 1.12): decrypt, divide by a power of two and encrypt again under this key pair, without decoding. enc: a "
+           "SEALValuation or a SEALValuationBatch (the same kind comes back); signature: that of the program that will consume the result — "
+           "every encrypted input `name` of it is made from enc[(rename or {}).get(name, name)] at the input's level and scale 2^b. The "
+           "integer message M becomes floor((M + 2^(t-1)) / 2^t) with 2^t the ratio of the scales (0 <= t <= 62; ties towards +infinity). "
+           "inputs: the consumer's unencrypted inputs. Randomness as encrypt_batch(..., device_sampling=True); seed != 0 is the reproducible "
+           "test hook and not secret-grade. Every result is seeded (c0 + the 32-byte seed of c1)")
       .def("decrypt", &HipSecret::decrypt, py::arg("enc_outputs"), py::arg("signature"))
       .def("decrypt_batch", &HipSecret::decrypt_batch, py::arg("enc_outputs"), py::arg("signature"),
            "decrypt() of every valuation of a list, bit for bit; on the device up to 64 outputs of one name are decrypted and decoded in one call")

@@ -512,6 +512,25 @@ int evah_encode_encrypt_symmetric_array_dev(evah_ctx *ctx, uint32_t batch, const
 int evah_decrypt_decode_rows(evah_ctx *ctx, const evah_ct *const *cts, uint32_t n_handles, uint32_t n_out, int dtype_out, void *out,
                              size_t row_pitch, int out_on_device, int wait);
 
+/* ---- the refresh ---------------------------------------------------------------------------------
+ * Decrypt, divide by a power of two and encrypt again under the same secret key, without decoding: the interactive
+ * substitute for bootstrapping.  cts: what evah_decrypt_decode_handles takes (single and batched handles, views, slices,
+ * mod-switched views, read in place), at most 64 instances of one size (1..3), limb count l and scale 2^a together.
+ * Per coefficient the decrypted integer M in (-Q_l / 2, Q_l / 2] becomes M' = floor((M + 2^(t-1)) / 2^t) (t = 0: M), with
+ * 2^t = scale / scale_out, 0 <= t <= 62: ties go towards +infinity.  M' is reduced under the first limbs_out chain
+ * primes (limbs_out below, at or above l) and encrypted as evah_encode_encrypt_symmetric_sampled_many encrypts its
+ * plaintexts: error drawn on the device from ekeys [n][32] (secret), c1 expanded from seeds [n][32] (public).
+ * out: ONE batched handle [n][2][limbs_out][N] at scale_out, instances in list order, then instance order.  Exact integer
+ * arithmetic throughout: every word follows from (cts, the secret key, limbs_out, t, ekeys, seeds).
+ * Refusals: a capturing context, a limb shard, null pointers, "secret key not present", mismatches in the list by
+ * argument index, more than 64 instances, a size outside 1..3, "invalid limb count for this context", a scale that is
+ * not 2^a with a an integer, a target scale above the value's (t < 0), t > 62, N not divisible by 256.  One host -> device
+ * copy of the keys (and one of the seeds above 8 instances), no device -> host copy, one drain of the queue;
+ * evah_ctx_transfer_stats out[4] grows by 64 n.  The decrypted messages, the error keys and NTT(e) are zeroed on the
+ * queue before their memory returns to the pool, also when the call fails. */
+int evah_refresh_handles(evah_ctx *ctx, const evah_ct *const *cts, uint32_t n_handles, uint32_t limbs_out, double scale_out,
+                         const uint8_t *ekeys, const uint8_t *seeds, evah_ct **out);
+
 /* ---- whole-DAG submit: a topologically sorted flat op list over a value table.
  * One call replaces the per-node loop ProgramTraversal::forwardPass + SEALExecutor::operator()
  * (program_traversal.h:36-93, seal_executor.h:279-404) for the encrypted part of a program.
