@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libeva_hip.so")
 
 KEY_RELIN = 0
 KEY_GALOIS = 1
+KEY_REKEY = 4  # a re-key key to the context's key pair, by slot
 # value types of the array calls (include/eva_hip.h EVAH_F64 / EVAH_F32 / EVAH_U8)
 F64, F32, U8 = 0, 1, 2
 _DTYPES = {np.dtype(np.float64): F64, np.dtype(np.float32): F32, np.dtype(np.uint8): U8}
@@ -168,6 +169,9 @@ _SIGS = {
                         C.POINTER(C.c_uint8), C.c_int, _u64p],
     "evah_keygen_public": [_vp, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_int, _u64p],
     "evah_key_download_c0": [_vp, C.c_int, C.c_uint32, C.c_uint32, _u64p],
+    # re-key to another key pair
+    "evah_keygen_rekey": [_vp, _u64p, C.c_uint32, C.POINTER(C.c_uint8), _u64p],
+    "evah_rekey_many": [_vp, C.c_uint32, _vpp, C.c_uint32, _vpp],
     # limb-sharded execution
     "evah_ctx_set_shard": [_vp, C.c_uint32, C.c_uint32],
     "evah_ctx_shard_info": [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
@@ -924,6 +928,31 @@ class Context:
         pk = np.empty((2, self.k, self.N), dtype=np.uint64)
         _chk(_lib.evah_keygen_public(self.h, _keys32([ekey], 1), _keys32([seed], 1), int(bool(install)), _p(pk)))
         return pk
+
+    def keygen_rekey(self, pk_target, rkeys):
+        """evah_keygen_rekey: the re-key key [digits][2][k][N] from the uploaded secret key to the key pair
+        whose public key is pk_target [2][k][N]; rkeys [digits][32] uint8, digit J's (u, e0, e1) = sampled_small(rkeys[J], 0..2)"""
+        pk_target = np.ascontiguousarray(pk_target, dtype=np.uint64)
+        rkeys = np.ascontiguousarray(rkeys, dtype=np.uint8)
+        assert pk_target.shape == (2, self.k, self.N) and rkeys.ndim == 2 and rkeys.shape[1] == 32
+        out = np.empty((rkeys.shape[0], 2, self.k, self.N), dtype=np.uint64)
+        _chk(_lib.evah_keygen_rekey(self.h, _p(pk_target), rkeys.shape[0], rkeys.ctypes.data_as(C.POINTER(C.c_uint8)), _p(out)))
+        return out
+
+    def upload_rekey_key(self, slot, key):
+        """evah_key_upload(KEY_REKEY): a re-key key TO this context's key pair, kept under `slot` (any uint32)"""
+        key = np.ascontiguousarray(key, dtype=np.uint64)
+        assert key.shape[1:] == (2, self.k, self.N)
+        _chk(_lib.evah_key_upload(self.h, KEY_REKEY, int(slot), key.shape[0], _p(key)))
+
+    def rekey_many(self, slot, cts):
+        """evah_rekey_many: the handles (single, batched, views; also another context's on this GPU) re-keyed to this
+        context's key pair with the key of `slot`; one result per handle, with as many instances"""
+        n = len(cts)
+        ins = (C.c_void_p * max(n, 1))(*[ct.h for ct in cts])
+        outs = (C.c_void_p * max(n, 1))()
+        _chk(_lib.evah_rekey_many(self.h, C.c_uint32(int(slot)), ins, n, outs))
+        return [Ciphertext(self, C.c_void_p(outs[i])) for i in range(n)]
 
     def key_download_c0(self, kind, elt=0, digits=None):
         """evah_key_download_c0: c0 [digits][k][N] of an installed key"""

@@ -201,6 +201,7 @@ struct SharedDev {
   std::map<uint32_t, u64 *> crt_tabs; // decoder (client.hip): the Garner tables of a level, built at its first use
   std::map<uint32_t, u64 *> lift_tabs; // refresh (client.hip): the lift table of (l, L, t), key l | L << 8 | t << 16
   std::map<uint32_t, KeyDev> galois;
+  std::map<uint32_t, KeyDev> rekey; // re-key keys to this state's key pair, by slot
   std::map<uint32_t, uint32_t *> perms;
   std::map<uint32_t, uint32_t *> perms_inv; // the inverse tables (hoisted rotation sets)
   // hoisted rotations (rotation_sets.hip.h): NTT of the sign pattern of a Galois element under every prime
@@ -229,6 +230,10 @@ struct SharedDev {
       (void)hipFree(kv.second.d);
       if (kv.second.d_split) (void)hipFree(kv.second.d_split);
       if (kv.second.d_perm) (void)hipFree(kv.second.d_perm);
+    }
+    for (auto &kv : rekey) {
+      (void)hipFree(kv.second.d);
+      if (kv.second.d_split) (void)hipFree(kv.second.d_split);
     }
     for (auto &kv : perms) (void)hipFree(kv.second);
     for (auto &kv : perms_inv) (void)hipFree(kv.second);

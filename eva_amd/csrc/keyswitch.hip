@@ -691,6 +691,77 @@ int evah_relinearize_many(evah_ctx *c, const evah_ct *const *cts, uint32_t n, ev
   API_END
 }
 
+// Re-key: every instance of the handles through the key switch with the re-key key of `slot`, c1 the
+// target and c0 the polynomial added to K = 0 — evah_rotate's call without the permutation.  The instances are read where
+// they are, through the pointer tables (handles of another device state on this GPU behind acquire()), KS_BATCH_MAX per
+// launch set; the results share one buffer, handle i viewing as many instances as cts[i] holds.
+int evah_rekey_many(evah_ctx *c, uint32_t slot, const evah_ct *const *cts, uint32_t n_handles, evah_ct **outs) {
+  API_BEGIN
+  use(c);
+  if (c->capturing) throw std::logic_error("re-key cannot be captured into a graph");
+  if (c->dev.pstep > 1) throw std::invalid_argument("re-key is not available on a limb shard");
+  if (!cts || !outs) throw std::invalid_argument("ciphertext list pointer is null");
+  if (n_handles < 1) throw std::invalid_argument("re-key needs at least one ciphertext");
+  auto kit = c->sh->rekey.find(slot);
+  if (kit == c->sh->rekey.end()) throw std::invalid_argument("re-key key not present");
+  const KeyDev *key = &kit->second;
+  size_t total = 0;
+  for (uint32_t i = 0; i < n_handles; i++) {
+    const evah_ct *a = cts[i];
+    if (!a) throw std::invalid_argument("ciphertext pointer is null");
+    if (a->size != 2) throw std::invalid_argument("re-key expects a size-2 ciphertext (relinearize first)");
+    if (a->limbs != cts[0]->limbs) throw std::invalid_argument("encrypted parameter mismatch in batch");
+    const evah_ctx *owner = a->buf->owner;
+    if (owner != c && ctx_alive(owner)) { // a value of another context: the same GPU and the same parameters
+      if (owner->device != c->device) throw std::invalid_argument("the ciphertext lives on another GPU (copy it first: evah_ct_copy)");
+      if (owner->N != c->N || owner->primes != c->primes) throw std::invalid_argument("the ciphertext's parameters differ from this context's");
+    }
+    total += a->batch;
+  }
+  const uint32_t l = cts[0]->limbs;
+  if (l < 1 || l > c->k - 1) throw std::invalid_argument("invalid limb count for this context");
+  for (uint32_t i = 0; i < n_handles; i++) acquire(c, cts[i]->buf);
+  const size_t pps = (size_t)l * c->N;
+  FreshBuf ob(c, total * 2 * pps);
+  // (handle, instance) pairs in list order, a chunk at a time
+  uint32_t h = 0, b = 0;
+  for (size_t i0 = 0; i0 < total; i0 += KS_BATCH_MAX) {
+    const uint32_t n = (uint32_t)std::min<size_t>(KS_BATCH_MAX, total - i0);
+    PtrTab c1{}, c0{};
+    for (uint32_t x = 0; x < n; x++) {
+      const evah_ct *a = cts[h];
+      const u64 *inst = a->d + (size_t)b * 2 * a->ps;
+      c0.p[2 * x] = inst; // nothing is added to K = 1
+      c1.p[x] = inst + a->ps;
+      if (++b == a->batch) b = 0, h++;
+    }
+    std::vector<const KeyDev *> keys(n, key);
+    KsCall q;
+    q.targets = c1, q.keys = keys.data(), q.n = n;
+    q.fold = ks_caps(c).fold; // P * c0 joins the inner product of K = 0 (KS_FOLDADD); otherwise the combine pass adds c0
+    q.adds = q.fold ? &c0 : nullptr;
+    OpModDown::Params mp = md_combine(nullptr, 0, 0, ob.d() + i0 * 2 * pps, pps);
+    mp.use_add_tab = !q.fold;
+    mp.add_tab = c0;
+    switch_key_mod_down(c, l, q, mp);
+  }
+  // (ct_views with a batch per handle)
+  size_t at = 0;
+  for (uint32_t i = 0; i < n_handles; i++) {
+    evah_ct *t = new evah_ct;
+    t->buf = ob.b;
+    t->d = ob.b->d + at * 2 * pps;
+    t->size = 2, t->limbs = l, t->ps = pps;
+    t->scale = cts[i]->scale;
+    t->batch = cts[i]->batch;
+    outs[i] = t;
+    at += cts[i]->batch;
+  }
+  ob.b->refs = (int)n_handles;
+  ob.b = nullptr;
+  API_END
+}
+
 // a batched handle is batch * size polynomials at stride ps (more than a PtrTab holds: evah_rescale_many's tables do not apply)
 int evah_rescale(evah_ctx *c, const evah_ct *a, uint32_t divisor_bits, evah_ct **out) {
   API_BEGIN

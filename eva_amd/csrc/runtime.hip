@@ -370,6 +370,13 @@ void key_install(evah_ctx *c, int kind, uint32_t galois_elt, const KeyDev &kd) {
         ++hc;
       }
     }
+  } else if (kind == EVAH_KEY_REKEY) { // galois_elt names a slot: any value
+    auto it = c->sh->rekey.find(galois_elt);
+    if (it != c->sh->rekey.end()) {
+      (void)hipFree(it->second.d);
+      if (it->second.d_split) (void)hipFree(it->second.d_split);
+    }
+    c->sh->rekey[galois_elt] = kd;
   } else {
     (void)hipFree(kd.d);
     if (kd.d_split) (void)hipFree(kd.d_split);
@@ -424,6 +431,9 @@ int evah_test_key_words(evah_ctx *c, int kind, uint32_t galois_elt, int which, u
   } else if (kind == EVAH_KEY_GALOIS) {
     auto it = c->sh->galois.find(galois_elt);
     if (it != c->sh->galois.end()) kd = &it->second;
+  } else if (kind == EVAH_KEY_REKEY) {
+    auto it = c->sh->rekey.find(galois_elt);
+    if (it != c->sh->rekey.end()) kd = &it->second;
   } else {
     throw std::invalid_argument("unknown key kind");
   }
@@ -742,6 +752,7 @@ int evah_ctx_key_bytes(evah_ctx *c, uint64_t *bytes) {
   API_BEGIN
   uint64_t b = c->sh->relin.d ? c->sh->relin.bytes : 0;
   for (auto &kv : c->sh->galois) b += kv.second.bytes;
+  for (auto &kv : c->sh->rekey) b += kv.second.bytes;
   *bytes = b;
   API_END
 }
@@ -775,6 +786,7 @@ int evah_ctx_key_bytes_detail(evah_ctx *c, uint64_t out[3]) {
   };
   count(c->sh->relin);
   for (auto &kv : c->sh->galois) count(kv.second);
+  for (auto &kv : c->sh->rekey) count(kv.second);
   API_END
 }
 

@@ -6,7 +6,8 @@
 // evah_keygen_switch makes the whole key here: c0 as well, from the resident secret key and N int8 error
 // draws per digit.  evah_keygen_set makes a whole set of them, and evah_keygen_public the public key, from
 // 32-byte randomness keys the device expands itself — one k_keygen_set launch for the set —, and evah_key_download_c0
-// hands c0 of such a key to the host when it is first needed there.
+// hands c0 of such a key to the host when it is first needed there.  evah_keygen_rekey makes the key
+// that takes ciphertexts to ANOTHER key pair, from that pair's public key: one k_keygen_rekey launch.
 
 #include "launch.hip.h"
 #include "seeded.hip.h"
@@ -210,6 +211,35 @@ static void keygen_chunk(evah_ctx *c, const KeySetEntry *tab, uint32_t n, uint32
   w_en.now();
 }
 
+// The re-key key to another key pair from that pair's public key: digit J, prime row i is the public-key
+// zero encryption k_encrypt_zero forms — pk_K u_J + e_K,J — with [i == J] (P mod q_J) s_i added to K = 0, both polynomials
+// from one read of u.  small: the NTT forms [digit][3][k][N] of (u, e0, e1); pk [2][k][N]; sk [k][N]; d [digit][2][k][N].
+// One thread per two coefficients, 16-byte accesses; the i == J branch is uniform over the block.
+// grid = (ceil(N / 2 / 256), k, n_digits)
+__global__ void __launch_bounds__(256)
+k_keygen_rekey(DevCtx cx, const u64 *__restrict__ pk, const u64 *__restrict__ small, const u64 *__restrict__ sk, u64 *__restrict__ d) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y, J = blockIdx.z;
+  if (2 * t >= cx.N || i >= cx.k) return;
+  const DevPrime pm = cx.primes[i];
+  const size_t poly = (size_t)cx.k * cx.N, row = (size_t)i * cx.N + 2 * (size_t)t;
+  const u64 *sm = small + (size_t)J * 3 * poly + row;
+  const ulonglong2 u = ld2(sm), e0 = ld2(sm + poly), e1 = ld2(sm + 2 * poly), p0 = ld2(pk + row), p1 = ld2(pk + poly + row);
+  ulonglong2 b0, b1;
+  b0.x = addmod(mulmod(p0.x, u.x, pm), e0.x, pm.q);
+  b0.y = addmod(mulmod(p0.y, u.y, pm), e0.y, pm.q);
+  b1.x = addmod(mulmod(p1.x, u.x, pm), e1.x, pm.q);
+  b1.y = addmod(mulmod(p1.y, u.y, pm), e1.y, pm.q);
+  if (i == J) {
+    const u64 pmod = cx.modq[(size_t)(cx.k - 1) * cx.k + J].x; // P mod q_J
+    const ulonglong2 s = ld2(sk + row);
+    b0.x = addmod(b0.x, mulmod(s.x, pmod, pm), pm.q);
+    b0.y = addmod(b0.y, mulmod(s.y, pmod, pm), pm.q);
+  }
+  u64 *at = d + (size_t)2 * J * poly + row;
+  st2(at, b0);
+  st2(at + poly, b1);
+}
+
 // the refusals evah_keygen_switch, evah_keygen_set and evah_keygen_public share, with evah_keygen_switch's messages
 static void keygen_checks(evah_ctx *c) {
   if (c->dev.pstep > 1) throw std::invalid_argument("a limb shard holds no whole secret key");
@@ -226,6 +256,7 @@ int evah_key_upload_seeded(evah_ctx *c, int kind, uint32_t galois_elt, uint32_t 
   API_BEGIN
   use(c);
   KeyDev kd = key_shape(c, n_digits);
+  if (kind == EVAH_KEY_REKEY) throw std::invalid_argument("a re-key key is not seed-compressible: upload it whole (evah_key_upload)");
   if (kind != EVAH_KEY_RELIN && kind != EVAH_KEY_GALOIS) throw std::invalid_argument("unknown key kind");
   if (kind == EVAH_KEY_GALOIS && (!(galois_elt & 1) || galois_elt >= 2 * c->N)) throw std::invalid_argument("Galois element is not valid");
   if (!c0) throw std::invalid_argument("key pointer is null");
@@ -280,6 +311,7 @@ int evah_keygen_switch(evah_ctx *c, int kind, uint32_t galois_elt, uint32_t n_di
   use(c);
   if (c->dev.pstep > 1) throw std::invalid_argument("a limb shard holds no whole secret key");
   KeyDev kd = key_shape(c, n_digits);
+  if (kind == EVAH_KEY_REKEY) throw std::invalid_argument("a re-key key is generated by evah_keygen_rekey");
   if (kind != EVAH_KEY_RELIN && kind != EVAH_KEY_GALOIS) throw std::invalid_argument("unknown key kind");
   if (kind == EVAH_KEY_GALOIS && (!(galois_elt & 1) || galois_elt >= 2 * c->N)) throw std::invalid_argument("Galois element is not valid");
   if (!errors) throw std::invalid_argument("error pointer is null");
@@ -355,6 +387,7 @@ int evah_keygen_set(evah_ctx *c, uint32_t n_keys, const int *kinds, const uint32
   if (!kinds || !elts) throw std::invalid_argument("key list pointer is null");
   if ((uint64_t)n_keys * n_digits > 65535) throw std::invalid_argument("a key set holds at most 65535 digits");
   for (uint32_t j = 0; j < n_keys; j++) {
+    if (kinds[j] == EVAH_KEY_REKEY) throw std::invalid_argument("a re-key key is generated by evah_keygen_rekey");
     if (kinds[j] != EVAH_KEY_RELIN && kinds[j] != EVAH_KEY_GALOIS) throw std::invalid_argument("unknown key kind");
     if (kinds[j] == EVAH_KEY_GALOIS && (!(elts[j] & 1) || elts[j] >= 2 * c->N)) throw std::invalid_argument("Galois element is not valid");
     for (uint32_t i = 0; i < j; i++)
@@ -449,6 +482,41 @@ int evah_keygen_public(evah_ctx *c, const uint8_t *ekey32, const uint8_t *seed32
   } else {
     (void)hipFree(kd.d);
   }
+  API_END
+}
+
+// The re-key key from this context's key pair to the pair whose public key is pk_target.  Launch plan:
+// pk_target and the randomness keys up on the queue (into scratch: the context's own public key stays), the NTT forms of
+// (u, e0, e1) of every digit (sample_to_ntt: k_sample_small + the two forward passes), ONE k_keygen_rekey, the key back.
+int evah_keygen_rekey(evah_ctx *c, const uint64_t *pk_target, uint32_t n_digits, const uint8_t *rkeys, uint64_t *key_out) {
+  API_BEGIN
+  use(c);
+  keygen_checks(c);
+  const KeyDev shape = key_shape(c, n_digits);
+  if (!pk_target) throw std::invalid_argument("key pointer is null");
+  if (!rkeys) throw std::invalid_argument("randomness key pointer is null");
+  if (!key_out) throw std::invalid_argument("output pointer is null");
+  if (c->N % 256) throw std::invalid_argument("key generation needs N divisible by 256");
+  if (!c->sh->sk.d) throw std::invalid_argument("secret key not present");
+  const size_t poly = (size_t)c->k * c->N;
+  try {
+    Scratch pk(c, 2 * poly), rk(c, (size_t)4 * n_digits), sm(c, (size_t)n_digits * 3 * poly), key(c, (size_t)n_digits * 2 * poly);
+    // the randomness keys, the sampled residues and their NTT forms do not stay behind in pool memory the next call reuses
+    Wipe w_rk{c, rk.d, (size_t)32 * n_digits}, w_sm{c, sm.d, sizeof(u64) * n_digits * 3 * poly};
+    HIPCHK(hipMemcpyAsync(pk.d, pk_target, sizeof(u64) * 2 * poly, hipMemcpyHostToDevice, c->stream));
+    sample_to_ntt(c, n_digits, rkeys, rk.d, 3, 0, c->k, sm.d);
+    EW_LAUNCH(k_keygen_rekey, dim3((c->N / 2 + 255) / 256, c->k, n_digits), dim3(256), 0, c->stream, c->dev, pk.d, sm.d, c->sh->sk.d, key.d);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(key_out, key.d, shape.bytes, hipMemcpyDeviceToHost, c->stream));
+    w_rk.now();
+    w_sm.now();
+    HIPCHK(hipStreamSynchronize(c->stream)); // the arguments are pageable; the scratch returns to the pool drained
+  } catch (...) {
+    (void)hipStreamSynchronize(c->stream);
+    throw;
+  }
+  c->sh->xfer[4] += sizeof(u64) * 2 * poly + (size_t)32 * n_digits;
+  c->sh->xfer[5] += shape.bytes;
   API_END
 }
 

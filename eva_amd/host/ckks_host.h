@@ -926,4 +926,52 @@ inline HostCipher refresh_host(const HostContext &cx, const SecretKey &sk, const
   return out;
 }
 
+// ---- re-key to another key pair
+// The key that takes ciphertexts under key pair A to key pair B of the same parameters: what B's public context installs
+// and applies.  Not seed-compressible (its c1 is pkB1 u + e1, no expansion): kept, saved and sent whole.
+struct RekeyKey {
+  uint32_t N = 0, n_digits = 0;
+  std::vector<u64> primes;
+  std::vector<u64> data; // [digit][2][k][N], NTT form
+};
+// The host twin of evah_keygen_rekey, word for word: for digit J and prime row i
+//   d[J][0][i] = pkB0_i u_J + NTT_i(e0_J) + [i == J] (P mod q_J) sA_i,   d[J][1][i] = pkB1_i u_J + NTT_i(e1_J)
+// with (u_J, e0_J, e1_J) = sampled_small(rkeys[J], 0 / 1 / 2) — the zero encryption of encrypt() above under B's public
+// key, at the key level and without its mod-down, plus P sA on the digit's own row.
+inline std::vector<u64> rekey_keygen_host(const HostContext &cx, const SecretKey &sk, const PublicKey &pk_target, uint32_t n_digits,
+                                          const std::array<uint8_t, 32> *rkeys) {
+  const uint32_t N = cx.N, k = cx.k;
+  if (n_digits == 0 || n_digits > k - 1) throw std::invalid_argument("invalid key digit count");
+  if (pk_target.data.size() != (size_t)2 * k * N) throw std::invalid_argument("the target's public key does not match the encryption parameters");
+  if (sk.s_ntt.size() != (size_t)k * N) throw std::invalid_argument("secret key not present");
+  const size_t poly = (size_t)k * N;
+  const u64 P = cx.primes[k - 1];
+  std::vector<u64> out((size_t)n_digits * 2 * poly), un(N), en(N);
+  for (uint32_t J = 0; J < n_digits; J++) {
+    std::vector<int8_t> small = sampled_small3(rkeys[J], N);
+    std::vector<int8_t> u(small.begin(), small.begin() + N), e(N);
+    for (uint32_t i = 0; i < k; i++) {
+      const u64 q = cx.primes[i];
+      cx.small_to_ntt(u, i, un.data());
+      for (uint32_t K = 0; K < 2; K++) {
+        std::copy_n(small.begin() + (size_t)(1 + K) * N, N, e.begin());
+        cx.small_to_ntt(e, i, en.data());
+        const u64 *p = pk_target.data.data() + (size_t)K * poly + (size_t)i * N;
+        u64 *dst = out.data() + ((size_t)2 * J + K) * poly + (size_t)i * N;
+        for (uint32_t j = 0; j < N; j++) dst[j] = evah::addmod(cx.mulm(p[j], un[j], i), en[j], q);
+        if (K == 0 && i == J) {
+          const u64 pmod = P % q, *s = sk.s_ntt.data() + (size_t)i * N;
+          for (uint32_t j = 0; j < N; j++) dst[j] = evah::addmod(dst[j], cx.mulm(s[j], pmod, i), q);
+        }
+      }
+    }
+    wipe(small);
+    wipe(u);
+    wipe(e);
+  }
+  std::fill(un.begin(), un.end(), 0);
+  std::fill(en.begin(), en.end(), 0);
+  return out;
+}
+
 } // namespace evahost

@@ -593,6 +593,116 @@ inline HipValuationBatch HipPublic::encrypt_array(const std::map<std::string, Ar
   return out;
 }
 
+// ---- re-key to this key pair
+// what differs between a re-key key's parameters and a context's, or "" — the two key pairs share N and the prime list
+inline std::string rekey_params_differ(uint32_t N, const std::vector<u64> &primes, const HostContext &hc) {
+  if (N != hc.N) return "poly_modulus_degree differs (" + std::to_string(N) + " against " + std::to_string(hc.N) + ")";
+  if (primes.size() != hc.primes.size())
+    return "the number of primes differs (" + std::to_string(primes.size()) + " against " + std::to_string(hc.primes.size()) + ")";
+  for (size_t i = 0; i < primes.size(); i++)
+    if (primes[i] != hc.primes[i]) return "prime " + std::to_string(i) + " differs (" + std::to_string(primes[i]) + " against " + std::to_string(hc.primes[i]) + ")";
+  return "";
+}
+inline uint32_t HipPublic::install_rekey_key(const std::shared_ptr<const RekeyKey> &rk) {
+  if (!rk) throw std::invalid_argument("rekey: the re-key key is None");
+  for (auto &kv : rekey_slots)
+    if (kv.first == rk) return kv.second;
+  const std::string diff = rekey_params_differ(rk->N, rk->primes, *host);
+  if (!diff.empty()) throw std::invalid_argument("rekey: the re-key key was made for other encryption parameters: " + diff);
+  if (rk->n_digits == 0 || rk->n_digits > host->k - 1 || rk->data.size() != (size_t)rk->n_digits * 2 * host->k * host->N)
+    throw std::invalid_argument("rekey: the re-key key's words do not match its shape");
+  // evaluator work, like execute(): EVA_DEVICE_CLIENT does not apply; without a device ensure_device() fails by name
+  if (!resident) throw std::runtime_error("rekey needs resident valuations: resident = False (EVA_RESIDENT=0) keeps them on the host");
+  ensure_device(false);
+  const uint32_t slot = (uint32_t)rekey_slots.size();
+  chk(evah_key_upload(dev->h, EVAH_KEY_REKEY, slot, rk->n_digits, (const uint64_t *)rk->data.data()));
+  rekey_slots.emplace_back(rk, slot);
+  return slot;
+}
+// one value as a handle evah_rekey_many reads: resident on this GPU — in place; on another GPU — copied over; host words —
+// uploaded.  `keep` owns what was made for the call.
+inline const evah_ct *rekey_source(const std::shared_ptr<DeviceCtx> &dev, const HostContext &hc, const std::string &name, const HostCipher &c,
+                                   std::vector<CtHandle> &keep) {
+  if (c.size != 2) throw std::invalid_argument("rekey: value " + name + ": re-key expects a size-2 ciphertext (relinearize first)");
+  if (c.limbs < 1 || c.limbs > hc.k - 1 || (c.dev && c.dev->N != hc.N) || (!resident_only(c) && words(c).size() != (size_t)2 * c.limbs * hc.N))
+    throw std::runtime_error("rekey: value " + name + ": ciphertext shape does not match its data or the encryption parameters");
+  if (c.dev && c.dev->root->device == dev->device) return c.dev->h->h;
+  evah_ct *h = nullptr;
+  if (c.dev) chk(evah_ct_copy(dev->h, c.dev->h->h, &h));
+  else chk(evah_ct_upload(dev->h, 2, c.limbs, c.scale, (const uint64_t *)words(c).data(), &h));
+  keep.emplace_back(dev->h, h);
+  return h;
+}
+inline HipValuation HipPublic::rekey(const HipValuation &enc, const std::shared_ptr<const RekeyKey> &rk) {
+  for (auto &kv : enc.values) // (before anything is uploaded)
+    if (auto *c = std::get_if<HostCipher>(&kv.second))
+      if (c->size != 2) throw std::invalid_argument("rekey: value " + kv.first + ": re-key expects a size-2 ciphertext (relinearize first)");
+  const uint32_t slot = install_rekey_key(rk);
+  if (enc.params && !rekey_params_differ(enc.params->N, enc.params->primes, *host).empty())
+    throw std::invalid_argument("rekey: the valuation belongs to other encryption parameters: " + rekey_params_differ(enc.params->N, enc.params->primes, *host));
+  HipValuation out;
+  out.params = host;
+  for (auto &kv : enc.values) {
+    const HostCipher *c = std::get_if<HostCipher>(&kv.second);
+    if (!c) { // unencrypted and raw values pass through
+      out.values[kv.first] = kv.second;
+      continue;
+    }
+    std::vector<CtHandle> keep;
+    const evah_ct *h = rekey_source(dev, *host, kv.first, *c, keep);
+    evah_ct *o = nullptr;
+    chk(evah_rekey_many(dev->h, slot, &h, 1, &o));
+    out.values[kv.first] = cipher_of_handle(dev, *host, o, c->limbs, c->scale, /*resident=*/true);
+  }
+  return out;
+}
+inline HipValuationBatch HipPublic::rekey_batch(const HipValuationBatch &vb, const std::shared_ptr<const RekeyKey> &rk) {
+  for (auto &nc : vb.ciphers)
+    for (auto &seg : nc.second.segments)
+      if (seg.size != 2) throw std::invalid_argument("rekey: value " + nc.first + ": re-key expects a size-2 ciphertext (relinearize first)");
+  const uint32_t slot = install_rekey_key(rk);
+  if (vb.params && !rekey_params_differ(vb.params->N, vb.params->primes, *host).empty())
+    throw std::invalid_argument("rekey: the batch belongs to other encryption parameters: " + rekey_params_differ(vb.params->N, vb.params->primes, *host));
+  if (!vb.root) throw std::runtime_error("rekey: the batch holds no device handles");
+  const bool same_gpu = vb.root->device == dev->device;
+  HipValuationBatch out;
+  out.B = vb.B;
+  out.params = host;
+  out.root = dev;
+  out.shared = vb.shared;
+  out.plains = vb.plains;
+  for (auto &nc : vb.ciphers) {
+    const auto &segs = nc.second.segments;
+    BatchCipher &bc = out.ciphers[nc.first];
+    size_t row = 0;
+    for (size_t s0 = 0; s0 < segs.size();) {
+      std::vector<CtHandle> keep;
+      std::vector<const evah_ct *> hs;
+      size_t n = 0, s1 = s0;
+      while (s1 < segs.size() && n + segs[s1].n <= CLIENT_BATCH_MAX && segs[s1].limbs == segs[s0].limbs) {
+        if (same_gpu) {
+          hs.push_back(segs[s1].h->h);
+        } else {
+          evah_ct *h = nullptr;
+          chk(evah_ct_copy(dev->h, segs[s1].h->h, &h));
+          keep.emplace_back(dev->h, h);
+          hs.push_back(h);
+        }
+        n += segs[s1++].n;
+      }
+      if (s1 == s0) throw std::runtime_error("value " + nc.first + ": a segment holds more than 64 instances");
+      std::vector<evah_ct *> outs(hs.size(), nullptr);
+      chk(evah_rekey_many(dev->h, slot, hs.data(), (uint32_t)hs.size(), outs.data()));
+      for (size_t s = s0; s < s1; s++)
+        bc.segments.push_back(BatchSegment{std::make_shared<CtHandle>(dev->h, outs[s - s0]), segs[s].n, nullptr, 2, segs[s].limbs, segs[s].scale});
+      row += n;
+      s0 = s1;
+    }
+    if (row != vb.B) throw std::runtime_error("value " + nc.first + ": the segments do not hold every instance");
+  }
+  return out;
+}
+
 class HipSecret {
 public:
   std::shared_ptr<HostContext> host;
@@ -941,6 +1051,42 @@ public:
       }
     }
     return out;
+  }
+
+  // ---- the re-key key from this key pair to `target`'s: made here, from the target's PUBLIC key, and
+  // handed to whoever holds the target's public context (HipPublic::rekey).  Both pairs share N and the prime list.
+  // Randomness: one secret stream per call, digits in order, 4 words per digit, all drawn before the first device call
+  // and wiped afterwards.  seed != 0 is the reproducible test hook (stream (seed, 3)) and is NOT secret-grade.  On the
+  // device where one is present (evah_keygen_rekey), else the host twin — the same words.
+  std::shared_ptr<RekeyKey> make_rekey_key(const HipPublic &target, uint64_t seed = 0) {
+    const std::string diff = rekey_params_differ(target.host->N, target.host->primes, *host);
+    if (!diff.empty()) throw std::invalid_argument("make_rekey_key: the two key pairs must share their encryption parameters: " + diff);
+    if (sk.s_ntt.size() != (size_t)host->k * host->N) throw std::invalid_argument("make_rekey_key: secret key not present");
+    if (target.pk.data.size() != (size_t)2 * host->k * host->N) throw std::invalid_argument("make_rekey_key: the target context holds no public key");
+    const uint32_t D = host->k - 1;
+    std::unique_ptr<SecureRng> stream = seed ? std::make_unique<SecureRng>(seed, 3) : std::make_unique<SecureRng>();
+    std::vector<std::vector<std::array<uint8_t, 32>>> rk(1);
+    WipeKeyRows wipe_keys{rk};
+    for (uint32_t J = 0; J < D; J++) rk[0].push_back(draw_key32(*stream));
+    auto out = std::make_shared<RekeyKey>();
+    out->N = host->N;
+    out->primes = host->primes;
+    out->n_digits = D;
+    if (on_device()) {
+      out->data.resize((size_t)D * 2 * host->k * host->N);
+      std::vector<uint8_t> flat = keys_flat(rk[0].data(), D);
+      const int rc = evah_keygen_rekey(dev->h, (const uint64_t *)target.pk.data.data(), D, flat.data(), (uint64_t *)out->data.data());
+      wipe_bytes(flat.data(), flat.size());
+      chk(rc);
+    } else {
+      out->data = rekey_keygen_host(*host, sk, target.pk, D, rk[0].data());
+    }
+    return out;
+  }
+  std::array<uint64_t, 6> transfer_stats() {
+    std::array<uint64_t, 6> st{0, 0, 0, 0, 0, 0};
+    if (dev) chk(evah_ctx_transfer_stats(dev->h, st.data()));
+    return st;
   }
 
   // ---- the refresh: decrypt, divide by a power of two and encrypt again under this key pair, without

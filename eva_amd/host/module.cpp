@@ -200,6 +200,13 @@ PYBIND11_MODULE(_eva, m) {
     if (seal) save_wire_to_file("SEALSecret", sealfmt::encode_secret(o, c), path);
     else save_to_file(Kind::Secret, o, path);
   }, py::arg("obj"), py::arg("path"), py::arg("format") = "native");
+  // a re-key key has this repo's container only: SEAL has no such object
+  m.def("save", [seal_compr](const RekeyKey &o, const std::string &path, const std::string &format) {
+    bool seal = false;
+    (void)seal_compr(format, seal);
+    if (seal) throw std::invalid_argument("a RekeyKey has no SEAL format: save it with format='native'");
+    save_to_file(Kind::RekeyKey, o, path);
+  }, py::arg("obj"), py::arg("path"), py::arg("format") = "native");
   // test hooks of the SEAL object format
   m.def("_blake2b_256", [](py::bytes data) {
     const std::string s = data;
@@ -259,6 +266,7 @@ PYBIND11_MODULE(_eva, m) {
     if (auto *p = std::get_if<CKKSSignature>(&k)) return py::cast(*p);
     if (auto *p = std::get_if<HipValuation>(&k)) return py::cast(std::move(*p));
     if (auto *p = std::get_if<std::shared_ptr<HipPublic>>(&k)) return py::cast(*p);
+    if (auto *p = std::get_if<std::shared_ptr<RekeyKey>>(&k)) return py::cast(*p);
     return py::cast(std::get<std::shared_ptr<HipSecret>>(k));
   }, py::arg("path"), "Load a previously saved object (same class as was saved)");
 
@@ -329,6 +337,30 @@ PYBIND11_MODULE(_eva, m) {
     sampled_small((const uint8_t *)k.data(), p, N, out.mutable_data());
     return out;
   }, py::arg("rkey"), py::arg("p"), py::arg("N"));
+  // test hook: the host twin of evah_keygen_rekey (ckks_host.h rekey_keygen_host) on raw words -> [digits][2][k][N]
+  mseal.def("_rekey_keygen_host", [](uint32_t N, const std::vector<uint64_t> &primes, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> s_ntt,
+                                     py::array_t<uint64_t, py::array::c_style | py::array::forcecast> pk,
+                                     py::array_t<uint8_t, py::array::c_style | py::array::forcecast> rkeys) {
+    HostContext h(N, std::vector<u64>(primes.begin(), primes.end()));
+    if (rkeys.ndim() != 2 || rkeys.shape(1) != 32) throw std::invalid_argument("randomness keys are [digits][32] bytes");
+    SecretKey sk;
+    sk.s_ntt.assign((const u64 *)s_ntt.data(), (const u64 *)s_ntt.data() + s_ntt.size());
+    PublicKey pkt;
+    pkt.data.assign((const u64 *)pk.data(), (const u64 *)pk.data() + pk.size());
+    const uint32_t D = (uint32_t)rkeys.shape(0);
+    std::vector<std::array<uint8_t, 32>> rk(D);
+    for (uint32_t J = 0; J < D; J++) std::memcpy(rk[J].data(), rkeys.data() + (size_t)32 * J, 32);
+    return to_numpy(rekey_keygen_host(h, sk, pkt, D, rk.data()), {(py::ssize_t)D, 2, (py::ssize_t)h.k, (py::ssize_t)N});
+  }, py::arg("N"), py::arg("primes"), py::arg("s_ntt"), py::arg("pk"), py::arg("rkeys"));
+  py::class_<RekeyKey, std::shared_ptr<RekeyKey>>(mseal, "RekeyKey",
+                                                  "The key that takes results under one key pair to another of the same parameters (DESIGN.md 1.13): made by "
+                                                  "SEALSecret.make_rekey_key from the target's public context, applied by the target's SEALPublic.rekey")
+      .def_readonly("poly_modulus_degree", &RekeyKey::N)
+      .def_readonly("primes", &RekeyKey::primes)
+      .def_readonly("n_digits", &RekeyKey::n_digits)
+      .def("words", [](const RekeyKey &k) {
+        return to_numpy(k.data, {(py::ssize_t)k.n_digits, 2, (py::ssize_t)k.primes.size(), (py::ssize_t)k.N});
+      }, "the key [digits][2][k][N], NTT form");
   py::class_<HipValuation>(mseal, "SEALValuation", "Inputs or outputs of execute(): ciphertexts, plaintexts or raw vectors")
       .def(py::init<>())
       .def("_set_cipher", [](HipValuation &v, const std::string &name, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> data, double scale) {
@@ -546,6 +578,16 @@ PYBIND11_MODULE(_eva, m) {
       .def_readwrite("resident", &HipPublic::resident, "keep valuations in HBM: encrypt/execute return device handles and execute does not wait for the GPU (EVA_RESIDENT=0: host valuations)")
       .def_readwrite("graph_copy_limit", &HipPublic::graph_copy_limit, "device-resident inputs above this many bytes are walked eagerly instead of copied into a captured graph's slots")
       .def("synchronize", &HipPublic::synchronize, "wait for everything this context has enqueued")
+      .def("install_rekey_key", [](HipPublic &p, std::shared_ptr<RekeyKey> rk) { return p.install_rekey_key(rk); }, py::arg("rekey_key"),
+           "upload a RekeyKey to this context's device state (once per key); returns its slot")
+      .def("rekey", [](HipPublic &p, py::object enc, std::shared_ptr<RekeyKey> rk) -> py::object {
+        if (py::isinstance<HipValuationBatch>(enc)) return py::cast(p.rekey_batch(enc.cast<const HipValuationBatch &>(), rk));
+        return py::cast(p.rekey(enc.cast<const HipValuation &>(), rk));
+      }, py::arg("enc"), py::arg("rekey_key"),
+           "Re-key (DESIGN.md 1.13): the encrypted values of a SEALValuation or SEALValuationBatch under another key pair become values under "
+           "this one, with the RekeyKey that pair's secret context made from this public context; level and scale stay, the results are "
+           "resident on this context's device state, unencrypted and raw values pass through. Size-2 ciphertexts only (relinearize first). "
+           "A value on this GPU is read in place; no secret key is involved")
       .def("transfer_stats", [](HipPublic &p) {
         auto st = p.transfer_stats();
         py::dict d;
@@ -729,6 +771,18 @@ PYBIND11_MODULE(_eva, m) {
            "integer message M becomes floor((M + 2^(t-1)) / 2^t) with 2^t the ratio of the scales (0 <= t <= 62; ties towards +infinity). "
            "inputs: the consumer's unencrypted inputs. Randomness as encrypt_batch(..., device_sampling=True); seed != 0 is the reproducible "
            "test hook and not secret-grade. Every result is seeded (c0 + the 32-byte seed of c1)")
+      .def("make_rekey_key", [](HipSecret &s, const HipPublic &target, uint64_t seed) { return s.make_rekey_key(target, seed); },
+           py::arg("target_public_ctx"), py::arg("seed") = 0,
+           "The RekeyKey from this key pair to the one `target_public_ctx` belongs to (same poly_modulus_degree and primes), made from the "
+           "target's public key (DESIGN.md 1.13). Whoever holds it together with the target's secret key learns this secret key: that is "
+           "inherent to proxy re-encryption. seed != 0 is the reproducible test hook and not secret-grade")
+      .def("transfer_stats", [](HipSecret &s) {
+        auto st = s.transfer_stats();
+        py::dict d;
+        d["ct_uploads"] = st[0]; d["ct_downloads"] = st[1]; d["pt_uploads"] = st[2]; d["pt_downloads"] = st[3];
+        d["h2d_bytes"] = st[4]; d["d2h_bytes"] = st[5];
+        return d;
+      }, "ciphertext / plaintext transfers across the host boundary of the key pair's device state")
       .def("decrypt", &HipSecret::decrypt, py::arg("enc_outputs"), py::arg("signature"))
       .def("decrypt_batch", &HipSecret::decrypt_batch, py::arg("enc_outputs"), py::arg("signature"),
            "decrypt() of every valuation of a list, bit for bit; on the device up to 64 outputs of one name are decrypted and decoded in one call")

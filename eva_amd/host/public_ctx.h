@@ -108,6 +108,19 @@ public:
   HipValuationBatch encrypt_array(const std::map<std::string, ArrayView> &arrays, const Valuation &shared, const CKKSSignature &sig,
                                   uint64_t seed = 0, const std::map<std::string, ArrayView> &plains = {});
 
+  // ---- re-key: results under another key pair A of the same parameters become results under THIS key
+  // pair, with a key A's secret context made from this context's public key (HipSecret::make_rekey_key).  No secret key
+  // is needed here.  install_rekey_key uploads the key to this context's device state once and returns its slot; rekey
+  // installs on first use.  Encrypted values are re-keyed — a value resident on a device state of this GPU is read in
+  // place, one on another GPU is copied over first, host words are uploaded — and the results are resident on this
+  // context's device state; unencrypted and raw values pass through.  Needs a device and resident valuations.
+  uint32_t install_rekey_key(const std::shared_ptr<const RekeyKey> &rk);
+  HipValuation rekey(const HipValuation &enc, const std::shared_ptr<const RekeyKey> &rk);
+  // the same for a batch: per name, consecutive segments of one shape go out in calls of <= 64 instances, as decrypt_array
+  // packs them; every call's result is one segment of the new batch
+  HipValuationBatch rekey_batch(const HipValuationBatch &vb, const std::shared_ptr<const RekeyKey> &rk);
+  std::vector<std::pair<std::shared_ptr<const RekeyKey>, uint32_t>> rekey_slots; // the keys installed so far
+
   // SEALPublic::execute (seal.cpp:104-122) — THE hot path.  First call for a program: upload
   // inputs, walk the DAG issuing HIP work over the queues, download outputs.  From the second call
   // on (same program object, same input shapes, no Raw inputs) the whole walk is replayed from a

@@ -15,7 +15,7 @@ namespace evahost {
 
 constexpr uint32_t FORMAT_MAGIC = 0x48415645; // "EVAH"
 constexpr uint32_t FORMAT_VERSION = 1;
-enum class Kind : uint32_t { Program = 1, Parameters = 2, Signature = 3, Valuation = 4, Public = 5, Secret = 6 };
+enum class Kind : uint32_t { Program = 1, Parameters = 2, Signature = 3, Valuation = 4, Public = 5, Secret = 6, RekeyKey = 7 };
 
 class Writer {
 public:
@@ -348,6 +348,26 @@ inline std::shared_ptr<HipSecret> read_secret(Reader &r) {
   return s;
 }
 
+// A re-key key: the parameters it was made for, the digit count and the words, whole
+inline void write(Writer &w, const RekeyKey &k) {
+  w.pod(k.N);
+  w.vec(k.primes);
+  w.pod(k.n_digits);
+  w.vec(k.data);
+}
+inline std::shared_ptr<RekeyKey> read_rekey_key(Reader &r) {
+  const std::shared_ptr<HostContext> h = read_ctx(r);
+  auto k = std::make_shared<RekeyKey>();
+  k->N = h->N;
+  k->primes = h->primes;
+  k->n_digits = r.pod<uint32_t>();
+  k->data = r.vec<u64>();
+  if (k->n_digits == 0 || k->n_digits > h->k - 1 || k->data.size() != (size_t)k->n_digits * 2 * h->k * h->N)
+    throw std::runtime_error("Could not parse message: re-key key has the wrong size for its parameters");
+  check_residues(k->data, *h, "re-key key");
+  return k;
+}
+
 template <class T> void save_to_file(Kind kind, const T &obj, const std::string &path) {
   Writer w;
   w.pod(FORMAT_MAGIC); w.pod(FORMAT_VERSION); w.pod<uint32_t>((uint32_t)kind);
@@ -371,7 +391,8 @@ inline void save_wire_to_file(const std::string &type, const std::string &payloa
   f.write(buf.data(), (std::streamsize)buf.size());
 }
 
-using KnownType = std::variant<std::unique_ptr<Program>, CKKSParameters, CKKSSignature, HipValuation, std::shared_ptr<HipPublic>, std::shared_ptr<HipSecret>>;
+using KnownType = std::variant<std::unique_ptr<Program>, CKKSParameters, CKKSSignature, HipValuation, std::shared_ptr<HipPublic>, std::shared_ptr<HipSecret>,
+                               std::shared_ptr<RekeyKey>>;
 inline KnownType load_from_file(const std::string &path) {
   std::ifstream f(path, std::ios::binary);
   if (!f) throw std::runtime_error("Could not open file " + path);
@@ -399,6 +420,7 @@ inline KnownType load_from_file(const std::string &path) {
   case Kind::Valuation: return read_valuation(r);
   case Kind::Public: return read_public(r);
   case Kind::Secret: return read_secret(r);
+  case Kind::RekeyKey: return read_rekey_key(r);
   }
   throw std::runtime_error("Unknown inner message type");
 }

@@ -125,7 +125,8 @@ struct PtHandle {
 // ---- device contexts (seal.h:45-97 keeps a SEALContext per key set; here: tables + keys in HBM)
 struct DeviceCtx {
   evah_ctx *h = nullptr;
-  DeviceCtx(uint32_t N, const std::vector<u64> &primes, int device) {
+  int device = 0; // the GPU the state lives on
+  DeviceCtx(uint32_t N, const std::vector<u64> &primes, int device_) : device(device_) {
     chk(evah_ctx_create(N, (uint32_t)primes.size(), (const uint64_t *)primes.data(), device, &h));
   }
   ~DeviceCtx() { evah_ctx_destroy(h); }

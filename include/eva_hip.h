@@ -71,6 +71,10 @@ int evah_ctx_mem_info(evah_ctx *ctx, size_t *in_use, size_t *cached);
 #define EVAH_KEY_GALOIS 1
 #define EVAH_KEY_PUBLIC 2 /* evah_client_key_upload */
 #define EVAH_KEY_SECRET 3
+/* a re-key key TO this context's key pair: evah_key_upload takes it with galois_elt naming a slot (any
+ * uint32), keeps it beside the Galois keys and builds the split copy under the same condition; evah_rekey_many applies it.
+ * Not seed-compressible (its c1 is no expansion): evah_key_upload_seeded, evah_keygen_switch and evah_keygen_set refuse it. */
+#define EVAH_KEY_REKEY 4
 int evah_key_upload(evah_ctx *ctx, int kind, uint32_t galois_elt, uint32_t n_digits,
                     const uint64_t *data);
 /* The same key from its seed-compressed form (what SEAL's KeyGenerator::create_relin_keys /
@@ -109,6 +113,18 @@ int evah_keygen_set(evah_ctx *ctx, uint32_t n_keys, const int *kinds /* [n_keys]
  * becomes ctx's public key, as after evah_client_key_upload(EVAH_KEY_PUBLIC); pk_out != NULL: it is copied back. */
 int evah_keygen_public(evah_ctx *ctx, const uint8_t *ekey32, const uint8_t *seed32, int install,
                        uint64_t *pk_out /* [2][k][N] or NULL */);
+/* The re-key key from ctx's key pair A to another key pair B of the same parameters, generated on the device from B's
+ * PUBLIC key (SEAL has no such call — it is KeyGenerator's key-switching key with a public-key
+ * encryption of zero in place of the symmetric one): for digit J and prime row i
+ *   d[J][0][i] = pkB0_i u_J + NTT_i(e0_J) + [i == J] (P mod q_J) sA_i,   d[J][1][i] = pkB1_i u_J + NTT_i(e1_J),
+ * (u_J, e0_J, e1_J) = sampled_small(rkeys[J], 0 / 1 / 2) (eva_amd/host/csprng.h), sA the secret key
+ * evah_client_key_upload(EVAH_KEY_SECRET) left on ctx.  pk_target goes up on ctx's queue into scratch and does not replace
+ * ctx's own public key; one launch forms both polynomials of every digit; key_out [n_digits][2][k][N] is the layout
+ * evah_key_upload(EVAH_KEY_REKEY) takes on B's side.  The randomness keys are secrets: they, the sampled residues and
+ * their NTT forms are zeroed on the queue before their memory returns to the pool, also when the call fails.  Refuses a
+ * capturing context, a limb shard, null pointers, a missing secret key, a bad digit count and N not divisible by 256. */
+int evah_keygen_rekey(evah_ctx *ctx, const uint64_t *pk_target /* [2][k][N] */, uint32_t n_digits,
+                      const uint8_t *rkeys /* [n_digits][32] */, uint64_t *key_out /* [n_digits][2][k][N] */);
 /* c0 of an installed relinearization or Galois key (what saving the RelinKeys / GaloisKeys of
  * generateKeys, seal.cpp:174-203, needs of a key that was generated in place): d[J][0] of every digit -> out, one
  * linear copy per digit on ctx's queue, then a drain.  Refuses a key that is not present and a limb shard. */
@@ -196,7 +212,7 @@ int evah_ctx_tail_variant(evah_ctx *ctx, uint32_t out[3]);
  * limbs; out[1] = the fewest workgroups the first key-switch slice (2 n N / 256 for n instances) must have for it, 0 when
  * EVAH_KS_TAIL=1 asks for every such launch set.  Same words either way. */
 int evah_ctx_ks_tail(evah_ctx *ctx, uint32_t out[2]);
-/* bytes of HBM the evaluation keys (relinearization + Galois) of this context's device state occupy.  After
+/* bytes of HBM the evaluation keys (relinearization + Galois + re-key) of this context's device state occupy.  After
  * evah_ctx_set_shard(ctx, s, G) an upload keeps only shard s's prime rows of a key (its data limbs and the
  * special prime): (ceil((k-1)/G) + 1) / k of the whole key. */
 int evah_ctx_key_bytes(evah_ctx *ctx, uint64_t *bytes);
@@ -346,6 +362,15 @@ int evah_rotate_many(evah_ctx *ctx, const evah_ct *a, const int32_t *steps, uint
  * as one launch set; outs[i] == evah_rotate(cts[i], steps[i]) bit for bit.  A ciphertext that occurs
  * in several pairs is decomposed once for all of them when the set is large enough (hoisting, as above). */
 int evah_rotate_pairs(evah_ctx *ctx, const evah_ct *const *cts, const int32_t *steps, uint32_t n, evah_ct **outs);
+/* Re-key: size-2 ciphertexts under another key pair A become ciphertexts under ctx's key pair, with the
+ * key evah_key_upload(EVAH_KEY_REKEY, slot) left on ctx — out = (c0 + KS(c1)_0, KS(c1)_1), KS being
+ * Evaluator::switch_key_inplace as evah_rotate applies it (seal_executor.h:181 without the permutation), bit for bit;
+ * level and scale stay.  cts: single and batched handles, evah_ct_slice / evah_ct_unstack and mod-switched views, of ONE
+ * level, read in place — also handles owned by a context of another device state on the same GPU (the read is ordered
+ * behind their producer, no copy).  outs[i] holds as many instances as cts[i]; all of them view one allocation.  The
+ * instances go out 64 at a time, each chunk one launch set in the form every key switch of that size takes.  Refuses an
+ * empty slot ("re-key key not present"), size 3, mixed levels, a handle on another GPU, a limb shard. */
+int evah_rekey_many(evah_ctx *ctx, uint32_t slot, const evah_ct *const *cts, uint32_t n_handles, evah_ct **outs);
 /* Sums of plaintext-weighted rotations, the convolution pattern of EVA programs
  * (/root/reference/examples/image_processing.py:22-34 convolutionXY: rotated = image << (i*w + j);
  *  Ix += rotated * filter[i][j]; Iy += rotated * filter[j][i]) — the rotate_vector (seal_executor.h:181/188),
