@@ -153,6 +153,10 @@ _SIGS = {
     "evah_decrypt_decode_rows": [_vp, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.c_int, _vp, C.c_size_t, C.c_int, C.c_int],
     # the refresh
     "evah_refresh_handles": [_vp, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.c_double, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _vpp],
+    # threshold decryption
+    "evah_decrypt_share_handles": [_vp, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8), _vpp],
+    "evah_decrypt_combine_rows": [_vp, C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.c_int, _vp,
+                                  C.c_size_t, C.c_int, C.c_int],
     "evah_ct_slice": [_vp, _vp, C.c_uint32, C.c_uint32, _vpp],
     "evah_ctx_stack_stats": [_vp, _u64p],
     # batched plaintexts
@@ -721,6 +725,33 @@ class Context:
         _chk(_lib.evah_refresh_handles(self.h, ptrs, len(cts), int(limbs_out), float(scale_out), _keys32(ekeys, rows), _keys32(seeds, rows),
                                        C.byref(h)))
         return Ciphertext(self, h)
+
+    # ---- threshold decryption
+    def decrypt_share_handles(self, cts, smudge_bits, fkeys):
+        """this party's decryption share h = c1 s_p + NTT(E) of every instance of the size-2 handles of `cts` (as
+        decrypt_decode_handles takes them) -> one batched size-1 handle [instances][1][l][N] (evah_decrypt_share_handles);
+        fkeys: one 32-byte flooding key per instance, or None (the null pointer, which the call refuses)"""
+        rows = sum(ct.batch for ct in cts)
+        ptrs = (C.c_void_p * max(len(cts), 1))(*[ct.h for ct in cts])
+        h = C.c_void_p()
+        _chk(_lib.evah_decrypt_share_handles(self.h, ptrs, len(cts), int(smudge_bits), _keys32(fkeys, rows), C.byref(h)))
+        return Ciphertext(self, h)
+
+    def decrypt_combine_rows(self, cts, shares, n_out, out, wait=True, dtype_code=None, pitch=None):
+        """decrypt_decode_rows with the dot product replaced by c0 + the sum of the parties' shares
+        (evah_decrypt_combine_rows): shares = one size-1 handle per party holding the instances of `cts`; needs no secret
+        key.  out: as decrypt_decode_rows takes it"""
+        ptrs = (C.c_void_p * max(len(cts), 1))(*[ct.h for ct in cts])
+        sptrs = (C.c_void_p * max(len(shares), 1))(*[sh.h for sh in shares])
+        if isinstance(out, np.ndarray):
+            assert out.ndim == 2 and out.strides[1] == out.itemsize
+            ptr, row_pitch, on_device, dt = C.c_void_p(out.ctypes.data), out.strides[0], 0, out.dtype
+        else:
+            ptr, row_pitch, on_device, dt = C.c_void_p(out.ptr), out.pitch, 1, out.dtype
+        code = _DTYPES.get(np.dtype(dt), -1) if dtype_code is None else int(dtype_code)
+        _chk(_lib.evah_decrypt_combine_rows(self.h, ptrs, len(cts), sptrs, len(shares), int(n_out), code, ptr,
+                                            int(row_pitch if pitch is None else pitch), on_device, 1 if wait else 0))
+        return out
 
     # ---- the array calls on device memory (DESIGN.md 1.11): rows = a DeviceView, or anything with .ptr, .shape, .dtype, .pitch
     @staticmethod

@@ -285,6 +285,89 @@ k_decrypt_dot(DevCtx cx, DotTab tab, uint32_t size, uint32_t l, const u64 *sk, u
   m[(size_t)inst * l * cx.N + off] = acc;
 }
 
+// ---- threshold decryption: flooding noise, a party's share, the combination of all shares
+// The flooding noise of instance blockIdx.y from its key fkeys[inst][8], as canonical residues out [n][l][N] under the
+// chain primes 0 .. l - 1: r = |E| mod q (barrett64: |E| reaches 2^62 while q may have 30 bits), negative -> q - r,
+// k_enc_round_many's rule.  The mapping is k_sample_small's: a workgroup draws FLOOD_TILE consecutive coefficients, one
+// ChaCha20 block of 8 per thread, parks them in LDS as 8-byte words (16 KiB), and writes them limb by limb, thread t the
+// coefficients 2 t, 2 t + 1 (+ 512 r): one 16-byte store per lane, 1 KiB contiguous per wave instruction, no block
+// computed twice.  N = 1024 is half a tile: threads 128 .. 255 draw nothing and the stores stop at `pairs`.
+// (A thread parks its 64 bytes at stride 64, which the LDS serves with conflicts; that is 4 writes beside a ChaCha20
+// block.  Counted, not timed.)
+constexpr uint32_t FLOOD_THREADS = 256, FLOOD_TILE = 8 * FLOOD_THREADS;
+__global__ void __launch_bounds__(FLOOD_THREADS)
+k_sample_flood(DevCtx cx, const uint32_t *__restrict__ fkeys, uint32_t sigma, uint32_t limbs, u64 *out) {
+  __shared__ ulonglong2 tile[FLOOD_TILE / 2];
+  const uint32_t tid = threadIdx.x, inst = blockIdx.y;
+  const uint32_t blk = blockIdx.x * FLOOD_THREADS + tid;
+  if (blk < cx.N / 8) {
+    uint32_t key[8];
+#pragma unroll
+    for (int w = 0; w < 8; w++) key[w] = fkeys[8 * inst + w];
+    int64_t e[8];
+    flood_block(key, sigma, blk, e);
+#pragma unroll
+    for (int r = 0; r < 4; r++) tile[4 * tid + r] = make_ulonglong2((u64)e[2 * r], (u64)e[2 * r + 1]);
+  }
+  __syncthreads();
+  constexpr uint32_t R = FLOOD_TILE / 2 / FLOOD_THREADS;
+  const uint32_t base = blockIdx.x * FLOOD_TILE, pairs = min(FLOOD_TILE, cx.N - base) / 2; // N is a multiple of 512 (the entry point refuses anything else)
+  u64 mag[R][2];
+  bool neg[R][2];
+#pragma unroll
+  for (uint32_t r = 0; r < R; r++) {
+    const uint32_t e = tid + r * FLOOD_THREADS;
+    const ulonglong2 v = e < pairs ? tile[e] : make_ulonglong2(0, 0);
+    const int64_t a = (int64_t)v.x, b = (int64_t)v.y;
+    neg[r][0] = a < 0;
+    neg[r][1] = b < 0;
+    mag[r][0] = a < 0 ? (u64)(-a) : (u64)a;
+    mag[r][1] = b < 0 ? (u64)(-b) : (u64)b;
+  }
+  u64 *rows = out + (size_t)inst * limbs * cx.N + base;
+  for (uint32_t i = 0; i < limbs; i++) {
+    const DevPrime pm = cx.primes[i]; // (as k_decrypt_dot and the two kernels below: a limb shard is refused by the entry points)
+#pragma unroll
+    for (uint32_t r = 0; r < R; r++) {
+      const uint32_t e = tid + r * FLOOD_THREADS;
+      if (e < pairs) {
+        const u64 x = barrett64(mag[r][0], pm.q, pm.brt), y = barrett64(mag[r][1], pm.q, pm.brt);
+        st2(rows + (size_t)i * cx.N + 2 * e, make_ulonglong2(neg[r][0] && x ? pm.q - x : x, neg[r][1] && y ? pm.q - y : y));
+      }
+    }
+  }
+}
+// h[inst][i] = c1 s + En in place over the noise en [n][l][N] (NTT form), which becomes the share; c1 = polynomial 1 of
+// ciphertext inst through the table.  Two coefficients per thread, 16-byte accesses; grid (N / 512, l, n).
+__global__ void __launch_bounds__(256)
+k_decrypt_share(DevCtx cx, DotTab tab, uint32_t l, const u64 *sk, u64 *en) {
+  const size_t n = 2 * ((size_t)blockIdx.x * blockDim.x + threadIdx.x);
+  const uint32_t i = blockIdx.y, inst = blockIdx.z;
+  const DevPrime pm = cx.primes[i];
+  const size_t off = (size_t)i * cx.N + n;
+  const ulonglong2 a = ld2(tab.ct[inst] + (size_t)tab.ct_ps[inst] * cx.N + off), s = ld2(sk + off);
+  u64 *h = en + (size_t)inst * l * cx.N + off;
+  const ulonglong2 e = ld2(h);
+  st2(h, make_ulonglong2(addmod(mulmod(a.x, s.x, pm), e.x, pm.q), addmod(mulmod(a.y, s.y, pm), e.y, pm.q)));
+}
+// m[inst][i] = c0 + sum_p h_p: c0 = polynomial 0 of ciphertext inst through the table, shares[p * n + inst] = instance
+// inst of party p's share ([l][N], canonical residues).  One launch whatever the number of parties: the P n pointers lie
+// in a buffer of the call.  Two coefficients per thread, 16-byte accesses; grid (N / 512, l, n).
+__global__ void __launch_bounds__(256)
+k_combine_shares(DevCtx cx, DotTab tab, const u64 *const *__restrict__ shares, uint32_t n_parties, uint32_t l, u64 *m) {
+  const size_t n = 2 * ((size_t)blockIdx.x * blockDim.x + threadIdx.x);
+  const uint32_t i = blockIdx.y, inst = blockIdx.z, n_inst = gridDim.z;
+  const u64 q = cx.primes[i].q;
+  const size_t off = (size_t)i * cx.N + n;
+  ulonglong2 acc = ld2(tab.ct[inst] + off);
+  for (uint32_t p = 0; p < n_parties; p++) {
+    const ulonglong2 h = ld2(shares[(size_t)p * n_inst + inst] + off);
+    acc.x = addmod(acc.x, h.x, q);
+    acc.y = addmod(acc.y, h.y, q);
+  }
+  st2(m + (size_t)inst * l * cx.N + off, acc);
+}
+
 // Garner tables of a level: inv_prefix[i] = (q_0..q_{i-1})^-1 mod q_i, pre_mod[i][t] = q_0..q_{t-1} mod q_i,
 // prefix[i][w] = word w of q_0..q_{i-1} (base 2^64, l words), qwords[w] / half[w] = word w of Q / of floor(Q/2)
 struct CrtTab {
@@ -652,22 +735,26 @@ static void decrypt_to_coeff(evah_ctx *c, const DotTab &tab, uint32_t size, uint
   OpPlain::Params ip{m, m, (size_t)l * c->N, (size_t)l * c->N, l, 0, 0, {}};
   ntt_inverse<OpPlain>(c, ip, n * l);
 }
-static void decrypt_decode(evah_ctx *c, const evah_ct *const *cts, uint32_t n_handles, uint32_t n, uint32_t n_out, int dtype_out, void *out,
-                           const RowsDst *rows = nullptr) {
-  const uint32_t l = cts[0]->limbs, N = c->N;
+// The decoder behind the messages: front(m) puts the n messages [n][l][N] of scale `scale` on the queue in coefficient
+// form — the decryptor's dot product and inverse transforms (decrypt_decode), or the sum of decryption shares
+// (decrypt_combine) —, everything behind it is one body: Garner, the FFT, the gather in the row's type,
+// the copy, the wipes and the statistics.
+template <class Front>
+static void decode_messages(evah_ctx *c, uint32_t l, double scale, uint32_t n, uint32_t n_out, int dtype_out, void *out, const RowsDst *rows,
+                            Front front) {
+  const uint32_t N = c->N;
   enc_tables(c);
   dec_tables(c);
   const CrtTab t = crt_tab_cached(c, l);
-  const DotTab tab = dot_tab_of(c, cts, n_handles);
   const size_t B = n, row_bytes = dtype_size(dtype_out) * n_out, out_bytes = row_bytes * B;
   const bool to_dev = rows && rows->on_device;
   Scratch m(c, B * l * N), cbuf(c, B * 2 * N), outd(c, to_dev ? 1 : (out_bytes + 7) / 8);
   {
     // the decrypted messages, their FP images and the slot values do not stay behind in pool memory the next call reuses
     Wipe w_m{c, m.d, sizeof(u64) * B * l * N}, w_c{c, cbuf.d, sizeof(double2) * B * N}, w_o{c, outd.d, out_bytes, to_dev};
-    decrypt_to_coeff(c, tab, cts[0]->size, l, n, m.d);
+    front(m.d);
     double2 *cd = reinterpret_cast<double2 *>(cbuf.d);
-    EW_LAUNCH(k_crt_to_double, dim3(N / 256, n), dim3(256), 0, c->stream, c->dev, t, l, m.d, 1.0 / cts[0]->scale, cd);
+    EW_LAUNCH(k_crt_to_double, dim3(N / 256, n), dim3(256), 0, c->stream, c->dev, t, l, m.d, 1.0 / scale, cd);
     HIPCHK(hipGetLastError());
     fft_batched<false>(c, cd, c->sh->dec_roots, n, make_double2(0.0, 0.0), 0.0);
     if (rows) { // the caller's rows, or (host rows) the scratch at its own pitch
@@ -693,6 +780,77 @@ static void decrypt_decode(evah_ctx *c, const evah_ct *const *cts, uint32_t n_ha
   }
   if (!to_dev || rows->wait) HIPCHK(hipStreamSynchronize(c->stream));
   if (rows && !to_dev) c->sh->xfer[5] += out_bytes; // evah_decrypt_decode_rows counts what it brings to the host: device rows, nothing
+}
+static void decrypt_decode(evah_ctx *c, const evah_ct *const *cts, uint32_t n_handles, uint32_t n, uint32_t n_out, int dtype_out, void *out,
+                           const RowsDst *rows = nullptr) {
+  const uint32_t l = cts[0]->limbs;
+  decode_messages(c, l, cts[0]->scale, n, n_out, dtype_out, out, rows, [&](u64 *m) {
+    const DotTab tab = dot_tab_of(c, cts, n_handles);
+    decrypt_to_coeff(c, tab, cts[0]->size, l, n, m);
+  });
+}
+
+// ---- threshold decryption
+// is P 2^(sigma + 2) > Q_l ?  (P <= 64, sigma <= 62: the left side is below 2^71.)  A share is refused with P = 1; the
+// shares of a handle do not carry sigma, so the rule for P parties is the caller's (client.h combine_shares) to apply.
+static bool flood_exceeds_modulus(const evah_ctx *c, uint32_t l, uint32_t parties, uint32_t sigma) {
+  u128 Q = 1;
+  for (uint32_t i = 0; i < l; i++) {
+    if (Q >> 64) return false; // Q_l >= 2^64 2^29 already
+    Q *= c->primes[i];
+  }
+  return ((u128)parties << (sigma + 2)) > Q;
+}
+// evah_decrypt_share_handles: the share h = c1 s + NTT(E) of every instance of the handles, E drawn here from fkeys
+// [n][32], into one handle [n][1][l][N].  Launches: the key copy, k_sample_flood, the forward transform of the n l rows,
+// k_decrypt_share, the wipe of the keys, one drain — their number does not depend on n.
+static evah_ct *decrypt_share(evah_ctx *c, const evah_ct *const *cts, uint32_t n_handles, uint32_t n, uint32_t sigma, const uint8_t *fkeys) {
+  const uint32_t l = cts[0]->limbs;
+  const size_t N = c->N, B = n;
+  const DotTab tab = dot_tab_of(c, cts, n_handles);
+  Scratch keys(c, 4 * B);
+  evah_ct *o = ct_new(c, 1, l, cts[0]->scale, n);
+  try {
+    Wipe w_keys{c, keys.d, 32 * B}; // whoever learns E learns c1 s: the keys do not stay behind in pool memory
+    HIPCHK(hipMemcpyAsync(keys.d, fkeys, 32 * B, hipMemcpyHostToDevice, c->stream));
+    EW_LAUNCH(k_sample_flood, dim3((c->N + FLOOD_TILE - 1) / FLOOD_TILE, n), dim3(FLOOD_THREADS), 0, c->stream, c->dev,
+              reinterpret_cast<const uint32_t *>(keys.d), sigma, l, o->d);
+    HIPCHK(hipGetLastError());
+    OpPlain::Params fp{o->d, o->d, (size_t)l * N, (size_t)l * N, l, 0, 0, {}};
+    ntt_forward<OpPlain>(c, fp, n * l);
+    EW_LAUNCH(k_decrypt_share, dim3(c->N / 512, l, n), dim3(256), 0, c->stream, c->dev, tab, l, c->sh->sk.d, o->d);
+    HIPCHK(hipGetLastError());
+    w_keys.now();
+    HIPCHK(hipStreamSynchronize(c->stream)); // `fkeys` is pageable host memory
+  } catch (...) {
+    (void)hipStreamSynchronize(c->stream);
+    evah_ct_free(c, o);
+    throw;
+  }
+  c->sh->xfer[4] += 32 * B; // the keys: what the call sends up
+  return o;
+}
+// evah_decrypt_combine_rows: decode_messages behind m = c0 + sum_p h_p.  The P n share pointers cross in one copy on the
+// queue into a buffer of the call (a launch's arguments cannot hold 64 x 64 of them); the copy of pageable memory
+// returns once the words are staged, so the table may leave with this scope.
+static void decrypt_combine(evah_ctx *c, const evah_ct *const *cts, uint32_t n_handles, uint32_t n, const evah_ct *const *shares,
+                            uint32_t n_parties, uint32_t n_out, int dtype_out, void *out, const RowsDst *rows) {
+  const uint32_t l = cts[0]->limbs;
+  std::vector<const u64 *> ptrs((size_t)n_parties * n);
+  Scratch pd(c, ptrs.size());
+  decode_messages(c, l, cts[0]->scale, n, n_out, dtype_out, out, rows, [&](u64 *m) {
+    const DotTab tab = dot_tab_of(c, cts, n_handles);
+    for (uint32_t p = 0; p < n_parties; p++) {
+      acquire(c, shares[p]->buf);
+      for (uint32_t j = 0; j < n; j++) ptrs[(size_t)p * n + j] = shares[p]->d + (size_t)j * shares[p]->size * shares[p]->ps;
+    }
+    HIPCHK(hipMemcpyAsync(pd.d, ptrs.data(), sizeof(u64 *) * ptrs.size(), hipMemcpyHostToDevice, c->stream));
+    EW_LAUNCH(k_combine_shares, dim3(c->N / 512, l, n), dim3(256), 0, c->stream, c->dev, tab, reinterpret_cast<const u64 *const *>(pd.d), n_parties, l,
+              m);
+    HIPCHK(hipGetLastError());
+    OpPlain::Params ip{m, m, (size_t)l * c->N, (size_t)l * c->N, l, 0, 0, {}};
+    ntt_inverse<OpPlain>(c, ip, n * l);
+  });
 }
 
 // ---- the _many calls: values in, one batched handle out
@@ -1194,9 +1352,10 @@ int evah_decrypt_decode_many(evah_ctx *c, const evah_ct *const *cts, uint32_t n,
 // evah_decrypt_decode_many over handles that may be batched: the same checks in the same order, the
 // instances counted over the whole list
 // the checks of evah_decrypt_decode_handles before and behind its dtype check (evah_decrypt_decode_rows makes the same)
-static uint32_t handles_checks_list(evah_ctx *c, const evah_ct *const *cts, uint32_t n_handles, const void *out) {
+// need_sk = false: evah_decrypt_combine_rows, the one reader of ciphertexts here that uses no secret key
+static uint32_t handles_checks_list(evah_ctx *c, const evah_ct *const *cts, uint32_t n_handles, const void *out, bool need_sk = true) {
   if (c->capturing) throw std::logic_error("this call synchronises with the host and cannot be captured into a graph");
-  if (!c->sh->sk.d) throw std::invalid_argument("secret key not present");
+  if (need_sk && !c->sh->sk.d) throw std::invalid_argument("secret key not present");
   if (n_handles < 1) throw std::invalid_argument("batch must be 1..64");
   if (!cts || !out) throw std::invalid_argument("ciphertext list and output are required");
   uint64_t n = 0;
@@ -1270,6 +1429,51 @@ int evah_decrypt_decode_rows(evah_ctx *c, const evah_ct *const *cts, uint32_t n_
   check_rows_shape(c, out, dtype_out, "unknown output dtype (EVAH_F64, EVAH_F32 or EVAH_U8)", n, n_out, row_pitch, out_on_device != 0, "out");
   const RowsDst rows{row_pitch, out_on_device != 0, wait != 0};
   decrypt_decode(c, cts, n_handles, n, n_out, dtype_out, out, &rows);
+  API_END
+}
+
+// ---- threshold decryption
+int evah_decrypt_share_handles(evah_ctx *c, const evah_ct *const *cts, uint32_t n_handles, uint32_t smudge_bits, const uint8_t *fkeys,
+                               evah_ct **out) {
+  API_BEGIN
+  use(c);
+  if (c->dev.pstep > 1) throw std::invalid_argument("a limb shard holds no whole secret key");
+  const uint32_t n = handles_checks_list(c, cts, n_handles, out);
+  if (!fkeys) throw std::invalid_argument("flooding keys are required");
+  if (cts[0]->size != 2) throw std::invalid_argument("decryption share expects a size-2 ciphertext (relinearize first)");
+  if (cts[0]->limbs < 1 || cts[0]->limbs > c->k - 1) throw std::invalid_argument("invalid limb count for this context");
+  if (cts[0]->limbs > 61) throw std::invalid_argument("too many limbs");
+  if (c->N % 512) throw std::invalid_argument("decryption needs N divisible by 512");
+  if (smudge_bits < 1 || smudge_bits > 62) throw std::invalid_argument("smudge_bits must be 1..62");
+  if (flood_exceeds_modulus(c, cts[0]->limbs, 1, smudge_bits)) throw std::invalid_argument("smudge_bits leaves no room at this level");
+  *out = decrypt_share(c, cts, n_handles, n, smudge_bits, fkeys);
+  API_END
+}
+
+int evah_decrypt_combine_rows(evah_ctx *c, const evah_ct *const *cts, uint32_t n_handles, const evah_ct *const *shares, uint32_t n_parties,
+                              uint32_t n_out, int dtype_out, void *out, size_t row_pitch, int out_on_device, int wait) {
+  API_BEGIN
+  use(c);
+  if (c->dev.pstep > 1) throw std::invalid_argument("a limb shard holds no whole ciphertext");
+  const uint32_t n = handles_checks_list(c, cts, n_handles, out, false);
+  if (cts[0]->size != 2) throw std::invalid_argument("decryption share expects a size-2 ciphertext (relinearize first)");
+  if (!shares) throw std::invalid_argument("share list is required");
+  if (n_parties < 1 || n_parties > 64) throw std::invalid_argument("the number of parties must be 1..64");
+  for (uint32_t p = 0; p < n_parties; p++) {
+    const std::string at = "share " + std::to_string(p);
+    if (!shares[p]) throw std::invalid_argument(at + " is null");
+    if (shares[p]->size != 1) throw std::invalid_argument(at + " is not a decryption share (size 1)");
+    if (shares[p]->limbs != cts[0]->limbs) throw std::invalid_argument(at + ": limb count differs from the ciphertexts'");
+    if (shares[p]->scale != cts[0]->scale) throw std::invalid_argument(at + ": scale differs from the ciphertexts'");
+    if (shares[p]->batch != n) throw std::invalid_argument(at + ": instance count differs from the ciphertexts'");
+  }
+  if (!dtype_size(dtype_out)) throw std::invalid_argument("unknown output dtype (EVAH_F64, EVAH_F32 or EVAH_U8)");
+  handles_checks_shape(c, cts, n_out);
+  if (cts[0]->limbs > c->k - 1) throw std::invalid_argument("invalid limb count for this context");
+  if (c->N % 512) throw std::invalid_argument("decryption needs N divisible by 512");
+  check_rows_shape(c, out, dtype_out, "unknown output dtype (EVAH_F64, EVAH_F32 or EVAH_U8)", n, n_out, row_pitch, out_on_device != 0, "out");
+  const RowsDst rows{row_pitch, out_on_device != 0, wait != 0};
+  decrypt_combine(c, cts, n_handles, n, shares, n_parties, n_out, dtype_out, out, &rows);
   API_END
 }
 

@@ -26,4 +26,17 @@ __device__ __forceinline__ u64 sampled_block(const uint32_t *key, uint32_t p, ui
   return packed;
 }
 
+// The flooding noise of a decryption share: coefficient j of the noise of key fk from the little-endian
+// u64 word w = j % 8 of the ChaCha20 block of key = fk, block counter = j / 8, nonce = 0x666c000000000000 (a tag of its
+// own: no block is shared with a seeded polynomial or a small one).  E = (w >> (63 - sigma)) - 2^sigma, exactly uniform
+// on [-2^sigma, 2^sigma) for 1 <= sigma <= 62, no rejection.  Host twin: eva_amd/host/csprng.h flood_wide.
+constexpr uint32_t FLOOD_NONCE_HI = 0x666c0000u;
+
+__device__ __forceinline__ void flood_block(const uint32_t *key, uint32_t sigma, uint64_t blk, int64_t e[8]) {
+  uint32_t x[16];
+  chacha_block(key, blk, 0, FLOOD_NONCE_HI, x);
+#pragma unroll
+  for (int r = 0; r < 8; r++) e[r] = (int64_t)(chacha_w64(x, r) >> (63 - sigma)) - ((int64_t)1 << sigma);
+}
+
 } // namespace evah

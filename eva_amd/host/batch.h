@@ -127,6 +127,7 @@ inline void HipPublic::run_batch_groups(Program &program, size_t n_instances, bo
 }
 
 inline std::vector<HipValuation> HipPublic::execute_batch(Program &program, const std::vector<const HipValuation *> &inputs) {
+  refuse_relinearize(program);
   ensure_device();
   if (batch_chunk < 1 || batch_chunk > 64) throw std::runtime_error("batch_chunk must be 1..64");
   std::vector<HipValuation> all(inputs.size());
@@ -158,6 +159,7 @@ inline std::vector<HipValuation> HipPublic::execute_batch(Program &program, cons
 }
 
 inline HipValuationBatch HipPublic::execute_batch(Program &program, const HipValuationBatch &inputs) {
+  refuse_relinearize(program);
   ensure_device();
   if (batch_chunk < 1 || batch_chunk > 64) throw std::runtime_error("batch_chunk must be 1..64");
   if (devices.size() > 1 || !shard_mode.empty()) { // the multi-device modes: through the list path
@@ -195,6 +197,7 @@ inline HipValuationBatch HipPublic::execute_batch(Program &program, const HipVal
 // device.  (The driver's scaling curve uses one process per GPU, eva_amd/dist.py; this is the same
 // partition inside one execute_batch call.)
 inline std::vector<HipValuation> HipPublic::execute_batch_multi(Program &program, const std::vector<const HipValuation *> &inputs) {
+  refuse_relinearize(program);
   if (batch_chunk < 1 || batch_chunk > 64) throw std::runtime_error("batch_chunk must be 1..64");
   ensure_group(false);
   const size_t G = group->size();

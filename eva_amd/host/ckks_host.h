@@ -485,7 +485,10 @@ public:
     std::map<uint32_t, std::vector<uint8_t>> ekeys; // 0: the relinearization key's [digits][32], Galois element: that key's
   } kept;
   const bool keep;
-  KeyGenerator(const HostContext &c, uint64_t seed, bool sampled_ = false) : cx(c), sampled(sampled_), keep(sampled_ && seed != 0) {
+  // common_seed32: `pub` is keyed with these 32 bytes instead — the stream every party of a collective
+  // key generation draws the same seeds from; the draw order is untouched
+  KeyGenerator(const HostContext &c, uint64_t seed, bool sampled_ = false, const uint8_t *common_seed32 = nullptr)
+      : cx(c), sampled(sampled_), keep(sampled_ && seed != 0) {
     if (seed) {
       secret = std::make_unique<SecureRng>(seed, 1);
       pub = std::make_unique<SecureRng>(seed, 2);
@@ -493,6 +496,7 @@ public:
       secret = std::make_unique<SecureRng>();
       pub = std::make_unique<SecureRng>();
     }
+    if (common_seed32) pub = std::make_unique<SecureRng>(SecureRng::CommonSeed{common_seed32});
     if (sampled) {
       std::array<uint8_t, 32> rk_s = draw_key32(*secret);
       ek_pk = draw_key32(*secret);
@@ -924,6 +928,66 @@ inline HostCipher refresh_host(const HostContext &cx, const SecretKey &sk, const
   wipe_bytes(m.data(), m.size() * sizeof(u64));
   wipe_bytes(pt.data.data(), pt.data.size() * sizeof(u64));
   return out;
+}
+
+// ---- threshold decryption: the host twins of evah_decrypt_share_handles and evah_decrypt_combine_rows
+// is P 2^(sigma + 2) > Q_l ?  The flooding noise of P parties must leave the message below Q_l / 2.
+inline bool flood_exceeds_modulus(const std::vector<u64> &primes, uint32_t l, uint32_t parties, uint32_t sigma) {
+  unsigned __int128 Q = 1;
+  for (uint32_t i = 0; i < l; i++) {
+    if (Q >> 64) return false; // Q_l >= 2^64 2^29 already: above 64 2^64
+    Q *= primes[i];
+  }
+  return ((unsigned __int128)parties << (sigma + 2)) > Q;
+}
+// One party's share of a size-2 ciphertext of l limbs: h[i] = c1[i] s_p[i] + NTT_i(E), E = flood_wide(fk, sigma), the
+// residue of E_j under q_i being |E_j| mod q_i, negated for E_j < 0.  [l][N], canonical residues: the device's words.
+inline std::vector<u64> decrypt_share_host(const HostContext &cx, const SecretKey &sk, const HostCipher &ct, uint32_t sigma,
+                                           const std::array<uint8_t, 32> &fk) {
+  const uint32_t N = cx.N, l = ct.limbs;
+  if (ct.size != 2) throw std::invalid_argument("decryption share expects a size-2 ciphertext (relinearize first)");
+  if (l < 1 || l > cx.k - 1) throw std::invalid_argument("invalid limb count for this context");
+  if (ct.data.size() != (size_t)2 * l * N) throw std::invalid_argument("ciphertext words do not match its shape");
+  if (sk.s_ntt.size() != (size_t)cx.k * N) throw std::invalid_argument("secret key not present");
+  if (sigma < 1 || sigma > 62) throw std::invalid_argument("smudge_bits must be 1..62");
+  if (flood_exceeds_modulus(cx.primes, l, 1, sigma)) throw std::invalid_argument("smudge_bits leaves no room at this level");
+  std::vector<int64_t> E(N);
+  flood_wide(fk.data(), sigma, N, E.data());
+  std::vector<u64> h((size_t)l * N);
+  for (uint32_t i = 0; i < l; i++) {
+    const u64 q = cx.primes[i];
+    u64 *dst = h.data() + (size_t)i * N;
+    for (uint32_t j = 0; j < N; j++) {
+      const u64 r = (u64)(E[j] < 0 ? -E[j] : E[j]) % q;
+      dst[j] = E[j] < 0 && r ? q - r : r;
+    }
+    cx.ntt(i, dst);
+    const u64 *c1 = ct.data.data() + ((size_t)l + i) * N, *s = sk.s_ntt.data() + (size_t)i * N;
+    for (uint32_t j = 0; j < N; j++) dst[j] = evah::addmod(cx.mulm(c1[j], s[j], i), dst[j], q);
+  }
+  wipe_bytes(E.data(), E.size() * sizeof(int64_t));
+  return h;
+}
+// m = c0 + sum_p h_p per limb, in coefficient form [l][N] (decrypt_to_coeff's inverse transforms): what decode_coeff
+// turns into the slot values at the ciphertext's scale.  Needs no secret key.
+inline std::vector<u64> combine_shares_host(const HostContext &cx, const HostCipher &ct, const std::vector<const u64 *> &shares, uint32_t sigma) {
+  const uint32_t N = cx.N, l = ct.limbs;
+  if (ct.size != 2) throw std::invalid_argument("decryption share expects a size-2 ciphertext (relinearize first)");
+  if (l < 1 || l > cx.k - 1) throw std::invalid_argument("invalid limb count for this context");
+  if (ct.data.size() != (size_t)2 * l * N) throw std::invalid_argument("ciphertext words do not match its shape");
+  if (shares.empty() || shares.size() > 64) throw std::invalid_argument("the number of parties must be 1..64");
+  if (sigma < 1 || sigma > 62) throw std::invalid_argument("smudge_bits must be 1..62");
+  if (flood_exceeds_modulus(cx.primes, l, (uint32_t)shares.size(), sigma))
+    throw std::invalid_argument("smudge_bits leaves no room at this level for this many parties");
+  std::vector<u64> m(ct.data.begin(), ct.data.begin() + (size_t)l * N);
+  for (uint32_t i = 0; i < l; i++) {
+    const u64 q = cx.primes[i];
+    u64 *dst = m.data() + (size_t)i * N;
+    for (const u64 *h : shares)
+      for (uint32_t j = 0; j < N; j++) dst[j] = evah::addmod(dst[j], h[(size_t)i * N + j], q);
+    cx.intt(i, dst);
+  }
+  return m;
 }
 
 // ---- re-key to another key pair

@@ -703,6 +703,152 @@ inline HipValuationBatch HipPublic::rekey_batch(const HipValuationBatch &vb, con
   return out;
 }
 
+// a value of a valuation that is not a ciphertext, as decrypt() returns it: a plaintext decoded, a raw vector expanded
+inline std::vector<double> decode_unencrypted(const HostContext &hc, const SchemeValue &value, size_t vec_size) {
+  std::vector<double> v;
+  if (auto *p = std::get_if<HostPlain>(&value)) {
+    std::vector<u64> m = p->data;
+    for (uint32_t i = 0; i < p->limbs; i++) hc.intt(i, m.data() + (size_t)i * hc.N);
+    hc.decode_coeff(m.data(), p->limbs, p->scale, v);
+  } else {
+    ConstantValue{std::get<std::vector<double>>(value)}.expand_to(v, vec_size);
+  }
+  v.resize(vec_size);
+  return v;
+}
+// ---- threshold decryption: the joint opening of a valuation from every party's shares.  No secret key:
+// any context over the same parameters runs it.
+inline void HipPublic::check_shares(const std::vector<std::shared_ptr<DecryptionShares>> &shares) const {
+  if (shares.empty() || shares.size() > 64) throw std::invalid_argument("combine_shares: shares of 1..64 parties are needed");
+  for (size_t p = 0; p < shares.size(); p++) {
+    const std::string at = "combine_shares: share " + std::to_string(p);
+    if (!shares[p]) throw std::invalid_argument(at + " is None");
+    const std::string diff = rekey_params_differ(shares[p]->N, shares[p]->primes, *host);
+    if (!diff.empty()) throw std::invalid_argument(at + " was made under other encryption parameters: " + diff);
+    if (shares[p]->smudge_bits != shares[0]->smudge_bits)
+      throw std::invalid_argument(at + ": smudge_bits differs from share 0 (" + std::to_string(shares[p]->smudge_bits) + " against " +
+                                  std::to_string(shares[0]->smudge_bits) + ")");
+  }
+}
+// party p's piece for the rows [row, row + n) of value `name` at `limbs` limbs and `scale`; the piece must start there
+inline const SharePiece &HipPublic::share_piece(const DecryptionShares &sh, size_t p, const std::string &name, size_t row, size_t n, uint32_t limbs,
+                                                double scale) const {
+  const std::string at = "combine_shares: share " + std::to_string(p) + ", value " + name;
+  auto it = sh.values.find(name);
+  if (it == sh.values.end()) throw std::out_of_range(at + ": the share holds no such value");
+  size_t r = 0;
+  for (const SharePiece &piece : it->second) {
+    if (r == row) {
+      if (piece.n != n) throw std::invalid_argument(at + ": the instances are packed differently from the valuation's");
+      if (piece.limbs != limbs) throw std::invalid_argument(at + ": limb count differs from the ciphertext's");
+      if (piece.scale != scale) throw std::invalid_argument(at + ": scale differs from the ciphertext's");
+      return piece;
+    }
+    r += piece.n;
+  }
+  throw std::invalid_argument(at + ": the instances are packed differently from the valuation's");
+}
+// the piece as a handle this context's device reads: resident on this GPU — in place; else its words, uploaded
+inline const evah_ct *HipPublic::share_handle(const SharePiece &piece, std::vector<CtHandle> &keep) {
+  if (piece.h && piece.root->device == dev->device) return piece.h->h;
+  const std::vector<u64> &w = words(piece, host->N);
+  if (w.size() != (size_t)piece.n * piece.limbs * host->N) throw std::runtime_error("combine_shares: a share's words do not match its shape");
+  evah_ct *h = nullptr;
+  chk(evah_ct_upload_batch(dev->h, piece.n, 1, piece.limbs, piece.scale, (const uint64_t *)w.data(), &h));
+  keep.emplace_back(dev->h, h);
+  return h;
+}
+inline void HipPublic::check_combine_room(const std::string &name, uint32_t limbs, size_t parties, uint32_t smudge_bits) const {
+  if (limbs >= 1 && limbs <= host->k - 1 && flood_exceeds_modulus(host->primes, limbs, (uint32_t)parties, smudge_bits))
+    throw std::invalid_argument("value " + name + ": smudge_bits leaves no room at this level for this many parties");
+}
+inline Valuation HipPublic::combine_shares(const HipValuation &enc, const std::vector<std::shared_ptr<DecryptionShares>> &shares, const CKKSSignature &sig) {
+  check_shares(shares);
+  if (sig.vec_size <= 0) throw std::runtime_error("Signature vector size must be positive");
+  const bool on_dev = device_client_enabled();
+  if (on_dev) ensure_device(false);
+  Valuation out;
+  for (auto &kv : enc.values) {
+    const HostCipher *c = std::get_if<HostCipher>(&kv.second);
+    std::vector<double> v;
+    if (!c) { // unencrypted outputs pass through, as in decrypt()
+      out[kv.first] = decode_unencrypted(*host, kv.second, (size_t)sig.vec_size);
+      continue;
+    }
+    if (c->size != 2) throw std::invalid_argument("value " + kv.first + ": decryption share expects a size-2 ciphertext (relinearize first)");
+    check_combine_room(kv.first, c->limbs, shares.size(), shares[0]->smudge_bits);
+    std::vector<const SharePiece *> pieces;
+    for (size_t p = 0; p < shares.size(); p++) pieces.push_back(&share_piece(*shares[p], p, kv.first, 0, 1, c->limbs, c->scale));
+    if (on_dev) {
+      std::vector<CtHandle> keep;
+      const evah_ct *h = rekey_source(dev, *host, kv.first, *c, keep);
+      std::vector<const evah_ct *> hs;
+      for (const SharePiece *piece : pieces) hs.push_back(share_handle(*piece, keep));
+      v.resize((size_t)sig.vec_size);
+      chk(evah_decrypt_combine_rows(dev->h, &h, 1, hs.data(), (uint32_t)hs.size(), (uint32_t)sig.vec_size, EVAH_F64, v.data(), sizeof(double) * v.size(),
+                                    0, 1));
+    } else {
+      if (c->limbs < 1 || c->limbs > host->k - 1 || words(*c).size() != (size_t)2 * c->limbs * host->N)
+        throw std::runtime_error("value " + kv.first + ": ciphertext shape does not match its data or the encryption parameters");
+      std::vector<const u64 *> hs;
+      for (const SharePiece *piece : pieces) {
+        const std::vector<u64> &w = words(*piece, host->N);
+        if (w.size() != (size_t)c->limbs * host->N) throw std::runtime_error("combine_shares: a share's words do not match its shape");
+        hs.push_back(w.data());
+      }
+      const std::vector<u64> m = combine_shares_host(*host, *c, hs, shares[0]->smudge_bits);
+      host->decode_coeff(m.data(), c->limbs, c->scale, v);
+      v.resize((size_t)sig.vec_size);
+    }
+    out[kv.first] = std::move(v);
+  }
+  return out;
+}
+// the same for a batch, into rows as decrypt_array writes them: rows[name] is an array [B][vec_size] of dtype_out on the host,
+// or (rows_on_device) device memory of this context's state
+inline void HipPublic::combine_shares_array(const HipValuationBatch &vb, const std::vector<std::shared_ptr<DecryptionShares>> &shares,
+                                            const CKKSSignature &sig, int dtype_out, const std::map<std::string, void *> &rows, bool rows_on_device) {
+  check_shares(shares);
+  if (sig.vec_size <= 0) throw std::runtime_error("Signature vector size must be positive");
+  if (!device_client_enabled()) throw std::runtime_error("combine_shares of a batch needs a HIP device: none is visible, or EVA_DEVICE_CLIENT=0 keeps the client on the host");
+  ensure_device(false);
+  if (!vb.root) throw std::runtime_error("combine_shares: the batch holds no device handles");
+  const bool same_gpu = vb.root->device == dev->device;
+  const uint32_t n_out = (uint32_t)sig.vec_size;
+  const size_t row_bytes = (size_t)n_out * (dtype_out == EVAH_F32 ? 4 : dtype_out == EVAH_U8 ? 1 : 8);
+  for (auto &nc : vb.ciphers) {
+    char *out = static_cast<char *>(rows.at(nc.first));
+    const auto &segs = nc.second.segments;
+    size_t row = 0;
+    for (size_t s0 = 0; s0 < segs.size();) {
+      std::vector<CtHandle> keep;
+      std::vector<const evah_ct *> hs, sh;
+      size_t n = 0, s1 = s0;
+      while (s1 < segs.size() && n + segs[s1].n <= CLIENT_BATCH_MAX && segs[s1].limbs == segs[s0].limbs && segs[s1].scale == segs[s0].scale) {
+        if (segs[s1].size != 2) throw std::invalid_argument("value " + nc.first + ": decryption share expects a size-2 ciphertext (relinearize first)");
+        if (same_gpu) {
+          hs.push_back(segs[s1].h->h);
+        } else {
+          evah_ct *h = nullptr;
+          chk(evah_ct_copy(dev->h, segs[s1].h->h, &h));
+          keep.emplace_back(dev->h, h);
+          hs.push_back(h);
+        }
+        n += segs[s1++].n;
+      }
+      if (s1 == s0) throw std::runtime_error("value " + nc.first + ": a segment holds more than 64 instances");
+      check_combine_room(nc.first, segs[s0].limbs, shares.size(), shares[0]->smudge_bits);
+      for (size_t p = 0; p < shares.size(); p++) sh.push_back(share_handle(share_piece(*shares[p], p, nc.first, row, n, segs[s0].limbs, segs[s0].scale), keep));
+      chk(evah_decrypt_combine_rows(dev->h, hs.data(), (uint32_t)hs.size(), sh.data(), (uint32_t)sh.size(), n_out, dtype_out, out + row * row_bytes, row_bytes,
+                                    rows_on_device ? 1 : 0, rows_on_device ? 0 : 1));
+      if (rows_on_device) chk(evah_ctx_sync(dev->h)); // the uploads and copies made for this call are released behind it
+      row += n;
+      s0 = s1;
+    }
+    if (row != vb.B) throw std::runtime_error("value " + nc.first + ": the segments do not hold every instance");
+  }
+}
+
 class HipSecret {
 public:
   std::shared_ptr<HostContext> host;
@@ -987,12 +1133,8 @@ public:
       (void)words(*c);
       auto m = decrypt_to_coeff(*host, sk, *c);
       host->decode_coeff(m.data(), c->limbs, c->scale, v);
-    } else if (auto *p = std::get_if<HostPlain>(&value)) {
-      std::vector<u64> m = p->data;
-      for (uint32_t i = 0; i < p->limbs; i++) host->intt(i, m.data() + (size_t)i * host->N);
-      host->decode_coeff(m.data(), p->limbs, p->scale, v);
     } else {
-      ConstantValue{std::get<std::vector<double>>(value)}.expand_to(v, (size_t)sig.vec_size);
+      return decode_unencrypted(*host, value, (size_t)sig.vec_size);
     }
     v.resize((size_t)sig.vec_size);
     return v;
@@ -1232,6 +1374,129 @@ public:
     }
     return out;
   }
+
+  // ---- threshold decryption: this party's share h = c1 s_p + NTT(E) of every encrypted value, E flooding
+  // noise of smudge_bits bits drawn from a 32-byte key per value.  One secret stream per call (seed != 0: SecureRng(seed,
+  // 5), the reproducible test hook, NOT secret-grade): names sorted, instances in order, 4 words per value, all drawn before
+  // the first device call and wiped after.  Unencrypted and raw values are skipped.
+  std::shared_ptr<DecryptionShares> new_shares(uint32_t smudge_bits, bool batch, size_t B) const {
+    if (smudge_bits < 1 || smudge_bits > 62) throw std::invalid_argument("smudge_bits must be 1..62");
+    if (sk.s_ntt.size() != (size_t)host->k * host->N) throw std::invalid_argument("decrypt_share: secret key not present");
+    auto out = std::make_shared<DecryptionShares>();
+    out->N = host->N;
+    out->smudge_bits = smudge_bits;
+    out->primes = host->primes;
+    out->batch = batch;
+    out->B = B;
+    return out;
+  }
+  std::shared_ptr<DecryptionShares> decrypt_share(const HipValuation &enc, uint32_t smudge_bits, uint64_t seed = 0) {
+    auto out = new_shares(smudge_bits, false, 1);
+    std::vector<std::pair<std::string, const HostCipher *>> cs; // (std::map / sorted below: names in order)
+    for (auto &kv : enc.values)
+      if (auto *c = std::get_if<HostCipher>(&kv.second)) cs.emplace_back(kv.first, c);
+    std::sort(cs.begin(), cs.end(), [](auto &a, auto &b) { return a.first < b.first; });
+    for (auto &nc : cs) {
+      if (nc.second->size != 2) throw std::invalid_argument("value " + nc.first + ": decryption share expects a size-2 ciphertext (relinearize first)");
+      if (nc.second->limbs >= 1 && nc.second->limbs <= host->k - 1 && flood_exceeds_modulus(host->primes, nc.second->limbs, 1, smudge_bits))
+        throw std::invalid_argument("value " + nc.first + ": smudge_bits leaves no room at this level");
+    }
+    std::unique_ptr<SecureRng> stream = seed ? std::make_unique<SecureRng>(seed, 5) : std::make_unique<SecureRng>();
+    std::vector<std::vector<std::array<uint8_t, 32>>> fk(1);
+    WipeKeyRows wipe_keys{fk};
+    for (size_t i = 0; i < cs.size(); i++) fk[0].push_back(draw_key32(*stream));
+    for (size_t i = 0; i < cs.size(); i++) {
+      const std::string &name = cs[i].first;
+      const HostCipher &c = *cs[i].second;
+      SharePiece piece;
+      piece.n = 1;
+      piece.limbs = c.limbs;
+      piece.scale = c.scale;
+      if (on_device()) {
+        check_device_shape(name, c);
+        std::vector<CtHandle> keep;
+        const evah_ct *h = nullptr;
+        if (c.dev && c.dev->root->device == dev->device) { // resident on this GPU, whichever key pair's state: read in place
+          h = c.dev->h->h;
+        } else {
+          evah_ct *up = nullptr;
+          chk(evah_ct_upload(dev->h, c.size, c.limbs, c.scale, (const uint64_t *)words(c).data(), &up));
+          keep.emplace_back(dev->h, up);
+          h = up;
+        }
+        evah_ct *o = nullptr;
+        chk(evah_decrypt_share_handles(dev->h, &h, 1, smudge_bits, fk[0][i].data(), &o));
+        piece.h = std::make_shared<CtHandle>(dev->h, o);
+        piece.root = dev;
+      } else {
+        if (c.limbs < 1 || c.limbs > host->k - 1 || words(c).size() != (size_t)2 * c.limbs * host->N)
+          throw std::runtime_error("value " + name + ": ciphertext shape does not match its data or the encryption parameters");
+        piece.data = decrypt_share_host(*host, sk, c, smudge_bits, fk[0][i]);
+      }
+      out->values[name].push_back(std::move(piece));
+    }
+    return out;
+  }
+  // the same for a batch of batched handles: per name, consecutive segments of one level are packed into calls of <= 64
+  // instances, as decrypt_array packs them; a batch resident on another state of the same GPU is read in place
+  std::shared_ptr<DecryptionShares> decrypt_share_batch(const HipValuationBatch &vb, uint32_t smudge_bits, uint64_t seed = 0) {
+    require_array_path(on_device(), resident, "decrypt_share");
+    auto out = new_shares(smudge_bits, true, vb.B);
+    if (!vb.root) throw std::runtime_error("decrypt_share: the batch holds no device handles");
+    const bool same_gpu = vb.root->device == dev->device;
+    for (auto &nc : vb.ciphers)
+      for (auto &seg : nc.second.segments) {
+        if (seg.size != 2) throw std::invalid_argument("value " + nc.first + ": decryption share expects a size-2 ciphertext (relinearize first)");
+        if (seg.limbs >= 1 && seg.limbs <= host->k - 1 && flood_exceeds_modulus(host->primes, seg.limbs, 1, smudge_bits))
+          throw std::invalid_argument("value " + nc.first + ": smudge_bits leaves no room at this level");
+      }
+    std::unique_ptr<SecureRng> stream = seed ? std::make_unique<SecureRng>(seed, 5) : std::make_unique<SecureRng>();
+    std::vector<std::vector<std::array<uint8_t, 32>>> fk(vb.ciphers.size()); // per name (sorted: std::map), per instance
+    WipeKeyRows wipe_keys{fk};
+    for (size_t i = 0; i < vb.ciphers.size(); i++)
+      for (size_t b = 0; b < vb.B; b++) fk[i].push_back(draw_key32(*stream));
+    size_t i = 0;
+    for (auto &nc : vb.ciphers) {
+      const auto &segs = nc.second.segments;
+      std::vector<SharePiece> &pieces = out->values[nc.first];
+      size_t row = 0;
+      for (size_t s0 = 0; s0 < segs.size();) {
+        std::vector<CtHandle> keep;
+        std::vector<const evah_ct *> hs;
+        size_t n = 0, s1 = s0;
+        while (s1 < segs.size() && n + segs[s1].n <= CLIENT_BATCH_MAX && segs[s1].limbs == segs[s0].limbs && segs[s1].scale == segs[s0].scale) {
+          if (same_gpu) {
+            hs.push_back(segs[s1].h->h);
+          } else {
+            evah_ct *h = nullptr;
+            chk(evah_ct_copy(dev->h, segs[s1].h->h, &h));
+            keep.emplace_back(dev->h, h);
+            hs.push_back(h);
+          }
+          n += segs[s1++].n;
+        }
+        if (s1 == s0) throw std::runtime_error("value " + nc.first + ": a segment holds more than 64 instances");
+        if (row + n > vb.B) throw std::runtime_error("value " + nc.first + ": the segments hold more instances than the batch");
+        std::vector<uint8_t> keys = keys_flat(fk[i].data() + row, n);
+        evah_ct *o = nullptr;
+        const int rc = evah_decrypt_share_handles(dev->h, hs.data(), (uint32_t)hs.size(), smudge_bits, keys.data(), &o);
+        wipe_bytes(keys.data(), keys.size());
+        chk(rc);
+        SharePiece piece;
+        piece.n = (uint32_t)n;
+        piece.limbs = segs[s0].limbs;
+        piece.scale = segs[s0].scale;
+        piece.h = std::make_shared<CtHandle>(dev->h, o);
+        piece.root = dev;
+        pieces.push_back(std::move(piece));
+        row += n;
+        s0 = s1;
+      }
+      if (row != vb.B) throw std::runtime_error("value " + nc.first + ": the segments do not hold every instance");
+      i++;
+    }
+    return out;
+  }
 };
 
 // generateKeys (seal.cpp:174-203): prime chain from bit sizes, secret/public key, one Galois key
@@ -1246,14 +1511,20 @@ public:
 // (KeyGenerator's sampled mode says which) — compressed keys again.  With device_keygen the device draws them:
 // one evah_keygen_public and one evah_keygen_set for all evaluation keys, and in the default single-device mode no c0
 // comes back until somebody needs it (SwitchKey::c0_words).  Without it the host twin computes the same words.
+// common_seed: the collective key generation — the sampled derivation with the public stream keyed by 32
+// bytes every party knows, so that all parties expand the same a and the same c1 of every digit, and their keys add up
+// (combine_public_contexts).  The secret stream is the party's own, as ever.
 inline std::pair<std::shared_ptr<HipPublic>, std::shared_ptr<HipSecret>>
 generate_keys(const CKKSParameters &params, uint64_t seed = 0, bool compress_keys = false, bool device_keygen = false,
-              const std::vector<int> *devices = nullptr, const std::string *shard = nullptr, bool device_sampling = false) {
+              const std::vector<int> *devices = nullptr, const std::string *shard = nullptr, bool device_sampling = false,
+              const std::array<uint8_t, 32> *common_seed = nullptr) {
+  if (common_seed) device_sampling = true; // the collective key generation is the sampled derivation on a stream the parties share
   std::vector<int> bits(params.prime_bits.begin(), params.prime_bits.end());
   if (bits.size() < 2) throw std::invalid_argument("need at least two primes (data + special)");
   auto primes = evah::coeff_modulus_create(params.poly_modulus_degree, bits);
   auto host = std::make_shared<HostContext>(params.poly_modulus_degree, primes);
-  KeyGenerator kg(*host, seed, device_sampling); // seed == 0: keyed from the OS; otherwise the reproducible test hook
+  // seed == 0: keyed from the OS; otherwise the reproducible test hook.  common_seed: the public stream the parties share
+  KeyGenerator kg(*host, seed, device_sampling, common_seed ? common_seed->data() : nullptr);
   auto pub = std::make_shared<HipPublic>();
   auto sec = std::make_shared<HipSecret>();
   sec->holder = pub->holder; // one device state for the pair: results stay resident from encrypt to decrypt
@@ -1357,6 +1628,72 @@ generate_keys(const CKKSParameters &params, uint64_t seed = 0, bool compress_key
   if (device_keygen && install) pub->eval_keys_installed();
   sec->key_randomness = std::move(kg.kept);
   return {pub, sec};
+}
+
+// The collective public context of parties whose keys were generated with one common_seed: the public
+// key and every Galois key present in ALL contexts, under s = sum_p s_p.  All parties expanded the same a (pk[1]) and the
+// same c1 of every digit, so c0 adds: sum_p -(a s_p + e_p) = -(a s + sum_p e_p), and a Galois digit's P s_p(X^elt) terms
+// add to P s(X^elt).  The sums run on the host.  No relinearization key: s^2 is not the sum of the s_p^2.
+inline std::shared_ptr<HipPublic> combine_public_contexts(const std::vector<std::shared_ptr<HipPublic>> &ctxs) {
+  if (ctxs.empty() || ctxs.size() > 64) throw std::invalid_argument("combine_public_contexts: 1..64 public contexts are needed");
+  for (auto &c : ctxs)
+    if (!c) throw std::invalid_argument("combine_public_contexts: a context is None");
+  const HostContext &hc = *ctxs[0]->host;
+  const size_t N = hc.N, k = hc.k, poly = k * N;
+  auto add_rows = [&](std::vector<u64> &acc, const u64 *src, size_t rows) { // acc [rows][N] += src, row r under prime r % k
+    for (size_t r = 0; r < rows; r++) {
+      const u64 q = hc.primes[r % k];
+      u64 *a = acc.data() + r * N;
+      const u64 *b = src + r * N;
+      for (size_t j = 0; j < N; j++) a[j] = evah::addmod(a[j], b[j], q);
+    }
+  };
+  auto out = std::make_shared<HipPublic>();
+  out->host = ctxs[0]->host;
+  out->collective = true;
+  out->pk.data.assign(ctxs[0]->pk.data.begin(), ctxs[0]->pk.data.end());
+  if (out->pk.data.size() != 2 * poly) throw std::invalid_argument("combine_public_contexts: context 0 holds no public key");
+  for (size_t p = 1; p < ctxs.size(); p++) {
+    const std::string diff = rekey_params_differ(ctxs[p]->host->N, ctxs[p]->host->primes, hc);
+    if (!diff.empty())
+      throw std::invalid_argument("combine_public_contexts: context " + std::to_string(p) + " has other encryption parameters than context 0: " + diff);
+    const auto &pk = ctxs[p]->pk.data;
+    if (pk.size() != 2 * poly) throw std::invalid_argument("combine_public_contexts: context " + std::to_string(p) + " holds no public key");
+    if (!std::equal(pk.begin() + poly, pk.end(), out->pk.data.begin() + poly))
+      throw std::invalid_argument("public contexts do not share a common seed (context " + std::to_string(p) + " differs from context 0)");
+    std::vector<u64> c0(out->pk.data.begin(), out->pk.data.begin() + poly);
+    add_rows(c0, pk.data(), k);
+    std::copy(c0.begin(), c0.end(), out->pk.data.begin());
+  }
+  for (size_t p = 1; p < ctxs.size(); p++) // elements context 0 lacks are dropped as well
+    for (auto &kv : ctxs[p]->galois)
+      if (!ctxs[0]->galois.count(kv.first) && std::find(out->dropped_galois.begin(), out->dropped_galois.end(), kv.first) == out->dropped_galois.end())
+        out->dropped_galois.push_back(kv.first);
+  for (auto &kv : ctxs[0]->galois) {
+    const uint32_t elt = kv.first;
+    bool everywhere = true;
+    for (size_t p = 1; p < ctxs.size(); p++) everywhere = everywhere && ctxs[p]->galois.count(elt);
+    if (!everywhere) { // kept out, and named: rotations by it are refused at execute ("Galois key not present")
+      out->dropped_galois.push_back(elt);
+      continue;
+    }
+    const SwitchKey &k0 = kv.second;
+    if (!k0.compressed()) throw std::invalid_argument("combine_public_contexts: context 0's Galois keys are not seed-compressed (generate_keys(..., common_seed))");
+    SwitchKey sum;
+    sum.n_digits = k0.n_digits;
+    sum.seeds = k0.seeds;
+    sum.c0 = k0.c0_words();
+    for (size_t p = 1; p < ctxs.size(); p++) {
+      const SwitchKey &kp = ctxs[p]->galois.at(elt);
+      if (kp.n_digits != k0.n_digits || kp.seeds != k0.seeds)
+        throw std::invalid_argument("public contexts do not share a common seed (context " + std::to_string(p) + " differs from context 0)");
+      const std::vector<u64> &c0 = kp.c0_words();
+      if (c0.size() != sum.c0.size()) throw std::invalid_argument("combine_public_contexts: context " + std::to_string(p) + ": Galois key words do not match their shape");
+      add_rows(sum.c0, c0.data(), (size_t)sum.n_digits * k);
+    }
+    out->galois.emplace(elt, std::move(sum));
+  }
+  return out;
 }
 
 } // namespace evahost

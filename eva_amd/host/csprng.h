@@ -85,6 +85,36 @@ inline void sampled_small(const uint8_t rk[32], uint32_t p, uint32_t N, int8_t *
   for (int i = 0; i < 16; i++) v[i] = 0;
 }
 
+// The flooding noise of a decryption share from its 32-byte key fk: coefficient j takes the little-endian
+// u64 word w = j % 8 of the ChaCha20 block with key = fk, block counter j / 8 (state words 12-13), nonce
+// 0x666c000000000000 (words 14-15; a tag of its own beside 0x6331... of the seeded polynomials and 0x736d... of the small
+// ones).  E_j = (int64)(w >> (63 - sigma)) - 2^sigma: exactly uniform on [-2^sigma, 2^sigma), no rejection,
+// 1 <= sigma <= 62.  A shorter N is a prefix.  The device twin is csrc/sampled.hip.h flood_block.
+constexpr uint64_t FLOOD_NONCE = 0x666c000000000000ull;
+inline void flood_wide(const uint8_t fk[32], uint32_t sigma, uint32_t N, int64_t *out) {
+  if (sigma < 1 || sigma > 62) throw std::invalid_argument("smudge_bits must be 1..62");
+  static const uint32_t sg[4] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u};
+  uint32_t st[16], w[16];
+  std::memcpy(st, sg, 16);
+  std::memcpy(st + 4, fk, 32);
+  st[14] = (uint32_t)FLOOD_NONCE;
+  st[15] = (uint32_t)(FLOOD_NONCE >> 32);
+  for (uint32_t j0 = 0; j0 < N; j0 += 8) {
+    const uint64_t blk = j0 / 8;
+    st[12] = (uint32_t)blk;
+    st[13] = (uint32_t)(blk >> 32);
+    chacha20_block(st, w);
+    for (uint32_t r = 0; r < 8 && j0 + r < N; r++) {
+      const uint64_t x = (uint64_t)w[2 * r] | ((uint64_t)w[2 * r + 1] << 32);
+      out[j0 + r] = (int64_t)(x >> (63 - sigma)) - ((int64_t)1 << sigma);
+    }
+  }
+  volatile uint32_t *v = st; // the key and the last block do not stay on the stack
+  for (int i = 0; i < 16; i++) v[i] = 0;
+  v = w;
+  for (int i = 0; i < 16; i++) v[i] = 0;
+}
+
 class SecureRng {
 public:
   using result_type = uint64_t;
@@ -109,6 +139,10 @@ public:
     std::memcpy(nonce, &stream, 8);
     init(key, nonce);
   }
+  // the common public stream of a collective key generation: every party that keys it with the same 32
+  // bytes draws the same seeds; nothing secret comes from it
+  struct CommonSeed { const uint8_t *key32; };
+  explicit SecureRng(CommonSeed cs) { init(cs.key32, reinterpret_cast<const unsigned char *>("evacrs\0\0")); }
   ~SecureRng() { wipe(state_, sizeof state_); wipe(block_, sizeof block_); }
   SecureRng(const SecureRng &) = delete;
   SecureRng &operator=(const SecureRng &) = delete;

@@ -191,6 +191,8 @@ PYBIND11_MODULE(_eva, m) {
   m.def("save", [seal_compr](const HipPublic &o, const std::string &path, const std::string &format) {
     bool seal = false;
     const sealfmt::Compr c = seal_compr(format, seal);
+    if (seal && o.collective)
+      throw std::invalid_argument("a collective context has no relinearization key, which the SEAL format requires: save it with format='native'");
     if (seal) save_wire_to_file("SEALPublic", sealfmt::encode_public(o, c), path);
     else save_to_file(Kind::Public, o, path);
   }, py::arg("obj"), py::arg("path"), py::arg("format") = "native");
@@ -206,6 +208,13 @@ PYBIND11_MODULE(_eva, m) {
     (void)seal_compr(format, seal);
     if (seal) throw std::invalid_argument("a RekeyKey has no SEAL format: save it with format='native'");
     save_to_file(Kind::RekeyKey, o, path);
+  }, py::arg("obj"), py::arg("path"), py::arg("format") = "native");
+  // decryption shares have this repo's container only (kind 8): SEAL has no such object
+  m.def("save", [seal_compr](const DecryptionShares &o, const std::string &path, const std::string &format) {
+    bool seal = false;
+    (void)seal_compr(format, seal);
+    if (seal) throw std::invalid_argument("DecryptionShares have no SEAL format: save them with format='native'");
+    save_to_file(Kind::Shares, o, path);
   }, py::arg("obj"), py::arg("path"), py::arg("format") = "native");
   // test hooks of the SEAL object format
   m.def("_blake2b_256", [](py::bytes data) {
@@ -267,6 +276,7 @@ PYBIND11_MODULE(_eva, m) {
     if (auto *p = std::get_if<HipValuation>(&k)) return py::cast(std::move(*p));
     if (auto *p = std::get_if<std::shared_ptr<HipPublic>>(&k)) return py::cast(*p);
     if (auto *p = std::get_if<std::shared_ptr<RekeyKey>>(&k)) return py::cast(*p);
+    if (auto *p = std::get_if<std::shared_ptr<DecryptionShares>>(&k)) return py::cast(*p);
     return py::cast(std::get<std::shared_ptr<HipSecret>>(k));
   }, py::arg("path"), "Load a previously saved object (same class as was saved)");
 
@@ -318,17 +328,28 @@ PYBIND11_MODULE(_eva, m) {
   // device_keygen: the same compressed keys, generated on the GPU from the secret key and the host's draws
   // device_sampling: every polynomial of the key set from a 32-byte key of its own, drawn on the GPU with device_keygen
   mseal.def("generate_keys", [](const CKKSParameters &p, uint64_t seed, py::object devices, py::object shard, bool compress_keys, bool device_keygen,
-                                bool device_sampling) {
+                                bool device_sampling, py::object common_seed) {
     // devices / shard reach generate_keys before any key is made: device key generation runs on member 0's device
     std::vector<int> dv;
     std::string sh;
     if (!devices.is_none()) dv = devices.cast<std::vector<int>>();
     if (!shard.is_none()) sh = shard.cast<std::string>();
-    auto kp = generate_keys(p, seed, compress_keys, device_keygen, devices.is_none() ? nullptr : &dv, shard.is_none() ? nullptr : &sh, device_sampling);
+    std::array<uint8_t, 32> cs{};
+    if (!common_seed.is_none()) {
+      const std::string k = common_seed.cast<py::bytes>();
+      if (k.size() != 32) throw std::invalid_argument("common_seed is 32 bytes");
+      std::memcpy(cs.data(), k.data(), 32);
+    }
+    auto kp = generate_keys(p, seed, compress_keys, device_keygen, devices.is_none() ? nullptr : &dv, shard.is_none() ? nullptr : &sh, device_sampling,
+                            common_seed.is_none() ? nullptr : &cs);
     if (g_num_threads > 1) kp.first->num_queues = std::min(g_num_threads, 8);
     return kp;
   }, py::arg("abstract_params"), py::arg("seed") = 0, py::arg("devices") = py::none(), py::arg("shard") = py::none(),
-     py::arg("compress_keys") = false, py::arg("device_keygen") = false, py::arg("device_sampling") = false);
+     py::arg("compress_keys") = false, py::arg("device_keygen") = false, py::arg("device_sampling") = false, py::arg("common_seed") = py::none());
+  mseal.def("combine_public_contexts", &combine_public_contexts, py::arg("public_contexts"),
+            "The collective public context of parties whose keys were made with one generate_keys(..., common_seed=) (DESIGN.md 1.14): "
+            "public key and the Galois keys present in all contexts under the sum of the parties' secrets; no relinearization key. "
+            "It encrypts, executes everything but relinearize, is a make_rekey_key target, and saves / loads");
   // test hook: small polynomial p of a 32-byte randomness key (csprng.h sampled_small) -> int8 [N]
   mseal.def("_sampled_small", [](py::bytes rk, uint32_t p, uint32_t N) {
     const std::string k = rk;
@@ -337,6 +358,51 @@ PYBIND11_MODULE(_eva, m) {
     sampled_small((const uint8_t *)k.data(), p, N, out.mutable_data());
     return out;
   }, py::arg("rkey"), py::arg("p"), py::arg("N"));
+  // test hooks of threshold decryption: the flooding noise of a 32-byte key (csprng.h flood_wide) -> int64
+  // [N], and the host twins of evah_decrypt_share_handles / evah_decrypt_combine_rows (ckks_host.h) on raw words
+  mseal.def("_flood_wide", [](py::bytes fk, uint32_t sigma, uint32_t N) {
+    const std::string k = fk;
+    if (k.size() != 32) throw std::invalid_argument("a flooding key is 32 bytes");
+    py::array_t<int64_t> out({(py::ssize_t)N});
+    flood_wide((const uint8_t *)k.data(), sigma, N, out.mutable_data());
+    return out;
+  }, py::arg("fkey"), py::arg("smudge_bits"), py::arg("N"));
+  mseal.def("_decrypt_share_host", [](uint32_t N, const std::vector<uint64_t> &primes, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> s_ntt,
+                                      py::array_t<uint64_t, py::array::c_style | py::array::forcecast> ct, uint32_t sigma, py::bytes fk) {
+    HostContext h(N, std::vector<u64>(primes.begin(), primes.end()));
+    const std::string k = fk;
+    if (k.size() != 32) throw std::invalid_argument("a flooding key is 32 bytes");
+    if (ct.ndim() != 3) throw std::invalid_argument("ciphertext words are [size][limbs][N]");
+    SecretKey sk;
+    sk.s_ntt.assign((const u64 *)s_ntt.data(), (const u64 *)s_ntt.data() + s_ntt.size());
+    HostCipher c;
+    c.size = (uint32_t)ct.shape(0);
+    c.limbs = (uint32_t)ct.shape(1);
+    c.data.assign((const u64 *)ct.data(), (const u64 *)ct.data() + ct.size());
+    std::array<uint8_t, 32> key;
+    std::memcpy(key.data(), k.data(), 32);
+    return to_numpy(decrypt_share_host(h, sk, c, sigma, key), {(py::ssize_t)c.limbs, (py::ssize_t)N});
+  }, py::arg("N"), py::arg("primes"), py::arg("s_ntt"), py::arg("ct"), py::arg("smudge_bits"), py::arg("fkey"));
+  mseal.def("_combine_shares_host", [](uint32_t N, const std::vector<uint64_t> &primes, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> ct,
+                                       py::array_t<uint64_t, py::array::c_style | py::array::forcecast> shares, uint32_t sigma, double scale) {
+    HostContext h(N, std::vector<u64>(primes.begin(), primes.end()));
+    if (ct.ndim() != 3) throw std::invalid_argument("ciphertext words are [size][limbs][N]");
+    HostCipher c;
+    c.size = (uint32_t)ct.shape(0);
+    c.limbs = (uint32_t)ct.shape(1);
+    c.scale = scale;
+    c.data.assign((const u64 *)ct.data(), (const u64 *)ct.data() + ct.size());
+    if (shares.ndim() != 3 || shares.shape(1) != (py::ssize_t)c.limbs || shares.shape(2) != (py::ssize_t)N)
+      throw std::invalid_argument("shares are [parties][limbs][N]");
+    std::vector<const u64 *> hs;
+    for (py::ssize_t p = 0; p < shares.shape(0); p++) hs.push_back((const u64 *)shares.data() + (size_t)p * c.limbs * N);
+    const std::vector<u64> m = combine_shares_host(h, c, hs, sigma);
+    std::vector<double> v;
+    h.decode_coeff(m.data(), c.limbs, scale, v);
+    py::array_t<double> vals({(py::ssize_t)v.size()});
+    std::memcpy(vals.mutable_data(), v.data(), v.size() * sizeof(double));
+    return py::make_tuple(to_numpy(m, {(py::ssize_t)c.limbs, (py::ssize_t)N}), vals);
+  }, py::arg("N"), py::arg("primes"), py::arg("ct"), py::arg("shares"), py::arg("smudge_bits"), py::arg("scale"));
   // test hook: the host twin of evah_keygen_rekey (ckks_host.h rekey_keygen_host) on raw words -> [digits][2][k][N]
   mseal.def("_rekey_keygen_host", [](uint32_t N, const std::vector<uint64_t> &primes, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> s_ntt,
                                      py::array_t<uint64_t, py::array::c_style | py::array::forcecast> pk,
@@ -352,6 +418,27 @@ PYBIND11_MODULE(_eva, m) {
     for (uint32_t J = 0; J < D; J++) std::memcpy(rk[J].data(), rkeys.data() + (size_t)32 * J, 32);
     return to_numpy(rekey_keygen_host(h, sk, pkt, D, rk.data()), {(py::ssize_t)D, 2, (py::ssize_t)h.k, (py::ssize_t)N});
   }, py::arg("N"), py::arg("primes"), py::arg("s_ntt"), py::arg("pk"), py::arg("rkeys"));
+  py::class_<DecryptionShares, std::shared_ptr<DecryptionShares>>(mseal, "DecryptionShares",
+                                                                  "One party's contribution to the joint opening of a valuation (DESIGN.md 1.14): made by "
+                                                                  "SEALSecret.decrypt_share, combined by SEALPublic.combine_shares; saves and loads")
+      .def_readonly("poly_modulus_degree", &DecryptionShares::N)
+      .def_readonly("primes", &DecryptionShares::primes)
+      .def_readonly("smudge_bits", &DecryptionShares::smudge_bits)
+      .def_readonly("batch", &DecryptionShares::batch)
+      .def_readonly("B", &DecryptionShares::B)
+      .def("names", [](const DecryptionShares &d) {
+        std::vector<std::string> n;
+        for (auto &kv : d.values) n.push_back(kv.first);
+        return n;
+      })
+      .def("words", [](const DecryptionShares &d, const std::string &name) {
+        auto it = d.values.find(name);
+        if (it == d.values.end()) throw py::key_error(name);
+        py::list out; // one array [n][limbs][N] per piece (a resident piece is downloaded)
+        for (const SharePiece &p : it->second)
+          out.append(to_numpy(words(p, d.N), {(py::ssize_t)p.n, (py::ssize_t)p.limbs, (py::ssize_t)d.N}));
+        return out;
+      }, py::arg("name"), "the share of `name` as host words: a list of arrays [instances][limbs][N], one per device call");
   py::class_<RekeyKey, std::shared_ptr<RekeyKey>>(mseal, "RekeyKey",
                                                   "The key that takes results under one key pair to another of the same parameters (DESIGN.md 1.13): made by "
                                                   "SEALSecret.make_rekey_key from the target's public context, applied by the target's SEALPublic.rekey")
@@ -578,6 +665,44 @@ PYBIND11_MODULE(_eva, m) {
       .def_readwrite("resident", &HipPublic::resident, "keep valuations in HBM: encrypt/execute return device handles and execute does not wait for the GPU (EVA_RESIDENT=0: host valuations)")
       .def_readwrite("graph_copy_limit", &HipPublic::graph_copy_limit, "device-resident inputs above this many bytes are walked eagerly instead of copied into a captured graph's slots")
       .def("synchronize", &HipPublic::synchronize, "wait for everything this context has enqueued")
+      .def("combine_shares", [](HipPublic &p, py::object enc, const std::vector<std::shared_ptr<DecryptionShares>> &shares, const CKKSSignature &sig,
+                                py::object dtype, bool device) -> py::object {
+        if (!py::isinstance<HipValuationBatch>(enc)) return py::cast(p.combine_shares(enc.cast<const HipValuation &>(), shares, sig));
+        const HipValuationBatch &vb = enc.cast<const HipValuationBatch &>();
+        const py::dtype dt = py::dtype::from_args(dtype);
+        int code;
+        if (dt.kind() == 'f' && dt.itemsize() == 8) code = EVAH_F64;
+        else if (dt.kind() == 'f' && dt.itemsize() == 4) code = EVAH_F32;
+        else if (dt.kind() == 'u' && dt.itemsize() == 1) code = EVAH_U8;
+        else throw std::invalid_argument("combine_shares: dtype must be float64, float32 or uint8");
+        if (sig.vec_size <= 0) throw std::runtime_error("Signature vector size must be positive");
+        py::dict out;
+        std::map<std::string, void *> rows;
+        for (auto &kv : vb.ciphers) {
+          if (device) {
+            auto a = std::make_shared<DeviceArray>(p.device_state(), code, vb.B, (size_t)sig.vec_size);
+            rows[kv.first] = a->ptr();
+            out[py::str(kv.first)] = a;
+          } else {
+            py::array a(dt, std::vector<py::ssize_t>{(py::ssize_t)vb.B, (py::ssize_t)sig.vec_size});
+            rows[kv.first] = a.mutable_data();
+            out[py::str(kv.first)] = a;
+          }
+        }
+        p.combine_shares_array(vb, shares, sig, code, rows, device);
+        for (auto &kv : vb.shared) { // one value for all instances, as decrypt_array returns it
+          if (std::holds_alternative<HostCipher>(kv.second)) continue;
+          const std::vector<double> v = decode_unencrypted(*p.host, kv.second, (size_t)sig.vec_size);
+          py::array_t<double> a({(py::ssize_t)vb.B, (py::ssize_t)sig.vec_size});
+          for (size_t b = 0; b < vb.B; b++) std::copy(v.begin(), v.end(), a.mutable_data() + b * v.size());
+          out[py::str(kv.first)] = code == EVAH_U8 ? as_uint8(a) : code == EVAH_F32 ? py::array(a.attr("astype")(dt)) : py::array(a);
+        }
+        return out;
+      }, py::arg("enc"), py::arg("shares"), py::arg("signature"), py::arg("dtype") = py::module_::import("numpy").attr("float64"), py::arg("device") = false,
+           "Open a valuation from the decryption shares of EVERY party of a collective key (DESIGN.md 1.14): m = c0 + the sum of the shares, "
+           "then decrypt()'s decoder. Needs no secret key. enc: a SEALValuation (returns what decrypt returns) or a SEALValuationBatch (returns what "
+           "decrypt_array returns, dtype and device as there); shares: one DecryptionShares per party, made from this enc with one smudge_bits. "
+           "A slot differs from the decryption under the whole key by at most N * P * 2^smudge_bits / scale")
       .def("install_rekey_key", [](HipPublic &p, std::shared_ptr<RekeyKey> rk) { return p.install_rekey_key(rk); }, py::arg("rekey_key"),
            "upload a RekeyKey to this context's device state (once per key); returns its slot")
       .def("rekey", [](HipPublic &p, py::object enc, std::shared_ptr<RekeyKey> rk) -> py::object {
@@ -606,6 +731,9 @@ PYBIND11_MODULE(_eva, m) {
       .def_readwrite("num_queues", &HipPublic::num_queues, "HIP streams independent DAG nodes are spread over")
       .def_property_readonly("poly_modulus_degree", [](const HipPublic &p) { return p.host->N; })
       .def_property_readonly("primes", [](const HipPublic &p) { return std::vector<uint64_t>(p.host->primes.begin(), p.host->primes.end()); })
+      .def_readonly("dropped_galois_elements", &HipPublic::dropped_galois,
+                    "combine_public_contexts: the Galois elements that some party's context lacked and this collective context therefore has no key for")
+      .def_readonly("collective", &HipPublic::collective, "made by combine_public_contexts (DESIGN.md 1.14): no relinearization key")
       // host FP64 encoder + host NTT: the plaintext an Encode node produces (tests pin the
       // integer path "from the encoded plaintext onward")
       .def("_encode", [](const HipPublic &p, const std::vector<double> &values, uint32_t scale_bits, uint32_t level) {
@@ -623,6 +751,7 @@ PYBIND11_MODULE(_eva, m) {
       }, py::arg("values"), py::arg("scale_bits"), py::arg("level"))
       // the full words of a key, materialised for the caller when the context keeps it compressed (which it goes on doing)
       .def("relin_key", [](const HipPublic &p) {
+        if (p.collective) throw std::invalid_argument("relinearization key not present (a collective context has none)");
         std::vector<u64> tmp;
         return to_numpy(p.relin.words(*p.host, tmp), {(py::ssize_t)p.relin.n_digits, 2, (py::ssize_t)p.host->k, (py::ssize_t)p.host->N});
       })
@@ -635,7 +764,7 @@ PYBIND11_MODULE(_eva, m) {
           return a;
         };
         py::dict d;
-        d[py::int_(0)] = seeds_of(p.relin);
+        if (!p.collective) d[py::int_(0)] = seeds_of(p.relin);
         for (auto &kv : p.galois) d[py::int_(kv.first)] = seeds_of(kv.second);
         return d;
       }, "{0: the relinearization key's seeds [digits][32], Galois element: that key's} of a compressed context (DESIGN.md 1.4), else None")
@@ -783,6 +912,16 @@ PYBIND11_MODULE(_eva, m) {
         d["h2d_bytes"] = st[4]; d["d2h_bytes"] = st[5];
         return d;
       }, "ciphertext / plaintext transfers across the host boundary of the key pair's device state")
+      .def("decrypt_share", [](HipSecret &s, py::object enc, uint32_t smudge_bits, uint64_t seed) {
+        if (py::isinstance<HipValuationBatch>(enc)) return s.decrypt_share_batch(enc.cast<const HipValuationBatch &>(), smudge_bits, seed);
+        return s.decrypt_share(enc.cast<const HipValuation &>(), smudge_bits, seed);
+      }, py::arg("enc"), py::arg("smudge_bits"), py::arg("seed") = 0,
+           "This party's decryption share of every encrypted value of enc (a SEALValuation or a SEALValuationBatch) under a collective key "
+           "(DESIGN.md 1.14): h = c1 * s_p + NTT(E) with E uniform on [-2^smudge_bits, 2^smudge_bits), drawn on the GPU from a 32-byte key per "
+           "value. smudge_bits (1..62) is the caller's security parameter and has no default: it should exceed the ciphertext's noise bits by "
+           "the statistical security wanted, since a CKKS decryption leaks its noise and the flood is what hides it; 2^(smudge_bits + 2) times "
+           "the number of parties must stay below the modulus of the value's level. seed != 0 is the reproducible test hook, not secret-grade. "
+           "Unencrypted and raw values are skipped. Returns DecryptionShares for SEALPublic.combine_shares")
       .def("decrypt", &HipSecret::decrypt, py::arg("enc_outputs"), py::arg("signature"))
       .def("decrypt_batch", &HipSecret::decrypt_batch, py::arg("enc_outputs"), py::arg("signature"),
            "decrypt() of every valuation of a list, bit for bit; on the device up to 64 outputs of one name are decrypted and decoded in one call")

@@ -22,7 +22,19 @@ public:
   SwitchKey relin;
   std::map<uint32_t, SwitchKey> galois; // by Galois element
   // the evaluation keys are kept as c0 + one seed per digit (generate_keys(..., compress_keys))
-  bool keys_compressed() const { return relin.compressed(); }
+  bool keys_compressed() const { return collective ? true : relin.compressed(); }
+  // A collective context (combine_public_contexts): the keys belong to s = sum_p s_p, a secret nobody holds.
+  // It has NO relinearization key (s^2 is not the sum of the s_p^2): `relin` stays empty, no key of that kind is uploaded,
+  // and a program that relinearizes is refused before anything runs.
+  bool collective = false;
+  std::vector<uint32_t> dropped_galois; // combine_public_contexts: the Galois elements some party lacked, left out of this context
+  void refuse_relinearize(const Program &program) const {
+    if (!collective) return;
+    const std::vector<char> live = program.live_mask();
+    for (TermId t = 0; t < live.size(); t++)
+      if (live[t] && program.at(t).op == Op::Relinearize)
+        throw std::invalid_argument("relinearization key not present (a collective context has none)");
+  }
   int device = 0;
   bool free_eagerly = true;
   std::array<double, 3> last_timing{0, 0, 0}; // ms: input upload, DAG enqueue (host), drain + output download
@@ -121,12 +133,26 @@ public:
   HipValuationBatch rekey_batch(const HipValuationBatch &vb, const std::shared_ptr<const RekeyKey> &rk);
   std::vector<std::pair<std::shared_ptr<const RekeyKey>, uint32_t>> rekey_slots; // the keys installed so far
 
+  // ---- threshold decryption: open a valuation from the decryption shares of every party
+  // (HipSecret::decrypt_share).  m = c0 + sum_p h_p, then decrypt()'s decoder; needs no secret key.  A SEALValuation gives
+  // what decrypt() gives (on the device when one is present, else the host twin: the same doubles); a batch is written
+  // into rows as decrypt_array writes them (device only).  Unencrypted outputs pass through.
+  Valuation combine_shares(const HipValuation &enc, const std::vector<std::shared_ptr<DecryptionShares>> &shares, const CKKSSignature &sig);
+  void combine_shares_array(const HipValuationBatch &vb, const std::vector<std::shared_ptr<DecryptionShares>> &shares, const CKKSSignature &sig,
+                            int dtype_out, const std::map<std::string, void *> &rows, bool rows_on_device = false);
+  void check_shares(const std::vector<std::shared_ptr<DecryptionShares>> &shares) const;
+  const SharePiece &share_piece(const DecryptionShares &sh, size_t p, const std::string &name, size_t row, size_t n, uint32_t limbs, double scale) const;
+  const evah_ct *share_handle(const SharePiece &piece, std::vector<CtHandle> &keep);
+  void check_combine_room(const std::string &name, uint32_t limbs, size_t parties, uint32_t smudge_bits) const;
+  std::shared_ptr<DeviceCtx> device_state() { ensure_device(false); return dev; }
+
   // SEALPublic::execute (seal.cpp:104-122) — THE hot path.  First call for a program: upload
   // inputs, walk the DAG issuing HIP work over the queues, download outputs.  From the second call
   // on (same program object, same input shapes, no Raw inputs) the whole walk is replayed from a
   // captured hipGraph: per call the host refills the input slots, launches one graph, downloads.
   bool use_graphs = true; // EVA_GRAPH=0 disables
   HipValuation execute(Program &program, const HipValuation &inputs) {
+    refuse_relinearize(program);
     const bool multi = devices.size() > 1;
     if ((multi || limb_hooks) && shard_mode == "limb") {
       ensure_device(false);
@@ -415,7 +441,7 @@ private:
       if (k.compressed()) chk(evah_key_upload_seeded(c, kind, elt, k.n_digits, (const uint64_t *)k.c0_words().data(), k.seeds.data()));
       else chk(evah_key_upload(c, kind, elt, k.n_digits, (const uint64_t *)k.data.data()));
     };
-    up(EVAH_KEY_RELIN, 0, relin);
+    if (!collective) up(EVAH_KEY_RELIN, 0, relin);
     for (auto &kv : galois) up(EVAH_KEY_GALOIS, kv.first, kv.second);
   }
   void check_devices() const {

@@ -15,7 +15,7 @@ namespace evahost {
 
 constexpr uint32_t FORMAT_MAGIC = 0x48415645; // "EVAH"
 constexpr uint32_t FORMAT_VERSION = 1;
-enum class Kind : uint32_t { Program = 1, Parameters = 2, Signature = 3, Valuation = 4, Public = 5, Secret = 6, RekeyKey = 7 };
+enum class Kind : uint32_t { Program = 1, Parameters = 2, Signature = 3, Valuation = 4, Public = 5, Secret = 6, RekeyKey = 7, Shares = 8 };
 
 class Writer {
 public:
@@ -43,6 +43,12 @@ public:
     T v;
     std::memcpy(&v, buf.data() + pos, sizeof(T));
     pos += sizeof(T);
+    return v;
+  }
+  template <class T> T peek() { // the next value, left unread
+    need(sizeof(T));
+    T v;
+    std::memcpy(&v, buf.data() + pos, sizeof(T));
     return v;
   }
   std::string str() {
@@ -251,14 +257,20 @@ inline HipValuation read_valuation(Reader &r) {
   return v;
 }
 inline void write_ctx(Writer &w, const HostContext &h) { w.pod(h.N); w.vec(h.primes); }
-inline std::shared_ptr<HostContext> read_ctx(Reader &r) {
-  uint32_t N = r.pod<uint32_t>();
+// the parameters a file was written under, checked: N and the primes, no tables built
+inline std::vector<u64> read_params(Reader &r, uint32_t &N) {
+  N = r.pod<uint32_t>();
   auto primes = r.vec<u64>();
   if (N < 1024 || N > 131072 || (N & (N - 1)) || primes.size() < 2 || primes.size() > 62)
     throw std::runtime_error("Could not parse message: invalid encryption parameters");
   for (u64 q : primes)
     if (q < 2 || q >= ((u64)1 << 60) || (q - 1) % (2ull * N) || !evah::is_prime(q))
       throw std::runtime_error("Could not parse message: invalid coefficient modulus");
+  return primes;
+}
+inline std::shared_ptr<HostContext> read_ctx(Reader &r) {
+  uint32_t N = 0;
+  const std::vector<u64> primes = read_params(r, N);
   return std::make_shared<HostContext>(N, primes);
 }
 // A switch key: its digit count and words.  A compressed key sets the top bit of the digit count and
@@ -282,10 +294,14 @@ inline SwitchKey read_switch_key(Reader &r) {
   }
   return k;
 }
+// A collective context has no relinearization key: in its place the file holds this digit count alone,
+// which no context has, so a reader from before that form refuses the file ("wrong size for its context").
+constexpr uint32_t SWITCH_KEY_ABSENT = 0x40000000u;
 inline void write(Writer &w, const HipPublic &p) {
   write_ctx(w, *p.host);
   w.vec(p.pk.data);
-  write(w, p.relin);
+  if (p.collective) w.pod<uint32_t>(SWITCH_KEY_ABSENT);
+  else write(w, p.relin);
   w.pod<uint64_t>(p.galois.size());
   for (auto &kv : p.galois) { w.pod(kv.first); write(w, kv.second); }
 }
@@ -318,8 +334,13 @@ inline std::shared_ptr<HipPublic> read_public(Reader &r) {
   p->pk.data = r.vec<u64>();
   if (p->pk.data.size() != (size_t)2 * p->host->k * p->host->N) throw std::runtime_error("Could not parse message: public key has the wrong size for its context");
   check_residues(p->pk.data, *p->host, "public key");
-  p->relin = read_switch_key(r);
-  check_switch_key(p->relin, *p->host, "relinearization key");
+  if (r.peek<uint32_t>() == SWITCH_KEY_ABSENT) {
+    (void)r.pod<uint32_t>();
+    p->collective = true;
+  } else {
+    p->relin = read_switch_key(r);
+    check_switch_key(p->relin, *p->host, "relinearization key");
+  }
   uint64_t n = r.pod<uint64_t>();
   for (uint64_t i = 0; i < n; i++) {
     uint32_t elt = r.pod<uint32_t>();
@@ -368,6 +389,60 @@ inline std::shared_ptr<RekeyKey> read_rekey_key(Reader &r) {
   return k;
 }
 
+// Decryption shares: the parameters and smudge_bits they were made under, then per name the pieces with
+// their words [n][limbs][N] (a resident piece is downloaded for the file)
+inline void write(Writer &w, const DecryptionShares &d) {
+  w.pod(d.N);
+  w.vec(d.primes);
+  w.pod(d.smudge_bits);
+  w.pod<uint32_t>(d.batch ? 1 : 0);
+  w.pod<uint64_t>(d.B);
+  w.pod<uint64_t>(d.values.size());
+  for (auto &kv : d.values) {
+    w.str(kv.first);
+    w.pod<uint64_t>(kv.second.size());
+    for (const SharePiece &p : kv.second) {
+      w.pod(p.n); w.pod(p.limbs); w.pod(p.scale);
+      w.vec(words(p, d.N));
+    }
+  }
+}
+inline std::shared_ptr<DecryptionShares> read_shares(Reader &r) {
+  auto d = std::make_shared<DecryptionShares>();
+  d->primes = read_params(r, d->N); // (no HostContext: a share file needs no transform tables)
+  const size_t N = d->N, k = d->primes.size();
+  d->smudge_bits = r.pod<uint32_t>();
+  d->batch = r.pod<uint32_t>() != 0;
+  d->B = r.pod<uint64_t>();
+  if (d->smudge_bits < 1 || d->smudge_bits > 62) throw std::runtime_error("Could not parse message: smudge_bits out of range");
+  if (d->B < 1 || d->B > ((uint64_t)1 << 32) || (!d->batch && d->B != 1)) throw std::runtime_error("Could not parse message: decryption share instance count out of range");
+  const uint64_t names = r.pod<uint64_t>();
+  for (uint64_t i = 0; i < names; i++) {
+    const std::string name = r.str();
+    const uint64_t n_pieces = r.pod<uint64_t>();
+    if (n_pieces < 1 || n_pieces > d->B) throw std::runtime_error("Could not parse message: decryption share piece count out of range"); // a piece holds an instance at least
+    std::vector<SharePiece> &pieces = d->values[name];
+    uint64_t rows = 0;
+    for (uint64_t j = 0; j < n_pieces; j++) {
+      SharePiece p;
+      p.n = r.pod<uint32_t>(); p.limbs = r.pod<uint32_t>(); p.scale = r.pod<double>();
+      p.data = r.vec<u64>();
+      if (p.n < 1 || p.n > 64 || p.limbs < 1 || p.limbs > k - 1 || p.data.size() != (size_t)p.n * p.limbs * N)
+        throw std::runtime_error("Could not parse message: decryption share shape does not match its data");
+      for (size_t row = 0; row < (size_t)p.n * p.limbs; row++) {
+        const u64 q = d->primes[row % p.limbs];
+        const u64 *wd = p.data.data() + row * N;
+        for (size_t t = 0; t < N; t++)
+          if (wd[t] >= q) throw std::runtime_error("Could not parse message: decryption share holds a word that is not reduced modulo its prime");
+      }
+      rows += p.n;
+      pieces.push_back(std::move(p));
+    }
+    if (rows != d->B) throw std::runtime_error("Could not parse message: decryption share does not hold every instance");
+  }
+  return d;
+}
+
 template <class T> void save_to_file(Kind kind, const T &obj, const std::string &path) {
   Writer w;
   w.pod(FORMAT_MAGIC); w.pod(FORMAT_VERSION); w.pod<uint32_t>((uint32_t)kind);
@@ -392,7 +467,7 @@ inline void save_wire_to_file(const std::string &type, const std::string &payloa
 }
 
 using KnownType = std::variant<std::unique_ptr<Program>, CKKSParameters, CKKSSignature, HipValuation, std::shared_ptr<HipPublic>, std::shared_ptr<HipSecret>,
-                               std::shared_ptr<RekeyKey>>;
+                               std::shared_ptr<RekeyKey>, std::shared_ptr<DecryptionShares>>;
 inline KnownType load_from_file(const std::string &path) {
   std::ifstream f(path, std::ios::binary);
   if (!f) throw std::runtime_error("Could not open file " + path);
@@ -421,6 +496,7 @@ inline KnownType load_from_file(const std::string &path) {
   case Kind::Public: return read_public(r);
   case Kind::Secret: return read_secret(r);
   case Kind::RekeyKey: return read_rekey_key(r);
+  case Kind::Shares: return read_shares(r);
   }
   throw std::runtime_error("Unknown inner message type");
 }

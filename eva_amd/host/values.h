@@ -256,4 +256,31 @@ inline bool seeded_upload_ok(const HostCipher &c, const HostContext &host) {
   return true;
 }
 
+// ---- decryption shares: what one party contributes to the joint opening of a valuation.  Per encrypted
+// name a list of pieces — one per device call, at most 64 instances of one level each; a single valuation has one piece of
+// one instance — held as a resident batched handle [n][1][l][N], as host words [n][l][N], or both (the words of a resident
+// piece are downloaded on demand, as a HostCipher's are).
+struct SharePiece {
+  uint32_t n = 0, limbs = 0;
+  double scale = 1.0;
+  mutable std::vector<u64> data;  // [n][limbs][N]; empty while the piece lives only on the device
+  std::shared_ptr<CtHandle> h;
+  std::shared_ptr<DeviceCtx> root; // the device state the handle belongs to
+};
+struct DecryptionShares {
+  uint32_t N = 0, smudge_bits = 0;
+  std::vector<u64> primes;        // the chain of the parameters (special prime last)
+  bool batch = false;             // made from a SEALValuationBatch: B instances per name
+  size_t B = 1;
+  std::map<std::string, std::vector<SharePiece>> values;
+};
+inline const std::vector<u64> &words(const SharePiece &p, uint32_t N) {
+  if (p.data.empty() && p.h) {
+    std::vector<u64> w((size_t)p.n * p.limbs * N);
+    chk(evah_ct_download(p.root->h, p.h->h, (uint64_t *)w.data()));
+    p.data = std::move(w);
+  }
+  return p.data;
+}
+
 } // namespace evahost

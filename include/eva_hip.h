@@ -556,6 +556,38 @@ int evah_decrypt_decode_rows(evah_ctx *ctx, const evah_ct *const *cts, uint32_t 
 int evah_refresh_handles(evah_ctx *ctx, const evah_ct *const *cts, uint32_t n_handles, uint32_t limbs_out, double scale_out,
                          const uint8_t *ekeys, const uint8_t *seeds, evah_ct **out);
 
+/* ---- threshold decryption --------------------------------------------------------------------------
+ * A result is opened by parties that each hold a share s_p of the secret key s = sum_p s_p, none of them the whole.
+ * The two calls restate SEAL's Decryptor::decrypt (dot_product_ct_sk_array: c0 + c1 s) split over the parties, with the
+ * noise flooding ("smudging") of the multiparty CKKS protocols in front of CKKSEncoder::decode; the reference
+ * (seal.cpp:124-146, SEALSecret::decrypt) has the one-party form only.
+ *
+ * evah_decrypt_share_handles: on a context with the party's secret key s_p installed (evah_client_key_upload,
+ * evah_keygen_*).  cts: what evah_decrypt_decode_handles takes, at most 64 instances of size 2, one limb count l and one
+ * scale together, read in place.  Instance r gets h = c1 s_p + NTT(E) per limb (canonical residues), E drawn on the
+ * device from fkeys[r] (32 bytes, SECRET: whoever learns E learns c1 s_p): coefficient j = word j % 8 of the ChaCha20
+ * block j / 8 under the nonce 0x666c000000000000, E_j = (w >> (63 - smudge_bits)) - 2^smudge_bits, uniform on
+ * [-2^smudge_bits, 2^smudge_bits).  out: ONE batched size-1 handle [n][1][l][N] at the ciphertexts' scale, instances in
+ * list order, then instance order.  Refusals: a capturing context, a limb shard, "secret key not present", null
+ * pointers, mismatches in the list by argument index, more than 64 instances, "decryption share expects a size-2
+ * ciphertext (relinearize first)", smudge_bits outside 1..62, "smudge_bits leaves no room at this level"
+ * (2^(smudge_bits + 2) > Q_l).  One host -> device copy of the keys, nothing back, one drain of the queue;
+ * evah_ctx_transfer_stats out[4] grows by 32 n.  The keys are zeroed on the queue before their memory returns to the
+ * pool, also when the call fails. */
+int evah_decrypt_share_handles(evah_ctx *ctx, const evah_ct *const *cts, uint32_t n_handles, uint32_t smudge_bits, const uint8_t *fkeys,
+                               evah_ct **out);
+/* evah_decrypt_combine_rows: m = c0 + sum_p h_p per limb, then everything evah_decrypt_decode_rows does behind its dot
+ * product (inverse transforms, exact recomposition, the FFT, the gather into rows of dtype_out on the host or in device
+ * memory, pitched; the same meaning of row_pitch, out_on_device and wait).  shares: n_parties (1..64) size-1 handles as
+ * evah_decrypt_share_handles returns them, each holding the n instances of cts in the same order, with the ciphertexts'
+ * limb count and scale; a share made elsewhere arrives through evah_ct_upload_batch.  Needs NO secret key: any context
+ * over the same parameters can run it.  The caller refuses P 2^(smudge_bits + 2) > Q_l (a handle does not carry
+ * smudge_bits); a slot then differs from the decryption under s by at most N P 2^smudge_bits / scale.  Refusals: a
+ * capturing context, a limb shard, null pointers, mismatches by ciphertext or share index, more than 64 instances,
+ * a size other than 2, and those of evah_decrypt_decode_rows for the rows. */
+int evah_decrypt_combine_rows(evah_ctx *ctx, const evah_ct *const *cts, uint32_t n_handles, const evah_ct *const *shares, uint32_t n_parties,
+                              uint32_t n_out, int dtype_out, void *out, size_t row_pitch, int out_on_device, int wait);
+
 /* ---- whole-DAG submit: a topologically sorted flat op list over a value table.
  * One call replaces the per-node loop ProgramTraversal::forwardPass + SEALExecutor::operator()
  * (program_traversal.h:36-93, seal_executor.h:279-404) for the encrypted part of a program.
