@@ -159,6 +159,7 @@ _SIGS = {
                                   C.c_size_t, C.c_int, C.c_int],
     "evah_ct_slice": [_vp, _vp, C.c_uint32, C.c_uint32, _vpp],
     "evah_ctx_stack_stats": [_vp, _u64p],
+    "evah_ctx_loop_stats": [_vp, _u64p],
     # batched plaintexts
     "evah_pt_encode_array": [_vp, C.c_uint32, _vp, C.c_int, C.c_uint32, C.c_uint32, C.c_double, _vpp],
     "evah_pt_encode_array_async": [_vp, C.c_uint32, _vp, C.c_int, C.c_uint32, C.c_uint32, C.c_double, _vpp],
@@ -805,6 +806,13 @@ class Context:
         """(evah_ct_stack calls on this device state, instances they copied)"""
         out = (C.c_uint64 * 2)()
         _chk(_lib.evah_ctx_stack_stats(self.h, out))
+        return tuple(int(x) for x in out)
+
+    def loop_stats(self):
+        """contiguous passes this context launched as the looped kernel (evah_ctx_loop_stats): launches as (inverse pass 1,
+        plain forward pass 2, key-switch digit pass 2, mod-down pass 2), jobs along their loop axes, walks along them"""
+        out = (C.c_uint64 * 6)()
+        _chk(_lib.evah_ctx_loop_stats(self.h, out))
         return tuple(int(x) for x in out)
 
     def copy_here(self, value):

@@ -462,6 +462,9 @@ struct evah_ctx {
   std::vector<hipEvent_t> prof_free;
   double prof_ms[KC_COUNT] = {0};
   uint64_t prof_n[KC_COUNT] = {0};
+  // evah_ctx_loop_stats: launches of ntt_loop_kernel by this queue as inverse pass 1 / plain forward pass 2 / key-switch
+  // digit pass 2 / mod-down pass 2, the jobs along their loop axes, the walks along them (launch_loop_pass, launch.hip.h)
+  uint64_t looped[6] = {0, 0, 0, 0, 0, 0};
 };
 
 namespace evah {

@@ -101,6 +101,12 @@ static bool launch_loop_pass(evah_ctx *c, const typename Op::Params &prm, uint32
   hipLaunchKernelGGL((ntt_loop_kernel<P, LR, INVERSE, Op>), dim3(ext[0] * n_tiles, ext[1], ext[2]), dim3(tile >> LR), lds, c->stream,
                      c->dev, prm, logC, log_tiles, nloop, count);
   HIPCHK(hipGetLastError());
+  // evah_ctx_loop_stats: which of its four profile classes the kernel ran as, its jobs and its walks along the loop axis
+  constexpr int cls = INVERSE ? KC_INTT_A : OpClass<Op>::fwd_b;
+  static_assert(cls == KC_INTT_A || cls == KC_NTT_B || cls == KC_KSDIGIT_B || cls == KC_MODDOWN_B, "a class evah_ctx_loop_stats has no word for");
+  c->looped[cls == KC_INTT_A ? 0 : cls == KC_NTT_B ? 1 : cls == KC_KSDIGIT_B ? 2 : 3]++;
+  c->looped[4] += count;
+  c->looped[5] += ext[Op::loop_axis];
   return true;
 }
 template <bool INVERSE, class Op>

@@ -775,6 +775,15 @@ int evah_ctx_stack_stats(evah_ctx *c, uint64_t out[2]) {
   API_END
 }
 
+// contiguous transform passes this queue launched as ntt_loop_kernel so far (launch_loop_pass; counted on the host at
+// launch, so also while a graph is captured): the looped kernel and ntt_pass_kernel report the same profile class, and
+// this is what tells them apart
+int evah_ctx_loop_stats(evah_ctx *c, uint64_t out[6]) {
+  API_BEGIN
+  for (int i = 0; i < 6; i++) out[i] = c->looped[i];
+  API_END
+}
+
 int evah_ctx_key_bytes_detail(evah_ctx *c, uint64_t out[3]) {
   API_BEGIN
   out[0] = out[1] = out[2] = 0;

@@ -230,6 +230,13 @@ int evah_ctx_key_upload_stats(evah_ctx *ctx, uint64_t out[2]);
  * out[0] = calls, out[1] = the instances they copied.  A batch passed on as slices of its handles (evah_ct_slice) counts
  * in neither. */
 int evah_ctx_stack_stats(evah_ctx *ctx, uint64_t out[2]);
+/* Contiguous transform passes that ctx (this queue, not its forks) has launched in the looped form so far: one 64-thread
+ * workgroup per 256-coefficient tile that walks several jobs of one prime with the tile's twiddles staged once.  The
+ * counters only grow, and count launches made while a graph is captured too.  out[0..3] = launches as inverse pass 1, as
+ * plain forward pass 2, as key-switch digit pass 2 and as mod-down pass 2 (the profile classes intt_pass1, ntt_pass2,
+ * ksdigit_pass2, moddown_pass2, which the plain form of these passes reports as well); out[4] = the jobs along the
+ * launches' loop axes, summed; out[5] = the walks along them, summed (ceil(jobs / jobs per walk) of each launch). */
+int evah_ctx_loop_stats(evah_ctx *ctx, uint64_t out[6]);
 int evah_ct_info(const evah_ct *ct, uint32_t *size, uint32_t *limbs, double *scale);
 int evah_ct_download(evah_ctx *ctx, const evah_ct *ct, uint64_t *out /* [size][limbs][N] */);
 void evah_ct_free(evah_ctx *ctx, evah_ct *ct);
