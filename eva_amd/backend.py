@@ -176,6 +176,8 @@ _SIGS = {
     "evah_key_download_c0": [_vp, C.c_int, C.c_uint32, C.c_uint32, _u64p],
     # re-key to another key pair
     "evah_keygen_rekey": [_vp, _u64p, C.c_uint32, C.POINTER(C.c_uint8), _u64p],
+    "evah_keygen_relin_round1": [_vp, C.c_uint32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _u64p],
+    "evah_keygen_relin_round2": [_vp, C.c_uint32, _u64p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _u64p],
     "evah_rekey_many": [_vp, C.c_uint32, _vpp, C.c_uint32, _vpp],
     # limb-sharded execution
     "evah_ctx_set_shard": [_vp, C.c_uint32, C.c_uint32],
@@ -976,6 +978,31 @@ class Context:
         assert pk_target.shape == (2, self.k, self.N) and rkeys.ndim == 2 and rkeys.shape[1] == 32
         out = np.empty((rkeys.shape[0], 2, self.k, self.N), dtype=np.uint64)
         _chk(_lib.evah_keygen_rekey(self.h, _p(pk_target), rkeys.shape[0], rkeys.ctypes.data_as(C.POINTER(C.c_uint8)), _p(out)))
+        return out
+
+    def keygen_relin_round1(self, seeds, r1keys):
+        """evah_keygen_relin_round1: this party's round-1 share [digits][2][k][N] of the collective
+        relinearization key from the uploaded secret key; seeds [digits][32] uint8 the derived common seeds, r1keys [digits][32]
+        the ephemeral keys, digit J's (u, e0, e1) = sampled_small(r1keys[J], 0..2)"""
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint8)
+        r1keys = np.ascontiguousarray(r1keys, dtype=np.uint8)
+        assert seeds.ndim == 2 and seeds.shape[1] == 32 and r1keys.shape == seeds.shape
+        u8p = C.POINTER(C.c_uint8)
+        out = np.empty((seeds.shape[0], 2, self.k, self.N), dtype=np.uint64)
+        _chk(_lib.evah_keygen_relin_round1(self.h, seeds.shape[0], seeds.ctypes.data_as(u8p), r1keys.ctypes.data_as(u8p), _p(out)))
+        return out
+
+    def keygen_relin_round2(self, agg1, r1keys, r2keys):
+        """evah_keygen_relin_round2: this party's round-2 share [digits][k][N] from the sum of the round-1
+        shares agg1 [digits][2][k][N], the round-1 keys again (u) and fresh keys r2keys [digits][32] for (e2, e3)"""
+        agg1 = np.ascontiguousarray(agg1, dtype=np.uint64)
+        r1keys = np.ascontiguousarray(r1keys, dtype=np.uint8)
+        r2keys = np.ascontiguousarray(r2keys, dtype=np.uint8)
+        D = agg1.shape[0]
+        assert agg1.shape == (D, 2, self.k, self.N) and r1keys.shape == (D, 32) and r2keys.shape == (D, 32)
+        u8p = C.POINTER(C.c_uint8)
+        out = np.empty((D, self.k, self.N), dtype=np.uint64)
+        _chk(_lib.evah_keygen_relin_round2(self.h, D, _p(agg1), r1keys.ctypes.data_as(u8p), r2keys.ctypes.data_as(u8p), _p(out)))
         return out
 
     def upload_rekey_key(self, slot, key):

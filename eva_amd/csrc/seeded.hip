@@ -8,6 +8,8 @@
 // 32-byte randomness keys the device expands itself — one k_keygen_set launch for the set —, and evah_key_download_c0
 // hands c0 of such a key to the host when it is first needed there.  evah_keygen_rekey makes the key
 // that takes ciphertexts to ANOTHER key pair, from that pair's public key: one k_keygen_rekey launch.
+// evah_keygen_relin_round1 / _round2 make a party's two shares of a committee's relinearization key:
+// one k_relin_round1 / k_relin_round2 launch each.
 
 #include "launch.hip.h"
 #include "seeded.hip.h"
@@ -238,6 +240,70 @@ k_keygen_rekey(DevCtx cx, const u64 *__restrict__ pk, const u64 *__restrict__ sm
   u64 *at = d + (size_t)2 * J * poly + row;
   st2(at, b0);
   st2(at + poly, b1);
+}
+
+// Round 1 of the collective relinearization key: this party's share of digit J, prime row i,
+//   h0 = -(a u_J) + NTT(e0_J) + [i == J] (P mod q_J) s,   h1 = a s + NTT(e1_J),
+// with a = seeded_block(seed'_J, i, .) in registers only — the common row every party expands, never stored.  small: the
+// NTT forms [digit][3][k][N] of (u, e0, e1); sk [k][N], read once for both polynomials; out [digit][2][k][N], both halves
+// from the same registers.  One thread per ChaCha block (4 coefficients), 16-byte accesses; the i == J branch is uniform
+// over the block.  grid = (ceil(N / 4 / 256), k, digits).  Seeds as in k_key_expand.
+__global__ void __launch_bounds__(256)
+k_relin_round1(DevCtx cx, Seeds8 seeds, const uint32_t *__restrict__ seed_buf, const u64 *__restrict__ small, const u64 *__restrict__ sk,
+               u64 *__restrict__ out) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y, J = blockIdx.z;
+  if (t >= cx.N / 4 || i >= cx.k) return;
+  const DevPrime pm = cx.primes[i];
+  uint32_t key[8];
+  if (seed_buf) {
+#pragma unroll
+    for (int w = 0; w < 8; w++) key[w] = seed_buf[8 * J + w];
+  } else {
+#pragma unroll
+    for (int w = 0; w < 8; w++) key[w] = seeds.w[J][w];
+  }
+  u64 a[4], h0[4], h1[4];
+  seeded_block(key, i, t, pm, a);
+  const size_t poly = (size_t)cx.k * cx.N, row = (size_t)i * cx.N + 4 * (size_t)t;
+  const u64 *sm = small + (size_t)J * 3 * poly + row;
+  const ulonglong2 u01 = ld2(sm), u23 = ld2(sm + 2), e01 = ld2(sm + poly), e23 = ld2(sm + poly + 2);
+  const ulonglong2 f01 = ld2(sm + 2 * poly), f23 = ld2(sm + 2 * poly + 2), s01 = ld2(sk + row), s23 = ld2(sk + row + 2);
+  const u64 uv[4] = {u01.x, u01.y, u23.x, u23.y}, e0[4] = {e01.x, e01.y, e23.x, e23.y}, e1[4] = {f01.x, f01.y, f23.x, f23.y};
+  const u64 sv[4] = {s01.x, s01.y, s23.x, s23.y};
+#pragma unroll
+  for (int r = 0; r < 4; r++) {
+    h0[r] = addmod(negmod(mulmod(a[r], uv[r], pm), pm.q), e0[r], pm.q);
+    h1[r] = addmod(mulmod(a[r], sv[r], pm), e1[r], pm.q);
+  }
+  if (i == J) {
+    const u64 pmod = cx.modq[(size_t)(cx.k - 1) * cx.k + J].x; // P mod q_J
+#pragma unroll
+    for (int r = 0; r < 4; r++) h0[r] = addmod(h0[r], mulmod(sv[r], pmod, pm), pm.q);
+  }
+  u64 *at = out + (size_t)2 * J * poly + row;
+  st2(at, make_ulonglong2(h0[0], h0[1]));
+  st2(at + 2, make_ulonglong2(h0[2], h0[3]));
+  st2(at + poly, make_ulonglong2(h1[0], h1[1]));
+  st2(at + poly + 2, make_ulonglong2(h1[2], h1[3]));
+}
+
+// Round 2: g = s H0 + NTT(e2_J) + (u_J - s) H1 + NTT(e3_J) for digit J, prime row i.  agg [digit][2][k][N]
+// (H0, H1: the sums of the round-1 shares); un [digit][k][N]: NTT(u_J) of this party's round-1 keys; en [digit][2][k][N]:
+// NTT(e2_J), NTT(e3_J); sk [k][N]; out [digit][k][N].  One thread per two coefficients, 16-byte accesses, no branch.
+// grid = (ceil(N / 2 / 256), k, digits)
+__global__ void __launch_bounds__(256)
+k_relin_round2(DevCtx cx, const u64 *__restrict__ agg, const u64 *__restrict__ un, const u64 *__restrict__ en, const u64 *__restrict__ sk,
+               u64 *__restrict__ out) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y, J = blockIdx.z;
+  if (2 * t >= cx.N || i >= cx.k) return;
+  const DevPrime pm = cx.primes[i];
+  const size_t poly = (size_t)cx.k * cx.N, row = (size_t)i * cx.N + 2 * (size_t)t;
+  const u64 *ag = agg + (size_t)2 * J * poly + row, *e = en + (size_t)2 * J * poly + row;
+  const ulonglong2 H0 = ld2(ag), H1 = ld2(ag + poly), u = ld2(un + (size_t)J * poly + row), e2 = ld2(e), e3 = ld2(e + poly), s = ld2(sk + row);
+  ulonglong2 g;
+  g.x = addmod(addmod(mulmod(s.x, H0.x, pm), e2.x, pm.q), addmod(mulmod(submod(u.x, s.x, pm.q), H1.x, pm), e3.x, pm.q), pm.q);
+  g.y = addmod(addmod(mulmod(s.y, H0.y, pm), e2.y, pm.q), addmod(mulmod(submod(u.y, s.y, pm.q), H1.y, pm), e3.y, pm.q), pm.q);
+  st2(out + (size_t)J * poly + row, g);
 }
 
 // the refusals evah_keygen_switch, evah_keygen_set and evah_keygen_public share, with evah_keygen_switch's messages
@@ -517,6 +583,92 @@ int evah_keygen_rekey(evah_ctx *c, const uint64_t *pk_target, uint32_t n_digits,
   }
   c->sh->xfer[4] += sizeof(u64) * 2 * poly + (size_t)32 * n_digits;
   c->sh->xfer[5] += shape.bytes;
+  API_END
+}
+
+// Round 1 of the collective relinearization-key generation: this party's public share [n_digits][2][k][N]
+// from the resident secret key, the derived common seeds (relin_round_seed) and one ephemeral 32-byte key per digit.
+// Launch plan: the randomness keys (and, above SEEDS_PER_LAUNCH digits, the seeds) up, the NTT forms of (u, e0, e1) of
+// every digit (sample_to_ntt), ONE k_relin_round1, the share back, the wipes, one drain.
+int evah_keygen_relin_round1(evah_ctx *c, uint32_t n_digits, const uint8_t *seeds, const uint8_t *r1keys, uint64_t *share_out) {
+  API_BEGIN
+  use(c);
+  keygen_checks(c);
+  const KeyDev shape = key_shape(c, n_digits);
+  if (!seeds) throw std::invalid_argument("seed pointer is null");
+  if (!r1keys) throw std::invalid_argument("randomness key pointer is null");
+  if (!share_out) throw std::invalid_argument("output pointer is null");
+  if (c->N % 256) throw std::invalid_argument("key generation needs N divisible by 256");
+  if (!c->sh->sk.d) throw std::invalid_argument("secret key not present");
+  const size_t poly = (size_t)c->k * c->N;
+  Seeds8 s8;
+  std::memset(&s8, 0, sizeof s8);
+  try {
+    Scratch rk(c, (size_t)4 * n_digits), sd(c, (size_t)4 * n_digits), sm(c, (size_t)n_digits * 3 * poly), share(c, (size_t)n_digits * 2 * poly);
+    // the randomness keys, the sampled residues and their NTT forms do not stay behind in pool memory the next call reuses
+    Wipe w_rk{c, rk.d, (size_t)32 * n_digits}, w_sm{c, sm.d, sizeof(u64) * n_digits * 3 * poly};
+    const uint32_t *seed_buf = nullptr;
+    if (n_digits <= SEEDS_PER_LAUNCH) {
+      std::memcpy(s8.w, seeds, (size_t)32 * n_digits); // little-endian key words, as the host generator reads its key
+    } else {
+      HIPCHK(hipMemcpyAsync(sd.d, seeds, (size_t)32 * n_digits, hipMemcpyHostToDevice, c->stream));
+      seed_buf = reinterpret_cast<const uint32_t *>(sd.d);
+    }
+    sample_to_ntt(c, n_digits, r1keys, rk.d, 3, 0, c->k, sm.d);
+    EW_LAUNCH(k_relin_round1, seeded_grid(c, c->k, n_digits), dim3(256), 0, c->stream, c->dev, s8, seed_buf, sm.d, c->sh->sk.d, share.d);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(share_out, share.d, shape.bytes, hipMemcpyDeviceToHost, c->stream));
+    w_rk.now();
+    w_sm.now();
+    HIPCHK(hipStreamSynchronize(c->stream)); // the arguments are pageable; the scratch returns to the pool drained
+  } catch (...) {
+    (void)hipStreamSynchronize(c->stream);
+    throw;
+  }
+  c->sh->xfer[4] += (size_t)64 * n_digits;
+  c->sh->xfer[5] += shape.bytes;
+  API_END
+}
+
+// Round 2: this party's share [n_digits][k][N] from the sum of the round-1 shares agg1 [n_digits][2][k][N],
+// the round-1 keys again (u_J is regenerated from them, never kept) and fresh keys for (e2, e3).  Launch plan: agg1 and
+// both key lists up, NTT(u) from r1keys and NTT(e2), NTT(e3) from r2keys (sample_to_ntt, once per key list), ONE
+// k_relin_round2, the share back, the wipes, one drain.
+int evah_keygen_relin_round2(evah_ctx *c, uint32_t n_digits, const uint64_t *agg1, const uint8_t *r1keys, const uint8_t *r2keys,
+                             uint64_t *share_out) {
+  API_BEGIN
+  use(c);
+  keygen_checks(c);
+  const KeyDev shape = key_shape(c, n_digits);
+  if (!agg1) throw std::invalid_argument("key pointer is null");
+  if (!r1keys || !r2keys) throw std::invalid_argument("randomness key pointer is null");
+  if (!share_out) throw std::invalid_argument("output pointer is null");
+  if (c->N % 256) throw std::invalid_argument("key generation needs N divisible by 256");
+  if (!c->sh->sk.d) throw std::invalid_argument("secret key not present");
+  const size_t poly = (size_t)c->k * c->N;
+  try {
+    Scratch agg(c, (size_t)n_digits * 2 * poly), k1(c, (size_t)4 * n_digits), k2(c, (size_t)4 * n_digits), un(c, (size_t)n_digits * poly),
+        en(c, (size_t)n_digits * 2 * poly), share(c, (size_t)n_digits * poly);
+    // the randomness keys, the sampled residues and their NTT forms do not stay behind in pool memory the next call reuses
+    Wipe w_k1{c, k1.d, (size_t)32 * n_digits}, w_k2{c, k2.d, (size_t)32 * n_digits}, w_un{c, un.d, sizeof(u64) * n_digits * poly},
+        w_en{c, en.d, sizeof(u64) * n_digits * 2 * poly};
+    HIPCHK(hipMemcpyAsync(agg.d, agg1, shape.bytes, hipMemcpyHostToDevice, c->stream));
+    sample_to_ntt(c, n_digits, r1keys, k1.d, 1, 0, c->k, un.d);
+    sample_to_ntt(c, n_digits, r2keys, k2.d, 2, 1, c->k, en.d);
+    EW_LAUNCH(k_relin_round2, dim3((c->N / 2 + 255) / 256, c->k, n_digits), dim3(256), 0, c->stream, c->dev, agg.d, un.d, en.d, c->sh->sk.d, share.d);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(share_out, share.d, shape.bytes / 2, hipMemcpyDeviceToHost, c->stream));
+    w_k1.now();
+    w_k2.now();
+    w_un.now();
+    w_en.now();
+    HIPCHK(hipStreamSynchronize(c->stream)); // the arguments are pageable; the scratch returns to the pool drained
+  } catch (...) {
+    (void)hipStreamSynchronize(c->stream);
+    throw;
+  }
+  c->sh->xfer[4] += shape.bytes + (size_t)64 * n_digits;
+  c->sh->xfer[5] += shape.bytes / 2;
   API_END
 }
 

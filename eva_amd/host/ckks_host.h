@@ -1038,4 +1038,101 @@ inline std::vector<u64> rekey_keygen_host(const HostContext &cx, const SecretKey
   return out;
 }
 
+// ---- the collective relinearization key: the host twins of evah_keygen_relin_round1 / _round2, word for
+// word.  A share of either round, as it travels between the parties: round 1 [digit][2][k][N], round 2 [digit][k][N].
+struct RelinShare {
+  uint32_t round = 0, N = 0, n_digits = 0;
+  std::vector<u64> primes;
+  std::vector<u64> data; // NTT form, canonical
+};
+// the derived common seeds [n_digits][32] of the public relinearization-key seeds [n_digits][32] (csprng.h relin_round_seed)
+inline std::vector<uint8_t> relin_round_seeds(const std::vector<uint8_t> &relin_seeds) {
+  std::vector<uint8_t> out(relin_seeds.size());
+  for (size_t J = 0; J + 1 <= relin_seeds.size() / 32; J++) relin_round_seed(relin_seeds.data() + 32 * J, out.data() + 32 * J);
+  return out;
+}
+// are the rows [..][k][N] canonical residues of their primes (row r under prime r % k)?  What the kernels' lazy-reduction
+// bounds assume of every key word, asked of words that did not come through a file (serialization.h check_residues)
+inline bool residues_canonical(const std::vector<u64> &words, const HostContext &h) {
+  const size_t N = h.N, rows = words.size() / N;
+  for (size_t r = 0; r < rows; r++) {
+    const u64 q = h.primes[r % h.k], *w = words.data() + r * N;
+    for (size_t j = 0; j < N; j++)
+      if (w[j] >= q) return false;
+  }
+  return true;
+}
+inline void relin_round_checks(const HostContext &cx, const SecretKey &sk, uint32_t n_digits) {
+  if (n_digits == 0 || n_digits > cx.k - 1) throw std::invalid_argument("invalid key digit count");
+  if (sk.s_ntt.size() != (size_t)cx.k * cx.N) throw std::invalid_argument("secret key not present");
+}
+// round 1: h0[J][i] = -(a_J[i] u_J[i]) + NTT_i(e0_J) + [i == J] (P mod q_J) s[i],  h1[J][i] = a_J[i] s[i] + NTT_i(e1_J), with
+// a_J[i] = seeded_limb(seeds[J], i) and (u_J, e0_J, e1_J) = sampled_small(r1keys[J], 0 / 1 / 2) -> [n_digits][2][k][N]
+inline std::vector<u64> relin_round1_host(const HostContext &cx, const SecretKey &sk, uint32_t n_digits, const uint8_t *seeds,
+                                          const std::array<uint8_t, 32> *r1keys) {
+  relin_round_checks(cx, sk, n_digits);
+  const uint32_t N = cx.N, k = cx.k;
+  const size_t poly = (size_t)k * N;
+  const u64 P = cx.primes[k - 1];
+  std::vector<u64> out((size_t)n_digits * 2 * poly), a(N), un(N), en(N);
+  std::vector<int8_t> p(N);
+  for (uint32_t J = 0; J < n_digits; J++) {
+    std::vector<int8_t> small = sampled_small3(r1keys[J], N);
+    for (uint32_t i = 0; i < k; i++) {
+      const u64 q = cx.primes[i], *s = sk.s_ntt.data() + (size_t)i * N;
+      seeded_limb(seeds + (size_t)32 * J, i, q, N, (uint64_t *)a.data());
+      u64 *h0 = out.data() + (size_t)2 * J * poly + (size_t)i * N, *h1 = h0 + poly;
+      std::copy_n(small.begin(), N, p.begin());
+      cx.small_to_ntt(p, i, un.data());
+      std::copy_n(small.begin() + N, N, p.begin());
+      cx.small_to_ntt(p, i, en.data());
+      for (uint32_t j = 0; j < N; j++) h0[j] = evah::addmod(evah::negmod(cx.mulm(a[j], un[j], i), q), en[j], q);
+      if (i == J) {
+        const u64 pmod = P % q;
+        for (uint32_t j = 0; j < N; j++) h0[j] = evah::addmod(h0[j], cx.mulm(s[j], pmod, i), q);
+      }
+      std::copy_n(small.begin() + (size_t)2 * N, N, p.begin());
+      cx.small_to_ntt(p, i, en.data());
+      for (uint32_t j = 0; j < N; j++) h1[j] = evah::addmod(cx.mulm(a[j], s[j], i), en[j], q);
+    }
+    wipe(small);
+  }
+  wipe(p);
+  wipe_bytes(un.data(), un.size() * sizeof(u64));
+  wipe_bytes(en.data(), en.size() * sizeof(u64));
+  return out;
+}
+// round 2: g[J][i] = s[i] H0[J][i] + NTT_i(e2_J) + (u_J[i] - s[i]) H1[J][i] + NTT_i(e3_J), (H0, H1) = agg1[J], u_J =
+// sampled_small(r1keys[J], 0), (e2_J, e3_J) = sampled_small(r2keys[J], 1 / 2) -> [n_digits][k][N]
+inline std::vector<u64> relin_round2_host(const HostContext &cx, const SecretKey &sk, uint32_t n_digits, const u64 *agg1,
+                                          const std::array<uint8_t, 32> *r1keys, const std::array<uint8_t, 32> *r2keys) {
+  relin_round_checks(cx, sk, n_digits);
+  const uint32_t N = cx.N, k = cx.k;
+  const size_t poly = (size_t)k * N;
+  std::vector<u64> out((size_t)n_digits * poly), un(N), e2(N), e3(N);
+  std::vector<int8_t> u(N), e(N);
+  for (uint32_t J = 0; J < n_digits; J++) {
+    sampled_small(r1keys[J].data(), 0, N, u.data());
+    for (uint32_t i = 0; i < k; i++) {
+      const u64 q = cx.primes[i], *s = sk.s_ntt.data() + (size_t)i * N;
+      const u64 *H0 = agg1 + (size_t)2 * J * poly + (size_t)i * N, *H1 = H0 + poly;
+      cx.small_to_ntt(u, i, un.data());
+      sampled_small(r2keys[J].data(), 1, N, e.data());
+      cx.small_to_ntt(e, i, e2.data());
+      sampled_small(r2keys[J].data(), 2, N, e.data());
+      cx.small_to_ntt(e, i, e3.data());
+      u64 *g = out.data() + (size_t)J * poly + (size_t)i * N;
+      for (uint32_t j = 0; j < N; j++)
+        g[j] = evah::addmod(evah::addmod(cx.mulm(s[j], H0[j], i), e2[j], q),
+                            evah::addmod(cx.mulm(evah::submod(un[j], s[j], q), H1[j], i), e3[j], q), q);
+    }
+  }
+  wipe(u);
+  wipe(e);
+  wipe_bytes(un.data(), un.size() * sizeof(u64));
+  wipe_bytes(e2.data(), e2.size() * sizeof(u64));
+  wipe_bytes(e3.data(), e3.size() * sizeof(u64));
+  return out;
+}
+
 } // namespace evahost

@@ -849,11 +849,33 @@ inline void HipPublic::combine_shares_array(const HipValuationBatch &vb, const s
   }
 }
 
+// What a party keeps between the two rounds of the collective relinearization-key generation: the 32-byte
+// keys u_J is regenerated from, and nothing else.  Whoever learns them learns s_p (h1 - NTT(e1) = a s_p with a public), so
+// the object cannot be saved, pickled or copied, serves ONE round 2 of the context that made it, and is wiped when used
+// and when destroyed.
+struct RelinEphemeral {
+  std::vector<std::array<uint8_t, 32>> r1;
+  std::shared_ptr<const char> owner; // HipSecret::identity of the context that made it
+  bool used = false;
+  RelinEphemeral() = default;
+  RelinEphemeral(const RelinEphemeral &) = delete;
+  RelinEphemeral &operator=(const RelinEphemeral &) = delete;
+  void wipe_keys() {
+    for (auto &k : r1) wipe_bytes(k.data(), 32);
+  }
+  ~RelinEphemeral() { wipe_keys(); }
+};
+
 class HipSecret {
 public:
   std::shared_ptr<HostContext> host;
   SecretKey sk;
   int device = 0;
+  // generate_keys(..., common_seed): the PUBLIC seeds [digits][32] of this pair's relinearization key, equal
+  // across the parties — what the collective relinearization-key rounds derive their common rows from.
+  // Empty for every other pair, and for a context loaded from a file (the secret file does not carry them).
+  std::vector<uint8_t> common_relin_seeds;
+  std::shared_ptr<const char> identity = std::make_shared<char>(); // which context made a RelinEphemeral
   // test hook of generate_keys(..., seed != 0, device_sampling): the 32-byte keys its secret stream gave;
   // empty for every other pair
   KeyGenerator::Randomness key_randomness;
@@ -1223,6 +1245,74 @@ public:
     } else {
       out->data = rekey_keygen_host(*host, sk, target.pk, D, rk[0].data());
     }
+    return out;
+  }
+
+  // ---- the collective relinearization key: this party's two shares.  Round 1 draws one ephemeral key per
+  // digit (stream (seed, 6) under the test hook, else the OS) and returns them beside the public share; round 2 takes them
+  // back — once — with the sum of all parties' round-1 shares, and draws fresh keys (stream (seed, 7)).  On the device
+  // where one is present (evah_keygen_relin_round1 / _round2), else the host twins — the same words.
+  std::pair<std::shared_ptr<RelinEphemeral>, std::shared_ptr<RelinShare>> relin_round1(uint64_t seed = 0) {
+    const uint32_t D = host->k - 1;
+    if (common_relin_seeds.size() != (size_t)32 * D)
+      throw std::invalid_argument("relin_round1: this context's keys were not generated with a common seed (generate_keys(..., common_seed=)): "
+                                  "the parties share no public relinearization seeds");
+    if (sk.s_ntt.size() != (size_t)host->k * host->N) throw std::invalid_argument("relin_round1: secret key not present");
+    std::unique_ptr<SecureRng> stream = seed ? std::make_unique<SecureRng>(seed, 6) : std::make_unique<SecureRng>();
+    auto eph = std::make_shared<RelinEphemeral>();
+    eph->owner = identity;
+    for (uint32_t J = 0; J < D; J++) eph->r1.push_back(draw_key32(*stream));
+    const std::vector<uint8_t> seeds = relin_round_seeds(common_relin_seeds);
+    auto out = std::make_shared<RelinShare>();
+    out->round = 1;
+    out->N = host->N;
+    out->primes = host->primes;
+    out->n_digits = D;
+    if (on_device()) {
+      out->data.resize((size_t)D * 2 * host->k * host->N);
+      std::vector<uint8_t> flat = keys_flat(eph->r1.data(), D);
+      const int rc = evah_keygen_relin_round1(dev->h, D, seeds.data(), flat.data(), (uint64_t *)out->data.data());
+      wipe_bytes(flat.data(), flat.size());
+      chk(rc);
+    } else {
+      out->data = relin_round1_host(*host, sk, D, seeds.data(), eph->r1.data());
+    }
+    return {eph, out};
+  }
+  std::shared_ptr<RelinShare> relin_round2(const std::shared_ptr<RelinEphemeral> &eph, const std::shared_ptr<const RelinShare> &agg1, uint64_t seed = 0) {
+    if (!eph) throw std::invalid_argument("relin_round2: the ephemeral state is None");
+    if (!agg1) throw std::invalid_argument("relin_round2: the round-1 aggregate is None");
+    if (eph->owner != identity) throw std::invalid_argument("relin_round2: the ephemeral state was made by another secret context");
+    if (eph->used) throw std::invalid_argument("relin_round2: the ephemeral state was already used (a second share would reuse u)");
+    const uint32_t D = host->k - 1;
+    if (agg1->round != 1) throw std::invalid_argument("relin_round2: the aggregate is not made of round-1 shares (it is a round-" + std::to_string(agg1->round) + " share)");
+    const std::string diff = rekey_params_differ(agg1->N, agg1->primes, *host);
+    if (!diff.empty()) throw std::invalid_argument("relin_round2: the aggregate was made under other encryption parameters: " + diff);
+    if (agg1->n_digits != D || eph->r1.size() != D || agg1->data.size() != (size_t)D * 2 * host->k * host->N)
+      throw std::invalid_argument("relin_round2: the aggregate's words do not match its shape");
+    if (!residues_canonical(agg1->data, *host)) throw std::invalid_argument("relin_round2: the aggregate holds a word that is not reduced modulo its prime");
+    if (sk.s_ntt.size() != (size_t)host->k * host->N) throw std::invalid_argument("relin_round2: secret key not present");
+    std::unique_ptr<SecureRng> stream = seed ? std::make_unique<SecureRng>(seed, 7) : std::make_unique<SecureRng>();
+    std::vector<std::vector<std::array<uint8_t, 32>>> rk(1);
+    WipeKeyRows wipe_keys{rk};
+    for (uint32_t J = 0; J < D; J++) rk[0].push_back(draw_key32(*stream));
+    auto out = std::make_shared<RelinShare>();
+    out->round = 2;
+    out->N = host->N;
+    out->primes = host->primes;
+    out->n_digits = D;
+    if (on_device()) {
+      out->data.resize((size_t)D * host->k * host->N);
+      std::vector<uint8_t> f1 = keys_flat(eph->r1.data(), D), f2 = keys_flat(rk[0].data(), D);
+      const int rc = evah_keygen_relin_round2(dev->h, D, (const uint64_t *)agg1->data.data(), f1.data(), f2.data(), (uint64_t *)out->data.data());
+      wipe_bytes(f1.data(), f1.size());
+      wipe_bytes(f2.data(), f2.size());
+      chk(rc);
+    } else {
+      out->data = relin_round2_host(*host, sk, D, agg1->data.data(), eph->r1.data(), rk[0].data());
+    }
+    eph->used = true; // u served its one share
+    eph->wipe_keys();
     return out;
   }
   std::array<uint64_t, 6> transfer_stats() {
@@ -1627,17 +1717,60 @@ generate_keys(const CKKSParameters &params, uint64_t seed = 0, bool compress_key
   }
   if (device_keygen && install) pub->eval_keys_installed();
   sec->key_randomness = std::move(kg.kept);
+  if (common_seed) sec->common_relin_seeds = pub->relin.seeds; // public, equal across the parties: what DESIGN.md 1.15 derives its rows from
   return {pub, sec};
 }
 
 // The collective public context of parties whose keys were generated with one common_seed: the public
 // key and every Galois key present in ALL contexts, under s = sum_p s_p.  All parties expanded the same a (pk[1]) and the
 // same c1 of every digit, so c0 adds: sum_p -(a s_p + e_p) = -(a s + sum_p e_p), and a Galois digit's P s_p(X^elt) terms
-// add to P s(X^elt).  The sums run on the host.  No relinearization key: s^2 is not the sum of the s_p^2.
-inline std::shared_ptr<HipPublic> combine_public_contexts(const std::vector<std::shared_ptr<HipPublic>> &ctxs) {
+// add to P s(X^elt).  The sums run on the host.  The relinearization key does not add up (s^2 is not the sum of the
+// s_p^2): it comes from the two rounds of DESIGN.md 1.15 — relin_round1 = the sum of the round-1 shares
+// (combine_relin_shares), relin_round2 = one round-2 share per context — as (c0, c1) = (sum_p g_p, H1), an ordinary
+// uncompressed key.  Both or neither: without them the context has no relinearization key, as before.
+inline std::shared_ptr<HipPublic> combine_public_contexts(const std::vector<std::shared_ptr<HipPublic>> &ctxs,
+                                                          const std::shared_ptr<const RelinShare> &relin_round1 = nullptr,
+                                                          const std::vector<std::shared_ptr<const RelinShare>> *relin_round2 = nullptr) {
   if (ctxs.empty() || ctxs.size() > 64) throw std::invalid_argument("combine_public_contexts: 1..64 public contexts are needed");
   for (auto &c : ctxs)
     if (!c) throw std::invalid_argument("combine_public_contexts: a context is None");
+  if ((relin_round1 != nullptr) != (relin_round2 != nullptr))
+    throw std::invalid_argument("combine_public_contexts: relin_round1 and relin_round2 go together: give both or neither");
+  SwitchKey collective_relin;
+  if (relin_round1) {
+    const HostContext &h0 = *ctxs[0]->host;
+    const size_t poly0 = (size_t)h0.k * h0.N;
+    if (relin_round2->size() != ctxs.size())
+      throw std::invalid_argument("combine_public_contexts: " + std::to_string(relin_round2->size()) + " round-2 shares for " +
+                                  std::to_string(ctxs.size()) + " public contexts: every party contributes one");
+    auto check = [&](const RelinShare *s, uint32_t round, const std::string &what) {
+      if (!s) throw std::invalid_argument("combine_public_contexts: " + what + " is None");
+      if (s->round != round) throw std::invalid_argument("combine_public_contexts: " + what + " is a round-" + std::to_string(s->round) + " share");
+      const std::string diff = rekey_params_differ(s->N, s->primes, h0);
+      if (!diff.empty()) throw std::invalid_argument("combine_public_contexts: " + what + " was made under other encryption parameters than context 0: " + diff);
+      if (s->n_digits == 0 || s->n_digits > h0.k - 1 || s->data.size() != (size_t)s->n_digits * (round == 1 ? 2 : 1) * poly0)
+        throw std::invalid_argument("combine_public_contexts: " + what + ": the words do not match the shape");
+      if (!residues_canonical(s->data, h0)) throw std::invalid_argument("combine_public_contexts: " + what + " holds a word that is not reduced modulo its prime");
+    };
+    check(relin_round1.get(), 1, "relin_round1");
+    const uint32_t D = relin_round1->n_digits;
+    collective_relin.n_digits = D;
+    collective_relin.data.assign((size_t)D * 2 * poly0, 0);
+    for (size_t p = 0; p < relin_round2->size(); p++) {
+      const RelinShare *g = (*relin_round2)[p].get();
+      check(g, 2, "round-2 share " + std::to_string(p));
+      if (g->n_digits != D) throw std::invalid_argument("combine_public_contexts: round-2 share " + std::to_string(p) + " has another digit count than relin_round1");
+      for (uint32_t J = 0; J < D; J++) // c0 of digit J += g_p[J]
+        for (size_t r = 0; r < h0.k; r++) {
+          const u64 q = h0.primes[r];
+          u64 *a = collective_relin.data.data() + ((size_t)2 * J * h0.k + r) * h0.N;
+          const u64 *b = g->data.data() + ((size_t)J * h0.k + r) * h0.N;
+          for (size_t j = 0; j < h0.N; j++) a[j] = evah::addmod(a[j], b[j], q);
+        }
+    }
+    for (uint32_t J = 0; J < D; J++) // c1 of digit J = H1[J]
+      std::copy_n(relin_round1->data.begin() + ((size_t)2 * J + 1) * poly0, poly0, collective_relin.data.begin() + ((size_t)2 * J + 1) * poly0);
+  }
   const HostContext &hc = *ctxs[0]->host;
   const size_t N = hc.N, k = hc.k, poly = k * N;
   auto add_rows = [&](std::vector<u64> &acc, const u64 *src, size_t rows) { // acc [rows][N] += src, row r under prime r % k
@@ -1692,6 +1825,42 @@ inline std::shared_ptr<HipPublic> combine_public_contexts(const std::vector<std:
       add_rows(sum.c0, c0.data(), (size_t)sum.n_digits * k);
     }
     out->galois.emplace(elt, std::move(sum));
+  }
+  if (relin_round1) out->relin = std::move(collective_relin);
+  return out;
+}
+
+// Aggregate 1 of DESIGN.md 1.15: (H0, H1) = the row-by-row sums of the parties' round-1 shares, itself a round-1 share.
+// Public: anyone may form it.  On the host, as the Galois sums above (the shares arrive as host words or files anyway).
+inline std::shared_ptr<RelinShare> combine_relin_shares(const std::vector<std::shared_ptr<const RelinShare>> &shares) {
+  if (shares.empty() || shares.size() > 64) throw std::invalid_argument("combine_relin_shares: round-1 shares of 1..64 parties are needed");
+  for (size_t p = 0; p < shares.size(); p++) {
+    if (!shares[p]) throw std::invalid_argument("combine_relin_shares: share " + std::to_string(p) + " is None");
+    if (shares[p]->round != 1)
+      throw std::invalid_argument("combine_relin_shares: share " + std::to_string(p) + " is a round-" + std::to_string(shares[p]->round) + " share: round-1 shares are summed");
+  }
+  const RelinShare &s0 = *shares[0];
+  const size_t k = s0.primes.size(), N = s0.N, words = (size_t)s0.n_digits * 2 * k * N;
+  if (s0.n_digits == 0 || k < 2 || s0.n_digits > k - 1 || s0.data.size() != words) throw std::invalid_argument("combine_relin_shares: share 0: the words do not match the shape");
+  auto out = std::make_shared<RelinShare>(s0);
+  for (size_t p = 1; p < shares.size(); p++) {
+    const RelinShare &s = *shares[p];
+    if (s.N != s0.N)
+      throw std::invalid_argument("combine_relin_shares: share " + std::to_string(p) + " was made under other encryption parameters than share 0: poly_modulus_degree differs (" +
+                                  std::to_string(s.N) + " against " + std::to_string(s0.N) + ")");
+    if (s.primes.size() != k)
+      throw std::invalid_argument("combine_relin_shares: share " + std::to_string(p) + " was made under other encryption parameters than share 0: the number of primes differs");
+    for (size_t i = 0; i < k; i++)
+      if (s.primes[i] != s0.primes[i])
+        throw std::invalid_argument("combine_relin_shares: share " + std::to_string(p) + " was made under other encryption parameters than share 0: prime " + std::to_string(i) + " differs");
+    if (s.n_digits != s0.n_digits) throw std::invalid_argument("combine_relin_shares: share " + std::to_string(p) + " has another digit count than share 0");
+    if (s.data.size() != words) throw std::invalid_argument("combine_relin_shares: share " + std::to_string(p) + ": the words do not match the shape");
+    for (size_t r = 0; r < words / N; r++) {
+      const u64 q = s0.primes[r % k];
+      u64 *a = out->data.data() + r * N;
+      const u64 *b = s.data.data() + r * N;
+      for (size_t j = 0; j < N; j++) a[j] = evah::addmod(a[j], b[j], q);
+    }
   }
   return out;
 }

@@ -115,6 +115,24 @@ inline void flood_wide(const uint8_t fk[32], uint32_t sigma, uint32_t N, int64_t
   for (int i = 0; i < 16; i++) v[i] = 0;
 }
 
+// The common seed of digit J's public rows a_J in the collective relinearization-key generation: the
+// first 32 bytes of the ChaCha20 block with key = the digit's PUBLIC relinearization-key seed (equal across the parties of
+// one common_seed), block counter 0 and the 8-byte nonce "evarlk\0\0" (state words 14-15, beside "evacrs\0\0" of the
+// common stream and the tags 0x6331 / 0x736d / 0x666c of the expansions).  It must differ from its input: a party's own
+// relinearization key publishes c0 = -(a s_p + e) + w s_p^2 under the input seed's a, and a round-1 share a s_p + e1 under
+// the SAME a would cancel a s_p and leave w s_p^2 plus small noise in the open.  The one derivation of the host and of
+// the callers of evah_keygen_relin_round1.
+inline void relin_round_seed(const uint8_t relin_seed[32], uint8_t out[32]) {
+  static const uint32_t sigma[4] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u};
+  uint32_t st[16], w[16];
+  std::memcpy(st, sigma, 16);
+  std::memcpy(st + 4, relin_seed, 32);
+  st[12] = st[13] = 0;
+  std::memcpy(st + 14, "evarlk\0\0", 8);
+  chacha20_block(st, w);
+  std::memcpy(out, w, 32);
+}
+
 class SecureRng {
 public:
   using result_type = uint64_t;

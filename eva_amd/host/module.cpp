@@ -191,8 +191,12 @@ PYBIND11_MODULE(_eva, m) {
   m.def("save", [seal_compr](const HipPublic &o, const std::string &path, const std::string &format) {
     bool seal = false;
     const sealfmt::Compr c = seal_compr(format, seal);
-    if (seal && o.collective)
+    // the SEAL format keeps refusing every collective context: without the key of DESIGN.md 1.15 it lacks what SEAL's
+    // RelinKeys needs, and with it the file could not say `collective` or name the dropped Galois elements
+    if (seal && o.collective && !o.has_relin_key())
       throw std::invalid_argument("a collective context has no relinearization key, which the SEAL format requires: save it with format='native'");
+    if (seal && o.collective)
+      throw std::invalid_argument("the SEAL format cannot mark a context as collective or name its dropped Galois elements: save it with format='native'");
     if (seal) save_wire_to_file("SEALPublic", sealfmt::encode_public(o, c), path);
     else save_to_file(Kind::Public, o, path);
   }, py::arg("obj"), py::arg("path"), py::arg("format") = "native");
@@ -215,6 +219,13 @@ PYBIND11_MODULE(_eva, m) {
     (void)seal_compr(format, seal);
     if (seal) throw std::invalid_argument("DecryptionShares have no SEAL format: save them with format='native'");
     save_to_file(Kind::Shares, o, path);
+  }, py::arg("obj"), py::arg("path"), py::arg("format") = "native");
+  // a share of the collective relinearization-key generation has this repo's container only (kind 9)
+  m.def("save", [seal_compr](const RelinShare &o, const std::string &path, const std::string &format) {
+    bool seal = false;
+    (void)seal_compr(format, seal);
+    if (seal) throw std::invalid_argument("a RelinShare has no SEAL format: save it with format='native'");
+    save_to_file(Kind::RelinShare, o, path);
   }, py::arg("obj"), py::arg("path"), py::arg("format") = "native");
   // test hooks of the SEAL object format
   m.def("_blake2b_256", [](py::bytes data) {
@@ -277,6 +288,7 @@ PYBIND11_MODULE(_eva, m) {
     if (auto *p = std::get_if<std::shared_ptr<HipPublic>>(&k)) return py::cast(*p);
     if (auto *p = std::get_if<std::shared_ptr<RekeyKey>>(&k)) return py::cast(*p);
     if (auto *p = std::get_if<std::shared_ptr<DecryptionShares>>(&k)) return py::cast(*p);
+    if (auto *p = std::get_if<std::shared_ptr<RelinShare>>(&k)) return py::cast(*p);
     return py::cast(std::get<std::shared_ptr<HipSecret>>(k));
   }, py::arg("path"), "Load a previously saved object (same class as was saved)");
 
@@ -346,10 +358,96 @@ PYBIND11_MODULE(_eva, m) {
     return kp;
   }, py::arg("abstract_params"), py::arg("seed") = 0, py::arg("devices") = py::none(), py::arg("shard") = py::none(),
      py::arg("compress_keys") = false, py::arg("device_keygen") = false, py::arg("device_sampling") = false, py::arg("common_seed") = py::none());
-  mseal.def("combine_public_contexts", &combine_public_contexts, py::arg("public_contexts"),
+  mseal.def("combine_public_contexts", [](const std::vector<std::shared_ptr<HipPublic>> &ctxs, py::object r1, py::object r2) {
+    if (r1.is_none() != r2.is_none()) throw std::invalid_argument("combine_public_contexts: relin_round1 and relin_round2 go together: give both or neither");
+    if (r1.is_none()) return combine_public_contexts(ctxs);
+    const auto agg = r1.cast<std::shared_ptr<RelinShare>>();
+    std::vector<std::shared_ptr<const RelinShare>> g;
+    for (auto &s : r2.cast<std::vector<std::shared_ptr<RelinShare>>>()) g.push_back(s);
+    return combine_public_contexts(ctxs, agg, &g);
+  }, py::arg("public_contexts"), py::arg("relin_round1") = py::none(), py::arg("relin_round2") = py::none(),
             "The collective public context of parties whose keys were made with one generate_keys(..., common_seed=) (DESIGN.md 1.14): "
-            "public key and the Galois keys present in all contexts under the sum of the parties' secrets; no relinearization key. "
-            "It encrypts, executes everything but relinearize, is a make_rekey_key target, and saves / loads");
+            "public key and the Galois keys present in all contexts under the sum of the parties' secrets. relin_round1 (the "
+            "combine_relin_shares aggregate) and relin_round2 (one SEALSecret.relin_round2 share per context) go together and give it the "
+            "collective relinearization key (DESIGN.md 1.15); without them it has none and executes everything but relinearize. "
+            "It encrypts, is a make_rekey_key target, and saves / loads");
+  mseal.def("combine_relin_shares", [](const std::vector<std::shared_ptr<RelinShare>> &shares) {
+    std::vector<std::shared_ptr<const RelinShare>> s(shares.begin(), shares.end());
+    return combine_relin_shares(s);
+  }, py::arg("round1_shares"),
+            "The sum of the parties' round-1 shares of the collective relinearization key (DESIGN.md 1.15), itself a round-1 RelinShare: "
+            "what every party's relin_round2 and combine_public_contexts(relin_round1=) take. Public: anyone may form it");
+  // test hooks: the seed derivation and the host twins of evah_keygen_relin_round1 / _round2 (ckks_host.h) on raw words
+  mseal.def("_relin_round_seeds", [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> seeds) {
+    if (seeds.ndim() != 2 || seeds.shape(1) != 32) throw std::invalid_argument("seeds are [digits][32] bytes");
+    const std::vector<uint8_t> out = relin_round_seeds(std::vector<uint8_t>(seeds.data(), seeds.data() + seeds.size()));
+    py::array_t<uint8_t> a({seeds.shape(0), (py::ssize_t)32});
+    std::memcpy(a.mutable_data(), out.data(), out.size());
+    return a;
+  }, py::arg("relin_seeds"));
+  mseal.def("_relin_round1_host", [](uint32_t N, const std::vector<uint64_t> &primes, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> s_ntt,
+                                     py::array_t<uint8_t, py::array::c_style | py::array::forcecast> seeds,
+                                     py::array_t<uint8_t, py::array::c_style | py::array::forcecast> r1keys) {
+    HostContext h(N, std::vector<u64>(primes.begin(), primes.end()));
+    if (seeds.ndim() != 2 || seeds.shape(1) != 32 || r1keys.ndim() != 2 || r1keys.shape(1) != 32 || r1keys.shape(0) != seeds.shape(0))
+      throw std::invalid_argument("seeds and randomness keys are [digits][32] bytes");
+    SecretKey sk;
+    sk.s_ntt.assign((const u64 *)s_ntt.data(), (const u64 *)s_ntt.data() + s_ntt.size());
+    const uint32_t D = (uint32_t)seeds.shape(0);
+    std::vector<std::array<uint8_t, 32>> rk(D);
+    for (uint32_t J = 0; J < D; J++) std::memcpy(rk[J].data(), r1keys.data() + (size_t)32 * J, 32);
+    return to_numpy(relin_round1_host(h, sk, D, seeds.data(), rk.data()), {(py::ssize_t)D, 2, (py::ssize_t)h.k, (py::ssize_t)N});
+  }, py::arg("N"), py::arg("primes"), py::arg("s_ntt"), py::arg("seeds"), py::arg("r1keys"));
+  mseal.def("_relin_round2_host", [](uint32_t N, const std::vector<uint64_t> &primes, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> s_ntt,
+                                     py::array_t<uint64_t, py::array::c_style | py::array::forcecast> agg1,
+                                     py::array_t<uint8_t, py::array::c_style | py::array::forcecast> r1keys,
+                                     py::array_t<uint8_t, py::array::c_style | py::array::forcecast> r2keys) {
+    HostContext h(N, std::vector<u64>(primes.begin(), primes.end()));
+    if (r1keys.ndim() != 2 || r1keys.shape(1) != 32 || r2keys.ndim() != 2 || r2keys.shape(1) != 32 || r1keys.shape(0) != r2keys.shape(0))
+      throw std::invalid_argument("randomness keys are [digits][32] bytes");
+    const uint32_t D = (uint32_t)r1keys.shape(0);
+    if (agg1.ndim() != 4 || agg1.shape(0) != (py::ssize_t)D || agg1.shape(1) != 2 || agg1.shape(2) != (py::ssize_t)h.k || agg1.shape(3) != (py::ssize_t)N)
+      throw std::invalid_argument("the aggregate is [digits][2][k][N]");
+    SecretKey sk;
+    sk.s_ntt.assign((const u64 *)s_ntt.data(), (const u64 *)s_ntt.data() + s_ntt.size());
+    std::vector<std::array<uint8_t, 32>> k1(D), k2(D);
+    for (uint32_t J = 0; J < D; J++) {
+      std::memcpy(k1[J].data(), r1keys.data() + (size_t)32 * J, 32);
+      std::memcpy(k2[J].data(), r2keys.data() + (size_t)32 * J, 32);
+    }
+    return to_numpy(relin_round2_host(h, sk, D, (const u64 *)agg1.data(), k1.data(), k2.data()), {(py::ssize_t)D, (py::ssize_t)h.k, (py::ssize_t)N});
+  }, py::arg("N"), py::arg("primes"), py::arg("s_ntt"), py::arg("agg1"), py::arg("r1keys"), py::arg("r2keys"));
+  py::class_<RelinShare, std::shared_ptr<RelinShare>>(mseal, "RelinShare",
+                                                      "One party's public share of the collective relinearization-key generation, or the sum of the "
+                                                      "round-1 shares (DESIGN.md 1.15): made by SEALSecret.relin_round1 / relin_round2 and "
+                                                      "combine_relin_shares, taken by combine_public_contexts; saves and loads")
+      .def_readonly("round", &RelinShare::round)
+      .def_readonly("N", &RelinShare::N)
+      .def_readonly("poly_modulus_degree", &RelinShare::N)
+      .def_readonly("primes", &RelinShare::primes)
+      .def_readonly("n_digits", &RelinShare::n_digits)
+      .def("words", [](const RelinShare &s) {
+        if (s.round == 1) return to_numpy(s.data, {(py::ssize_t)s.n_digits, 2, (py::ssize_t)s.primes.size(), (py::ssize_t)s.N});
+        return to_numpy(s.data, {(py::ssize_t)s.n_digits, (py::ssize_t)s.primes.size(), (py::ssize_t)s.N});
+      }, "round 1: [digits][2][k][N]; round 2: [digits][k][N]; NTT form")
+      // test hook: a share from raw words, unchecked (what a file would be checked for is checked where the share is used)
+      .def_static("_from_words", [](uint32_t round, const std::vector<uint64_t> &primes, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> words) {
+        if (words.ndim() < 3) throw std::invalid_argument("share words are [digits][2][k][N] or [digits][k][N]");
+        auto s = std::make_shared<RelinShare>();
+        s->round = round;
+        s->n_digits = (uint32_t)words.shape(0);
+        s->N = (uint32_t)words.shape(words.ndim() - 1);
+        s->primes.assign(primes.begin(), primes.end());
+        s->data.assign((const u64 *)words.data(), (const u64 *)words.data() + words.size());
+        return s;
+      }, py::arg("round"), py::arg("primes"), py::arg("words"));
+  py::class_<RelinEphemeral, std::shared_ptr<RelinEphemeral>>(mseal, "RelinEphemeral",
+                                                              "What a party keeps between relin_round1 and relin_round2 (DESIGN.md 1.15): the keys its u is "
+                                                              "regenerated from. Secret (whoever learns it learns the party's secret key), opaque, serves one "
+                                                              "relin_round2 of the context that made it, cannot be saved or pickled, wiped when used and when destroyed")
+      .def_readonly("used", &RelinEphemeral::used)
+      .def("__reduce__", [](const RelinEphemeral &) -> py::object { throw py::type_error("a RelinEphemeral cannot be pickled: it holds a party's ephemeral secret"); })
+      .def("__reduce_ex__", [](const RelinEphemeral &, int) -> py::object { throw py::type_error("a RelinEphemeral cannot be pickled: it holds a party's ephemeral secret"); });
   // test hook: small polynomial p of a 32-byte randomness key (csprng.h sampled_small) -> int8 [N]
   mseal.def("_sampled_small", [](py::bytes rk, uint32_t p, uint32_t N) {
     const std::string k = rk;
@@ -733,7 +831,9 @@ PYBIND11_MODULE(_eva, m) {
       .def_property_readonly("primes", [](const HipPublic &p) { return std::vector<uint64_t>(p.host->primes.begin(), p.host->primes.end()); })
       .def_readonly("dropped_galois_elements", &HipPublic::dropped_galois,
                     "combine_public_contexts: the Galois elements that some party's context lacked and this collective context therefore has no key for")
-      .def_readonly("collective", &HipPublic::collective, "made by combine_public_contexts (DESIGN.md 1.14): no relinearization key")
+      .def_readonly("collective", &HipPublic::collective, "made by combine_public_contexts (DESIGN.md 1.14); see has_relin_key")
+      .def_property_readonly("has_relin_key", &HipPublic::has_relin_key,
+                             "False only for a collective context whose parties did not run the relinearization-key rounds (DESIGN.md 1.15)")
       // host FP64 encoder + host NTT: the plaintext an Encode node produces (tests pin the
       // integer path "from the encoded plaintext onward")
       .def("_encode", [](const HipPublic &p, const std::vector<double> &values, uint32_t scale_bits, uint32_t level) {
@@ -751,11 +851,12 @@ PYBIND11_MODULE(_eva, m) {
       }, py::arg("values"), py::arg("scale_bits"), py::arg("level"))
       // the full words of a key, materialised for the caller when the context keeps it compressed (which it goes on doing)
       .def("relin_key", [](const HipPublic &p) {
-        if (p.collective) throw std::invalid_argument("relinearization key not present (a collective context has none)");
+        if (!p.has_relin_key()) throw std::invalid_argument(p.no_relin_key_message());
         std::vector<u64> tmp;
         return to_numpy(p.relin.words(*p.host, tmp), {(py::ssize_t)p.relin.n_digits, 2, (py::ssize_t)p.host->k, (py::ssize_t)p.host->N});
       })
-      .def_property_readonly("keys_compressed", &HipPublic::keys_compressed, "the evaluation keys are kept, saved and uploaded as c0 + a 32-byte seed per digit (generate_keys(..., compress_keys=True))")
+      .def_property_readonly("keys_compressed", &HipPublic::keys_compressed, "the evaluation keys are kept, saved and uploaded as c0 + a 32-byte seed per digit (generate_keys(..., compress_keys=True)). "
+                             "For a collective context this speaks of the Galois keys: its relinearization key, if it has one, is kept whole")
       .def("key_seeds", [](const HipPublic &p) -> py::object {
         if (!p.keys_compressed()) return py::none();
         auto seeds_of = [](const SwitchKey &k) {
@@ -764,10 +865,11 @@ PYBIND11_MODULE(_eva, m) {
           return a;
         };
         py::dict d;
-        if (!p.collective) d[py::int_(0)] = seeds_of(p.relin);
+        if (p.relin.compressed()) d[py::int_(0)] = seeds_of(p.relin); // a collective context's key is whole: no entry
         for (auto &kv : p.galois) d[py::int_(kv.first)] = seeds_of(kv.second);
         return d;
-      }, "{0: the relinearization key's seeds [digits][32], Galois element: that key's} of a compressed context (DESIGN.md 1.4), else None")
+      }, "{0: the relinearization key's seeds [digits][32], Galois element: that key's} of a compressed context (DESIGN.md 1.4), else None; "
+         "a key that is kept whole (the relinearization key of a collective context) has no entry")
       .def("public_key", [](const HipPublic &p) { return to_numpy(p.pk.data, {2, (py::ssize_t)p.host->k, (py::ssize_t)p.host->N}); })
       .def("galois_keys", [](const HipPublic &p) {
         py::dict d;
@@ -905,6 +1007,18 @@ PYBIND11_MODULE(_eva, m) {
            "The RekeyKey from this key pair to the one `target_public_ctx` belongs to (same poly_modulus_degree and primes), made from the "
            "target's public key (DESIGN.md 1.13). Whoever holds it together with the target's secret key learns this secret key: that is "
            "inherent to proxy re-encryption. seed != 0 is the reproducible test hook and not secret-grade")
+      .def("relin_round1", [](HipSecret &s, uint64_t seed) {
+        auto r = s.relin_round1(seed);
+        return py::make_tuple(r.first, r.second);
+      }, py::arg("seed") = 0,
+           "Round 1 of the collective relinearization-key generation (DESIGN.md 1.15): returns (eph, share1). share1 is this party's public "
+           "RelinShare; eph is its ephemeral secret for relin_round2. Needs keys made by generate_keys(..., common_seed=). seed != 0 is the "
+           "reproducible test hook and not secret-grade")
+      .def("relin_round2", [](HipSecret &s, std::shared_ptr<RelinEphemeral> eph, std::shared_ptr<RelinShare> agg1, uint64_t seed) {
+        return s.relin_round2(eph, agg1, seed);
+      }, py::arg("eph"), py::arg("agg1"), py::arg("seed") = 0,
+           "Round 2 (DESIGN.md 1.15): this party's RelinShare from its own eph of relin_round1 — which serves once — and the "
+           "combine_relin_shares aggregate of ALL parties' round-1 shares. seed != 0 is the reproducible test hook and not secret-grade")
       .def("transfer_stats", [](HipSecret &s) {
         auto st = s.transfer_stats();
         py::dict d;

@@ -22,18 +22,24 @@ public:
   SwitchKey relin;
   std::map<uint32_t, SwitchKey> galois; // by Galois element
   // the evaluation keys are kept as c0 + one seed per digit (generate_keys(..., compress_keys))
+  // For a collective context this speaks of the Galois keys, which are sums of compressed keys; its relinearization key,
+  // when it has one, is kept whole (its c1 = H1 is no seed's expansion) and is absent from key_seeds()
   bool keys_compressed() const { return collective ? true : relin.compressed(); }
   // A collective context (combine_public_contexts): the keys belong to s = sum_p s_p, a secret nobody holds.
-  // It has NO relinearization key (s^2 is not the sum of the s_p^2): `relin` stays empty, no key of that kind is uploaded,
-  // and a program that relinearizes is refused before anything runs.
+  // Its relinearization key does not add up (s^2 is not the sum of the s_p^2): it is there only when the parties ran the two
+  // rounds of DESIGN.md 1.15.  Without it `relin` stays empty, no key of that kind is uploaded, and a program that
+  // relinearizes is refused before anything runs.
   bool collective = false;
+  bool has_relin_key() const { return relin.n_digits != 0; }
   std::vector<uint32_t> dropped_galois; // combine_public_contexts: the Galois elements some party lacked, left out of this context
   void refuse_relinearize(const Program &program) const {
-    if (!collective) return;
+    if (has_relin_key()) return;
     const std::vector<char> live = program.live_mask();
     for (TermId t = 0; t < live.size(); t++)
-      if (live[t] && program.at(t).op == Op::Relinearize)
-        throw std::invalid_argument("relinearization key not present (a collective context has none)");
+      if (live[t] && program.at(t).op == Op::Relinearize) throw std::invalid_argument(no_relin_key_message());
+  }
+  std::string no_relin_key_message() const {
+    return collective ? "relinearization key not present (a collective context has none)" : "relinearization key not present";
   }
   int device = 0;
   bool free_eagerly = true;
@@ -441,7 +447,7 @@ private:
       if (k.compressed()) chk(evah_key_upload_seeded(c, kind, elt, k.n_digits, (const uint64_t *)k.c0_words().data(), k.seeds.data()));
       else chk(evah_key_upload(c, kind, elt, k.n_digits, (const uint64_t *)k.data.data()));
     };
-    if (!collective) up(EVAH_KEY_RELIN, 0, relin);
+    if (has_relin_key()) up(EVAH_KEY_RELIN, 0, relin);
     for (auto &kv : galois) up(EVAH_KEY_GALOIS, kv.first, kv.second);
   }
   void check_devices() const {

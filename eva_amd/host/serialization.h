@@ -15,7 +15,7 @@ namespace evahost {
 
 constexpr uint32_t FORMAT_MAGIC = 0x48415645; // "EVAH"
 constexpr uint32_t FORMAT_VERSION = 1;
-enum class Kind : uint32_t { Program = 1, Parameters = 2, Signature = 3, Valuation = 4, Public = 5, Secret = 6, RekeyKey = 7, Shares = 8 };
+enum class Kind : uint32_t { Program = 1, Parameters = 2, Signature = 3, Valuation = 4, Public = 5, Secret = 6, RekeyKey = 7, Shares = 8, RelinShare = 9 };
 
 class Writer {
 public:
@@ -294,14 +294,23 @@ inline SwitchKey read_switch_key(Reader &r) {
   }
   return k;
 }
-// A collective context has no relinearization key: in its place the file holds this digit count alone,
+// A collective context whose parties did not run the rounds of DESIGN.md 1.15 has no relinearization key:
+// in its place the file holds this digit count alone,
 // which no context has, so a reader from before that form refuses the file ("wrong size for its context").
 constexpr uint32_t SWITCH_KEY_ABSENT = 0x40000000u;
+// A collective context WITH a relinearization key puts this word — again a digit count no context has —
+// and the list of its dropped Galois elements in front of the key, so that `collective` and dropped_galois_elements come
+// back with it.  A collective context without the key is written as before (SWITCH_KEY_ABSENT alone), bit for bit, and
+// files of either earlier form load as they did.
+constexpr uint32_t SWITCH_KEY_COLLECTIVE = 0x20000000u;
 inline void write(Writer &w, const HipPublic &p) {
   write_ctx(w, *p.host);
   w.vec(p.pk.data);
-  if (p.collective) w.pod<uint32_t>(SWITCH_KEY_ABSENT);
-  else write(w, p.relin);
+  if (!p.has_relin_key()) w.pod<uint32_t>(SWITCH_KEY_ABSENT);
+  else {
+    if (p.collective) { w.pod<uint32_t>(SWITCH_KEY_COLLECTIVE); w.vec(p.dropped_galois); }
+    write(w, p.relin);
+  }
   w.pod<uint64_t>(p.galois.size());
   for (auto &kv : p.galois) { w.pod(kv.first); write(w, kv.second); }
 }
@@ -338,6 +347,13 @@ inline std::shared_ptr<HipPublic> read_public(Reader &r) {
     (void)r.pod<uint32_t>();
     p->collective = true;
   } else {
+    if (r.peek<uint32_t>() == SWITCH_KEY_COLLECTIVE) {
+      (void)r.pod<uint32_t>();
+      p->collective = true;
+      p->dropped_galois = r.vec<uint32_t>();
+      for (uint32_t elt : p->dropped_galois)
+        if (!(elt & 1) || elt >= 2 * p->host->N) throw std::runtime_error("Could not parse message: Galois element is not valid");
+    }
     p->relin = read_switch_key(r);
     check_switch_key(p->relin, *p->host, "relinearization key");
   }
@@ -443,6 +459,34 @@ inline std::shared_ptr<DecryptionShares> read_shares(Reader &r) {
   return d;
 }
 
+// A share of the collective relinearization-key generation, kind 9: the parameters it was made under, its
+// round (1: [digits][2][k][N], also the aggregate; 2: [digits][k][N]), the digit count and the words
+inline void write(Writer &w, const RelinShare &s) {
+  w.pod(s.N);
+  w.vec(s.primes);
+  w.pod(s.round);
+  w.pod(s.n_digits);
+  w.vec(s.data);
+}
+inline std::shared_ptr<RelinShare> read_relin_share(Reader &r) {
+  auto s = std::make_shared<RelinShare>();
+  s->primes = read_params(r, s->N); // (no HostContext: a share file needs no transform tables)
+  const size_t N = s->N, k = s->primes.size();
+  s->round = r.pod<uint32_t>();
+  s->n_digits = r.pod<uint32_t>();
+  s->data = r.vec<u64>();
+  if (s->round != 1 && s->round != 2) throw std::runtime_error("Could not parse message: relinearization share round must be 1 or 2");
+  if (s->n_digits == 0 || s->n_digits > k - 1 || s->data.size() != (size_t)s->n_digits * (s->round == 1 ? 2 : 1) * k * N)
+    throw std::runtime_error("Could not parse message: relinearization share has the wrong size for its parameters");
+  for (size_t row = 0; row < s->data.size() / N; row++) {
+    const u64 q = s->primes[row % k];
+    const u64 *wd = s->data.data() + row * N;
+    for (size_t t = 0; t < N; t++)
+      if (wd[t] >= q) throw std::runtime_error("Could not parse message: relinearization share holds a word that is not reduced modulo its prime");
+  }
+  return s;
+}
+
 template <class T> void save_to_file(Kind kind, const T &obj, const std::string &path) {
   Writer w;
   w.pod(FORMAT_MAGIC); w.pod(FORMAT_VERSION); w.pod<uint32_t>((uint32_t)kind);
@@ -467,7 +511,7 @@ inline void save_wire_to_file(const std::string &type, const std::string &payloa
 }
 
 using KnownType = std::variant<std::unique_ptr<Program>, CKKSParameters, CKKSSignature, HipValuation, std::shared_ptr<HipPublic>, std::shared_ptr<HipSecret>,
-                               std::shared_ptr<RekeyKey>, std::shared_ptr<DecryptionShares>>;
+                               std::shared_ptr<RekeyKey>, std::shared_ptr<DecryptionShares>, std::shared_ptr<RelinShare>>;
 inline KnownType load_from_file(const std::string &path) {
   std::ifstream f(path, std::ios::binary);
   if (!f) throw std::runtime_error("Could not open file " + path);
@@ -497,6 +541,7 @@ inline KnownType load_from_file(const std::string &path) {
   case Kind::Secret: return read_secret(r);
   case Kind::RekeyKey: return read_rekey_key(r);
   case Kind::Shares: return read_shares(r);
+  case Kind::RelinShare: return read_relin_share(r);
   }
   throw std::runtime_error("Unknown inner message type");
 }

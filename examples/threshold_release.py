@@ -4,8 +4,9 @@
     PYTHONPATH=. python examples/threshold_release.py
 
 Three parties generate their keys from one common seed; the public halves add up to a collective public context whose
-secret key s = s_0 + s_1 + s_2 nobody holds.  The server encrypts and computes under it (everything but relinearize: the
-collective context has no relinearization key), and a result is opened only when every party contributes a share:
+secret key s = s_0 + s_1 + s_2 nobody holds.  The server encrypts and computes under it (everything but relinearize here:
+the relinearization key takes the two rounds of examples/threshold_multiply.py), and a result is opened only when every
+party contributes a share:
 
     leg 1   program under the collective key  ->  decrypt_share x 3  ->  combine_shares
     leg 2   one owner's x^2 under the owner's key  ->  public_ctx.rekey to the collective key  ->  the same opening

@@ -125,6 +125,23 @@ int evah_keygen_public(evah_ctx *ctx, const uint8_t *ekey32, const uint8_t *seed
  * capturing context, a limb shard, null pointers, a missing secret key, a bad digit count and N not divisible by 256. */
 int evah_keygen_rekey(evah_ctx *ctx, const uint64_t *pk_target /* [2][k][N] */, uint32_t n_digits,
                       const uint8_t *rkeys /* [n_digits][32] */, uint64_t *key_out /* [n_digits][2][k][N] */);
+/* The two rounds of the collective relinearization-key generation (SEAL has no such call — the protocol
+ * of Mouchet et al., "Multiparty homomorphic encryption from ring-learning-with-errors"), for a party whose secret key s
+ * evah_client_key_upload(EVAH_KEY_SECRET) left on ctx.  With w_J[i] = [i == J] (P mod q_J), for digit J and prime row i:
+ *   round 1:  h0[J][i] = -(a_J[i] u_J[i]) + NTT_i(e0_J) + w_J[i] s[i],   h1[J][i] = a_J[i] s[i] + NTT_i(e1_J),
+ *             a_J[i] = the expansion of seeds[J] under chain prime i (never stored), (u_J, e0_J, e1_J) =
+ *             sampled_small(r1keys[J], 0 / 1 / 2);
+ *   round 2:  g[J][i] = s[i] H0[J][i] + NTT_i(e2_J) + (u_J[i] - s[i]) H1[J][i] + NTT_i(e3_J),  (H0, H1) = agg1[J] the sums of
+ *             all parties' round-1 shares, u_J from r1keys[J] again, (e2_J, e3_J) = sampled_small(r2keys[J], 1 / 2).
+ * `seeds` are PUBLIC and common to all parties and must not be the seeds of any party's own relinearization key (the
+ * caller derives them: relin_round_seed, eva_amd/host/ckks_host.h).  The randomness keys are secrets: they, the sampled
+ * residues and their NTT forms are zeroed on the queue before their memory returns to the pool, also when the call
+ * fails.  One kernel launch per call after the sampling.  Both refuse what evah_keygen_rekey refuses. */
+int evah_keygen_relin_round1(evah_ctx *ctx, uint32_t n_digits, const uint8_t *seeds /* [n_digits][32] */,
+                             const uint8_t *r1keys /* [n_digits][32] */, uint64_t *share_out /* [n_digits][2][k][N] */);
+int evah_keygen_relin_round2(evah_ctx *ctx, uint32_t n_digits, const uint64_t *agg1 /* [n_digits][2][k][N] */,
+                             const uint8_t *r1keys /* [n_digits][32] */, const uint8_t *r2keys /* [n_digits][32] */,
+                             uint64_t *share_out /* [n_digits][k][N] */);
 /* c0 of an installed relinearization or Galois key (what saving the RelinKeys / GaloisKeys of
  * generateKeys, seal.cpp:174-203, needs of a key that was generated in place): d[J][0] of every digit -> out, one
  * linear copy per digit on ctx's queue, then a drain.  Refuses a key that is not present and a limb shard. */
