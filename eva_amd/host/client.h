@@ -179,6 +179,16 @@ struct WipeOnExit {
   std::vector<int8_t> &s;
   ~WipeOnExit() { wipe(s); }
 };
+// the 32-byte randomness keys of a call, per name (or one row), per instance
+struct WipeKeyRows {
+  std::vector<std::vector<std::array<uint8_t, 32>>> &k;
+  ~WipeKeyRows() { for (auto &n : k) for (auto &x : n) wipe_bytes(x.data(), 32); }
+};
+// stream k of a client call: keyed from the OS, or (seed != 0) the reproducible test hook — NOT secret-grade
+inline std::unique_ptr<SecureRng> client_stream(uint64_t seed, uint64_t k) {
+  if (seed) return std::make_unique<SecureRng>(seed, k);
+  return std::unique_ptr<SecureRng>(new SecureRng());
+}
 
 // ---- the array calls
 // What encrypt_array makes of its arguments before anything is drawn: the sorted names of the call with their classes
@@ -269,6 +279,86 @@ inline std::vector<uint8_t> keys_flat(const std::array<uint8_t, 32> *keys, size_
   for (size_t b = 0; b < n; b++) std::copy(keys[b].begin(), keys[b].end(), flat.begin() + b * 32);
   return flat;
 }
+// bytes of a row of n decoded values of dtype (EVAH_F64 / EVAH_F32 / EVAH_U8), as decrypt_array and combine_shares write them
+inline size_t row_bytes(int dtype, size_t n) { return n * (dtype == EVAH_F32 ? 4 : dtype == EVAH_U8 ? 1 : 8); }
+
+// ---- what the calls that consume handles share: one shape check, one way from a value to a handle the device reads, one
+// walk over a name's segments
+// A ciphertext of min_size .. max_size polynomials whose limb count fits the chain and whose words number size * limbs * N:
+// host words are counted; a value that is only resident has the device's own, size * limbs * dev->N of them, so its
+// degree is compared instead and nothing is downloaded.  label: "output NAME", "value NAME", "rekey: value NAME" — every
+// call keeps the prefix it always had.
+inline void check_cipher_shape(const HostContext &hc, const std::string &label, const HostCipher &c, uint32_t min_size, uint32_t max_size) {
+  if (c.size < min_size || c.size > max_size || c.limbs < 1 || c.limbs > hc.k - 1 ||
+      (!resident_only(c) && words(c).size() != (size_t)c.size * c.limbs * hc.N) || (c.dev && c.dev->N != hc.N))
+    throw std::runtime_error(label + ": ciphertext shape does not match its data or the encryption parameters");
+}
+// a handle of another GPU, copied to dev; keep owns the copy
+inline const evah_ct *copy_over(const std::shared_ptr<DeviceCtx> &dev, const evah_ct *src, std::vector<CtHandle> &keep) {
+  evah_ct *h = nullptr;
+  chk(evah_ct_copy(dev->h, src, &h));
+  keep.emplace_back(dev->h, h);
+  return h;
+}
+// which resident values a call reads where they are
+enum class InPlace {
+  SameState, // decrypt, decrypt_batch (1.6), refresh (1.12), a list given to decrypt_array (kept as found): the call's own device state
+  SameGpu,   // rekey, decrypt_share (1.14), combine_shares (kept as found): any device state of the call's GPU
+};
+// how every other value comes to the call's device
+enum class BringOver {
+  Upload, // decrypt, decrypt_batch, refresh, decrypt_array's list, decrypt_share: its words from the host (downloaded first where it is resident elsewhere)
+  Copy,   // rekey, combine_shares (kept as found): resident on another GPU — evah_ct_copy; host words — uploaded
+};
+// One value as a handle dev reads, its shape checked first (1 .. 3 polynomials; the calls that take size 2 alone have
+// refused every other size, in their own words, before they come here).  keep owns what was made for the call.
+inline const evah_ct *source_handle(const std::shared_ptr<DeviceCtx> &dev, const HostContext &hc, const std::string &label, const HostCipher &c,
+                                    std::vector<CtHandle> &keep, InPlace rule, BringOver how) {
+  check_cipher_shape(hc, label, c, 1, 3);
+  if (c.dev && (rule == InPlace::SameState ? c.dev->root == dev : c.dev->root->device == dev->device)) return c.dev->h->h;
+  if (c.dev && how == BringOver::Copy) return copy_over(dev, c.dev->h->h, keep);
+  evah_ct *h = nullptr;
+  chk(evah_ct_upload(dev->h, c.size, c.limbs, c.scale, (const uint64_t *)words(c).data(), &h));
+  keep.emplace_back(dev->h, h);
+  return h;
+}
+// The walk over the segments of one name of a batch, for decrypt_array, refresh, decrypt_share, rekey and
+// combine_shares: consecutive segments of one size, limb count and scale are packed into groups of <= 64 instances, and fn
+// makes its one device call per group.  The walk refuses, under label ("output NAME" / "value NAME"): a segment of more
+// than 64 instances; segments that hold more instances than the batch — before fn sees the group, so no row past the
+// caller's array is written; and, at the end, segments that do not hold every instance.  A batch on another GPU than dev
+// (rekey, decrypt_share, combine_shares; the others require root == dev) is copied over group by group.
+// One grouping rule for all five.  decrypt_share and combine_shares take size 2 alone, so for them it is (limbs, scale), as
+// before.  rekey grouped by limbs alone: the rule could only split a group whose segments share limbs and differ in scale,
+// which changes no word (evah_rekey_many treats every handle independently) and which no public call can build — batches
+// come from encrypt_array, execute_batch, refresh and rekey, all uniform per name.
+struct SegmentGroup {
+  size_t s0 = 0, s1 = 0, row = 0, n = 0; // segments [s0, s1): instances [row, row + n) of the batch
+  std::vector<const evah_ct *> hs;       // a handle per segment
+  std::vector<CtHandle> keep;            // owns the group's copies, and what fn adds, until the group is done
+};
+template <class F>
+void walk_segments(const std::string &label, const std::vector<BatchSegment> &segs, size_t B, const std::shared_ptr<DeviceCtx> &dev,
+                   const std::shared_ptr<DeviceCtx> &root, F fn) {
+  const bool same_gpu = root->device == dev->device;
+  size_t row = 0;
+  for (size_t s0 = 0; s0 < segs.size();) {
+    SegmentGroup g;
+    g.s0 = g.s1 = s0;
+    g.row = row;
+    while (g.s1 < segs.size() && g.n + segs[g.s1].n <= CLIENT_BATCH_MAX && segs[g.s1].size == segs[s0].size && segs[g.s1].limbs == segs[s0].limbs &&
+           segs[g.s1].scale == segs[s0].scale) {
+      g.hs.push_back(same_gpu ? segs[g.s1].h->h : copy_over(dev, segs[g.s1].h->h, g.keep));
+      g.n += segs[g.s1++].n;
+    }
+    if (g.s1 == s0) throw std::runtime_error(label + ": a segment holds more than 64 instances");
+    if (row + g.n > B) throw std::runtime_error(label + ": the segments hold more instances than the batch");
+    fn(g);
+    row += g.n;
+    s0 = g.s1;
+  }
+  if (row != B) throw std::runtime_error(label + ": the segments do not hold every instance");
+}
 // instance b of a batch as an ordinary valuation: every ciphertext a view of its segment (evah_ct_unstack), a symmetric
 // one with its seed, so that save() still writes it compressed — the bridge to decrypt, save and execute
 inline HipValuation batch_instance(const HipValuationBatch &vb, size_t b) {
@@ -307,7 +397,6 @@ inline HipValuation batch_instance(const HipValuationBatch &vb, size_t b) {
 // other is uploaded first (as decrypt() does); plaintexts and raw vectors are taken from instance 0
 inline HipValuationBatch batch_of_list(const std::vector<const HipValuation *> &list, const std::shared_ptr<DeviceCtx> &dev,
                                        const std::shared_ptr<HostContext> &host) {
-  const HostContext &hc = *host;
   HipValuationBatch vb;
   vb.B = list.size();
   vb.root = dev;
@@ -330,12 +419,10 @@ inline HipValuationBatch batch_of_list(const std::vector<const HipValuation *> &
       if (c->dev && c->dev->root == dev) {
         s.h = c->dev->h;
         s.queue = c->dev->queue;
-      } else {
-        if (c->size < 1 || c->size > 3 || c->limbs < 1 || c->limbs > hc.k - 1 || words(*c).size() != (size_t)c->size * c->limbs * hc.N)
-          throw std::runtime_error("value " + kv.first + ": ciphertext shape does not match its data or the encryption parameters");
-        evah_ct *h = nullptr;
-        chk(evah_ct_upload(dev->h, c->size, c->limbs, c->scale, (const uint64_t *)words(*c).data(), &h));
-        s.h = std::make_shared<CtHandle>(dev->h, h);
+      } else { // the segment owns the upload
+        std::vector<CtHandle> keep;
+        source_handle(dev, *host, "value " + kv.first, *c, keep, InPlace::SameState, BringOver::Upload);
+        s.h = std::make_shared<CtHandle>(std::move(keep.back()));
       }
       bc.segments.push_back(std::move(s));
     }
@@ -464,12 +551,9 @@ inline std::vector<HipValuation> HipPublic::encrypt_batch(const std::vector<Valu
     }
   };
   if (device_sampling) {
-    std::unique_ptr<SecureRng> stream = seed ? std::make_unique<SecureRng>(seed, 5) : std::make_unique<SecureRng>();
+    std::unique_ptr<SecureRng> stream = client_stream(seed, 5);
     std::vector<std::vector<std::array<uint8_t, 32>>> rkeys(names.size()); // per name, per instance
-    struct WipeKeys {
-      std::vector<std::vector<std::array<uint8_t, 32>>> &k;
-      ~WipeKeys() { for (auto &n : k) for (auto &x : n) wipe_bytes(x.data(), 32); }
-    } wipe_keys{rkeys};
+    WipeKeyRows wipe_keys{rkeys};
     std::vector<InputClass> cls;
     for (const std::string &name : names) cls.push_back(classify_input(*host, sig, name));
     for (size_t b = 0; b < inputs.size(); b++)
@@ -564,12 +648,9 @@ inline HipValuationBatch HipPublic::encrypt_array(const std::map<std::string, Ar
   ensure_public_key(); // (before the checks: a device array's rows are summed on the device state)
   const ArrayInputs in = plan_array_inputs(*host, arrays, shared, sig, out, plains, dev->h);
   out.root = dev;
-  std::unique_ptr<SecureRng> stream = seed ? std::make_unique<SecureRng>(seed, 5) : std::make_unique<SecureRng>();
+  std::unique_ptr<SecureRng> stream = client_stream(seed, 5);
   std::vector<std::vector<std::array<uint8_t, 32>>> rkeys(in.names.size()); // per name, per instance
-  struct WipeKeys {
-    std::vector<std::vector<std::array<uint8_t, 32>>> &k;
-    ~WipeKeys() { for (auto &n : k) for (auto &x : n) wipe_bytes(x.data(), 32); }
-  } wipe_keys{rkeys};
+  WipeKeyRows wipe_keys{rkeys};
   for (size_t b = 0; b < out.B; b++)
     for (size_t i = 0; i < in.names.size(); i++)
       if (in.arr[i]) rkeys[i].push_back(draw_key32(*stream));
@@ -619,20 +700,6 @@ inline uint32_t HipPublic::install_rekey_key(const std::shared_ptr<const RekeyKe
   rekey_slots.emplace_back(rk, slot);
   return slot;
 }
-// one value as a handle evah_rekey_many reads: resident on this GPU — in place; on another GPU — copied over; host words —
-// uploaded.  `keep` owns what was made for the call.
-inline const evah_ct *rekey_source(const std::shared_ptr<DeviceCtx> &dev, const HostContext &hc, const std::string &name, const HostCipher &c,
-                                   std::vector<CtHandle> &keep) {
-  if (c.size != 2) throw std::invalid_argument("rekey: value " + name + ": re-key expects a size-2 ciphertext (relinearize first)");
-  if (c.limbs < 1 || c.limbs > hc.k - 1 || (c.dev && c.dev->N != hc.N) || (!resident_only(c) && words(c).size() != (size_t)2 * c.limbs * hc.N))
-    throw std::runtime_error("rekey: value " + name + ": ciphertext shape does not match its data or the encryption parameters");
-  if (c.dev && c.dev->root->device == dev->device) return c.dev->h->h;
-  evah_ct *h = nullptr;
-  if (c.dev) chk(evah_ct_copy(dev->h, c.dev->h->h, &h));
-  else chk(evah_ct_upload(dev->h, 2, c.limbs, c.scale, (const uint64_t *)words(c).data(), &h));
-  keep.emplace_back(dev->h, h);
-  return h;
-}
 inline HipValuation HipPublic::rekey(const HipValuation &enc, const std::shared_ptr<const RekeyKey> &rk) {
   for (auto &kv : enc.values) // (before anything is uploaded)
     if (auto *c = std::get_if<HostCipher>(&kv.second))
@@ -648,8 +715,8 @@ inline HipValuation HipPublic::rekey(const HipValuation &enc, const std::shared_
       out.values[kv.first] = kv.second;
       continue;
     }
-    std::vector<CtHandle> keep;
-    const evah_ct *h = rekey_source(dev, *host, kv.first, *c, keep);
+    std::vector<CtHandle> keep; // resident on this GPU: in place; on another GPU: copied over; host words: uploaded
+    const evah_ct *h = source_handle(dev, *host, "rekey: value " + kv.first, *c, keep, InPlace::SameGpu, BringOver::Copy);
     evah_ct *o = nullptr;
     chk(evah_rekey_many(dev->h, slot, &h, 1, &o));
     out.values[kv.first] = cipher_of_handle(dev, *host, o, c->limbs, c->scale, /*resident=*/true);
@@ -664,7 +731,6 @@ inline HipValuationBatch HipPublic::rekey_batch(const HipValuationBatch &vb, con
   if (vb.params && !rekey_params_differ(vb.params->N, vb.params->primes, *host).empty())
     throw std::invalid_argument("rekey: the batch belongs to other encryption parameters: " + rekey_params_differ(vb.params->N, vb.params->primes, *host));
   if (!vb.root) throw std::runtime_error("rekey: the batch holds no device handles");
-  const bool same_gpu = vb.root->device == dev->device;
   HipValuationBatch out;
   out.B = vb.B;
   out.params = host;
@@ -674,31 +740,12 @@ inline HipValuationBatch HipPublic::rekey_batch(const HipValuationBatch &vb, con
   for (auto &nc : vb.ciphers) {
     const auto &segs = nc.second.segments;
     BatchCipher &bc = out.ciphers[nc.first];
-    size_t row = 0;
-    for (size_t s0 = 0; s0 < segs.size();) {
-      std::vector<CtHandle> keep;
-      std::vector<const evah_ct *> hs;
-      size_t n = 0, s1 = s0;
-      while (s1 < segs.size() && n + segs[s1].n <= CLIENT_BATCH_MAX && segs[s1].limbs == segs[s0].limbs) {
-        if (same_gpu) {
-          hs.push_back(segs[s1].h->h);
-        } else {
-          evah_ct *h = nullptr;
-          chk(evah_ct_copy(dev->h, segs[s1].h->h, &h));
-          keep.emplace_back(dev->h, h);
-          hs.push_back(h);
-        }
-        n += segs[s1++].n;
-      }
-      if (s1 == s0) throw std::runtime_error("value " + nc.first + ": a segment holds more than 64 instances");
-      std::vector<evah_ct *> outs(hs.size(), nullptr);
-      chk(evah_rekey_many(dev->h, slot, hs.data(), (uint32_t)hs.size(), outs.data()));
-      for (size_t s = s0; s < s1; s++)
-        bc.segments.push_back(BatchSegment{std::make_shared<CtHandle>(dev->h, outs[s - s0]), segs[s].n, nullptr, 2, segs[s].limbs, segs[s].scale});
-      row += n;
-      s0 = s1;
-    }
-    if (row != vb.B) throw std::runtime_error("value " + nc.first + ": the segments do not hold every instance");
+    walk_segments("value " + nc.first, segs, vb.B, dev, vb.root, [&](SegmentGroup &g) {
+      std::vector<evah_ct *> outs(g.hs.size(), nullptr);
+      chk(evah_rekey_many(dev->h, slot, g.hs.data(), (uint32_t)g.hs.size(), outs.data()));
+      for (size_t s = g.s0; s < g.s1; s++)
+        bc.segments.push_back(BatchSegment{std::make_shared<CtHandle>(dev->h, outs[s - g.s0]), segs[s].n, nullptr, 2, segs[s].limbs, segs[s].scale});
+    });
   }
   return out;
 }
@@ -781,15 +828,16 @@ inline Valuation HipPublic::combine_shares(const HipValuation &enc, const std::v
     for (size_t p = 0; p < shares.size(); p++) pieces.push_back(&share_piece(*shares[p], p, kv.first, 0, 1, c->limbs, c->scale));
     if (on_dev) {
       std::vector<CtHandle> keep;
-      const evah_ct *h = rekey_source(dev, *host, kv.first, *c, keep);
+      // (the source rule is rekey's, and so is the prefix of its shape refusal: kept as found)
+      const evah_ct *h = source_handle(dev, *host, "rekey: value " + kv.first, *c, keep, InPlace::SameGpu, BringOver::Copy);
       std::vector<const evah_ct *> hs;
       for (const SharePiece *piece : pieces) hs.push_back(share_handle(*piece, keep));
       v.resize((size_t)sig.vec_size);
       chk(evah_decrypt_combine_rows(dev->h, &h, 1, hs.data(), (uint32_t)hs.size(), (uint32_t)sig.vec_size, EVAH_F64, v.data(), sizeof(double) * v.size(),
                                     0, 1));
     } else {
-      if (c->limbs < 1 || c->limbs > host->k - 1 || words(*c).size() != (size_t)2 * c->limbs * host->N)
-        throw std::runtime_error("value " + kv.first + ": ciphertext shape does not match its data or the encryption parameters");
+      check_cipher_shape(*host, "value " + kv.first, *c, 2, 2);
+      (void)words(*c); // the host twin reads the words: a resident value comes down here
       std::vector<const u64 *> hs;
       for (const SharePiece *piece : pieces) {
         const std::vector<u64> &w = words(*piece, host->N);
@@ -813,39 +861,23 @@ inline void HipPublic::combine_shares_array(const HipValuationBatch &vb, const s
   if (!device_client_enabled()) throw std::runtime_error("combine_shares of a batch needs a HIP device: none is visible, or EVA_DEVICE_CLIENT=0 keeps the client on the host");
   ensure_device(false);
   if (!vb.root) throw std::runtime_error("combine_shares: the batch holds no device handles");
-  const bool same_gpu = vb.root->device == dev->device;
+  for (auto &nc : vb.ciphers) // (before anything is launched)
+    for (auto &seg : nc.second.segments)
+      if (seg.size != 2) throw std::invalid_argument("value " + nc.first + ": decryption share expects a size-2 ciphertext (relinearize first)");
   const uint32_t n_out = (uint32_t)sig.vec_size;
-  const size_t row_bytes = (size_t)n_out * (dtype_out == EVAH_F32 ? 4 : dtype_out == EVAH_U8 ? 1 : 8);
+  const size_t rb = row_bytes(dtype_out, n_out);
   for (auto &nc : vb.ciphers) {
     char *out = static_cast<char *>(rows.at(nc.first));
     const auto &segs = nc.second.segments;
-    size_t row = 0;
-    for (size_t s0 = 0; s0 < segs.size();) {
-      std::vector<CtHandle> keep;
-      std::vector<const evah_ct *> hs, sh;
-      size_t n = 0, s1 = s0;
-      while (s1 < segs.size() && n + segs[s1].n <= CLIENT_BATCH_MAX && segs[s1].limbs == segs[s0].limbs && segs[s1].scale == segs[s0].scale) {
-        if (segs[s1].size != 2) throw std::invalid_argument("value " + nc.first + ": decryption share expects a size-2 ciphertext (relinearize first)");
-        if (same_gpu) {
-          hs.push_back(segs[s1].h->h);
-        } else {
-          evah_ct *h = nullptr;
-          chk(evah_ct_copy(dev->h, segs[s1].h->h, &h));
-          keep.emplace_back(dev->h, h);
-          hs.push_back(h);
-        }
-        n += segs[s1++].n;
-      }
-      if (s1 == s0) throw std::runtime_error("value " + nc.first + ": a segment holds more than 64 instances");
-      check_combine_room(nc.first, segs[s0].limbs, shares.size(), shares[0]->smudge_bits);
-      for (size_t p = 0; p < shares.size(); p++) sh.push_back(share_handle(share_piece(*shares[p], p, nc.first, row, n, segs[s0].limbs, segs[s0].scale), keep));
-      chk(evah_decrypt_combine_rows(dev->h, hs.data(), (uint32_t)hs.size(), sh.data(), (uint32_t)sh.size(), n_out, dtype_out, out + row * row_bytes, row_bytes,
+    walk_segments("value " + nc.first, segs, vb.B, dev, vb.root, [&](SegmentGroup &g) {
+      const BatchSegment &s = segs[g.s0];
+      check_combine_room(nc.first, s.limbs, shares.size(), shares[0]->smudge_bits);
+      std::vector<const evah_ct *> sh;
+      for (size_t p = 0; p < shares.size(); p++) sh.push_back(share_handle(share_piece(*shares[p], p, nc.first, g.row, g.n, s.limbs, s.scale), g.keep));
+      chk(evah_decrypt_combine_rows(dev->h, g.hs.data(), (uint32_t)g.hs.size(), sh.data(), (uint32_t)sh.size(), n_out, dtype_out, out + g.row * rb, rb,
                                     rows_on_device ? 1 : 0, rows_on_device ? 0 : 1));
       if (rows_on_device) chk(evah_ctx_sync(dev->h)); // the uploads and copies made for this call are released behind it
-      row += n;
-      s0 = s1;
-    }
-    if (row != vb.B) throw std::runtime_error("value " + nc.first + ": the segments do not hold every instance");
+    });
   }
 }
 
@@ -906,8 +938,8 @@ public:
   // seed != 0 is the reproducible test hook (streams (seed, 4) and (seed, 3)) and is NOT secret-grade.
   HipValuation encrypt(const Valuation &inputs, const CKKSSignature &sig, uint64_t seed = 0) {
     check_vec_size(sig, host->N / 2);
-    std::unique_ptr<SecureRng> seeds = seed ? std::make_unique<SecureRng>(seed, 4) : std::make_unique<SecureRng>();
-    std::unique_ptr<SecureRng> errors = seed ? std::make_unique<SecureRng>(seed, 3) : std::make_unique<SecureRng>();
+    std::unique_ptr<SecureRng> seeds = client_stream(seed, 4);
+    std::unique_ptr<SecureRng> errors = client_stream(seed, 3);
     std::vector<std::string> names; // name order: the same seed gives the same valuation whatever the map's order
     for (auto &kv : inputs) names.push_back(kv.first);
     std::sort(names.begin(), names.end());
@@ -965,8 +997,8 @@ public:
     std::vector<HipValuation> out(inputs.size());
     if (inputs.empty()) return out;
     const std::vector<std::string> names = batch_input_names(inputs);
-    std::unique_ptr<SecureRng> seeds = seed ? std::make_unique<SecureRng>(seed, 4) : std::make_unique<SecureRng>();
-    std::unique_ptr<SecureRng> errors = seed ? std::make_unique<SecureRng>(seed, 3) : std::make_unique<SecureRng>();
+    std::unique_ptr<SecureRng> seeds = client_stream(seed, 4);
+    std::unique_ptr<SecureRng> errors = client_stream(seed, 3);
     struct Drawn {
       std::vector<std::vector<int8_t>> e;          // per instance
       std::vector<std::array<uint8_t, 32>> sd;
@@ -1057,13 +1089,10 @@ public:
     out.root = dev;
     std::map<std::string, ArrayView> arrays = arrays_in; // (plan_array_inputs attaches the sums of a device array to its view)
     const ArrayInputs in = plan_array_inputs(*host, arrays, shared, sig, out, plains, dev->h);
-    std::unique_ptr<SecureRng> seeds = seed ? std::make_unique<SecureRng>(seed, 4) : std::make_unique<SecureRng>();
-    std::unique_ptr<SecureRng> errors = seed ? std::make_unique<SecureRng>(seed, 3) : std::make_unique<SecureRng>();
+    std::unique_ptr<SecureRng> seeds = client_stream(seed, 4);
+    std::unique_ptr<SecureRng> errors = client_stream(seed, 3);
     std::vector<std::vector<std::array<uint8_t, 32>>> ek(in.names.size()); // per name, per instance
-    struct WipeKeys {
-      std::vector<std::vector<std::array<uint8_t, 32>>> &k;
-      ~WipeKeys() { for (auto &n : k) for (auto &x : n) wipe_bytes(x.data(), 32); }
-    } wipe_keys{ek};
+    WipeKeyRows wipe_keys{ek};
     for (size_t b = 0; b < out.B; b++)
       for (size_t i = 0; i < in.names.size(); i++)
         if (in.arr[i]) {
@@ -1092,7 +1121,7 @@ public:
     return out;
   }
   // decrypt_batch for a batch of batched handles: per name, consecutive segments of one size, limb count
-  // and scale are packed into calls of <= 64 instances of evah_decrypt_decode_handles, each writing straight into the rows
+  // and scale are packed (walk_segments) into calls of <= 64 instances of evah_decrypt_decode_handles, each writing straight into the rows
   // rows[name] + first instance * vec_size * itemsize of the caller's array [B][vec_size] (dtype_out: EVAH_F64, the doubles
   // of decrypt_batch bit for bit, or EVAH_F32).  Needs the device; the batch lives on this key pair's device state.
   // rows_on_device: the rows are device memory of this key pair's state, written group by group by
@@ -1103,53 +1132,27 @@ public:
     if (sig.vec_size <= 0) throw std::runtime_error("Signature vector size must be positive");
     if (vb.root != dev) throw std::runtime_error("decrypt_array: the batch lives on the device state of another key pair");
     const uint32_t n_out = (uint32_t)sig.vec_size;
-    const size_t row_bytes = (size_t)n_out * (dtype_out == EVAH_F32 ? 4 : dtype_out == EVAH_U8 ? 1 : 8);
+    const size_t rb = row_bytes(dtype_out, n_out);
     for (auto &kv : vb.ciphers) {
       char *out = static_cast<char *>(rows.at(kv.first));
-      const auto &segs = kv.second.segments;
-      size_t row = 0;
-      for (size_t s0 = 0; s0 < segs.size();) {
-        std::vector<const evah_ct *> hs;
-        size_t n = 0, s1 = s0;
-        while (s1 < segs.size() && n + segs[s1].n <= CLIENT_BATCH_MAX && segs[s1].size == segs[s0].size && segs[s1].limbs == segs[s0].limbs &&
-               segs[s1].scale == segs[s0].scale) {
-          hs.push_back(segs[s1].h->h);
-          n += segs[s1++].n;
-        }
-        if (s1 == s0) throw std::runtime_error("output " + kv.first + ": a segment holds more than 64 instances");
+      walk_segments("output " + kv.first, kv.second.segments, vb.B, dev, vb.root, [&](SegmentGroup &g) {
         if (rows_on_device || dtype_out == EVAH_U8)
-          chk(evah_decrypt_decode_rows(dev->h, hs.data(), (uint32_t)hs.size(), n_out, dtype_out, out + row * row_bytes, row_bytes, rows_on_device ? 1 : 0, 0));
+          chk(evah_decrypt_decode_rows(dev->h, g.hs.data(), (uint32_t)g.hs.size(), n_out, dtype_out, out + g.row * rb, rb, rows_on_device ? 1 : 0, 0));
         else
-          chk(evah_decrypt_decode_handles(dev->h, hs.data(), (uint32_t)hs.size(), n_out, dtype_out, out + row * row_bytes));
-        row += n;
-        s0 = s1;
-      }
-      if (row != vb.B) throw std::runtime_error("output " + kv.first + ": the segments do not hold every instance");
+          chk(evah_decrypt_decode_handles(dev->h, g.hs.data(), (uint32_t)g.hs.size(), n_out, dtype_out, out + g.row * rb));
+      });
     }
     if (rows_on_device) chk(evah_ctx_sync(dev->h));
-  }
-  // the shape check of a ciphertext that is decrypted on the device
-  void check_device_shape(const std::string &name, const HostCipher &c) const {
-    if (c.size < 1 || c.size > 3 || c.limbs < 1 || c.limbs > host->k - 1 ||
-        (!resident_only(c) && words(c).size() != (size_t)c.size * c.limbs * host->N) || (c.dev && c.dev->N != host->N))
-      throw std::runtime_error("output " + name + ": ciphertext shape does not match its data or the encryption parameters");
   }
   // one value of decrypt()
   std::vector<double> decrypt_value(const std::string &name, const SchemeValue &value, const CKKSSignature &sig) {
     std::vector<double> v;
     if (auto *c = std::get_if<HostCipher>(&value)) {
       if (on_device()) { // dot product with s, inverse transforms, recomposition and the special FFT on the GPU
-        check_device_shape(name, *c);
+        std::vector<CtHandle> keep; // resident on this key pair's device state: read in place; else uploaded for the call
+        const evah_ct *h = source_handle(dev, *host, "output " + name, *c, keep, InPlace::SameState, BringOver::Upload);
         v.resize((size_t)sig.vec_size);
-        if (c->dev && c->dev->root == dev) { // resident on this key pair's device state: read in place
-          chk(evah_decrypt_decode(dev->h, c->dev->h->h, (uint32_t)sig.vec_size, v.data()));
-        } else {
-          evah_ct *h = nullptr;
-          chk(evah_ct_upload(dev->h, c->size, c->limbs, c->scale, (const uint64_t *)words(*c).data(), &h));
-          int rc = evah_decrypt_decode(dev->h, h, (uint32_t)sig.vec_size, v.data());
-          evah_ct_free(dev->h, h);
-          chk(rc);
-        }
+        chk(evah_decrypt_decode(dev->h, h, (uint32_t)sig.vec_size, v.data()));
         return v;
       }
       (void)words(*c);
@@ -1195,15 +1198,7 @@ public:
         while (i1 < list.size() && i1 - i0 < CLIENT_BATCH_MAX) {
           const HostCipher *c = list[i1].second;
           if (c->size != first->size || c->limbs != first->limbs || c->scale != first->scale) break;
-          check_device_shape(nv.first, *c);
-          if (c->dev && c->dev->root == dev) {
-            hs.push_back(c->dev->h->h);
-          } else {
-            evah_ct *h = nullptr;
-            chk(evah_ct_upload(dev->h, c->size, c->limbs, c->scale, (const uint64_t *)words(*c).data(), &h));
-            uploaded.emplace_back(dev->h, h);
-            hs.push_back(h);
-          }
+          hs.push_back(source_handle(dev, *host, "output " + nv.first, *c, uploaded, InPlace::SameState, BringOver::Upload));
           i1++;
         }
         std::vector<double> flat(hs.size() * n_out);
@@ -1228,7 +1223,7 @@ public:
     if (sk.s_ntt.size() != (size_t)host->k * host->N) throw std::invalid_argument("make_rekey_key: secret key not present");
     if (target.pk.data.size() != (size_t)2 * host->k * host->N) throw std::invalid_argument("make_rekey_key: the target context holds no public key");
     const uint32_t D = host->k - 1;
-    std::unique_ptr<SecureRng> stream = seed ? std::make_unique<SecureRng>(seed, 3) : std::make_unique<SecureRng>();
+    std::unique_ptr<SecureRng> stream = client_stream(seed, 3);
     std::vector<std::vector<std::array<uint8_t, 32>>> rk(1);
     WipeKeyRows wipe_keys{rk};
     for (uint32_t J = 0; J < D; J++) rk[0].push_back(draw_key32(*stream));
@@ -1258,7 +1253,7 @@ public:
       throw std::invalid_argument("relin_round1: this context's keys were not generated with a common seed (generate_keys(..., common_seed=)): "
                                   "the parties share no public relinearization seeds");
     if (sk.s_ntt.size() != (size_t)host->k * host->N) throw std::invalid_argument("relin_round1: secret key not present");
-    std::unique_ptr<SecureRng> stream = seed ? std::make_unique<SecureRng>(seed, 6) : std::make_unique<SecureRng>();
+    std::unique_ptr<SecureRng> stream = client_stream(seed, 6);
     auto eph = std::make_shared<RelinEphemeral>();
     eph->owner = identity;
     for (uint32_t J = 0; J < D; J++) eph->r1.push_back(draw_key32(*stream));
@@ -1292,7 +1287,7 @@ public:
       throw std::invalid_argument("relin_round2: the aggregate's words do not match its shape");
     if (!residues_canonical(agg1->data, *host)) throw std::invalid_argument("relin_round2: the aggregate holds a word that is not reduced modulo its prime");
     if (sk.s_ntt.size() != (size_t)host->k * host->N) throw std::invalid_argument("relin_round2: secret key not present");
-    std::unique_ptr<SecureRng> stream = seed ? std::make_unique<SecureRng>(seed, 7) : std::make_unique<SecureRng>();
+    std::unique_ptr<SecureRng> stream = client_stream(seed, 7);
     std::vector<std::vector<std::array<uint8_t, 32>>> rk(1);
     WipeKeyRows wipe_keys{rk};
     for (uint32_t J = 0; J < D; J++) rk[0].push_back(draw_key32(*stream));
@@ -1349,32 +1344,19 @@ public:
         throw std::invalid_argument("refresh: input " + kv.first + " is encrypted: its value comes from the valuation, not from inputs");
     }
   }
-  struct WipeKeyRows {
-    std::vector<std::vector<std::array<uint8_t, 32>>> &k;
-    ~WipeKeyRows() { for (auto &n : k) for (auto &x : n) wipe_bytes(x.data(), 32); }
-  };
   // one value: on the device when one is present (a value resident on this key pair's state is read in place, any other
   // uploaded first, as decrypt_value does), else the host twin — the same words
   HostCipher refresh_value(const std::string &name, const HostCipher &c, uint32_t limbs, double scale, uint32_t shift,
                            const std::array<uint8_t, 32> &ek, const std::array<uint8_t, 32> &sd) {
     if (on_device()) {
-      check_device_shape(name, c);
-      CtHandle uploaded;
-      const evah_ct *h = nullptr;
-      if (c.dev && c.dev->root == dev) {
-        h = c.dev->h->h;
-      } else {
-        evah_ct *up = nullptr;
-        chk(evah_ct_upload(dev->h, c.size, c.limbs, c.scale, (const uint64_t *)words(c).data(), &up));
-        uploaded = CtHandle(dev->h, up);
-        h = up;
-      }
+      std::vector<CtHandle> keep;
+      const evah_ct *h = source_handle(dev, *host, "output " + name, c, keep, InPlace::SameState, BringOver::Upload);
       evah_ct *o = nullptr;
       chk(evah_refresh_handles(dev->h, &h, 1, limbs, scale, ek.data(), sd.data(), &o));
       return cipher_of_handle(dev, *host, o, limbs, scale, resident, &sd);
     }
-    if (c.size < 1 || c.size > 3 || c.limbs < 1 || c.limbs > host->k - 1 || words(c).size() != (size_t)c.size * c.limbs * host->N)
-      throw std::runtime_error("output " + name + ": ciphertext shape does not match its data or the encryption parameters");
+    check_cipher_shape(*host, "output " + name, c, 1, 3);
+    (void)words(c); // the host twin reads the words: a resident value comes down here
     return refresh_host(*host, sk, c, limbs, shift, ek, sd);
   }
   HipValuation refresh(const HipValuation &enc, const CKKSSignature &sig, const std::map<std::string, std::string> &rename = {},
@@ -1392,8 +1374,8 @@ public:
       if (!src[i]) throw std::invalid_argument("refresh: value " + plan[i].source + " is not a ciphertext");
       shift[i] = refresh_shift(src[i]->scale, plan[i].cls.scale);
     }
-    std::unique_ptr<SecureRng> seeds = seed ? std::make_unique<SecureRng>(seed, 4) : std::make_unique<SecureRng>();
-    std::unique_ptr<SecureRng> errors = seed ? std::make_unique<SecureRng>(seed, 3) : std::make_unique<SecureRng>();
+    std::unique_ptr<SecureRng> seeds = client_stream(seed, 4);
+    std::unique_ptr<SecureRng> errors = client_stream(seed, 3);
     std::vector<std::array<uint8_t, 32>> sd(plan.size());
     std::vector<std::vector<std::array<uint8_t, 32>>> ek(1);
     WipeKeyRows wipe_keys{ek};
@@ -1425,8 +1407,8 @@ public:
         throw std::out_of_range("refresh: no encrypted value named " + plan[i].source + " in the batch (input " + plan[i].name + ")");
       src[i] = &it->second;
     }
-    std::unique_ptr<SecureRng> seeds = seed ? std::make_unique<SecureRng>(seed, 4) : std::make_unique<SecureRng>();
-    std::unique_ptr<SecureRng> errors = seed ? std::make_unique<SecureRng>(seed, 3) : std::make_unique<SecureRng>();
+    std::unique_ptr<SecureRng> seeds = client_stream(seed, 4);
+    std::unique_ptr<SecureRng> errors = client_stream(seed, 3);
     std::vector<std::vector<std::array<uint8_t, 32>>> ek(plan.size()); // per name, per instance
     WipeKeyRows wipe_keys{ek};
     for (size_t b = 0; b < out.B; b++)
@@ -1438,29 +1420,16 @@ public:
       const auto &segs = src[i]->segments;
       const InputClass &cls = plan[i].cls;
       BatchCipher &bc = out.ciphers[plan[i].name];
-      size_t row = 0;
-      for (size_t s0 = 0; s0 < segs.size();) {
-        std::vector<const evah_ct *> hs;
-        size_t n = 0, s1 = s0;
-        while (s1 < segs.size() && n + segs[s1].n <= CLIENT_BATCH_MAX && segs[s1].size == segs[s0].size && segs[s1].limbs == segs[s0].limbs &&
-               segs[s1].scale == segs[s0].scale) {
-          hs.push_back(segs[s1].h->h);
-          n += segs[s1++].n;
-        }
-        if (s1 == s0) throw std::runtime_error("value " + plan[i].source + ": a segment holds more than 64 instances");
-        if (row + n > out.B) throw std::runtime_error("value " + plan[i].source + ": the segments hold more instances than the batch");
-        (void)refresh_shift(segs[s0].scale, cls.scale); // the scale rules, with the host's messages, before anything is launched
-        std::vector<uint8_t> ekeys = keys_flat(ek[i].data() + row, n);
-        const std::vector<uint8_t> sd = keys_flat(bc.seeds.data() + row, n);
+      walk_segments("value " + plan[i].source, segs, vb.B, dev, vb.root, [&](SegmentGroup &g) {
+        (void)refresh_shift(segs[g.s0].scale, cls.scale); // the scale rules, with the host's messages, before anything is launched
+        std::vector<uint8_t> ekeys = keys_flat(ek[i].data() + g.row, g.n);
+        const std::vector<uint8_t> sd = keys_flat(bc.seeds.data() + g.row, g.n);
         evah_ct *c = nullptr;
-        const int rc = evah_refresh_handles(dev->h, hs.data(), (uint32_t)hs.size(), cls.limbs, cls.scale, ekeys.data(), sd.data(), &c);
+        const int rc = evah_refresh_handles(dev->h, g.hs.data(), (uint32_t)g.hs.size(), cls.limbs, cls.scale, ekeys.data(), sd.data(), &c);
         wipe_bytes(ekeys.data(), ekeys.size());
         chk(rc);
-        bc.segments.push_back(BatchSegment{std::make_shared<CtHandle>(dev->h, c), (uint32_t)n, nullptr, 2, cls.limbs, cls.scale});
-        row += n;
-        s0 = s1;
-      }
-      if (row != vb.B) throw std::runtime_error("value " + plan[i].source + ": the segments do not hold every instance");
+        bc.segments.push_back(BatchSegment{std::make_shared<CtHandle>(dev->h, c), (uint32_t)g.n, nullptr, 2, cls.limbs, cls.scale});
+      });
     }
     return out;
   }
@@ -1491,7 +1460,7 @@ public:
       if (nc.second->limbs >= 1 && nc.second->limbs <= host->k - 1 && flood_exceeds_modulus(host->primes, nc.second->limbs, 1, smudge_bits))
         throw std::invalid_argument("value " + nc.first + ": smudge_bits leaves no room at this level");
     }
-    std::unique_ptr<SecureRng> stream = seed ? std::make_unique<SecureRng>(seed, 5) : std::make_unique<SecureRng>();
+    std::unique_ptr<SecureRng> stream = client_stream(seed, 5);
     std::vector<std::vector<std::array<uint8_t, 32>>> fk(1);
     WipeKeyRows wipe_keys{fk};
     for (size_t i = 0; i < cs.size(); i++) fk[0].push_back(draw_key32(*stream));
@@ -1503,24 +1472,15 @@ public:
       piece.limbs = c.limbs;
       piece.scale = c.scale;
       if (on_device()) {
-        check_device_shape(name, c);
-        std::vector<CtHandle> keep;
-        const evah_ct *h = nullptr;
-        if (c.dev && c.dev->root->device == dev->device) { // resident on this GPU, whichever key pair's state: read in place
-          h = c.dev->h->h;
-        } else {
-          evah_ct *up = nullptr;
-          chk(evah_ct_upload(dev->h, c.size, c.limbs, c.scale, (const uint64_t *)words(c).data(), &up));
-          keep.emplace_back(dev->h, up);
-          h = up;
-        }
+        std::vector<CtHandle> keep; // resident on this GPU, whichever key pair's state: read in place
+        const evah_ct *h = source_handle(dev, *host, "output " + name, c, keep, InPlace::SameGpu, BringOver::Upload);
         evah_ct *o = nullptr;
         chk(evah_decrypt_share_handles(dev->h, &h, 1, smudge_bits, fk[0][i].data(), &o));
         piece.h = std::make_shared<CtHandle>(dev->h, o);
         piece.root = dev;
       } else {
-        if (c.limbs < 1 || c.limbs > host->k - 1 || words(c).size() != (size_t)2 * c.limbs * host->N)
-          throw std::runtime_error("value " + name + ": ciphertext shape does not match its data or the encryption parameters");
+        check_cipher_shape(*host, "value " + name, c, 2, 2);
+        (void)words(c); // the host twin reads the words: a resident value comes down here
         piece.data = decrypt_share_host(*host, sk, c, smudge_bits, fk[0][i]);
       }
       out->values[name].push_back(std::move(piece));
@@ -1533,14 +1493,13 @@ public:
     require_array_path(on_device(), resident, "decrypt_share");
     auto out = new_shares(smudge_bits, true, vb.B);
     if (!vb.root) throw std::runtime_error("decrypt_share: the batch holds no device handles");
-    const bool same_gpu = vb.root->device == dev->device;
     for (auto &nc : vb.ciphers)
       for (auto &seg : nc.second.segments) {
         if (seg.size != 2) throw std::invalid_argument("value " + nc.first + ": decryption share expects a size-2 ciphertext (relinearize first)");
         if (seg.limbs >= 1 && seg.limbs <= host->k - 1 && flood_exceeds_modulus(host->primes, seg.limbs, 1, smudge_bits))
           throw std::invalid_argument("value " + nc.first + ": smudge_bits leaves no room at this level");
       }
-    std::unique_ptr<SecureRng> stream = seed ? std::make_unique<SecureRng>(seed, 5) : std::make_unique<SecureRng>();
+    std::unique_ptr<SecureRng> stream = client_stream(seed, 5);
     std::vector<std::vector<std::array<uint8_t, 32>>> fk(vb.ciphers.size()); // per name (sorted: std::map), per instance
     WipeKeyRows wipe_keys{fk};
     for (size_t i = 0; i < vb.ciphers.size(); i++)
@@ -1549,40 +1508,20 @@ public:
     for (auto &nc : vb.ciphers) {
       const auto &segs = nc.second.segments;
       std::vector<SharePiece> &pieces = out->values[nc.first];
-      size_t row = 0;
-      for (size_t s0 = 0; s0 < segs.size();) {
-        std::vector<CtHandle> keep;
-        std::vector<const evah_ct *> hs;
-        size_t n = 0, s1 = s0;
-        while (s1 < segs.size() && n + segs[s1].n <= CLIENT_BATCH_MAX && segs[s1].limbs == segs[s0].limbs && segs[s1].scale == segs[s0].scale) {
-          if (same_gpu) {
-            hs.push_back(segs[s1].h->h);
-          } else {
-            evah_ct *h = nullptr;
-            chk(evah_ct_copy(dev->h, segs[s1].h->h, &h));
-            keep.emplace_back(dev->h, h);
-            hs.push_back(h);
-          }
-          n += segs[s1++].n;
-        }
-        if (s1 == s0) throw std::runtime_error("value " + nc.first + ": a segment holds more than 64 instances");
-        if (row + n > vb.B) throw std::runtime_error("value " + nc.first + ": the segments hold more instances than the batch");
-        std::vector<uint8_t> keys = keys_flat(fk[i].data() + row, n);
+      walk_segments("value " + nc.first, segs, vb.B, dev, vb.root, [&](SegmentGroup &g) {
+        std::vector<uint8_t> keys = keys_flat(fk[i].data() + g.row, g.n);
         evah_ct *o = nullptr;
-        const int rc = evah_decrypt_share_handles(dev->h, hs.data(), (uint32_t)hs.size(), smudge_bits, keys.data(), &o);
+        const int rc = evah_decrypt_share_handles(dev->h, g.hs.data(), (uint32_t)g.hs.size(), smudge_bits, keys.data(), &o);
         wipe_bytes(keys.data(), keys.size());
         chk(rc);
         SharePiece piece;
-        piece.n = (uint32_t)n;
-        piece.limbs = segs[s0].limbs;
-        piece.scale = segs[s0].scale;
+        piece.n = (uint32_t)g.n;
+        piece.limbs = segs[g.s0].limbs;
+        piece.scale = segs[g.s0].scale;
         piece.h = std::make_shared<CtHandle>(dev->h, o);
         piece.root = dev;
         pieces.push_back(std::move(piece));
-        row += n;
-        s0 = s1;
-      }
-      if (row != vb.B) throw std::runtime_error("value " + nc.first + ": the segments do not hold every instance");
+      });
       i++;
     }
     return out;
