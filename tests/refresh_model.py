@@ -2,12 +2,12 @@
 +infinity, reduce under the target primes and encrypt again.  What the CPU and GPU tests of the refresh compare the host twin
 and the device with, word for word.  No test of its own.
 
-The transforms are exact radix-2 recursions over Python integers (numpy object arrays); test_refresh_cpu.py pins them to
-pyref.naive_ntt once."""
+The transforms are exact radix-2 passes over Python integers (numpy object arrays) with the powers of each root kept
+between calls; test_refresh_cpu.py pins them to pyref.naive_ntt and the recomposition to pyref.crt once."""
 import numpy as np
 
 from eva_amd import _eva
-from pyref import bitrev, centered, crt
+from pyref import bitrev, centered
 from test_seeded_cpu import expand_limb
 
 sampled_small = _eva._seal._sampled_small
@@ -28,45 +28,60 @@ def minimal_psi(N, q):
 
 
 def _dft(x, w, q):
-    """X[k] = sum_j x_j w^(jk) mod q, natural order in and out"""
+    """X[k] = sum_j x_j w^(jk) mod q, natural order in and out: decimation in time, one whole-array step per stage"""
     n = len(x)
-    if n == 1:
-        return x
-    w2 = w * w % q
-    ev, od = _dft(x[0::2], w2, q), _dft(x[1::2], w2, q)
-    tw = np.empty(n // 2, dtype=object)
-    p = 1
-    for k in range(n // 2):
-        tw[k] = p
-        p = p * w % q
-    t = od * tw % q
-    return np.concatenate([(ev + t) % q, (ev - t) % q])
+    x = x[_bitrev_index(n)]
+    m = 1
+    while m < n:   # n / 2m transforms of length 2m from their halves: X[k], X[k + m] = E[k] +- w_2m^k O[k]
+        x = x.reshape(n // (2 * m), 2, m)
+        t = x[:, 1, :] * _powers(pow(w, n // (2 * m), q), m, q) % q
+        x = np.concatenate([(x[:, 0, :] + t) % q, (x[:, 0, :] - t) % q], axis=1).reshape(n)
+        m *= 2
+    return x
+
+
+_power_tables = {}
 
 
 def _powers(b, n, q):
-    out = np.empty(n, dtype=object)
-    p = 1
-    for j in range(n):
-        out[j] = p
-        p = p * b % q
+    """b^0 .. b^(n-1) mod q in Python integers; kept per (b, n, q): a long chain transforms under one root many times"""
+    if (b, n, q) not in _power_tables:
+        out = np.empty(n, dtype=object)
+        p = 1
+        for j in range(n):
+            out[j] = p
+            p = p * b % q
+        _power_tables[(b, n, q)] = out
+    return _power_tables[(b, n, q)]
+
+
+_bitrevs = {}
+
+
+def _bitrev_index(n):
+    if n not in _bitrevs:
+        _bitrevs[n] = np.array([bitrev(i, n.bit_length() - 1) for i in range(n)])
+    return _bitrevs[n]
+
+
+def _objects(a):
+    out = np.empty(len(a), dtype=object)
+    out[:] = [int(v) for v in a]
     return out
 
 
 def ntt(a, psi, q):
     """pyref.naive_ntt: out[i] = sum_j a_j psi^((2 br(i) + 1) j) mod q"""
     n = len(a)
-    logn = n.bit_length() - 1
-    x = np.array([int(v) for v in a], dtype=object) * _powers(psi, n, q) % q
+    x = _objects(a) * _powers(psi, n, q) % q
     X = _dft(x, psi * psi % q, q)
-    return np.array([X[bitrev(i, logn)] for i in range(n)], dtype=object)
+    return X[_bitrev_index(n)]
 
 
 def intt(A, psi, q):
     n = len(A)
-    logn = n.bit_length() - 1
     X = np.empty(n, dtype=object)
-    for i in range(n):
-        X[bitrev(i, logn)] = int(A[i])
+    X[_bitrev_index(n)] = _objects(A)
     ipsi = pow(psi, -1, q)
     x = _dft(X, ipsi * ipsi % q, q)
     return x * _powers(ipsi, n, q) % q * pow(n, -1, q) % q
@@ -93,11 +108,20 @@ def decrypt_integers(ch, ct):
             acc = (acc + np.array([int(v) for v in ct[p][i]], dtype=object) * sp) % q
             sp = sp * s % q
         rows.append(intt(acc, ch.psi[i], q))
-    out = []
-    for n in range(N):
-        U, Q = crt([rows[i][n] for i in range(l)], ch.primes[:l])
-        out.append(centered(U, Q))
-    return out
+    return crt_centered(rows, ch.primes[:l])
+
+
+def crt_centered(rows, primes):
+    """centered(pyref.crt(...)) of every column of rows [l][N], with crt's per-prime constants (Q / q_i) ((Q / q_i)^-1 mod
+    q_i) formed once, not once per coefficient (test_refresh_cpu.py pins it to pyref.crt)"""
+    Q = 1
+    for q in primes:
+        Q *= q
+    U = np.zeros(len(rows[0]), dtype=object)
+    for row, q in zip(rows, primes):
+        Qi = Q // q
+        U = U + row * (Qi * pow(Qi, -1, q))
+    return [centered(int(u), Q) for u in U]
 
 
 def divide(M, t):
@@ -105,18 +129,31 @@ def divide(M, t):
     return M if t == 0 else (M + (1 << (t - 1))) >> t
 
 
-def encrypt_integers(ch, Mp, L, ek, seed):
-    """the symmetric encryption [2][L][N] of the integer polynomial Mp: e = sampled_small(ek, 1), c1 from seed"""
+def transformed(ch, Mp, L):
+    """NTT(Mp mod q_j) for j < L: the rows encrypt_integers hides.  A caller that encrypts one Mp at several L forms the
+    rows of the largest once"""
+    return [ntt([v % q for v in Mp], ch.psi[j], q) for j, q in enumerate(ch.primes[:L])]
+
+
+_error_rows = [None, 0, {}]
+
+
+def encrypt_integers(ch, Mp, L, ek, seed, rows=None):
+    """the symmetric encryption [2][L][N] of the integer polynomial Mp: e = sampled_small(ek, 1), c1 from seed;
+    rows = transformed(ch, Mp, L' >= L) if the caller has them"""
     N = ch.N
+    if _error_rows[:2] != [bytes(ek), N]:   # the rows of the last key stay: one key serves several L
+        _error_rows[:] = [bytes(ek), N, {}]
     e = [int(v) for v in sampled_small(bytes(ek), 1, N)]
+    rows = transformed(ch, Mp, L) if rows is None else rows
     out = np.empty((2, L, N), dtype=np.uint64)
     for j in range(L):
         q = ch.primes[j]
-        m = ntt([v % q for v in Mp], ch.psi[j], q)
-        en = ntt([v % q for v in e], ch.psi[j], q)
+        if q not in _error_rows[2]:
+            _error_rows[2][q] = ntt([v % q for v in e], ch.psi[j], q)
+        en = _error_rows[2][q]
         a = expand_limb(bytes(seed), j, q, N)
-        ao = np.array([int(v) for v in a], dtype=object)
-        out[0][j] = np.array((m - (ao * ch.s[j] + en)) % q, dtype=np.uint64)
+        out[0][j] = np.array((rows[j] - (_objects(a) * ch.s[j] + en)) % q, dtype=np.uint64)
         out[1][j] = a
     return out
 

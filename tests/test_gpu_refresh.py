@@ -1,6 +1,8 @@
 """GPU: the refresh.  k_refresh_lift at its arithmetic edges through the C-ABI against the Python-integer
-model (tests/refresh_model.py), the handle forms the call reads in place, the device against the host twin, what a
-refreshed value decrypts to, and a computation four times as deep as its modulus chain, end to end."""
+model (tests/refresh_model.py), each of its five forms at the first and last level it serves with the sign decided at every
+digit position (tests/refresh_edges.py), ciphertext sizes 1 and 3, the handle forms the call reads in place, the device
+against the host twin, what a refreshed value decrypts to, and a computation four times as deep as its modulus chain,
+end to end."""
 import os
 import subprocess
 import sys
@@ -9,6 +11,7 @@ import numpy as np
 import pytest
 
 import refresh_model as rm
+from refresh_edges import CHAINS, FORM_CASES, edge_messages, form_case_id, form_levels_out, form_messages
 from eva import EvaProgram, Input, Output, load
 from eva.ckks import CKKSCompiler, CKKSParameters, CKKSSignature, CKKSEncodingInfo
 from eva.metric import valuation_mse
@@ -20,7 +23,6 @@ from eva_amd.hostref import coeff_modulus_create
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHAINS = {"mixed": [60, 30, 45, 50, 33, 60], "all60": [60] * 4}
 B_BITS = 20
 
 
@@ -43,35 +45,9 @@ def env(chain, N):
     return _envs[(chain, N)]
 
 
-def edge_messages(primes, l, t, N, seed):
-    """N integers in (-Q_l / 2, Q_l / 2]: the sign boundary, the ends, ties of the division and their neighbours in both
-    signs, values whose mixed-radix digits exceed a smaller prime, and random fill"""
-    Q = 1
-    for q in primes[:l]:
-        Q *= q
-    half = Q // 2
-    lo = half + 1 - Q   # the most negative value, U = floor(Q / 2) + 1
-    vals = [0, 1, -1, half, lo, half - 1, lo + 1]
-    if t:
-        tie, step = 1 << (t - 1), 1 << t
-        for m in (0, 1, -1, -2, half // step - 1, -(half // step) + 1):
-            for d in (-1, 0, 1):
-                vals.append(tie + m * step + d)
-    U, pre = 0, 1
-    for q in primes[:l]:   # digits q_i - 1: v_0 ~ 2^60 is far above a 30-bit prime
-        U += (q - 1) * pre
-        pre *= q
-        vals.append(rm.centered(U, Q))
-    vals = [v for v in vals if lo <= v <= half]
-    rng = np.random.default_rng(seed)
-    while len(vals) < N:
-        vals.append(rm.centered(int.from_bytes(rng.bytes(64), "little") % Q, Q))
-    return vals[:N]
-
-
 @pytest.mark.parametrize("l_of", ["1", "2", "k-1"])
 @pytest.mark.parametrize("N", [1024, 4096])
-@pytest.mark.parametrize("chain", list(CHAINS))
+@pytest.mark.parametrize("chain", ["mixed", "all60"])
 def test_kernel_edges_against_the_integer_model(chain, N, l_of):
     g, ch = env(chain, N)
     k = len(ch.primes)
@@ -88,6 +64,81 @@ def test_kernel_edges_against_the_integer_model(chain, N, l_of):
             got = out.download()
             bad = np.argwhere(got != want)
             assert bad.size == 0, (chain, N, l, L, t, "first differing (poly, limb, n)", bad[0], "M", M[bad[0][2]])
+
+
+@pytest.mark.parametrize("case", FORM_CASES, ids=form_case_id)
+def test_every_kernel_form_at_both_of_its_edges(case):
+    """k_refresh_lift<4>, <8> and <16> at their first and last level, <62> at l = 17, 20, 32 and 61, to one prime, to the
+    value's own primes and to every prime but the last, on the edge list whose sign decision falls on every digit position
+    in both directions (refresh_edges.py; test_refresh_cpu.py accounts for what each list reaches).  All N coefficients of
+    every limb of both polynomials are compared.  The transforms of the divided messages are formed once per t for the
+    largest L: almost all of an id's time is the integer model's"""
+    chain, l, ts = case
+    N = 1024
+    g, ch = env(chain, N)
+    Ls = form_levels_out(case)
+    for t in ts:
+        M = form_messages(ch.primes, l, t, N)
+        ct = g.upload_ct(rm.message_ciphertext(ch, M, l), 2.0 ** (B_BITS + t))
+        rows = rm.transformed(ch, [rm.divide(v, t) for v in M], Ls[-1])
+        ek = key(3 * t)
+        for L in Ls:
+            sd = key(100 + 3 * t + L)
+            out = g.refresh_handles([ct], L, 2.0 ** B_BITS, [ek], [sd])
+            assert (out.size, out.limbs, out.scale, out.batch) == (2, L, 2.0 ** B_BITS, 1)
+            want = rm.encrypt_integers(ch, None, L, ek, sd, rows=rows)
+            got = out.download()
+            bad = np.argwhere(got != want)
+            assert bad.size == 0, (chain, N, l, L, t, "first differing (poly, limb, n)", bad[0], "M", M[bad[0][2]])
+
+
+def random_cts(ch, rng, size, limbs, n):
+    """[n][size][limbs][N] uniform words: with the uniform key every product of k_decrypt_dot matters"""
+    return np.stack([np.stack([np.stack([rng.integers(0, ch.primes[i], size=ch.N, dtype=np.uint64) for i in range(limbs)])
+                               for _ in range(size)]) for _ in range(n)])
+
+
+@pytest.mark.parametrize("l", [4, 9, 17])
+@pytest.mark.parametrize("size", [1, 3])
+def test_sizes_one_and_three_against_the_integer_model(size, l):
+    g, ch = env("mixed21", 1024)
+    k, t = len(ch.primes), 1
+    words = random_cts(ch, np.random.default_rng(10 * l + size), size, l, 1)[0]
+    M = rm.decrypt_integers(ch, words)
+    assert max(M) > 0 > min(M)
+    ct = g.upload_ct(words, 2.0 ** (B_BITS + t))
+    rows = rm.transformed(ch, [rm.divide(v, t) for v in M], k - 1)
+    ek = key(l)
+    for L in (1, k - 1):
+        sd = key(50 + L)
+        out = g.refresh_handles([ct], L, 2.0 ** B_BITS, [ek], [sd])
+        assert (out.size, out.limbs, out.scale, out.batch) == (2, L, 2.0 ** B_BITS, 1)
+        bad = np.argwhere(out.download() != rm.encrypt_integers(ch, None, L, ek, sd, rows=rows))
+        assert bad.size == 0, (size, l, L, "first differing (poly, limb, n)", bad[0], "M", M[bad[0][2]])
+
+
+@pytest.mark.parametrize("l", [16, 17])
+def test_64_instances_at_the_last_unrolled_level_and_the_first_looped_one(l):
+    """blockIdx.y = 0 .. 63 through k_refresh_lift<16> and through <62>, whose digits live in scratch memory: every
+    instance gives the words of the single call on its words, the first and the last those of the model as well"""
+    g, ch = env("mixed21", 1024)
+    N, k, t = 1024, len(ch.primes), 31
+    L, scale = k - 1, 2.0 ** (B_BITS + t)
+    rng = np.random.default_rng(l)
+    single = g.upload_ct(random_cts(ch, rng, 2, l, 1)[0], scale)
+    big = g.upload_ct_batch(random_cts(ch, rng, 2, l, 61), scale)
+    handles = [single, big, big.unstack(60), big.unstack(7)]
+    words = [single.download()] + list(big.download()) + [big.unstack(60).download(), big.unstack(7).download()]
+    assert len(words) == 64
+    eks, sds = [key(i) for i in range(64)], [key(200 + i) for i in range(64)]
+    out = g.refresh_handles(handles, L, 2.0 ** B_BITS, eks, sds)
+    assert (out.size, out.limbs, out.scale, out.batch) == (2, L, 2.0 ** B_BITS, 64)
+    got = out.download().reshape(64, 2, L, N)
+    for i in range(64):
+        one = g.refresh_handles([g.upload_ct(words[i], scale)], L, 2.0 ** B_BITS, [eks[i]], [sds[i]]).download()
+        assert np.array_equal(got[i], one), (l, i)
+    for i in (0, 63):
+        assert np.array_equal(got[i], rm.refresh(ch, words[i], L, t, eks[i], sds[i])), (l, i)
 
 
 def _err(fn, *a):
@@ -194,9 +245,9 @@ def _step(x):
 _CHILD = """
 import sys
 sys.path.insert(0, 'tests')
-from test_gpu_refresh import twin_case
+import test_gpu_refresh
 from eva import save
-save(twin_case(), sys.argv[1])
+save(getattr(test_gpu_refresh, sys.argv[2])(), sys.argv[1])
 """
 
 
@@ -211,18 +262,39 @@ def twin_case():
     return sec.refresh(enc, sig_out, seed=5)
 
 
-def test_device_equals_host_twin(tmp_path):
+def twin_case_long():
+    """the same on 19 primes of 60 bits: one value down from 17 limbs to 3 and to scale 2^20 (k_refresh_lift<62>), one up
+    from 2 limbs to 17"""
+    params = CKKSParameters([60] * 19, set(), 1024)
+    pub, sec = generate_keys(params, 7)
+    sig_in = CKKSSignature(64, {"a": CKKSEncodingInfo(Type.Cipher, 30, 1), "b": CKKSEncodingInfo(Type.Cipher, 30, 16)})
+    xs = np.random.default_rng(4).uniform(-2, 2, (2, 64))
+    enc = sec.encrypt({"a": xs[0].tolist(), "b": xs[1].tolist()}, sig_in, seed=3)
+    assert (enc.get("a")[2], enc.get("b")[2]) == (17, 2)
+    sig_out = CKKSSignature(64, {"a": CKKSEncodingInfo(Type.Cipher, 20, 15), "b": CKKSEncodingInfo(Type.Cipher, 30, 1)})
+    return sec.refresh(enc, sig_out, seed=5)
+
+
+def _device_equals_host_twin(tmp_path, case, limbs):
     path = str(tmp_path / "host.sealvals")
     child_env = dict(os.environ, PYTHONPATH=ROOT, EVA_DEVICE_CLIENT="0")
-    out = subprocess.run([sys.executable, "-c", _CHILD, path], cwd=ROOT, env=child_env, capture_output=True, text=True, timeout=300)
+    out = subprocess.run([sys.executable, "-c", _CHILD, path, case], cwd=ROOT, env=child_env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
-    host, dev = load(path), twin_case()
+    host, dev = load(path), globals()[case]()
     assert dev.is_resident("a")
     for name in ("a", "b"):
         h, d = host.get(name), dev.get(name)
         assert h[:4] == d[:4] and np.array_equal(h[4], d[4]), name
         assert host.seed(name) == dev.seed(name)
-    assert (dev.get("a")[2], dev.get("b")[2]) == (2, 5)   # "a" went down three levels, "b" up two
+    assert (dev.get("a")[2], dev.get("b")[2]) == limbs
+
+
+def test_device_equals_host_twin(tmp_path):
+    _device_equals_host_twin(tmp_path, "twin_case", (2, 5))   # "a" went down three levels, "b" up two
+
+
+def test_device_equals_host_twin_on_19_primes(tmp_path):
+    _device_equals_host_twin(tmp_path, "twin_case_long", (3, 17))
 
 
 def test_a_refreshed_value_decrypts_to_the_original():

@@ -1,18 +1,21 @@
-"""CPU: the refresh on the host twin against a Python-integer model of its contract, word for word; its
-refusals, its randomness contract and the file format of its results."""
+"""CPU: the refresh on the host twin against a Python-integer model of its contract, word for word, on short
+chains and at the levels of long ones where the device kernel changes its form; what the device test's edge lists reach
+(tests/refresh_edges.py); its refusals, its randomness contract and the file format of its results."""
 import numpy as np
 import pytest
 
+import refresh_edges as edges
 import refresh_model as rm
 from eva import save, load
 from eva.ckks import CKKSParameters, CKKSSignature, CKKSEncodingInfo
 from eva.seal import generate_keys, SEALValuation
 from eva_amd._eva import Type
-from pyref import naive_ntt
+from eva_amd.hostref import coeff_modulus_create
+from pyref import centered, crt, naive_ntt
 from sampled_keys import stream_keys
 
 N = 1024
-CHAINS = {"mixed": [60, 30, 45, 50, 33, 60], "all60": [60] * 4}
+CHAINS = edges.CHAINS
 B_BITS = 20   # the target scale 2^b
 
 
@@ -55,13 +58,20 @@ def test_model_transform_is_the_naive_one():
     assert [int(v) for v in rm.intt(rm.ntt(a, psi, q), psi, q)] == a
 
 
+def test_model_recomposition_is_pyref_crt():
+    primes = keys("mixed")[2].primes[:5]
+    rows = [rm._objects(np.random.default_rng(i).integers(0, q, size=8)) for i, q in enumerate(primes)]
+    want = [centered(*crt([int(r[n]) for r in rows], primes)) for n in range(8)]
+    assert rm.crt_centered(rows, primes) == want and max(want) > 0 > min(want)
+
+
 def _levels(chain):
     k = len(CHAINS[chain])
     return [(1, k - 1), (2, k - 1), (k - 1, k - 1), (3, 2)]
 
 
 @pytest.mark.parametrize("size", [2, 3])
-@pytest.mark.parametrize("case", [(c, i) for c in CHAINS for i in range(4)], ids=lambda c: f"{c[0]}-{c[1]}")
+@pytest.mark.parametrize("case", [(c, i) for c in ("mixed", "all60") for i in range(4)], ids=lambda c: f"{c[0]}-{c[1]}")
 def test_host_twin_equals_model(case, size):
     chain, idx = case
     pub, sec, ch = keys(chain)
@@ -77,6 +87,79 @@ def test_host_twin_equals_model(case, size):
         assert (kind, gsize, limbs, scale) == ("cipher", 2, L, 2.0 ** B_BITS)
         want = rm.refresh(ch, ct, L, t, stream_keys(seed, 3, 1)[0], stream_keys(seed, 4, 1)[0], M=M)
         assert np.array_equal(words, want), (chain, l, L, t, size)
+
+
+@pytest.mark.parametrize("case", edges.FORM_CASES, ids=edges.form_case_id)
+def test_edge_list_reaches_every_reachable_branch(case):
+    """the lists test_gpu_refresh.py refreshes at every (chain, l, t) of its kernel-form test, accounted for in Python
+    integers: every branch the triple allows is taken, the sign decision at every digit position in both directions
+    among them, and every branch it does not allow is named here with its reason"""
+    chain, l, ts = case
+    primes = coeff_modulus_create(N, CHAINS[chain])
+    k = len(primes)
+    for t in ts:
+        M = edges.form_messages(primes, l, t)
+        assert len(M) == N
+        hit = edges.coverage(primes, l, t, M)
+        yes, no = edges.reachable(primes, l, t)
+        assert not set(no) & yes
+        assert hit == yes, (chain, l, t, "missed", sorted(yes - hit), "beyond reachable", sorted(hit - yes))
+        assert {f"sign_{s}_at_{i}" for i in range(l) for s in ("neg", "pos")} <= hit
+        # what is out of reach, spelled out: the chains of one width list their primes in ascending order, so no digit
+        # reaches a later prime; on the mixed chain only l = k - 1 leaves no prime to lift to; t = 0 forms no remainder,
+        # t = 1 has d in {0, 1}, and 2^(t-1) reaches a 60-bit prime at t = 62 only, a 30-bit one from t = 31 on
+        want_no = set()
+        if chain in ("w60x21", "b30x62"):
+            want_no |= {"digit_over_in_garner", "digit_over_in_lift"}
+        elif l == k - 1:
+            want_no |= {"digit_over_in_lift"}
+        if t == 0:
+            want_no |= {"d_neg", "d_zero", "d_pos", "d_top", "d_over_prime_neg", "d_over_prime_pos"}
+        if t == 1:
+            want_no |= {"d_neg", "d_pos", "d_over_prime_neg", "d_over_prime_pos"}
+        if t == 31 and chain == "w60x21":
+            want_no |= {"d_over_prime_neg", "d_over_prime_pos"}
+        assert set(no) == want_no, (chain, l, t, no)
+
+
+LONG_CASES = [(c, l) for c in ("w60x21", "mixed21") for l in (4, 8, 9, 16, 17)] + [("b30x62", 61)]
+SIZE_AT = {4: 1, 8: 2, 9: 3, 16: 2, 17: 3, 61: 2}   # sizes 1 and 3 ride along: the dot product's powers of the key
+
+
+@pytest.mark.parametrize("case", LONG_CASES, ids=lambda c: f"{c[0]}-l{c[1]}")
+def test_host_twin_equals_model_on_long_chains(case):
+    """refresh_lift_coeff at the levels where the device kernel changes its form (4 | 5, 8 | 9, 16 | 17) and at the
+    deepest level there is, to fewer, as many and more primes than the value has, at both ends of the shift"""
+    chain, l = case
+    pub, sec, ch = keys(chain)
+    k, size = len(ch.primes), SIZE_AT[l]
+    ct = random_ct(ch.primes, size, l, 31 * l + size)
+    M = rm.decrypt_integers(ch, ct)
+    assert max(M) > 0 > min(M)
+    Ls = sorted({L for L in (1, l - 1, l, l + 1, k - 1) if 1 <= L <= k - 1})
+    assert Ls[0] < l and l in Ls and (Ls[-1] > l or l == k - 1)
+    for t in (0, 62):
+        seed = 1000 + t
+        ek, sd = stream_keys(seed, 3, 1)[0], stream_keys(seed, 4, 1)[0]
+        rows = rm.transformed(ch, [rm.divide(v, t) for v in M], Ls[-1])
+        for L in Ls:
+            kind, gsize, limbs, scale, words = sec.refresh(valuation("x", ct, B_BITS + t), signature(k, L), seed=seed).get("x")
+            assert (kind, gsize, limbs, scale) == ("cipher", 2, L, 2.0 ** B_BITS)
+            bad = np.argwhere(words != rm.encrypt_integers(ch, None, L, ek, sd, rows=rows))
+            assert bad.size == 0, (chain, l, L, t, "first differing (poly, limb, n)", bad[0], "M", M[bad[0][2]])
+
+
+@pytest.mark.parametrize("case", [("mixed21", 4), ("mixed21", 17), ("w60x21", 9)], ids=lambda c: f"{c[0]}-l{c[1]}")
+def test_host_twin_at_every_digit_position(case):
+    """the edge list of the device test through the host twin: the sign decided at every digit, both ways"""
+    chain, l = case
+    pub, sec, ch = keys(chain)
+    k, t, L = len(ch.primes), 31, len(ch.primes) - 1
+    M = edges.form_messages(ch.primes, l, t)
+    ct = rm.message_ciphertext(ch, M, l)
+    words = sec.refresh(valuation("x", ct, B_BITS + t), signature(k, L), seed=6).get("x")[4]
+    bad = np.argwhere(words != rm.encrypt_integers(ch, [rm.divide(v, t) for v in M], L, stream_keys(6, 3, 1)[0], stream_keys(6, 4, 1)[0]))
+    assert bad.size == 0, (chain, l, "first differing (poly, limb, n)", bad[0], "M", M[bad[0][2]])
 
 
 def test_ties_round_towards_plus_infinity():
