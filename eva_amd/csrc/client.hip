@@ -238,28 +238,18 @@ k_encrypt_symmetric(DevCtx cx, Seeds8 seeds, const uint32_t *__restrict__ seed_b
   const uint32_t prime = cx.prime_of(i);
   const DevPrime pm = cx.primes[prime];
   uint32_t key[8];
-  if (seed_buf) {
-#pragma unroll
-    for (int w = 0; w < 8; w++) key[w] = seed_buf[8 * z + w];
-  } else {
-#pragma unroll
-    for (int w = 0; w < 8; w++) key[w] = seeds.w[z][w];
-  }
-  u64 a[4];
+  seed_words(seeds, seed_buf, z, key);
+  u64 a[4], b[4], mv[4], ev[4], sv[4];
   seeded_block(key, prime, t, pm, a);
   const size_t row = (size_t)l * cx.N, off = (size_t)i * cx.N + 4 * (size_t)t, in = z * row + off;
-  const u64 *s = sk + (size_t)prime * cx.N + 4 * (size_t)t;
-  const ulonglong2 m01 = ld2(m + in), m23 = ld2(m + in + 2), e01 = ld2(en + in), e23 = ld2(en + in + 2);
-  const ulonglong2 s01 = ld2(s), s23 = ld2(s + 2);
-  const u64 mv[4] = {m01.x, m01.y, m23.x, m23.y}, ev[4] = {e01.x, e01.y, e23.x, e23.y}, sv[4] = {s01.x, s01.y, s23.x, s23.y};
-  u64 b[4];
+  ld4(m + in, mv);
+  ld4(en + in, ev);
+  ld4(sk + (size_t)prime * cx.N + 4 * (size_t)t, sv);
 #pragma unroll
   for (int r = 0; r < 4; r++) b[r] = submod(mv[r], addmod(mulmod(a[r], sv[r], pm), ev[r], pm.q), pm.q);
-  u64 *c0 = ct + (size_t)2 * z * row + off, *c1 = c0 + row;
-  st2(c1, make_ulonglong2(a[0], a[1]));
-  st2(c1 + 2, make_ulonglong2(a[2], a[3]));
-  st2(c0, make_ulonglong2(b[0], b[1]));
-  st2(c0 + 2, make_ulonglong2(b[2], b[3]));
+  u64 *c0 = ct + (size_t)2 * z * row + off;
+  st4(c0 + row, a);
+  st4(c0, b);
 }
 
 // ---- the decryptor's kernels
@@ -666,7 +656,7 @@ static evah_ct *encrypt_symmetric(evah_ctx *c, uint32_t batch, uint32_t l, doubl
                                   const uint8_t *ekeys, const uint8_t *seeds, bool drain = true) {
   const size_t N = c->N, B = batch;
   Scratch e8(c, ekeys ? 4 * B : (B * N + 7) / 8), en(c, B * l * N);
-  std::unique_ptr<Scratch> seed_dev; // more than 8 instances: the seeds as a device buffer, returned to the pool after the drain
+  std::optional<SeedArgs> sa; // more than 8 instances: its device buffer returns to the pool after the drain
   evah_ct *o = ct_new(c, 2, l, scale, batch);
   try {
     // the errors (or the keys they are drawn from) do not stay behind in pool memory the next call reuses
@@ -677,17 +667,8 @@ static evah_ct *encrypt_symmetric(evah_ctx *c, uint32_t batch, uint32_t l, doubl
       HIPCHK(hipMemcpyAsync(e8.d, e, B * N, hipMemcpyHostToDevice, c->stream));
       small_to_ntt(c, e8.d, batch, l, en.d);
     }
-    Seeds8 s8;
-    std::memset(&s8, 0, sizeof s8);
-    const uint32_t *seed_buf = nullptr;
-    if (batch <= SEEDS_PER_LAUNCH) {
-      std::memcpy(s8.w, seeds, (size_t)32 * batch); // little-endian key words, as the host generator reads its key
-    } else {
-      seed_dev = std::make_unique<Scratch>(c, (size_t)4 * batch);
-      HIPCHK(hipMemcpyAsync(seed_dev->d, seeds, (size_t)32 * batch, hipMemcpyHostToDevice, c->stream));
-      seed_buf = reinterpret_cast<const uint32_t *>(seed_dev->d);
-    }
-    EW_LAUNCH(k_encrypt_symmetric, seeded_grid(c, l, batch), dim3(256), 0, c->stream, c->dev, s8, seed_buf, m, en.d, c->sh->sk.d, l, o->d);
+    sa.emplace(c, seeds, batch);
+    EW_LAUNCH(k_encrypt_symmetric, seeded_grid(c, l, batch), dim3(256), 0, c->stream, c->dev, sa->s8, sa->buf, m, en.d, c->sh->sk.d, l, o->d);
     HIPCHK(hipGetLastError());
     w_en.now();
     w_e8.now();

@@ -26,6 +26,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <tuple>
@@ -765,6 +766,32 @@ bool hoist_wanted(const evah_ctx *c, uint32_t l, uint32_t n, uint32_t B);
 KeyDev key_shape(evah_ctx *c, uint32_t n_digits);
 hipError_t key_rows_h2d(evah_ctx *c, const KeyDev &kd, const u64 *src, uint32_t blocks, uint32_t first, uint32_t step);
 void key_install(evah_ctx *c, int kind, uint32_t galois_elt, const KeyDev &kd);
+// The allocations of a key of shape `shape` while a call fills them: freed on scope exit — declare it before the frame
+// that drains the queue — unless release() has handed them to key_install or the device state.  Takes the one decision
+// on the split copy ks_inner_kernel<MAC3> multiplies with: whole keys of contexts whose primes all have the top-bit
+// shape, when there is memory for it.
+struct KeyAlloc {
+  KeyDev kd;
+  KeyAlloc(evah_ctx *c, const KeyDev &shape, bool split = true) : kd(shape) {
+    HIPCHK(hipMalloc(&kd.d, kd.bytes));
+    if (split && c->all_tb && c->tun.mac3 && !(c->dev.pstep > 1) && hipMalloc(&kd.d_split, kd.bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      kd.d_split = nullptr; // no memory for the second copy: the 128-bit accumulation is used
+    }
+  }
+  KeyAlloc(KeyAlloc &&o) noexcept : kd(o.release()) {}
+  KeyAlloc(const KeyAlloc &) = delete;
+  KeyAlloc &operator=(const KeyAlloc &) = delete;
+  ~KeyAlloc() {
+    if (kd.d) (void)hipFree(kd.d);
+    if (kd.d_split) (void)hipFree(kd.d_split);
+  }
+  KeyDev release() {
+    const KeyDev out = kd;
+    kd.d = kd.d_split = nullptr;
+    return out;
+  }
+};
 
 struct Scratch { // pool-backed temporary, returned on scope exit (stream-ordered reuse)
   evah_ctx *c;

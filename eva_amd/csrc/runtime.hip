@@ -391,29 +391,20 @@ extern "C" {
 int evah_key_upload(evah_ctx *c, int kind, uint32_t galois_elt, uint32_t n_digits, const uint64_t *data) {
   API_BEGIN
   use(c);
-  KeyDev kd = key_shape(c, n_digits);
-  const bool local_rows = c->dev.pstep > 1;
-  HIPCHK(hipMalloc(&kd.d, kd.bytes));
-  if (!local_rows) {
+  KeyAlloc key(c, key_shape(c, n_digits));
+  const KeyDev &kd = key.kd;
+  if (c->dev.pstep <= 1) {
     h2d_now(c, kd.d, data, kd.bytes);
   } else {
     hipError_t e = key_rows_h2d(c, kd, (const u64 *)data, 2 * n_digits, 0, 1);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream); // complete before any queue reads the rows (h2d_now)
-    if (e != hipSuccess) {
-      (void)hipFree(kd.d);
-      HIPCHK(e);
-    }
+    HIPCHK(e);
   }
-  if (!local_rows && c->all_tb && c->tun.mac3) { // the split copy ks_inner_kernel<MAC3> multiplies with
-    if (hipMalloc(&kd.d_split, kd.bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      kd.d_split = nullptr; // no memory for the second copy: the 128-bit accumulation is used
-    } else {
-      key_split_launch(c, kd.d, kd.d_split, kd.bytes / sizeof(u64));
-      HIPCHK(hipStreamSynchronize(c->stream));
-    }
+  if (kd.d_split) {
+    key_split_launch(c, kd.d, kd.d_split, kd.bytes / sizeof(u64));
+    HIPCHK(hipStreamSynchronize(c->stream));
   }
-  key_install(c, kind, galois_elt, kd);
+  key_install(c, kind, galois_elt, key.release());
   c->sh->key_up[0]++;
   c->sh->key_up[1] += kd.bytes;
   API_END

@@ -10,6 +10,10 @@
 // that takes ciphertexts to ANOTHER key pair, from that pair's public key: one k_keygen_rekey launch.
 // evah_keygen_relin_round1 / _round2 make a party's two shares of a committee's relinearization key:
 // one k_relin_round1 / k_relin_round2 launch each.
+// What the generators share is written once: on the device the key equation (key_row, called by k_keygen_switch and
+// k_keygen_set), the seed fetch and the four-coefficient accessors (seeded.hip.h); on the host the refusals
+// (keygen_checks, keygen_ready, switch_kind_checks), the seeds of a launch (SeedArgs), the key's allocations (KeyAlloc,
+// internal.hip.h), the c0 copies (c0_download) and the frame that drains the queue on success and on failure (drained).
 
 #include "launch.hip.h"
 #include "seeded.hip.h"
@@ -26,9 +30,7 @@ k_expand_seeded(DevCtx cx, Seeds8 seeds, uint32_t limbs, u64 *dst, size_t inst_s
   const DevPrime pm = cx.primes[prime];
   u64 a[4];
   seeded_block(seeds.w[z], prime, t, pm, a);
-  u64 *row = dst + z * inst_stride + (size_t)i * cx.N + 4 * (size_t)t;
-  st2(row, make_ulonglong2(a[0], a[1]));
-  st2(row + 2, make_ulonglong2(a[2], a[3]));
+  st4(dst + z * inst_stride + (size_t)i * cx.N + 4 * (size_t)t, a);
 }
 
 // c1 of `batch` instances of ct from their seeds: instance b's c1 starts at ct->d + b * 2 * ps + ps
@@ -55,59 +57,43 @@ k_key_expand(DevCtx cx, Seeds8 seeds, const uint32_t *__restrict__ seed_buf, uin
   const uint32_t prime = cx.pstep > 1 && r + 1 == rows ? cx.k - 1 : cx.prime_of(r);
   const DevPrime pm = cx.primes[prime];
   uint32_t key[8];
-  if (seed_buf) {
-#pragma unroll
-    for (int i = 0; i < 8; i++) key[i] = seed_buf[8 * J + i];
-  } else {
-#pragma unroll
-    for (int i = 0; i < 8; i++) key[i] = seeds.w[J][i];
-  }
+  seed_words(seeds, seed_buf, J, key);
   u64 a[4];
   seeded_block(key, prime, t, pm, a);
   const size_t at0 = ((size_t)2 * J * rows + r) * cx.N + 4 * (size_t)t, at1 = at0 + (size_t)rows * cx.N;
-  st2(d + at1, make_ulonglong2(a[0], a[1]));
-  st2(d + at1 + 2, make_ulonglong2(a[2], a[3]));
+  st4(d + at1, a);
   if (d_split) {
-    st2(d_split + at1, make_ulonglong2(split30(a[0]), split30(a[1])));
-    st2(d_split + at1 + 2, make_ulonglong2(split30(a[2]), split30(a[3])));
-    const ulonglong2 b0 = ld2(d + at0), b1 = ld2(d + at0 + 2);
-    st2(d_split + at0, make_ulonglong2(split30(b0.x), split30(b0.y)));
-    st2(d_split + at0 + 2, make_ulonglong2(split30(b1.x), split30(b1.y)));
+    st4_split(d_split + at1, a);
+    u64 b[4];
+    ld4(d + at0, b);
+    st4_split(d_split + at0, b);
   }
 }
 
-// A whole key-switching key from the secret key and seeds, in the device layout d = [digit][2][k][N]: for
-// digit J and chain prime i, a = seeded_block(seed_J, i, .), c0 = -(a s + NTT(e_J)) and, on the row i == J (uniform over
-// the block), + (P mod q_J) s'.  s' is never stored: s * s for the relinearization key (perm == nullptr), s read through
-// the Galois element's permutation table otherwise (the table rotations use: s'[n] = s[perm[n]]).  en = NTT(e)
-// [digit][k][N], sk [k][N].  The split copy, when the key has one, leaves from the same registers.  One thread per
-// ChaCha block (4 coefficients); grid = (ceil(N / 4 / 256), k, digits).  Seeds as in k_key_expand.
-__global__ void __launch_bounds__(256)
-k_keygen_switch(DevCtx cx, Seeds8 seeds, const uint32_t *__restrict__ seed_buf, const u64 *__restrict__ en, const u64 *__restrict__ sk,
-                const uint32_t *__restrict__ perm, u64 *__restrict__ d, u64 *__restrict__ d_split) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y, J = blockIdx.z;
-  if (t >= cx.N / 4 || i >= cx.k) return;
+// what s' of a key-switching key is: s^2 (relinearization), s through the Galois element's permutation table, or no s'
+// row at all (the public key)
+enum : uint32_t { KS_SPRIME_SQUARE = 0, KS_SPRIME_PERM = 1, KS_SPRIME_NONE = 2 };
+
+// The key equation, one thread's four coefficients of digit J, chain prime i of a key in the device layout
+// d = [digit][2][k][N]: a = seeded_block(key, i, t), c0 = -(a s + NTT(e)) and, on the row i == J (uniform over the block)
+// of a key that has an s', + (P mod q_J) s'.  s' is never stored: s * s, or s read through perm (the table rotations use:
+// s'[n] = s[perm[n]]).  e: row i of the digit's NTT-form error; sk [k][N].  Both polynomials and, when the key has one,
+// the split copy leave from the same registers, 16 bytes per access.
+__device__ __forceinline__ void key_row(const DevCtx &cx, const uint32_t key[8], uint32_t i, uint32_t J, uint32_t t, const u64 *e, const u64 *sk,
+                                        uint32_t sprime, const uint32_t *perm, u64 *d, u64 *d_split) {
   const DevPrime pm = cx.primes[i];
-  uint32_t key[8];
-  if (seed_buf) {
-#pragma unroll
-    for (int w = 0; w < 8; w++) key[w] = seed_buf[8 * J + w];
-  } else {
-#pragma unroll
-    for (int w = 0; w < 8; w++) key[w] = seeds.w[J][w];
-  }
-  u64 a[4], b[4];
+  u64 a[4], b[4], sv[4], ev[4];
   seeded_block(key, i, t, pm, a);
   const size_t n0 = 4 * (size_t)t;
-  const u64 *s = sk + (size_t)i * cx.N, *e = en + ((size_t)J * cx.k + i) * cx.N + n0;
-  const ulonglong2 s01 = ld2(s + n0), s23 = ld2(s + n0 + 2), e01 = ld2(e), e23 = ld2(e + 2);
-  const u64 sv[4] = {s01.x, s01.y, s23.x, s23.y}, ev[4] = {e01.x, e01.y, e23.x, e23.y};
+  const u64 *s = sk + (size_t)i * cx.N;
+  ld4(s + n0, sv);
+  ld4(e + n0, ev);
 #pragma unroll
   for (int r = 0; r < 4; r++) b[r] = negmod(addmod(mulmod(a[r], sv[r], pm), ev[r], pm.q), pm.q);
-  if (i == J) {
+  if (i == J && sprime != KS_SPRIME_NONE) {
     const u64 pmod = cx.modq[(size_t)(cx.k - 1) * cx.k + J].x; // P mod q_J
     u64 sp[4];
-    if (perm) {
+    if (sprime == KS_SPRIME_PERM) {
       const uint4 pi = *reinterpret_cast<const uint4 *>(perm + n0);
       sp[0] = s[pi.x]; sp[1] = s[pi.y]; sp[2] = s[pi.z]; sp[3] = s[pi.w];
     } else {
@@ -118,75 +104,57 @@ k_keygen_switch(DevCtx cx, Seeds8 seeds, const uint32_t *__restrict__ seed_buf, 
     for (int r = 0; r < 4; r++) b[r] = addmod(b[r], mulmod(sp[r], pmod, pm), pm.q);
   }
   const size_t at0 = ((size_t)2 * J * cx.k + i) * cx.N + n0, at1 = at0 + (size_t)cx.k * cx.N;
-  st2(d + at0, make_ulonglong2(b[0], b[1]));
-  st2(d + at0 + 2, make_ulonglong2(b[2], b[3]));
-  st2(d + at1, make_ulonglong2(a[0], a[1]));
-  st2(d + at1 + 2, make_ulonglong2(a[2], a[3]));
+  st4(d + at0, b);
+  st4(d + at1, a);
   if (d_split) {
-    st2(d_split + at0, make_ulonglong2(split30(b[0]), split30(b[1])));
-    st2(d_split + at0 + 2, make_ulonglong2(split30(b[2]), split30(b[3])));
-    st2(d_split + at1, make_ulonglong2(split30(a[0]), split30(a[1])));
-    st2(d_split + at1 + 2, make_ulonglong2(split30(a[2]), split30(a[3])));
+    st4_split(d_split + at0, b);
+    st4_split(d_split + at1, a);
   }
 }
 
+// A whole key-switching key from the secret key and seeds: key_row for digit J = blockIdx.z and chain
+// prime i = blockIdx.y, with s' = s * s for the relinearization key (perm == nullptr) and s through perm otherwise.
+// en = NTT(e) [digit][k][N].  One thread per ChaCha block (4 coefficients); grid = (ceil(N / 4 / 256), k, digits).
+// Seeds as in k_key_expand.
+__global__ void __launch_bounds__(256)
+k_keygen_switch(DevCtx cx, Seeds8 seeds, const uint32_t *__restrict__ seed_buf, const u64 *__restrict__ en, const u64 *__restrict__ sk,
+                const uint32_t *__restrict__ perm, u64 *__restrict__ d, u64 *__restrict__ d_split) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y, J = blockIdx.z;
+  if (t >= cx.N / 4 || i >= cx.k) return;
+  uint32_t key[8];
+  seed_words(seeds, seed_buf, J, key);
+  key_row(cx, key, i, J, t, en + ((size_t)J * cx.k + i) * cx.N, sk, perm ? KS_SPRIME_PERM : KS_SPRIME_SQUARE, perm, d, d_split);
+}
+
 // One key of a set, read wave-uniformly by k_keygen_set: where its words go and what s' is
-enum : uint32_t { KS_SPRIME_SQUARE = 0, KS_SPRIME_PERM = 1, KS_SPRIME_NONE = 2 };
 struct KeySetEntry {
   u64 *d, *d_split;     // [digit][2][k][N] each; d_split null: no split copy
   const uint32_t *perm; // KS_SPRIME_PERM: the Galois element's permutation table
-  uint32_t sprime, pad; // s' = s^2 (relinearization), s through perm (Galois), or no s' row at all (the public key)
+  uint32_t sprime, pad; // KS_SPRIME_*
 };
 
 // k_keygen_switch for every key of a set in one launch: blockIdx.z = key * n_digits + J; the key's
-// {d, d_split, perm} come from tab[key], digit z's seed from seed_buf [z][8] and its NTT-form error from en [z][k][N]
-// (z counts within the launch).  Same mapping otherwise: one thread per ChaCha block (4 coefficients), 16-byte accesses,
-// the i == J branch uniform over the block, the split copy from the same registers.  A one-entry table with
-// KS_SPRIME_NONE and one digit is the public key (-(a s + NTT(e)), a) in its [2][k][N] layout.
-// grid = (ceil(N / 4 / 256), k, keys * n_digits)
+// {d, d_split, perm, sprime} come from tab[key], digit z's seed from seed_buf [z][8] and its NTT-form error from en
+// [z][k][N] (z counts within the launch); key_row does the rest.  A one-entry table with KS_SPRIME_NONE and one digit is
+// the public key (-(a s + NTT(e)), a) in its [2][k][N] layout.  grid = (ceil(N / 4 / 256), k, keys * n_digits)
 __global__ void __launch_bounds__(256)
 k_keygen_set(DevCtx cx, const uint32_t *__restrict__ seed_buf, const u64 *__restrict__ en, const u64 *__restrict__ sk,
              const KeySetEntry *__restrict__ tab, uint32_t n_digits) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y, z = blockIdx.z;
   if (t >= cx.N / 4 || i >= cx.k) return;
-  const uint32_t J = z % n_digits;
   const KeySetEntry ke = tab[z / n_digits];
-  const DevPrime pm = cx.primes[i];
   uint32_t key[8];
 #pragma unroll
   for (int w = 0; w < 8; w++) key[w] = seed_buf[8 * (size_t)z + w];
-  u64 a[4], b[4];
-  seeded_block(key, i, t, pm, a);
-  const size_t n0 = 4 * (size_t)t;
-  const u64 *s = sk + (size_t)i * cx.N, *e = en + ((size_t)z * cx.k + i) * cx.N + n0;
-  const ulonglong2 s01 = ld2(s + n0), s23 = ld2(s + n0 + 2), e01 = ld2(e), e23 = ld2(e + 2);
-  const u64 sv[4] = {s01.x, s01.y, s23.x, s23.y}, ev[4] = {e01.x, e01.y, e23.x, e23.y};
-#pragma unroll
-  for (int r = 0; r < 4; r++) b[r] = negmod(addmod(mulmod(a[r], sv[r], pm), ev[r], pm.q), pm.q);
-  if (i == J && ke.sprime != KS_SPRIME_NONE) {
-    const u64 pmod = cx.modq[(size_t)(cx.k - 1) * cx.k + J].x; // P mod q_J
-    u64 sp[4];
-    if (ke.sprime == KS_SPRIME_PERM) {
-      const uint4 pi = *reinterpret_cast<const uint4 *>(ke.perm + n0);
-      sp[0] = s[pi.x]; sp[1] = s[pi.y]; sp[2] = s[pi.z]; sp[3] = s[pi.w];
-    } else {
-#pragma unroll
-      for (int r = 0; r < 4; r++) sp[r] = mulmod(sv[r], sv[r], pm);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; r++) b[r] = addmod(b[r], mulmod(sp[r], pmod, pm), pm.q);
-  }
-  const size_t at0 = ((size_t)2 * J * cx.k + i) * cx.N + n0, at1 = at0 + (size_t)cx.k * cx.N;
-  st2(ke.d + at0, make_ulonglong2(b[0], b[1]));
-  st2(ke.d + at0 + 2, make_ulonglong2(b[2], b[3]));
-  st2(ke.d + at1, make_ulonglong2(a[0], a[1]));
-  st2(ke.d + at1 + 2, make_ulonglong2(a[2], a[3]));
-  if (ke.d_split) {
-    st2(ke.d_split + at0, make_ulonglong2(split30(b[0]), split30(b[1])));
-    st2(ke.d_split + at0 + 2, make_ulonglong2(split30(b[2]), split30(b[3])));
-    st2(ke.d_split + at1, make_ulonglong2(split30(a[0]), split30(a[1])));
-    st2(ke.d_split + at1 + 2, make_ulonglong2(split30(a[2]), split30(a[3])));
-  }
+  key_row(cx, key, i, z % n_digits, t, en + ((size_t)z * cx.k + i) * cx.N, sk, ke.sprime, ke.perm, ke.d, ke.d_split);
+}
+
+// the first polynomial of every digit of a key d [digit][2][k][N] -> out [digit][k][N] (host), enqueued: one linear copy
+// per digit (evah_ct_download on 2-D copies and pageable memory)
+static void c0_download(evah_ctx *c, const u64 *d, uint32_t n_digits, uint64_t *out) {
+  const size_t poly = (size_t)c->k * c->N;
+  for (uint32_t J = 0; J < n_digits; J++)
+    HIPCHK(hipMemcpyAsync(out + (size_t)J * poly, d + (size_t)J * 2 * poly, sizeof(u64) * poly, hipMemcpyDeviceToHost, c->stream));
 }
 
 // The keys [first, first + n) of a set — or the public key (n = 1, one digit) — into their allocations tab[.].d: the
@@ -204,11 +172,8 @@ static void keygen_chunk(evah_ctx *c, const KeySetEntry *tab, uint32_t n, uint32
   EW_LAUNCH(k_keygen_set, seeded_grid(c, c->k, (uint32_t)Z), dim3(256), 0, c->stream, c->dev, reinterpret_cast<const uint32_t *>(sd.d), en.d,
             c->sh->sk.d, reinterpret_cast<const KeySetEntry *>(tb.d), n_digits);
   HIPCHK(hipGetLastError());
-  if (out) // one linear copy per digit (evah_ct_download on 2-D copies and pageable memory)
-    for (uint32_t j = 0; j < n; j++)
-      for (uint32_t J = 0; J < n_digits; J++)
-        HIPCHK(hipMemcpyAsync(out + ((size_t)j * n_digits + J) * poly, tab[j].d + (size_t)J * 2 * poly, sizeof(u64) * poly, hipMemcpyDeviceToHost,
-                              c->stream));
+  if (out)
+    for (uint32_t j = 0; j < n; j++) c0_download(c, tab[j].d, n_digits, out + (size_t)j * n_digits * poly);
   w_ek.now();
   w_en.now();
 }
@@ -255,21 +220,15 @@ k_relin_round1(DevCtx cx, Seeds8 seeds, const uint32_t *__restrict__ seed_buf, c
   if (t >= cx.N / 4 || i >= cx.k) return;
   const DevPrime pm = cx.primes[i];
   uint32_t key[8];
-  if (seed_buf) {
-#pragma unroll
-    for (int w = 0; w < 8; w++) key[w] = seed_buf[8 * J + w];
-  } else {
-#pragma unroll
-    for (int w = 0; w < 8; w++) key[w] = seeds.w[J][w];
-  }
-  u64 a[4], h0[4], h1[4];
+  seed_words(seeds, seed_buf, J, key);
+  u64 a[4], h0[4], h1[4], uv[4], e0[4], e1[4], sv[4];
   seeded_block(key, i, t, pm, a);
   const size_t poly = (size_t)cx.k * cx.N, row = (size_t)i * cx.N + 4 * (size_t)t;
   const u64 *sm = small + (size_t)J * 3 * poly + row;
-  const ulonglong2 u01 = ld2(sm), u23 = ld2(sm + 2), e01 = ld2(sm + poly), e23 = ld2(sm + poly + 2);
-  const ulonglong2 f01 = ld2(sm + 2 * poly), f23 = ld2(sm + 2 * poly + 2), s01 = ld2(sk + row), s23 = ld2(sk + row + 2);
-  const u64 uv[4] = {u01.x, u01.y, u23.x, u23.y}, e0[4] = {e01.x, e01.y, e23.x, e23.y}, e1[4] = {f01.x, f01.y, f23.x, f23.y};
-  const u64 sv[4] = {s01.x, s01.y, s23.x, s23.y};
+  ld4(sm, uv);
+  ld4(sm + poly, e0);
+  ld4(sm + 2 * poly, e1);
+  ld4(sk + row, sv);
 #pragma unroll
   for (int r = 0; r < 4; r++) {
     h0[r] = addmod(negmod(mulmod(a[r], uv[r], pm), pm.q), e0[r], pm.q);
@@ -281,10 +240,8 @@ k_relin_round1(DevCtx cx, Seeds8 seeds, const uint32_t *__restrict__ seed_buf, c
     for (int r = 0; r < 4; r++) h0[r] = addmod(h0[r], mulmod(sv[r], pmod, pm), pm.q);
   }
   u64 *at = out + (size_t)2 * J * poly + row;
-  st2(at, make_ulonglong2(h0[0], h0[1]));
-  st2(at + 2, make_ulonglong2(h0[2], h0[3]));
-  st2(at + poly, make_ulonglong2(h1[0], h1[1]));
-  st2(at + poly + 2, make_ulonglong2(h1[2], h1[3]));
+  st4(at, h0);
+  st4(at + poly, h1);
 }
 
 // Round 2: g = s H0 + NTT(e2_J) + (u_J - s) H1 + NTT(e3_J) for digit J, prime row i.  agg [digit][2][k][N]
@@ -306,10 +263,34 @@ k_relin_round2(DevCtx cx, const u64 *__restrict__ agg, const u64 *__restrict__ u
   st2(out + (size_t)J * poly + row, g);
 }
 
-// the refusals evah_keygen_switch, evah_keygen_set and evah_keygen_public share, with evah_keygen_switch's messages
+// the refusals every generator shares: keygen_checks before it looks at its arguments, keygen_ready after
 static void keygen_checks(evah_ctx *c) {
   if (c->dev.pstep > 1) throw std::invalid_argument("a limb shard holds no whole secret key");
   if (c->capturing) throw std::logic_error("this call synchronises with the host and cannot be captured into a graph");
+}
+static void keygen_ready(evah_ctx *c) {
+  if (c->N % 256) throw std::invalid_argument("key generation needs N divisible by 256");
+  if (!c->sh->sk.d) throw std::invalid_argument("secret key not present");
+}
+// the kinds of key that travel seed-compressed or are generated from seeds: relinearization and Galois; rekey_msg says
+// where a re-key key goes instead
+static void switch_kind_checks(evah_ctx *c, int kind, uint32_t galois_elt, const char *rekey_msg) {
+  if (kind == EVAH_KEY_REKEY) throw std::invalid_argument(rekey_msg);
+  if (kind != EVAH_KEY_RELIN && kind != EVAH_KEY_GALOIS) throw std::invalid_argument("unknown key kind");
+  if (kind == EVAH_KEY_GALOIS && (!(galois_elt & 1) || galois_elt >= 2 * c->N)) throw std::invalid_argument("Galois element is not valid");
+}
+static const char *const REKEY_GENERATED = "a re-key key is generated by evah_keygen_rekey";
+
+// body(), then the drain of the queue — also when body throws, before anything the caller holds (key allocations,
+// scratch, pageable arguments) is let go
+template <class F> static void drained(evah_ctx *c, F &&body) {
+  try {
+    body();
+    HIPCHK(hipStreamSynchronize(c->stream));
+  } catch (...) {
+    (void)hipStreamSynchronize(c->stream);
+    throw;
+  }
 }
 
 } // namespace evah
@@ -321,50 +302,29 @@ extern "C" {
 int evah_key_upload_seeded(evah_ctx *c, int kind, uint32_t galois_elt, uint32_t n_digits, const uint64_t *c0, const uint8_t *seeds) {
   API_BEGIN
   use(c);
-  KeyDev kd = key_shape(c, n_digits);
-  if (kind == EVAH_KEY_REKEY) throw std::invalid_argument("a re-key key is not seed-compressible: upload it whole (evah_key_upload)");
-  if (kind != EVAH_KEY_RELIN && kind != EVAH_KEY_GALOIS) throw std::invalid_argument("unknown key kind");
-  if (kind == EVAH_KEY_GALOIS && (!(galois_elt & 1) || galois_elt >= 2 * c->N)) throw std::invalid_argument("Galois element is not valid");
+  const KeyDev shape = key_shape(c, n_digits);
+  switch_kind_checks(c, kind, galois_elt, "a re-key key is not seed-compressible: upload it whole (evah_key_upload)");
   if (!c0) throw std::invalid_argument("key pointer is null");
   if (!seeds) throw std::invalid_argument("seed pointer is null");
-  const bool local_rows = c->dev.pstep > 1;
-  Seeds8 s8;
-  std::memset(&s8, 0, sizeof s8);
-  std::unique_ptr<Scratch> seed_dev; // more than 8 digits: the seeds as a device buffer, returned to the pool after the drain
-  HIPCHK(hipMalloc(&kd.d, kd.bytes));
-  if (!local_rows && c->all_tb && c->tun.mac3 && hipMalloc(&kd.d_split, kd.bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    kd.d_split = nullptr; // no memory for the second copy: the 128-bit accumulation is used
-  }
-  try {
+  KeyAlloc key(c, shape);
+  const KeyDev &kd = key.kd;
+  std::optional<SeedArgs> sa; // its device buffer (more than 8 digits) returns to the pool after the drain
+  drained(c, [&] { // complete before any queue reads the rows (h2d_now)
     const size_t poly = (size_t)c->k * c->N;
     hipError_t e = hipSuccess;
-    if (!local_rows) // c0 of digit J into d[J][0]: one copy per digit
+    if (c->dev.pstep <= 1) // a whole key: c0 of digit J into d[J][0], one copy per digit
       for (uint32_t J = 0; J < n_digits && e == hipSuccess; J++)
         e = hipMemcpyAsync(kd.d + (size_t)J * 2 * poly, (const u64 *)c0 + (size_t)J * poly, sizeof(u64) * poly, hipMemcpyHostToDevice, c->stream);
     else
       e = key_rows_h2d(c, kd, (const u64 *)c0, n_digits, 0, 2);
     HIPCHK(e);
-    const uint32_t *seed_buf = nullptr;
-    if (n_digits <= SEEDS_PER_LAUNCH) {
-      std::memcpy(s8.w, seeds, (size_t)32 * n_digits); // little-endian key words, as the host generator reads its key
-    } else {
-      seed_dev = std::make_unique<Scratch>(c, (size_t)4 * n_digits);
-      HIPCHK(hipMemcpyAsync(seed_dev->d, seeds, (size_t)32 * n_digits, hipMemcpyHostToDevice, c->stream));
-      seed_buf = reinterpret_cast<const uint32_t *>(seed_dev->d);
-    }
-    EW_LAUNCH(k_key_expand, seeded_grid(c, kd.rows, n_digits), dim3(256), 0, c->stream, c->dev, s8, seed_buf, kd.rows, kd.d, kd.d_split);
+    sa.emplace(c, seeds, n_digits);
+    EW_LAUNCH(k_key_expand, seeded_grid(c, kd.rows, n_digits), dim3(256), 0, c->stream, c->dev, sa->s8, sa->buf, kd.rows, kd.d, kd.d_split);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream)); // complete before any queue reads the rows (h2d_now)
-  } catch (...) {
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(kd.d);
-    if (kd.d_split) (void)hipFree(kd.d_split);
-    throw;
-  }
-  key_install(c, kind, galois_elt, kd);
+  });
+  key_install(c, kind, galois_elt, key.release());
   c->sh->key_up[0]++;
-  c->sh->key_up[1] += kd.bytes / 2 + (size_t)32 * n_digits; // c0 of the rows kept + the seeds
+  c->sh->key_up[1] += shape.bytes / 2 + (size_t)32 * n_digits; // c0 of the rows kept + the seeds
   API_END
 }
 
@@ -375,68 +335,34 @@ int evah_keygen_switch(evah_ctx *c, int kind, uint32_t galois_elt, uint32_t n_di
                        int install, uint64_t *c0_out) {
   API_BEGIN
   use(c);
-  if (c->dev.pstep > 1) throw std::invalid_argument("a limb shard holds no whole secret key");
-  KeyDev kd = key_shape(c, n_digits);
-  if (kind == EVAH_KEY_REKEY) throw std::invalid_argument("a re-key key is generated by evah_keygen_rekey");
-  if (kind != EVAH_KEY_RELIN && kind != EVAH_KEY_GALOIS) throw std::invalid_argument("unknown key kind");
-  if (kind == EVAH_KEY_GALOIS && (!(galois_elt & 1) || galois_elt >= 2 * c->N)) throw std::invalid_argument("Galois element is not valid");
+  keygen_checks(c);
+  const KeyDev shape = key_shape(c, n_digits);
+  switch_kind_checks(c, kind, galois_elt, REKEY_GENERATED);
   if (!errors) throw std::invalid_argument("error pointer is null");
   if (!seeds) throw std::invalid_argument("seed pointer is null");
   if (!install && !c0_out) throw std::invalid_argument("the key is neither installed nor returned");
-  if (c->N % 256) throw std::invalid_argument("key generation needs N divisible by 256");
-  if (!c->sh->sk.d) throw std::invalid_argument("secret key not present");
+  keygen_ready(c);
   const uint32_t *perm = kind == EVAH_KEY_GALOIS ? perm_table(c, galois_elt) : nullptr;
-  const size_t N = c->N, poly = (size_t)c->k * N, e_bytes = (size_t)n_digits * N;
-  Seeds8 s8;
-  std::memset(&s8, 0, sizeof s8);
-  std::unique_ptr<Scratch> seed_dev; // more than 8 digits: the seeds as a device buffer, returned to the pool after the drain
-  HIPCHK(hipMalloc(&kd.d, kd.bytes));
-  if (c->all_tb && c->tun.mac3 && hipMalloc(&kd.d_split, kd.bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    kd.d_split = nullptr; // no memory for the second copy: the 128-bit accumulation is used
-  }
-  try {
-    Scratch e8(c, (e_bytes + 7) / 8), en(c, (size_t)n_digits * poly);
-    try {
-      HIPCHK(hipMemcpyAsync(e8.d, errors, e_bytes, hipMemcpyHostToDevice, c->stream));
-      small_to_ntt(c, e8.d, n_digits, c->k, en.d);
-      const uint32_t *seed_buf = nullptr;
-      if (n_digits <= SEEDS_PER_LAUNCH) {
-        std::memcpy(s8.w, seeds, (size_t)32 * n_digits); // little-endian key words, as the host generator reads its key
-      } else {
-        seed_dev = std::make_unique<Scratch>(c, (size_t)4 * n_digits);
-        HIPCHK(hipMemcpyAsync(seed_dev->d, seeds, (size_t)32 * n_digits, hipMemcpyHostToDevice, c->stream));
-        seed_buf = reinterpret_cast<const uint32_t *>(seed_dev->d);
-      }
-      EW_LAUNCH(k_keygen_switch, seeded_grid(c, c->k, n_digits), dim3(256), 0, c->stream, c->dev, s8, seed_buf, en.d, c->sh->sk.d, perm, kd.d,
-                kd.d_split);
-      HIPCHK(hipGetLastError());
-      if (c0_out) // c0 of digit J from d[J][0]: one linear copy per digit (evah_ct_download on 2-D copies and pageable memory)
-        for (uint32_t J = 0; J < n_digits; J++)
-          HIPCHK(hipMemcpyAsync(c0_out + (size_t)J * poly, kd.d + (size_t)J * 2 * poly, sizeof(u64) * poly, hipMemcpyDeviceToHost, c->stream));
-    } catch (...) {
-      (void)hipMemsetAsync(en.d, 0, sizeof(u64) * (size_t)n_digits * poly, c->stream);
-      (void)hipMemsetAsync(e8.d, 0, e_bytes, c->stream);
-      throw;
-    }
+  const size_t poly = (size_t)c->k * c->N, e_bytes = (size_t)n_digits * c->N;
+  KeyAlloc key(c, shape);
+  Scratch e8(c, (e_bytes + 7) / 8), en(c, (size_t)n_digits * poly);
+  std::optional<SeedArgs> sa; // its device buffer (more than 8 digits) returns to the pool after the drain
+  drained(c, [&] { // `errors` and c0_out are pageable; complete before any queue reads the key
     // the errors do not stay behind in pool memory the next call reuses
-    HIPCHK(hipMemsetAsync(en.d, 0, sizeof(u64) * (size_t)n_digits * poly, c->stream));
-    HIPCHK(hipMemsetAsync(e8.d, 0, e_bytes, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream)); // `errors` and c0_out are pageable; complete before any queue reads the key
-  } catch (...) {
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(kd.d);
-    if (kd.d_split) (void)hipFree(kd.d_split);
-    throw;
-  }
+    Wipe w_en{c, en.d, sizeof(u64) * (size_t)n_digits * poly}, w_e8{c, e8.d, e_bytes};
+    HIPCHK(hipMemcpyAsync(e8.d, errors, e_bytes, hipMemcpyHostToDevice, c->stream));
+    small_to_ntt(c, e8.d, n_digits, c->k, en.d);
+    sa.emplace(c, seeds, n_digits);
+    EW_LAUNCH(k_keygen_switch, seeded_grid(c, c->k, n_digits), dim3(256), 0, c->stream, c->dev, sa->s8, sa->buf, en.d, c->sh->sk.d, perm, key.kd.d,
+              key.kd.d_split);
+    HIPCHK(hipGetLastError());
+    if (c0_out) c0_download(c, key.kd.d, n_digits, c0_out);
+    w_en.now();
+    w_e8.now();
+  });
   c->sh->xfer[4] += e_bytes + (size_t)32 * n_digits;
   if (c0_out) c->sh->xfer[5] += sizeof(u64) * (size_t)n_digits * poly;
-  if (install) {
-    key_install(c, kind, galois_elt, kd);
-  } else {
-    (void)hipFree(kd.d);
-    if (kd.d_split) (void)hipFree(kd.d_split);
-  }
+  if (install) key_install(c, kind, galois_elt, key.release());
   API_END
 }
 
@@ -453,9 +379,7 @@ int evah_keygen_set(evah_ctx *c, uint32_t n_keys, const int *kinds, const uint32
   if (!kinds || !elts) throw std::invalid_argument("key list pointer is null");
   if ((uint64_t)n_keys * n_digits > 65535) throw std::invalid_argument("a key set holds at most 65535 digits");
   for (uint32_t j = 0; j < n_keys; j++) {
-    if (kinds[j] == EVAH_KEY_REKEY) throw std::invalid_argument("a re-key key is generated by evah_keygen_rekey");
-    if (kinds[j] != EVAH_KEY_RELIN && kinds[j] != EVAH_KEY_GALOIS) throw std::invalid_argument("unknown key kind");
-    if (kinds[j] == EVAH_KEY_GALOIS && (!(elts[j] & 1) || elts[j] >= 2 * c->N)) throw std::invalid_argument("Galois element is not valid");
+    switch_kind_checks(c, kinds[j], elts[j], REKEY_GENERATED);
     for (uint32_t i = 0; i < j; i++)
       if (kinds[i] == kinds[j] && (kinds[j] == EVAH_KEY_RELIN || elts[i] == elts[j]))
         throw std::invalid_argument("key " + std::to_string(j) + " repeats key " + std::to_string(i));
@@ -463,28 +387,21 @@ int evah_keygen_set(evah_ctx *c, uint32_t n_keys, const int *kinds, const uint32
   if (!ekeys) throw std::invalid_argument("error pointer is null");
   if (!seeds) throw std::invalid_argument("seed pointer is null");
   if (!install && !c0_out) throw std::invalid_argument("the key is neither installed nor returned");
-  if (c->N % 256) throw std::invalid_argument("key generation needs N divisible by 256");
-  if (!c->sh->sk.d) throw std::invalid_argument("secret key not present");
-  const size_t poly = (size_t)c->k * c->N, key_words = (size_t)n_digits * poly;
+  keygen_ready(c);
+  const size_t key_words = (size_t)n_digits * c->k * c->N;
+  std::vector<KeyAlloc> keys; // freed behind the drain unless every key of the set was made
   std::vector<KeySetEntry> tab(n_keys, KeySetEntry{nullptr, nullptr, nullptr, KS_SPRIME_SQUARE, 0});
-  auto free_all = [&] {
-    for (KeySetEntry &ke : tab) {
-      if (ke.d) (void)hipFree(ke.d);
-      if (ke.d_split) (void)hipFree(ke.d_split);
-    }
-  };
-  try {
+  keys.reserve(n_keys);
+  drained(c, [&] { // `ekeys`, `seeds` and c0_out are pageable; complete before any queue reads a key
     for (uint32_t j = 0; j < n_keys; j++) { // the permutation tables before the first launch (first use: a copy of its own)
       if (kinds[j] != EVAH_KEY_GALOIS) continue;
       tab[j].perm = perm_table(c, elts[j]);
       tab[j].sprime = KS_SPRIME_PERM;
     }
     for (KeySetEntry &ke : tab) {
-      HIPCHK(hipMalloc(&ke.d, shape.bytes));
-      if (c->all_tb && c->tun.mac3 && hipMalloc(&ke.d_split, shape.bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        ke.d_split = nullptr; // no memory for the second copy: the 128-bit accumulation is used
-      }
+      keys.emplace_back(c, shape);
+      ke.d = keys.back().kd.d;
+      ke.d_split = keys.back().kd.d_split;
     }
     // whole keys per launch list: as many as Tunables::keygen_set_words of NTT-form errors hold, at least one
     const uint32_t per_chunk = (uint32_t)std::min<size_t>(n_keys, std::max<size_t>(1, c->tun.keygen_set_words / key_words));
@@ -493,24 +410,11 @@ int evah_keygen_set(evah_ctx *c, uint32_t n_keys, const int *kinds, const uint32
       const size_t at = (size_t)32 * j0 * n_digits;
       keygen_chunk(c, tab.data() + j0, n, n_digits, ekeys + at, seeds + at, c0_out ? c0_out + (size_t)j0 * key_words : nullptr);
     }
-    HIPCHK(hipStreamSynchronize(c->stream)); // `ekeys`, `seeds` and c0_out are pageable; complete before any queue reads a key
-  } catch (...) {
-    (void)hipStreamSynchronize(c->stream);
-    free_all();
-    throw;
-  }
+  });
   c->sh->xfer[4] += (size_t)64 * n_keys * n_digits;
   if (c0_out) c->sh->xfer[5] += sizeof(u64) * n_keys * key_words;
-  if (!install) {
-    free_all();
-  } else {
-    for (uint32_t j = 0; j < n_keys; j++) {
-      KeyDev kd = shape;
-      kd.d = tab[j].d;
-      kd.d_split = tab[j].d_split;
-      key_install(c, kinds[j], elts[j], kd); // cannot refuse: kinds and elements were checked above
-    }
-  }
+  if (install)
+    for (uint32_t j = 0; j < n_keys; j++) key_install(c, kinds[j], elts[j], keys[j].release()); // cannot refuse: checked above
   API_END
 }
 
@@ -524,29 +428,22 @@ int evah_keygen_public(evah_ctx *c, const uint8_t *ekey32, const uint8_t *seed32
   if (!ekey32) throw std::invalid_argument("error pointer is null");
   if (!seed32) throw std::invalid_argument("seed pointer is null");
   if (!install && !pk_out) throw std::invalid_argument("the key is neither installed nor returned");
-  if (c->N % 256) throw std::invalid_argument("key generation needs N divisible by 256");
-  if (!c->sh->sk.d) throw std::invalid_argument("secret key not present");
-  KeyDev kd;
-  kd.n_digits = 1;
-  kd.bytes = sizeof(u64) * (size_t)2 * c->k * c->N;
-  HIPCHK(hipMalloc(&kd.d, kd.bytes));
-  try {
+  keygen_ready(c);
+  KeyDev shape;
+  shape.n_digits = 1;
+  shape.bytes = sizeof(u64) * (size_t)2 * c->k * c->N;
+  KeyAlloc key(c, shape, false); // encryption reads no split copy
+  const KeyDev &kd = key.kd;
+  drained(c, [&] { // the arguments are pageable; complete before any queue reads the key
     const KeySetEntry ke{kd.d, nullptr, nullptr, KS_SPRIME_NONE, 0};
     keygen_chunk(c, &ke, 1, 1, ekey32, seed32, nullptr);
     if (pk_out) HIPCHK(hipMemcpyAsync(pk_out, kd.d, kd.bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream)); // the arguments are pageable; complete before any queue reads the key
-  } catch (...) {
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(kd.d);
-    throw;
-  }
+  });
   c->sh->xfer[4] += 64;
   if (pk_out) c->sh->xfer[5] += kd.bytes;
   if (install) {
     if (c->sh->pk.d) (void)hipFree(c->sh->pk.d);
-    c->sh->pk = kd;
-  } else {
-    (void)hipFree(kd.d);
+    c->sh->pk = key.release();
   }
   API_END
 }
@@ -562,11 +459,10 @@ int evah_keygen_rekey(evah_ctx *c, const uint64_t *pk_target, uint32_t n_digits,
   if (!pk_target) throw std::invalid_argument("key pointer is null");
   if (!rkeys) throw std::invalid_argument("randomness key pointer is null");
   if (!key_out) throw std::invalid_argument("output pointer is null");
-  if (c->N % 256) throw std::invalid_argument("key generation needs N divisible by 256");
-  if (!c->sh->sk.d) throw std::invalid_argument("secret key not present");
+  keygen_ready(c);
   const size_t poly = (size_t)c->k * c->N;
-  try {
-    Scratch pk(c, 2 * poly), rk(c, (size_t)4 * n_digits), sm(c, (size_t)n_digits * 3 * poly), key(c, (size_t)n_digits * 2 * poly);
+  Scratch pk(c, 2 * poly), rk(c, (size_t)4 * n_digits), sm(c, (size_t)n_digits * 3 * poly), key(c, (size_t)n_digits * 2 * poly);
+  drained(c, [&] { // the arguments are pageable; the scratch returns to the pool drained
     // the randomness keys, the sampled residues and their NTT forms do not stay behind in pool memory the next call reuses
     Wipe w_rk{c, rk.d, (size_t)32 * n_digits}, w_sm{c, sm.d, sizeof(u64) * n_digits * 3 * poly};
     HIPCHK(hipMemcpyAsync(pk.d, pk_target, sizeof(u64) * 2 * poly, hipMemcpyHostToDevice, c->stream));
@@ -576,11 +472,7 @@ int evah_keygen_rekey(evah_ctx *c, const uint64_t *pk_target, uint32_t n_digits,
     HIPCHK(hipMemcpyAsync(key_out, key.d, shape.bytes, hipMemcpyDeviceToHost, c->stream));
     w_rk.now();
     w_sm.now();
-    HIPCHK(hipStreamSynchronize(c->stream)); // the arguments are pageable; the scratch returns to the pool drained
-  } catch (...) {
-    (void)hipStreamSynchronize(c->stream);
-    throw;
-  }
+  });
   c->sh->xfer[4] += sizeof(u64) * 2 * poly + (size_t)32 * n_digits;
   c->sh->xfer[5] += shape.bytes;
   API_END
@@ -598,33 +490,21 @@ int evah_keygen_relin_round1(evah_ctx *c, uint32_t n_digits, const uint8_t *seed
   if (!seeds) throw std::invalid_argument("seed pointer is null");
   if (!r1keys) throw std::invalid_argument("randomness key pointer is null");
   if (!share_out) throw std::invalid_argument("output pointer is null");
-  if (c->N % 256) throw std::invalid_argument("key generation needs N divisible by 256");
-  if (!c->sh->sk.d) throw std::invalid_argument("secret key not present");
+  keygen_ready(c);
   const size_t poly = (size_t)c->k * c->N;
-  Seeds8 s8;
-  std::memset(&s8, 0, sizeof s8);
-  try {
-    Scratch rk(c, (size_t)4 * n_digits), sd(c, (size_t)4 * n_digits), sm(c, (size_t)n_digits * 3 * poly), share(c, (size_t)n_digits * 2 * poly);
+  Scratch rk(c, (size_t)4 * n_digits), sm(c, (size_t)n_digits * 3 * poly), share(c, (size_t)n_digits * 2 * poly);
+  std::optional<SeedArgs> sa;
+  drained(c, [&] { // the arguments are pageable; the scratch returns to the pool drained
     // the randomness keys, the sampled residues and their NTT forms do not stay behind in pool memory the next call reuses
     Wipe w_rk{c, rk.d, (size_t)32 * n_digits}, w_sm{c, sm.d, sizeof(u64) * n_digits * 3 * poly};
-    const uint32_t *seed_buf = nullptr;
-    if (n_digits <= SEEDS_PER_LAUNCH) {
-      std::memcpy(s8.w, seeds, (size_t)32 * n_digits); // little-endian key words, as the host generator reads its key
-    } else {
-      HIPCHK(hipMemcpyAsync(sd.d, seeds, (size_t)32 * n_digits, hipMemcpyHostToDevice, c->stream));
-      seed_buf = reinterpret_cast<const uint32_t *>(sd.d);
-    }
+    sa.emplace(c, seeds, n_digits);
     sample_to_ntt(c, n_digits, r1keys, rk.d, 3, 0, c->k, sm.d);
-    EW_LAUNCH(k_relin_round1, seeded_grid(c, c->k, n_digits), dim3(256), 0, c->stream, c->dev, s8, seed_buf, sm.d, c->sh->sk.d, share.d);
+    EW_LAUNCH(k_relin_round1, seeded_grid(c, c->k, n_digits), dim3(256), 0, c->stream, c->dev, sa->s8, sa->buf, sm.d, c->sh->sk.d, share.d);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(share_out, share.d, shape.bytes, hipMemcpyDeviceToHost, c->stream));
     w_rk.now();
     w_sm.now();
-    HIPCHK(hipStreamSynchronize(c->stream)); // the arguments are pageable; the scratch returns to the pool drained
-  } catch (...) {
-    (void)hipStreamSynchronize(c->stream);
-    throw;
-  }
+  });
   c->sh->xfer[4] += (size_t)64 * n_digits;
   c->sh->xfer[5] += shape.bytes;
   API_END
@@ -643,12 +523,11 @@ int evah_keygen_relin_round2(evah_ctx *c, uint32_t n_digits, const uint64_t *agg
   if (!agg1) throw std::invalid_argument("key pointer is null");
   if (!r1keys || !r2keys) throw std::invalid_argument("randomness key pointer is null");
   if (!share_out) throw std::invalid_argument("output pointer is null");
-  if (c->N % 256) throw std::invalid_argument("key generation needs N divisible by 256");
-  if (!c->sh->sk.d) throw std::invalid_argument("secret key not present");
+  keygen_ready(c);
   const size_t poly = (size_t)c->k * c->N;
-  try {
-    Scratch agg(c, (size_t)n_digits * 2 * poly), k1(c, (size_t)4 * n_digits), k2(c, (size_t)4 * n_digits), un(c, (size_t)n_digits * poly),
-        en(c, (size_t)n_digits * 2 * poly), share(c, (size_t)n_digits * poly);
+  Scratch agg(c, (size_t)n_digits * 2 * poly), k1(c, (size_t)4 * n_digits), k2(c, (size_t)4 * n_digits), un(c, (size_t)n_digits * poly),
+      en(c, (size_t)n_digits * 2 * poly), share(c, (size_t)n_digits * poly);
+  drained(c, [&] { // the arguments are pageable; the scratch returns to the pool drained
     // the randomness keys, the sampled residues and their NTT forms do not stay behind in pool memory the next call reuses
     Wipe w_k1{c, k1.d, (size_t)32 * n_digits}, w_k2{c, k2.d, (size_t)32 * n_digits}, w_un{c, un.d, sizeof(u64) * n_digits * poly},
         w_en{c, en.d, sizeof(u64) * n_digits * 2 * poly};
@@ -662,11 +541,7 @@ int evah_keygen_relin_round2(evah_ctx *c, uint32_t n_digits, const uint64_t *agg
     w_k2.now();
     w_un.now();
     w_en.now();
-    HIPCHK(hipStreamSynchronize(c->stream)); // the arguments are pageable; the scratch returns to the pool drained
-  } catch (...) {
-    (void)hipStreamSynchronize(c->stream);
-    throw;
-  }
+  });
   c->sh->xfer[4] += shape.bytes + (size_t)64 * n_digits;
   c->sh->xfer[5] += shape.bytes / 2;
   API_END
@@ -691,14 +566,8 @@ int evah_key_download_c0(evah_ctx *c, int kind, uint32_t galois_elt, uint32_t n_
   if (!kd) throw std::invalid_argument("key not present");
   if (kd->rows != c->k) throw std::invalid_argument("a limb shard holds rows of the keys, not whole keys");
   if (n_digits != kd->n_digits) throw std::invalid_argument("invalid key digit count");
-  const size_t poly = (size_t)c->k * c->N;
-  hipError_t e = hipSuccess;
-  for (uint32_t J = 0; J < n_digits && e == hipSuccess; J++) // one linear copy per digit
-    e = hipMemcpyAsync(out + (size_t)J * poly, kd->d + (size_t)J * 2 * poly, sizeof(u64) * poly, hipMemcpyDeviceToHost, c->stream);
-  const hipError_t drained = hipStreamSynchronize(c->stream);
-  HIPCHK(e);
-  HIPCHK(drained);
-  c->sh->xfer[5] += sizeof(u64) * n_digits * poly;
+  drained(c, [&] { c0_download(c, kd->d, n_digits, out); });
+  c->sh->xfer[5] += sizeof(u64) * n_digits * c->k * c->N;
   API_END
 }
 

@@ -4,7 +4,7 @@
 // counter = j / 4 (state words 12-13), nonce = 0x6331000000000000 | i (words 14-15).  The result is limb i of c1 in NTT
 // form as stored; a limb depends only on (seed, i).  Host twin: eva_amd/host/csprng.h seeded_limb.
 #pragma once
-#include "internal.hip.h"
+#include "launch.hip.h"
 
 namespace evah {
 
@@ -49,6 +49,32 @@ __device__ __forceinline__ void seeded_block(const uint32_t *key, uint32_t prime
   for (int r = 0; r < 4; r++) out[r] = barrett128(u128_t{chacha_w64(x, 2 * r), chacha_w64(x, 2 * r + 1)}, pm);
 }
 
+// the key words of seed z of a launch: from the launch arguments for up to SEEDS_PER_LAUNCH seeds, else from seed_buf
+// ([seeds][8] words, uploaded on the same queue) — uniform over the launch
+__device__ __forceinline__ void seed_words(const Seeds8 &seeds, const uint32_t *seed_buf, uint32_t z, uint32_t key[8]) {
+  if (seed_buf) {
+#pragma unroll
+    for (int w = 0; w < 8; w++) key[w] = seed_buf[8 * z + w];
+  } else {
+#pragma unroll
+    for (int w = 0; w < 8; w++) key[w] = seeds.w[z][w];
+  }
+}
+
+// a thread's four coefficients (one ChaCha block) as two 16-byte accesses; st4_split stores their split30 forms
+__device__ __forceinline__ void ld4(const u64 *p, u64 v[4]) {
+  const ulonglong2 lo = ld2(p), hi = ld2(p + 2);
+  v[0] = lo.x; v[1] = lo.y; v[2] = hi.x; v[3] = hi.y;
+}
+__device__ __forceinline__ void st4(u64 *p, const u64 v[4]) {
+  st2(p, make_ulonglong2(v[0], v[1]));
+  st2(p + 2, make_ulonglong2(v[2], v[3]));
+}
+__device__ __forceinline__ void st4_split(u64 *p, const u64 v[4]) {
+  st2(p, make_ulonglong2(split30(v[0]), split30(v[1])));
+  st2(p + 2, make_ulonglong2(split30(v[2]), split30(v[3])));
+}
+
 inline Seeds8 seeds_of(const uint8_t *const *seeds, uint32_t first, uint32_t n) {
   Seeds8 s;
   std::memset(&s, 0, sizeof s);
@@ -58,6 +84,24 @@ inline Seeds8 seeds_of(const uint8_t *const *seeds, uint32_t first, uint32_t n) 
   }
   return s;
 }
+// The seeds of one launch as its kernel takes them (seed_words): n seeds [n][32] (host) as launch arguments, or above
+// SEEDS_PER_LAUNCH as a device buffer copied on the queue.  Declare it in the scope that drains the queue: the buffer
+// returns to the pool when it ends.
+struct SeedArgs {
+  Seeds8 s8;
+  std::unique_ptr<Scratch> dev;
+  const uint32_t *buf = nullptr;
+  SeedArgs(evah_ctx *c, const uint8_t *seeds, uint32_t n) {
+    std::memset(&s8, 0, sizeof s8);
+    if (n <= SEEDS_PER_LAUNCH) {
+      std::memcpy(s8.w, seeds, (size_t)32 * n); // little-endian key words, as the host generator reads its key
+    } else {
+      dev = std::make_unique<Scratch>(c, (size_t)4 * n);
+      HIPCHK(hipMemcpyAsync(dev->d, seeds, (size_t)32 * n, hipMemcpyHostToDevice, c->stream));
+      buf = reinterpret_cast<const uint32_t *>(dev->d);
+    }
+  }
+};
 // client.hip: small polynomials (int8 on the device) to their NTT forms under the first `limbs` chain primes
 void small_to_ntt(evah_ctx *c, const u64 *small8, uint32_t n_polys, uint32_t limbs, u64 *out);
 // client.hip: the randomness keys rkeys [batch][32] (host) copied into `keys` on the queue, then the NTT forms
