@@ -117,16 +117,17 @@ template <bool ENC> static void fft_batched(evah_ctx *c, double2 *cd, const doub
 }
 
 // ---- the encoder of the _many calls: evah_pt_encode's small kernels (elementwise.hip) with an instance index (grid.y)
+// Row b of the values lies at byte b * pitch of vals: the call's staged copy of a host array at the tight
+// pitch sizeof(T) * n_vals, or the caller's device memory at its own (a torch slice t[:, :n] is pitched).
 // T = the type the values arrived in (double, float, uint8_t: evah_encode_encrypt_array); every T converts to
 // double exactly, so the slots hold what the double instantiation holds for the converted array.  One scalar load per
-// thread: row b of a uint8_t array starts at byte b * n_vals, aligned to nothing, and the kernel is bound by its two
-// 16-byte stores per slot, not by the load.
+// thread: a uint8_t row may start at any byte, and the kernel is bound by its two 16-byte stores per slot, not by the load.
 template <class T>
 __global__ void __launch_bounds__(256)
-k_enc_scatter_many(const T *vals, uint32_t n_vals, const uint32_t *slot_map, double2 *c, uint32_t slots) {
+k_enc_scatter_rows(const unsigned char *vals, size_t pitch, uint32_t n_vals, const uint32_t *slot_map, double2 *c, uint32_t slots) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= slots) return;
-  const double v = (double)vals[(size_t)blockIdx.y * n_vals + i % n_vals];
+  const double v = (double)reinterpret_cast<const T *>(vals + (size_t)blockIdx.y * pitch)[i % n_vals];
   c += (size_t)blockIdx.y * 2 * slots;
   c[slot_map[i]] = make_double2(v, 0.0);
   c[slot_map[slots + i]] = make_double2(v, -0.0); // conjugate of a real value
@@ -147,12 +148,19 @@ k_enc_round_many(DevCtx cx, const double2 *c, uint32_t limbs, u64 *out) {
   }
 }
 
+// the forward (INVERSE: inverse) transform of n_polys polynomials d [n_polys][limbs][N] in place, under the chain primes
+// 0 .. limbs - 1
+template <bool INVERSE> static void rows_ntt(evah_ctx *c, u64 *d, uint32_t limbs, uint32_t n_polys) {
+  OpPlain::Params p{d, d, (size_t)limbs * c->N, (size_t)limbs * c->N, limbs, 0, 0, {}};
+  if (INVERSE) ntt_inverse<OpPlain>(c, p, n_polys * limbs);
+  else ntt_forward<OpPlain>(c, p, n_polys * limbs);
+}
+
 // ---- the small polynomials: the host's int8 draws, or drawn where they are used (sampled.hip.h)
 __global__ void __launch_bounds__(256)
-k_small_to_residues(DevCtx cx, const int8_t *small, uint32_t n_polys, uint32_t limbs, u64 *out) {
+k_small_to_residues(DevCtx cx, const int8_t *small, uint32_t limbs, u64 *out) {
   // out[p][i][n] = small[p][n] mod primes[i] (negative -> q - |v|)
   const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y, p = blockIdx.z;
-  (void)n_polys;
   const int v = small[(size_t)p * cx.N + n];
   const u64 q = cx.primes[cx.prime_of(i)].q;
   out[((size_t)p * limbs + i) * cx.N + n] = v < 0 ? q - (u64)(-v) : (u64)v;
@@ -160,9 +168,8 @@ k_small_to_residues(DevCtx cx, const int8_t *small, uint32_t n_polys, uint32_t l
 // NTT forms [n_polys][limbs][N] of n_polys small polynomials (int8 [n_polys][N] on the device) under the chain primes
 // 0 .. limbs - 1, on the calling queue: what the encryptions here and evah_keygen_switch (seeded.hip) make of their draws
 void small_to_ntt(evah_ctx *c, const u64 *small8, uint32_t n_polys, uint32_t limbs, u64 *out) {
-  EW_LAUNCH(k_small_to_residues, dim3(c->N / 256, limbs, n_polys), dim3(256), 0, c->stream, c->dev, reinterpret_cast<const int8_t *>(small8), n_polys, limbs, out);
-  OpPlain::Params fp{out, out, (size_t)limbs * c->N, (size_t)limbs * c->N, limbs, 0, 0, {}};
-  ntt_forward<OpPlain>(c, fp, n_polys * limbs);
+  EW_LAUNCH(k_small_to_residues, dim3(c->N / 256, limbs, n_polys), dim3(256), 0, c->stream, c->dev, reinterpret_cast<const int8_t *>(small8), limbs, out);
+  rows_ntt<false>(c, out, limbs, n_polys);
 }
 // Polynomials p0 .. p0 + n_polys - 1 of instance inst = blockIdx.y / n_polys from its randomness key rkeys[inst][8],
 // straight into residues out [batch][n_polys][limbs][N] under the chain primes 0 .. limbs - 1, k_small_to_residues'
@@ -211,8 +218,7 @@ void sample_to_ntt(evah_ctx *c, uint32_t batch, const uint8_t *rkeys, u64 *keys,
   HIPCHK(hipMemcpyAsync(keys, rkeys, (size_t)32 * batch, hipMemcpyHostToDevice, c->stream));
   EW_LAUNCH(k_sample_small, dim3((c->N + SAMPLE_TILE - 1) / SAMPLE_TILE, batch * n_polys), dim3(SAMPLE_THREADS), 0, c->stream, c->dev,
             reinterpret_cast<const uint32_t *>(keys), n_polys, p0, limbs, out);
-  OpPlain::Params fp{out, out, (size_t)limbs * c->N, (size_t)limbs * c->N, limbs, 0, 0, {}};
-  ntt_forward<OpPlain>(c, fp, batch * n_polys * limbs);
+  rows_ntt<false>(c, out, limbs, batch * n_polys);
 }
 
 // ---- the encryptors' kernels
@@ -389,22 +395,18 @@ static std::vector<u64> crt_tab_build(const evah_ctx *c, uint32_t l) {
   for (size_t t = 0; t < w.size() && t < l; t++) half[t] = (w[t] >> 1) | (t + 1 < w.size() ? w[t + 1] << 63 : 0);
   return tab;
 }
-// the tables of level l on the device, built once per context family (freed with it)
-static CrtTab crt_tab_cached(evah_ctx *c, uint32_t l) {
-  auto it = c->sh->crt_tabs.find(l);
-  if (it == c->sh->crt_tabs.end()) {
-    const std::vector<u64> tab = crt_tab_build(c, l);
-    u64 *d = nullptr;
-    HIPCHK(hipMalloc(&d, sizeof(u64) * tab.size()));
-    try {
-      h2d_now(c, d, tab.data(), sizeof(u64) * tab.size());
-    } catch (...) {
-      (void)hipFree(d);
-      throw;
-    }
-    it = c->sh->crt_tabs.emplace(l, d).first;
+// the table `key` of one of the device state's maps, built by build() and uploaded at its first use (freed with the
+// context family)
+template <class Build> static const u64 *tab_cached(evah_ctx *c, std::map<uint32_t, u64 *> &tabs, uint32_t key, Build build) {
+  auto it = tabs.find(key);
+  if (it == tabs.end()) {
+    const std::vector<u64> tab = build();
+    it = tabs.emplace(key, dev_upload<u64>(c, tab.data(), sizeof(u64) * tab.size())).first;
   }
-  return crt_tab_at(it->second, l);
+  return it->second;
+}
+static CrtTab crt_tab_cached(evah_ctx *c, uint32_t l) {
+  return crt_tab_at(tab_cached(c, c->sh->crt_tabs, l, [&] { return crt_tab_build(c, l); }), l);
 }
 // forward roots zeta^br(j) of the decoder's special FFT (hostmath.h), once per context family
 static void dec_tables(evah_ctx *c) {
@@ -413,18 +415,29 @@ static void dec_tables(evah_ctx *c) {
   const CkksRoots cr = ckks_roots(N);
   std::vector<double> roots(2 * (size_t)N);
   for (uint32_t j = 0; j < N; j++) { roots[2 * j] = cr.fwd[j].real(); roots[2 * j + 1] = cr.fwd[j].imag(); }
-  HIPCHK(hipMalloc(&c->sh->dec_roots, sizeof(double2) * N));
-  h2d_now(c, c->sh->dec_roots, roots.data(), sizeof(double2) * N);
+  c->sh->dec_roots = dev_upload<double2>(c, roots.data(), sizeof(double2) * N);
 }
 
-__device__ __forceinline__ void garner(const DevCtx &cx, const CrtTab &t, uint32_t l, const u64 *r, u64 *v) {
-  for (uint32_t i = 0; i < l; i++) {
-    const DevPrime pm = cx.primes[i];
-    u128_t acc = {0, 0};
-    for (uint32_t j = 0; j < i; j++) acc128(acc, v[j] >= pm.q ? barrett64(v[j], pm.q, pm.brt) : v[j], t.pre_mod[i * l + j]);
-    const u64 a = barrett128(acc, pm);
-    v[i] = i ? mulmod(submod(r[i], a, pm.q), t.inv_prefix[i], pm) : r[0];
-  }
+// Garner's mixed-radix digits v[0 .. l-1] of the residues r of a level-l value, l >= 1: U = sum_i v_i q_0..q_{i-1}.
+// LB bounds l.  Up to 16 the loop over the digits is unrolled with the bound as its trip count and the level as a
+// uniform predicate, so r[] and v[] are indexed by constants and stay in registers; LB = 62 keeps a loop of l trips over
+// arrays that live in scratch memory.  v[i] is not written from l on: its readers carry the same predicate.
+// (The shape is the one the register gate of DESIGN.md 1.12 passed: zeroing v[i] inside the loop, or an unroll pragma
+// on the inner loop, costs up to 12 VGPRs in the unrolled forms.)
+template <int LB> __device__ __forceinline__ void garner(const DevCtx &cx, const CrtTab &t, uint32_t l, const u64 *r, u64 *v) {
+  constexpr bool FLAT = LB <= 16;
+  constexpr int UNR = FLAT ? LB : 1;
+  const int trips = FLAT ? LB : (int)l;
+  v[0] = r[0];
+#pragma unroll UNR
+  for (int i = 1; i < trips; i++)
+    if (!FLAT || i < (int)l) {
+      const DevPrime pm = cx.primes[i];
+      const u64 *pre = t.pre_mod + i * l;
+      u128_t acc = {0, 0};
+      for (int j = 0; j < i; j++) acc128(acc, v[j] >= pm.q ? barrett64(v[j], pm.q, pm.brt) : v[j], pre[j]);
+      v[i] = mulmod(submod(r[i], barrett128(acc, pm), pm.q), t.inv_prefix[i], pm);
+    }
 }
 // SEAL 3.6 CKKSEncoder::decode_internal between the inverse NTTs and the FFT: the composed coefficient
 // x in [0, Q) as l base-2^64 words (here from the mixed-radix digits: x = sum_i v_i q_0..q_{i-1}, exact),
@@ -436,7 +449,7 @@ __device__ __forceinline__ double crt_to_double(const DevCtx &cx, const CrtTab &
 #pragma clang fp contract(off)
   u64 r[62], v[62], x[63];
   for (uint32_t i = 0; i < l; i++) r[i] = coeff[(size_t)i * cx.N + n];
-  garner(cx, t, l, r, v);
+  garner<62>(cx, t, l, r, v);
   for (uint32_t w = 0; w <= l; w++) x[w] = 0;
   for (uint32_t i = 0; i < l; i++) { // x += v_i * prefix_i (prefix_i has at most i words; the sum stays below Q)
     u64 carry = 0;
@@ -489,9 +502,9 @@ struct LiftTab {
 // rho = (M + 2^(t-1)) mod 2^t from M mod 2^64 = sum_i v_i (q_0..q_{i-1} mod 2^64) - [neg] (Q_l mod 2^64), wrapping.
 // Then M' = (M + 2^(t-1) - rho) / 2^t exactly, i.e. (M_j + (2^(t-1) - rho)) (2^t)^-1 mod q_j: rescale's exact division
 // with 2^t in place of a prime.  No multi-word integer is formed.
-// LB bounds l.  Up to 16 every loop over the digits is unrolled with the bound as its trip count and the level as a
-// uniform predicate, so r[] and v[] are indexed by constants and stay in registers; the LB = 62 form keeps the loops and
-// the arrays go to scratch memory, as crt_to_double's do.
+// LB bounds l, with garner()'s unrolling rule for every loop over the digits here: up to 16, r[] and v[] are indexed by
+// constants and stay in registers; the LB = 62 form keeps the loops and the arrays go to scratch memory, as
+// crt_to_double's do.
 template <int LB>
 __global__ void __launch_bounds__(256)
 k_refresh_lift(DevCtx cx, CrtTab g, LiftTab t, uint32_t l, uint32_t L, uint32_t sh, const u64 *coeff, u64 *out) {
@@ -502,17 +515,7 @@ k_refresh_lift(DevCtx cx, CrtTab g, LiftTab t, uint32_t l, uint32_t L, uint32_t 
   u64 r[LB], v[LB];
 #pragma unroll UNR
   for (int i = 0; i < LB; i++) r[i] = i < (int)l ? coeff[(size_t)i * cx.N] : 0;
-#pragma unroll UNR
-  for (int i = 0; i < LB; i++) { // garner(), with constant indices
-    v[i] = 0;
-    if (i < (int)l) {
-      const DevPrime pm = cx.primes[i];
-      u128_t acc = {0, 0};
-#pragma unroll UNR
-      for (int j = 0; j < i; j++) acc128(acc, v[j] >= pm.q ? barrett64(v[j], pm.q, pm.brt) : v[j], g.pre_mod[i * l + j]);
-      v[i] = i ? mulmod(submod(r[i], barrett128(acc, pm), pm.q), g.inv_prefix[i], pm) : r[0];
-    }
-  }
+  garner<LB>(cx, g, l, r, v);
   bool neg = false, decided = false; // U > floor(Q_l / 2): mixed radix is positional, the first differing digit from the top decides
 #pragma unroll UNR
   for (int i = LB - 1; i >= 0; i--)
@@ -552,16 +555,24 @@ k_refresh_lift(DevCtx cx, CrtTab g, LiftTab t, uint32_t l, uint32_t L, uint32_t 
   }
 }
 
-// T = double, or float: the double rounded to nearest-even here, so that half the bytes cross to the host
+// the slot value as the row's type: double as it is; float = the double rounded to nearest-even here, so that half the
+// bytes cross to the host; uint8_t = the nearest integer, ties to even, clamped to [0, 255], NaN -> 0
+// (np.clip(np.rint(np.nan_to_num(d, nan=0)), 0, 255))
+template <class T> __device__ __forceinline__ T dec_value(double x) { return (T)x; }
+template <> __device__ __forceinline__ uint8_t dec_value<uint8_t>(double x) {
+  const double r = rint(x);
+  return r != r ? (uint8_t)0 : (uint8_t)fmin(fmax(r, 0.0), 255.0);
+}
+// the first n_out slot values of instance blockIdx.y into row blockIdx.y of out, at byte blockIdx.y * pitch (DESIGN.md
+// 1.6): the call's scratch at the tight pitch sizeof(T) * n_out, or the caller's device memory at its own
 template <class T>
 __global__ void __launch_bounds__(256)
-k_dec_gather(const double2 *c, const uint32_t *slot_map, uint32_t n_out, uint32_t N, T *out) {
+k_dec_gather_rows(const double2 *c, const uint32_t *slot_map, uint32_t n_out, uint32_t N, unsigned char *out, size_t pitch) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n_out) out[(size_t)blockIdx.y * n_out + i] = (T)c[(size_t)blockIdx.y * N + slot_map[i]].x;
+  if (i < n_out) reinterpret_cast<T *>(out + (size_t)blockIdx.y * pitch)[i] = dec_value<T>(c[(size_t)blockIdx.y * N + slot_map[i]].x);
 }
 
-// ---- the kernels of the device-array calls: rows that live in the caller's device memory, row b at
-// byte b * pitch of the base (a torch slice t[:, :n] is pitched; a uint8_t row may start at any byte)
+// ---- the device-array calls' own kernel: rows in the caller's device memory, row b at byte b * pitch
 // what check_encodable adds up, where the rows are: sums[b] = sum_i |rows[b][i]| as doubles (every T converts exactly).
 // One workgroup per row, thread t adds the elements t, t + 256, ... in that order, then a fixed tree through LDS: no
 // atomics, so a row gives the same sum on every run.  A NaN or an infinity in the row makes its sum non-finite.
@@ -581,31 +592,6 @@ k_rows_abs_sum(const unsigned char *rows, size_t pitch, uint32_t n_values, doubl
     __syncthreads();
   }
   if (!tid) sums[blockIdx.x] = part[0];
-}
-// k_enc_scatter_many with a row pitch in bytes; one scalar load per thread, as there
-template <class T>
-__global__ void __launch_bounds__(256)
-k_enc_scatter_rows(const unsigned char *vals, size_t pitch, uint32_t n_vals, const uint32_t *slot_map, double2 *c, uint32_t slots) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= slots) return;
-  const double v = (double)reinterpret_cast<const T *>(vals + (size_t)blockIdx.y * pitch)[i % n_vals];
-  c += (size_t)blockIdx.y * 2 * slots;
-  c[slot_map[i]] = make_double2(v, 0.0);
-  c[slot_map[slots + i]] = make_double2(v, -0.0); // conjugate of a real value
-}
-// the slot value as the row's type: double and float as k_dec_gather casts them; uint8_t = the nearest integer, ties to
-// even, clamped to [0, 255], NaN -> 0 (np.clip(np.rint(np.nan_to_num(d, nan=0)), 0, 255))
-template <class T> __device__ __forceinline__ T dec_value(double x) { return (T)x; }
-template <> __device__ __forceinline__ uint8_t dec_value<uint8_t>(double x) {
-  const double r = rint(x);
-  return r != r ? (uint8_t)0 : (uint8_t)fmin(fmax(r, 0.0), 255.0);
-}
-// k_dec_gather with a destination pitch in bytes (rows in the caller's device memory, or the call's scratch)
-template <class T>
-__global__ void __launch_bounds__(256)
-k_dec_gather_rows(const double2 *c, const uint32_t *slot_map, uint32_t n_out, uint32_t N, unsigned char *out, size_t pitch) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n_out) reinterpret_cast<T *>(out + (size_t)blockIdx.y * pitch)[i] = dec_value<T>(c[(size_t)blockIdx.y * N + slot_map[i]].x);
 }
 
 // ---- one body per operation: no argument checks inside, every entry point below makes its own
@@ -683,20 +669,27 @@ static evah_ct *encrypt_symmetric(evah_ctx *c, uint32_t batch, uint32_t l, doubl
 
 // bytes per value of a value type of the array calls (EVAH_F64 / EVAH_F32 / EVAH_U8); 0: not a type
 static size_t dtype_size(int dtype) { return dtype == EVAH_F64 ? 8 : dtype == EVAH_F32 ? 4 : dtype == EVAH_U8 ? 1 : 0; }
+static const char *const VALUE_DTYPE_MSG = "unknown value dtype (EVAH_F64, EVAH_F32 or EVAH_U8)";
+// f(T{}) with T = the C++ type of a value type: the one place that maps a dtype to code.  Not a type: VALUE_DTYPE_MSG —
+// what encode_many_checks answers; every other site comes behind a dtype check of its entry point.
+template <class F> static void with_value_type(int dtype, F f) {
+  if (dtype == EVAH_F64) f(double{});
+  else if (dtype == EVAH_F32) f(float{});
+  else if (dtype == EVAH_U8) f(uint8_t{});
+  else throw std::invalid_argument(VALUE_DTYPE_MSG);
+}
+
+// host -> device bytes of a client call: the values, its randomness or keys and (symmetric) the seeds
+static void count_client_h2d(evah_ctx *c, size_t bytes) { c->sh->xfer[4] += bytes; }
 
 // SEAL Decryptor::decrypt + CKKSEncoder::decode of the n instances that n_handles handles of one size, limb count and
 // scale hold together (a single ciphertext is one instance; instance j of a batched handle is d + j * size * ps), read in
-// place: the first n_out slot values of each into out [n][n_out] (host) as double (EVAH_F64) or float (EVAH_F32), rows
-// in list order, then instance order.
-// rows (evah_decrypt_decode_rows): `out` has a row pitch in bytes, may be device memory — the gather then
-// writes the caller's rows and nothing crosses to the host — and dtype_out may be EVAH_U8; wait = false (device rows
-// only) leaves the call in queue order.
-struct RowsDst { size_t pitch; bool on_device, wait; };
-template <class T>
-static void dec_gather_rows(evah_ctx *c, const double2 *cd, uint32_t n, uint32_t n_out, void *out, size_t pitch) {
-  EW_LAUNCH(k_dec_gather_rows<T>, dim3((n_out + 255) / 256, n), dim3(256), 0, c->stream, cd, c->sh->enc_slot_map, n_out, c->N,
-            static_cast<unsigned char *>(out), pitch);
-}
+// place: the first n_out slot values of each into the rows of `out` as dtype_out, rows in list order, then instance order.
+// RowsDst says where the rows are: pitch bytes apart, on the host — the gather writes the call's scratch at the tight
+// pitch and a copy follows — or in device memory (evah_decrypt_decode_rows) — the gather writes the
+// caller's rows and nothing crosses to the host; wait = false (device rows only) leaves the call in queue order.
+// counted: the rows calls add what they bring to the host to the transfer statistics, the handle calls do not.
+struct RowsDst { size_t pitch; bool on_device, wait, counted; };
 // the instances of a call's handles, acquired, in list order, then instance order
 static DotTab dot_tab_of(evah_ctx *c, const evah_ct *const *cts, uint32_t n_handles) {
   DotTab tab{};
@@ -713,22 +706,21 @@ static DotTab dot_tab_of(evah_ctx *c, const evah_ct *const *cts, uint32_t n_hand
 // transforms (decrypt_decode and refresh)
 static void decrypt_to_coeff(evah_ctx *c, const DotTab &tab, uint32_t size, uint32_t l, uint32_t n, u64 *m) {
   EW_LAUNCH(k_decrypt_dot, dim3(c->N / 256, l, n), dim3(256), 0, c->stream, c->dev, tab, size, l, c->sh->sk.d, m);
-  OpPlain::Params ip{m, m, (size_t)l * c->N, (size_t)l * c->N, l, 0, 0, {}};
-  ntt_inverse<OpPlain>(c, ip, n * l);
+  rows_ntt<true>(c, m, l, n);
 }
 // The decoder behind the messages: front(m) puts the n messages [n][l][N] of scale `scale` on the queue in coefficient
 // form — the decryptor's dot product and inverse transforms (decrypt_decode), or the sum of decryption shares
 // (decrypt_combine) —, everything behind it is one body: Garner, the FFT, the gather in the row's type,
 // the copy, the wipes and the statistics.
 template <class Front>
-static void decode_messages(evah_ctx *c, uint32_t l, double scale, uint32_t n, uint32_t n_out, int dtype_out, void *out, const RowsDst *rows,
+static void decode_messages(evah_ctx *c, uint32_t l, double scale, uint32_t n, uint32_t n_out, int dtype_out, void *out, const RowsDst &rows,
                             Front front) {
   const uint32_t N = c->N;
   enc_tables(c);
   dec_tables(c);
   const CrtTab t = crt_tab_cached(c, l);
   const size_t B = n, row_bytes = dtype_size(dtype_out) * n_out, out_bytes = row_bytes * B;
-  const bool to_dev = rows && rows->on_device;
+  const bool to_dev = rows.on_device;
   Scratch m(c, B * l * N), cbuf(c, B * 2 * N), outd(c, to_dev ? 1 : (out_bytes + 7) / 8);
   {
     // the decrypted messages, their FP images and the slot values do not stay behind in pool memory the next call reuses
@@ -738,34 +730,30 @@ static void decode_messages(evah_ctx *c, uint32_t l, double scale, uint32_t n, u
     EW_LAUNCH(k_crt_to_double, dim3(N / 256, n), dim3(256), 0, c->stream, c->dev, t, l, m.d, 1.0 / scale, cd);
     HIPCHK(hipGetLastError());
     fft_batched<false>(c, cd, c->sh->dec_roots, n, make_double2(0.0, 0.0), 0.0);
-    if (rows) { // the caller's rows, or (host rows) the scratch at its own pitch
-      void *dst = to_dev ? out : outd.d;
-      const size_t pitch = to_dev ? rows->pitch : row_bytes;
-      if (dtype_out == EVAH_F32) dec_gather_rows<float>(c, cd, n, n_out, dst, pitch);
-      else if (dtype_out == EVAH_U8) dec_gather_rows<uint8_t>(c, cd, n, n_out, dst, pitch);
-      else dec_gather_rows<double>(c, cd, n, n_out, dst, pitch);
-    } else if (dtype_out == EVAH_F32)
-      EW_LAUNCH(k_dec_gather<float>, dim3((n_out + 255) / 256, n), dim3(256), 0, c->stream, cd, c->sh->enc_slot_map, n_out, N,
-                reinterpret_cast<float *>(outd.d));
-    else
-      EW_LAUNCH(k_dec_gather<double>, dim3((n_out + 255) / 256, n), dim3(256), 0, c->stream, cd, c->sh->enc_slot_map, n_out, N,
-                reinterpret_cast<double *>(outd.d));
+    // the one difference between the destinations: the caller's rows, or the scratch at the tight pitch and a copy
+    unsigned char *dst = static_cast<unsigned char *>(to_dev ? out : (void *)outd.d);
+    const size_t pitch = to_dev ? rows.pitch : row_bytes;
+    with_value_type(dtype_out, [&](auto tag) {
+      EW_LAUNCH(k_dec_gather_rows<decltype(tag)>, dim3((n_out + 255) / 256, n), dim3(256), 0, c->stream, cd, c->sh->enc_slot_map, n_out, N, dst, pitch);
+    });
     HIPCHK(hipGetLastError());
-    if (rows && !to_dev && rows->pitch != row_bytes)
-      HIPCHK(hipMemcpy2DAsync(out, rows->pitch, outd.d, row_bytes, row_bytes, B, hipMemcpyDeviceToHost, c->stream));
+    if (!to_dev && rows.pitch != row_bytes)
+      HIPCHK(hipMemcpy2DAsync(out, rows.pitch, outd.d, row_bytes, row_bytes, B, hipMemcpyDeviceToHost, c->stream));
     else if (!to_dev)
       HIPCHK(hipMemcpyAsync(out, outd.d, out_bytes, hipMemcpyDeviceToHost, c->stream));
     w_m.now();
     w_c.now();
     w_o.now();
   }
-  if (!to_dev || rows->wait) HIPCHK(hipStreamSynchronize(c->stream));
-  if (rows && !to_dev) c->sh->xfer[5] += out_bytes; // evah_decrypt_decode_rows counts what it brings to the host: device rows, nothing
+  if (!to_dev || rows.wait) HIPCHK(hipStreamSynchronize(c->stream));
+  if (rows.counted && !to_dev) c->sh->xfer[5] += out_bytes; // device rows: nothing comes to the host
 }
+// rows = nullptr: out [n][n_out] on the host (the calls that take no pitch)
 static void decrypt_decode(evah_ctx *c, const evah_ct *const *cts, uint32_t n_handles, uint32_t n, uint32_t n_out, int dtype_out, void *out,
                            const RowsDst *rows = nullptr) {
   const uint32_t l = cts[0]->limbs;
-  decode_messages(c, l, cts[0]->scale, n, n_out, dtype_out, out, rows, [&](u64 *m) {
+  const RowsDst tight{dtype_size(dtype_out) * n_out, false, true, false};
+  decode_messages(c, l, cts[0]->scale, n, n_out, dtype_out, out, rows ? *rows : tight, [&](u64 *m) {
     const DotTab tab = dot_tab_of(c, cts, n_handles);
     decrypt_to_coeff(c, tab, cts[0]->size, l, n, m);
   });
@@ -787,7 +775,7 @@ static bool flood_exceeds_modulus(const evah_ctx *c, uint32_t l, uint32_t partie
 // k_decrypt_share, the wipe of the keys, one drain — their number does not depend on n.
 static evah_ct *decrypt_share(evah_ctx *c, const evah_ct *const *cts, uint32_t n_handles, uint32_t n, uint32_t sigma, const uint8_t *fkeys) {
   const uint32_t l = cts[0]->limbs;
-  const size_t N = c->N, B = n;
+  const size_t B = n;
   const DotTab tab = dot_tab_of(c, cts, n_handles);
   Scratch keys(c, 4 * B);
   evah_ct *o = ct_new(c, 1, l, cts[0]->scale, n);
@@ -797,8 +785,7 @@ static evah_ct *decrypt_share(evah_ctx *c, const evah_ct *const *cts, uint32_t n
     EW_LAUNCH(k_sample_flood, dim3((c->N + FLOOD_TILE - 1) / FLOOD_TILE, n), dim3(FLOOD_THREADS), 0, c->stream, c->dev,
               reinterpret_cast<const uint32_t *>(keys.d), sigma, l, o->d);
     HIPCHK(hipGetLastError());
-    OpPlain::Params fp{o->d, o->d, (size_t)l * N, (size_t)l * N, l, 0, 0, {}};
-    ntt_forward<OpPlain>(c, fp, n * l);
+    rows_ntt<false>(c, o->d, l, n);
     EW_LAUNCH(k_decrypt_share, dim3(c->N / 512, l, n), dim3(256), 0, c->stream, c->dev, tab, l, c->sh->sk.d, o->d);
     HIPCHK(hipGetLastError());
     w_keys.now();
@@ -808,7 +795,7 @@ static evah_ct *decrypt_share(evah_ctx *c, const evah_ct *const *cts, uint32_t n
     evah_ct_free(c, o);
     throw;
   }
-  c->sh->xfer[4] += 32 * B; // the keys: what the call sends up
+  count_client_h2d(c, 32 * B); // the keys: what the call sends up
   return o;
 }
 // evah_decrypt_combine_rows: decode_messages behind m = c0 + sum_p h_p.  The P n share pointers cross in one copy on the
@@ -819,7 +806,7 @@ static void decrypt_combine(evah_ctx *c, const evah_ct *const *cts, uint32_t n_h
   const uint32_t l = cts[0]->limbs;
   std::vector<const u64 *> ptrs((size_t)n_parties * n);
   Scratch pd(c, ptrs.size());
-  decode_messages(c, l, cts[0]->scale, n, n_out, dtype_out, out, rows, [&](u64 *m) {
+  decode_messages(c, l, cts[0]->scale, n, n_out, dtype_out, out, *rows, [&](u64 *m) {
     const DotTab tab = dot_tab_of(c, cts, n_handles);
     for (uint32_t p = 0; p < n_parties; p++) {
       acquire(c, shares[p]->buf);
@@ -829,8 +816,7 @@ static void decrypt_combine(evah_ctx *c, const evah_ct *const *cts, uint32_t n_h
     EW_LAUNCH(k_combine_shares, dim3(c->N / 512, l, n), dim3(256), 0, c->stream, c->dev, tab, reinterpret_cast<const u64 *const *>(pd.d), n_parties, l,
               m);
     HIPCHK(hipGetLastError());
-    OpPlain::Params ip{m, m, (size_t)l * c->N, (size_t)l * c->N, l, 0, 0, {}};
-    ntt_inverse<OpPlain>(c, ip, n * l);
+    rows_ntt<true>(c, m, l, n);
   });
 }
 
@@ -851,10 +837,7 @@ static void encode_many_checks(evah_ctx *c, uint32_t batch, const void *values, 
   encode_shape_checks(c, batch, values, n_values, limbs, out);
   // evah_pt_encode's: "encoded values are too large", on the values in the type they came in (the verdict on their
   // float64 image: the conversion is exact, and a float NaN or infinity is a double NaN or infinity)
-  if (dtype == EVAH_F64) check_encodable(c, static_cast<const double *>(values), batch, n_values, scale);
-  else if (dtype == EVAH_F32) check_encodable(c, static_cast<const float *>(values), batch, n_values, scale);
-  else if (dtype == EVAH_U8) check_encodable(c, static_cast<const uint8_t *>(values), batch, n_values, scale);
-  else throw std::invalid_argument("unknown value dtype (EVAH_F64, EVAH_F32 or EVAH_U8)");
+  with_value_type(dtype, [&](auto tag) { check_encodable(c, static_cast<const decltype(tag) *>(values), batch, n_values, scale); });
 }
 // values [batch][n_values] of `dtype` (host) -> NTT-form plaintexts pt [batch][limbs][N] on the queue; vals, cbuf: the
 // call's scratch.  The values cross in their own type and become doubles in the scatter.
@@ -867,40 +850,25 @@ struct DevSrc {
   bool host_wait = false; // set by release(): no producer stream to hand back to, the call waits for dev_out on the host
   void release(evah_ctx *c);
 };
-template <class T>
-static void enc_scatter_rows(evah_ctx *c, uint32_t batch, const void *values, size_t pitch, uint32_t n_values, double2 *cd) {
-  const uint32_t slots = c->N >> 1;
-  EW_LAUNCH(k_enc_scatter_rows<T>, dim3((slots + 255) / 256, batch), dim3(256), 0, c->stream, static_cast<const unsigned char *>(values), pitch,
-            n_values, c->sh->enc_slot_map, cd, slots);
-}
 static void encode_many(evah_ctx *c, uint32_t batch, const void *values, int dtype, uint32_t n_values, uint32_t limbs, double scale, u64 *vals,
                         double2 *cd, u64 *pt, DevSrc *dev = nullptr) {
   const uint32_t N = c->N, slots = N >> 1;
   enc_tables(c);
-  if (!dev) HIPCHK(hipMemcpyAsync(vals, values, dtype_size(dtype) * (size_t)batch * n_values, hipMemcpyHostToDevice, c->stream));
-  const dim3 grid((slots + 255) / 256, batch);
-  if (dev) {
-    if (dtype == EVAH_F32) enc_scatter_rows<float>(c, batch, values, dev->pitch, n_values, cd);
-    else if (dtype == EVAH_U8) enc_scatter_rows<uint8_t>(c, batch, values, dev->pitch, n_values, cd);
-    else enc_scatter_rows<double>(c, batch, values, dev->pitch, n_values, cd);
-    HIPCHK(hipGetLastError());
-    dev->release(c);
-  } else if (dtype == EVAH_F32)
-    EW_LAUNCH(k_enc_scatter_many<float>, grid, dim3(256), 0, c->stream, reinterpret_cast<const float *>(vals), n_values, c->sh->enc_slot_map, cd, slots);
-  else if (dtype == EVAH_U8)
-    EW_LAUNCH(k_enc_scatter_many<uint8_t>, grid, dim3(256), 0, c->stream, reinterpret_cast<const uint8_t *>(vals), n_values, c->sh->enc_slot_map, cd, slots);
-  else
-    EW_LAUNCH(k_enc_scatter_many<double>, grid, dim3(256), 0, c->stream, reinterpret_cast<const double *>(vals), n_values, c->sh->enc_slot_map, cd, slots);
+  // the one difference between the sources: a host array is copied first and read at the tight pitch
+  const size_t pitch = dev ? dev->pitch : dtype_size(dtype) * n_values;
+  if (!dev) HIPCHK(hipMemcpyAsync(vals, values, pitch * batch, hipMemcpyHostToDevice, c->stream));
+  const unsigned char *src = static_cast<const unsigned char *>(dev ? values : vals);
+  with_value_type(dtype, [&](auto tag) {
+    EW_LAUNCH(k_enc_scatter_rows<decltype(tag)>, dim3((slots + 255) / 256, batch), dim3(256), 0, c->stream, src, pitch, n_values, c->sh->enc_slot_map, cd, slots);
+  });
+  HIPCHK(hipGetLastError());
+  if (dev) dev->release(c);
   const double fix = scale / (double)N;
   fft_batched<true>(c, cd, c->sh->enc_roots, batch, make_double2(c->sh->enc_last_root[0] * fix, c->sh->enc_last_root[1] * fix), fix);
   EW_LAUNCH(k_enc_round_many, dim3((N + 255) / 256, batch), dim3(256), 0, c->stream, c->dev, cd, limbs, pt);
   HIPCHK(hipGetLastError());
-  OpPlain::Params p{pt, pt, (size_t)limbs * N, (size_t)limbs * N, limbs, 0, 0, {}};
-  ntt_forward<OpPlain>(c, p, batch * limbs);
+  rows_ntt<false>(c, pt, limbs, batch);
 }
-// host -> device bytes of a batched encryption call: the values, its randomness and (symmetric) the seeds
-static void count_client_h2d(evah_ctx *c, size_t bytes) { c->sh->xfer[4] += bytes; }
-
 // evah_encode_encrypt_many (small: the host's draws), evah_encode_encrypt_sampled_many (rkeys: drawn here) and
 // evah_encode_encrypt_array (rkeys, values of `dtype`)
 static void encode_encrypt_many(evah_ctx *c, uint32_t batch, const void *values, int dtype, uint32_t n_values, uint32_t limbs, double scale,
@@ -1019,16 +987,12 @@ static void check_rows_shape(evah_ctx *c, const void *p, int dtype, const char *
   if ((uintptr_t)p % item) throw std::invalid_argument(what + " is not aligned to its item size");
   if (on_device) check_device_rows(c, p, (n_rows - 1) * pitch + item * n_cols, what);
 }
-static const char *const VALUE_DTYPE_MSG = "unknown value dtype (EVAH_F64, EVAH_F32 or EVAH_U8)";
-
 // sums[b] = k_rows_abs_sum of row b, brought to the host: one launch, one copy of 8 * rows bytes, one wait
 static void rows_abs_sum(evah_ctx *c, uint32_t rows, const void *values, int dtype, size_t pitch, uint32_t n_values, double *sums) {
   Scratch sd(c, rows);
   const unsigned char *v = static_cast<const unsigned char *>(values);
   double *d = reinterpret_cast<double *>(sd.d);
-  if (dtype == EVAH_F32) EW_LAUNCH(k_rows_abs_sum<float>, dim3(rows), dim3(256), 0, c->stream, v, pitch, n_values, d);
-  else if (dtype == EVAH_U8) EW_LAUNCH(k_rows_abs_sum<uint8_t>, dim3(rows), dim3(256), 0, c->stream, v, pitch, n_values, d);
-  else EW_LAUNCH(k_rows_abs_sum<double>, dim3(rows), dim3(256), 0, c->stream, v, pitch, n_values, d);
+  with_value_type(dtype, [&](auto tag) { EW_LAUNCH(k_rows_abs_sum<decltype(tag)>, dim3(rows), dim3(256), 0, c->stream, v, pitch, n_values, d); });
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(sums, d, sizeof(double) * rows, hipMemcpyDeviceToHost, c->stream);
   const hipError_t s = hipStreamSynchronize(c->stream); // also on an error: the scratch returns to the pool behind the launch
@@ -1118,22 +1082,8 @@ static void encode_encrypt_dev(evah_ctx *c, bool symmetric, uint32_t batch, cons
 // ---- the refresh
 // the lift table of (l, L, t) on the device, built once per context family (freed with it)
 static LiftTab lift_tab_cached(evah_ctx *c, uint32_t l, uint32_t L, uint32_t t) {
-  const uint32_t key = l | L << 8 | t << 16;
-  auto it = c->sh->lift_tabs.find(key);
-  if (it == c->sh->lift_tabs.end()) {
-    const std::vector<u64> tab = lift_table_build(c->primes, l, L, t);
-    u64 *d = nullptr;
-    HIPCHK(hipMalloc(&d, sizeof(u64) * tab.size()));
-    try {
-      h2d_now(c, d, tab.data(), sizeof(u64) * tab.size());
-    } catch (...) {
-      (void)hipFree(d);
-      throw;
-    }
-    it = c->sh->lift_tabs.emplace(key, d).first;
-  }
+  const u64 *d = tab_cached(c, c->sh->lift_tabs, l | L << 8 | t << 16, [&] { return lift_table_build(c->primes, l, L, t); });
   const LiftLayout at{l, L};
-  const u64 *d = it->second;
   // (Q_l mod 2^64 travels as an argument: wrapping products of the chain primes, as the builder forms them)
   u64 qw = 1;
   for (uint32_t i = 0; i < l; i++) qw *= c->primes[i];
@@ -1168,8 +1118,7 @@ static evah_ct *refresh(evah_ctx *c, const evah_ct *const *cts, uint32_t n_handl
     else launch_refresh_lift<62>(c, g, t, l, L, sh, n, m.d, mo.d);
     HIPCHK(hipGetLastError());
     w_m.now();
-    OpPlain::Params fp{mo.d, mo.d, (size_t)L * N, (size_t)L * N, L, 0, 0, {}};
-    ntt_forward<OpPlain>(c, fp, n * L);
+    rows_ntt<false>(c, mo.d, L, n);
     o = encrypt_symmetric(c, n, L, scale_out, mo.d, nullptr, ekeys, seeds, false);
     w_mo.now();
     HIPCHK(hipStreamSynchronize(c->stream)); // `ekeys` and `seeds` are pageable host memory
@@ -1205,17 +1154,17 @@ int evah_client_key_upload(evah_ctx *c, int kind, const uint64_t *data) {
   API_BEGIN
   use(c);
   if (kind != EVAH_KEY_PUBLIC && kind != EVAH_KEY_SECRET) throw std::invalid_argument("unknown key kind");
-  KeyDev kd;
-  kd.n_digits = 1;
-  kd.bytes = sizeof(u64) * (size_t)(kind == EVAH_KEY_PUBLIC ? 2 : 1) * c->k * c->N;
-  HIPCHK(hipMalloc(&kd.d, kd.bytes));
-  h2d_now(c, kd.d, data, kd.bytes);
+  KeyDev shape;
+  shape.n_digits = 1;
+  shape.bytes = sizeof(u64) * (size_t)(kind == EVAH_KEY_PUBLIC ? 2 : 1) * c->k * c->N;
+  KeyAlloc key(c, shape, false); // (no split copy: these are no key-switching keys) freed again if the upload fails
+  h2d_now(c, key.kd.d, data, key.kd.bytes);
   KeyDev &slot = kind == EVAH_KEY_PUBLIC ? c->sh->pk : c->sh->sk;
   if (slot.d) {
     if (kind == EVAH_KEY_SECRET) (void)hipMemset(slot.d, 0, slot.bytes); // no key material in freed HBM
     (void)hipFree(slot.d);
   }
-  slot = kd;
+  slot = key.release();
   API_END
 }
 
@@ -1408,7 +1357,7 @@ int evah_decrypt_decode_rows(evah_ctx *c, const evah_ct *const *cts, uint32_t n_
   if (!dtype_size(dtype_out)) throw std::invalid_argument("unknown output dtype (EVAH_F64, EVAH_F32 or EVAH_U8)");
   handles_checks_shape(c, cts, n_out);
   check_rows_shape(c, out, dtype_out, "unknown output dtype (EVAH_F64, EVAH_F32 or EVAH_U8)", n, n_out, row_pitch, out_on_device != 0, "out");
-  const RowsDst rows{row_pitch, out_on_device != 0, wait != 0};
+  const RowsDst rows{row_pitch, out_on_device != 0, wait != 0, true};
   decrypt_decode(c, cts, n_handles, n, n_out, dtype_out, out, &rows);
   API_END
 }
@@ -1453,7 +1402,7 @@ int evah_decrypt_combine_rows(evah_ctx *c, const evah_ct *const *cts, uint32_t n
   if (cts[0]->limbs > c->k - 1) throw std::invalid_argument("invalid limb count for this context");
   if (c->N % 512) throw std::invalid_argument("decryption needs N divisible by 512");
   check_rows_shape(c, out, dtype_out, "unknown output dtype (EVAH_F64, EVAH_F32 or EVAH_U8)", n, n_out, row_pitch, out_on_device != 0, "out");
-  const RowsDst rows{row_pitch, out_on_device != 0, wait != 0};
+  const RowsDst rows{row_pitch, out_on_device != 0, wait != 0, true};
   decrypt_combine(c, cts, n_handles, n, shares, n_parties, n_out, dtype_out, out, &rows);
   API_END
 }

@@ -444,12 +444,19 @@ void enc_tables(evah_ctx *c) {
     roots[2 * j] = cr.inv_seq[j].real();
     roots[2 * j + 1] = cr.inv_seq[j].imag();
   }
+  // both tables exist before either pointer is published: enc_roots is what the early exit above looks at
+  uint32_t *d_map = dev_upload<uint32_t>(c, map.data(), sizeof(uint32_t) * N);
+  double2 *d_roots = nullptr;
+  try {
+    d_roots = dev_upload<double2>(c, roots.data(), sizeof(double2) * N);
+  } catch (...) {
+    (void)hipFree(d_map);
+    throw;
+  }
+  c->sh->enc_slot_map = d_map;
   c->sh->enc_last_root[0] = cr.inv_seq[N - 1].real();
   c->sh->enc_last_root[1] = cr.inv_seq[N - 1].imag();
-  HIPCHK(hipMalloc(&c->sh->enc_slot_map, sizeof(uint32_t) * N));
-  HIPCHK(hipMalloc(&c->sh->enc_roots, sizeof(double2) * N));
-  h2d_now(c, c->sh->enc_slot_map, map.data(), sizeof(uint32_t) * N);
-  h2d_now(c, c->sh->enc_roots, roots.data(), sizeof(double2) * N);
+  c->sh->enc_roots = d_roots;
 }
 } // namespace evah
 extern "C" {

@@ -596,6 +596,20 @@ inline void h2d_now(evah_ctx *c, void *dst, const void *src, size_t bytes) {
   HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
 }
+// A device allocation of its own holding `bytes` of set-up data, complete when this returns (h2d_now).  An upload that
+// fails leaves nothing behind: the allocation is freed and the error goes on, so a pointer or a map entry of the device
+// state is assigned only from the return value, and the next call builds the table again.
+template <class T> inline T *dev_upload(evah_ctx *c, const void *src, size_t bytes) {
+  void *d = nullptr;
+  HIPCHK(hipMalloc(&d, bytes));
+  try {
+    h2d_now(c, d, src, bytes);
+  } catch (...) {
+    (void)hipFree(d);
+    throw;
+  }
+  return static_cast<T *>(d);
+}
 inline hipEvent_t sync_event(evah_ctx *c) {
   if (!c->capturing && !c->sync_events.empty()) {
     hipEvent_t e = c->sync_events.back();

@@ -46,9 +46,7 @@ const uint32_t *perm_table(evah_ctx *c, uint32_t elt) {
     u64 raw = (((u64)elt * reversed) >> 1) & (u64)(N - 1);
     tab[i] = bitrev((uint32_t)raw, c->logN);
   }
-  uint32_t *d = nullptr;
-  HIPCHK(hipMalloc(&d, sizeof(uint32_t) * N));
-  h2d_now(c, d, tab.data(), sizeof(uint32_t) * N);
+  uint32_t *d = dev_upload<uint32_t>(c, tab.data(), sizeof(uint32_t) * N);
   c->sh->perms.emplace(elt, d);
   return d;
 }
