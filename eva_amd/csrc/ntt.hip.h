@@ -106,6 +106,19 @@ template <bool SW> __device__ __forceinline__ u64 mad64w(uint32_t a, uint32_t b,
   if constexpr (SW) return mad64s(a, b, c);
   else return mad64(a, b, c);
 }
+// EVAH_KS_LOOP: ks_inner_kernel<MAC3>'s digit loop without what does not depend on the digit (ntt_ks_inner.hip.h):
+// sums that accumulate in place, the top-bit constant as a scalar factor, the epilogues' thread-id arithmetic computed
+// after the loop, and — slice B and the stored-product kernel at P = 8 — the first contiguous round's uniform twiddles
+// from scalar registers.  0 compiles every ks_inner_kernel to the instructions it had before (A/B switch of the build)
+#ifndef EVAH_KS_LOOP
+#define EVAH_KS_LOOP 1
+#endif
+// c += a * b, the sum updated in its own register pair (gfx950 takes a destination that IS the addend; the compiler
+// writes that form itself).  mad64's early-clobber result next to a separate addend gives a sum that is carried
+// across a loop a fresh pair each iteration and a v_mov_b64 back at the loop's end.
+__device__ __forceinline__ void mad64_acc(u64 &c, uint32_t a, uint32_t b) {
+  asm("v_mad_u64_u32 %0, vcc, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b) : "vcc");
+}
 // SM: so are the words of the modulus (a kernel that read its DevPrime with prime_uniform, below)
 template <bool SW = false, bool SM = false>
 __device__ __forceinline__ u64 mul_tw_lazy5_add_mad(u64 x, u64 w, u64 ws, u64 nq, u64 a) {
@@ -196,8 +209,9 @@ __device__ __forceinline__ void bfly_inv(u64 &X, u64 &Y, ulonglong2 w, u64 nq, u
 #ifndef EVAH_TW_SGPR
 #define EVAH_TW_SGPR 1 // 0: every round's twiddles from LDS (A/B switch of the build)
 #endif
-struct NoUTw {};
-template <int NU> struct UTw { ulonglong2 w[NU]; }; // w[k]: heap node k, 1 <= k < NU
+struct NoUTw { static constexpr int n = 0; };
+// w[k]: heap node k, 1 <= k < NU.  UTw<1> holds no twiddle: it only tells the rounds that the prime's words are uniform (SM)
+template <int NU> struct UTw { static constexpr int n = NU; ulonglong2 w[NU]; };
 template <class UT> struct IsUTw : std::false_type {};
 template <int NU> struct IsUTw<UTw<NU>> : std::bool_constant<EVAH_TW_SGPR != 0> {};
 // the uniform round's twiddles of a P-point strided pass at 2^LR coefficients per thread (NoUTw when the switch is off)
@@ -212,6 +226,24 @@ template <int NU> __device__ __forceinline__ void utw_load(UTw<NU> &ut, const ul
   for (int k = 1; k < NU; k++) {
     if (k < from) continue;
     const u64x2 v = p[k];
+    ut.w[k].x = v.x;
+    ut.w[k].y = v.y;
+  }
+}
+// The same for a contiguous pass on local heaps whose workgroup holds ONE sub-transform (ks_inner_kernel<MAC3> at
+// 2^P = 64 << LR): its first forward round and its last inverse round use local nodes 1 .. 2^RB - 1, and local node k at
+// depth d is node (root << d) + (k - 2^d) of the table, root = 2^pre + the sub-transform's index.  Read from the table,
+// not from the staged copy in LDS.
+template <class UT> __device__ __forceinline__ void utw_load_sub(UT &, const ulonglong2 *, uint32_t, uint32_t, uint32_t) {}
+template <int NU> __device__ __forceinline__ void utw_load_sub(UTw<NU> &ut, const ulonglong2 *table, uint32_t prime, uint32_t N, uint32_t root) {
+  typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+  typedef const __attribute__((address_space(4))) u64x2 *ConstTw;
+  const ConstTw p = (ConstTw)(table + (size_t)__builtin_amdgcn_readfirstlane(prime) * N);
+  const uint32_t r = __builtin_amdgcn_readfirstlane(root);
+#pragma unroll
+  for (int k = 1; k < NU; k++) {
+    const int d = 31 - __builtin_clz((unsigned)k);
+    const u64x2 v = p[((size_t)r << d) + (k - (1 << d))];
     ut.w[k].x = v.x;
     ut.w[k].y = v.y;
   }
@@ -286,8 +318,10 @@ __device__ __forceinline__ void ntt_round(u64 *sub_lds, int tid, uint32_t h, uin
   // -4.4 %, mod-down pass 1 -2.5 %); the contiguous passes (combine epilogue: +8 %), the one-wave
   // key-switch kernel (LR = 2: +1.5 %) and the inverse butterflies keep the compiler's form
   constexpr bool MAD = EVAH_MADLO && !INVERSE && STRIDED && LR == 3;
-  constexpr bool UNI = IsUTw<UT>::value && STRIDED && S0 == 0; // node == 1 for every thread: twiddle (1 << s) + v of ut
-  constexpr bool SM = IsUTw<UT>::value; // a pass that is given a UTw read pm with prime_uniform: scalar registers
+  constexpr bool UNI = IsUTw<UT>::value && STRIDED && S0 == 0 && UT::n >= NU; // node == 1 for every thread: twiddle (1 << s) + v of ut
+  // a pass that is given a UTw holds pm in scalar registers: read with prime_uniform, or (ks_inner_kernel) from the kernel
+  // argument's table above the kernel's first store, which the compiler turns into scalar loads as well
+  constexpr bool SM = IsUTw<UT>::value;
   u64 x[NTT_R];
 #pragma unroll
   for (int g = 0; g < G; g++) {

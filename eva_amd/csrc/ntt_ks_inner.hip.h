@@ -95,14 +95,29 @@ constexpr uint32_t MAC3_FOLD_DIGITS = 7;
 // for another prime (DevPrime (tb_c, tb_sh, tb_mask) = (0, 0, ~0))
 __device__ __forceinline__ u64 mac3_digit(u64 x, const DevPrime &pm) {
   const uint32_t hi = (uint32_t)(x >> 32);
-  return mad64(hi >> pm.tb_sh, pm.tb_c, ((u64)(hi & pm.tb_mask) << 32) | (uint32_t)x);
+  // (the constant is the workgroup's: it is named as the instruction's scalar source where it lies, not copied to a VGPR)
+  return mad64w<EVAH_KS_LOOP != 0>(hi >> pm.tb_sh, pm.tb_c, ((u64)(hi & pm.tb_mask) << 32) | (uint32_t)x);
 }
-// the four partial products of the digit (v0 + v1 2^30) and the split key word (kw = k0 | k1 << 32, k0, k1 < 2^30)
+// the four partial products of the digit (v0 + v1 2^30) and the split key word (kw = k0 | k1 << 32, k0, k1 < 2^30);
+// the sums live across the digit loop and are updated where they are: one v_mad_u64_u32 each whose destination is its
+// addend, no copy at the loop's end.  Three of the four are left to the compiler, which writes exactly that instruction
+// for `s += (u64)a * b` with a scalar carry sink; the second product into s1 is inline asm (mad64_acc), which keeps the
+// compiler from first adding the two cross products in a temporary pair (one more 64-bit add per coefficient and key
+// polynomial).  Why not all four as asm: asm statements that follow each other are kept apart by an s_nop (each clobbers
+// vcc), and alternating with the compiler's form halves the loop's s_nops at the same VALU count
+// (profiles/r12_ks_loop_notes.md).  The sum is the same 64-bit word in every form.
 __device__ __forceinline__ void mac3_acc(u64 &s0, u64 &s1, u64 &s2, uint32_t v0, uint32_t v1, u64 kw) {
+#if EVAH_KS_LOOP
+  s0 += (u64)v0 * (uint32_t)kw;
+  s1 += (u64)v0 * (uint32_t)(kw >> 32);
+  mad64_acc(s1, v1, (uint32_t)kw);
+  s2 += (u64)v1 * (uint32_t)(kw >> 32);
+#else
   s0 = mad64(v0, (uint32_t)kw, s0);
   s1 = mad64(v0, (uint32_t)(kw >> 32), s1);
   s1 = mad64(v1, (uint32_t)kw, s1);
   s2 = mad64(v1, (uint32_t)(kw >> 32), s2);
+#endif
 }
 // carry words up: s0, s1 < 2^30 afterwards, s0 + s1 2^30 + s2 2^60 unchanged
 __device__ __forceinline__ void mac3_fold(u64 &s0, u64 &s1, u64 &s2) {
@@ -229,6 +244,19 @@ ks_inner_kernel(DevCtx cx, const u64 *__restrict__ target_b, size_t target_bs, c
     }
   }
 
+  // EVAH_KS_LOOP, the one-wave radix-2^30 kernel: what its rounds read that no digit changes comes from scalar registers.
+  // The prime's words are the workgroup's (SM of the rounds; pm above is read before any store: scalar loads).  Where
+  // the wave holds ONE sub-transform (2^P = 64 << LR) the first round's nodes — 1, 2, 3 of the tile's heap — are the same
+  // for every lane: read once from the table (KsUT), the digits' first round and slice B's correction tile multiply by
+  // them from SGPRs instead of reading the staged copy back into 12 VGPRs per digit.  Not in slice A and the INVSP
+  // kernels: with their epilogues' scalar state the twelve words take the fused-multiply instantiations past the 100
+  // SGPRs a wave has (4 - 6 spilled); they keep the LDS reads.
+  constexpr bool KSL = EVAH_KS_LOOP != 0 && MAC3 && MAXT == 64;
+  constexpr int KS_NU = (KSL && TPS == 64 && !INVSP && TAIL != KS_TAIL_A) ? (1 << Rounds<P, LR>::bits(0)) : 1;
+  using KsUT = std::conditional_t<KSL, UTw<KS_NU>, NoUTw>;
+  KsUT ut;
+  if constexpr (KS_NU > 1) utw_load_sub(ut, cx.tw_fwd, kap, cx.N, (1u << pre) + sub0);
+
   u128_t acc0[NTT_R], acc1[NTT_R];
 #pragma unroll
   for (int i = 0; i < NTT_R; i++) { acc0[i] = {0, 0}; acc1[i] = {0, 0}; }
@@ -315,11 +343,11 @@ ks_inner_kernel(DevCtx cx, const u64 *__restrict__ target_b, size_t target_bs, c
         __builtin_amdgcn_wave_barrier(); // (one wave: DS operations are in order; no s_barrier, no vmcnt drain)
         // first round: from `lin` into the padded tile; then the next tile's load; then the remaining rounds
         auto next_tile = [&]() { if (J + 1 < l) dma_digits(J + 1); }; // (waits for the round's reads of `lin` first)
-        ntt_round<P, LR, RS::bits(0), RS::lo(0), false, true, true, true, true>(lds + sub * SP, tid, 0, 0, twl + (sub << P), pm,
-                                                                              lin + sub * S, next_tile);
+        ntt_round<P, LR, RS::bits(0), RS::lo(0), false, true, true, true, true, decltype(next_tile), KsUT>(
+            lds + sub * SP, tid, 0, 0, twl + (sub << P), pm, lin + sub * S, next_tile, ut);
         if constexpr (RS::NR > 1) {
           __builtin_amdgcn_wave_barrier();
-          RoundSeq<P, LR, 1, false, true, true, true, true, true>::run(lds + sub * SP, tid, 0, 0, twl + (sub << P), pm);
+          RoundSeq<P, LR, 1, false, true, true, true, true, true>::run(lds + sub * SP, tid, 0, 0, twl + (sub << P), pm, ut);
         }
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -403,6 +431,12 @@ ks_inner_kernel(DevCtx cx, const u64 *__restrict__ target_b, size_t target_bs, c
       acc1[i] = mac3_recombine(s0[1][i], s1[1][i], s2[1][i]);
     }
   }
+  // (EVAH_KS_LOOP) the epilogues index by a thread id the compiler cannot trace back to threadIdx.x.  What they derive
+  // from it — a dozen shifted and masked copies of the id, LDS and global offsets — was otherwise computed above the digit
+  // loop and held in VGPRs across it; now it is computed where it is used.
+  uint32_t etx = threadIdx.x;
+  if constexpr (KSL) asm volatile("" : "+v"(etx));
+  const int esub = etx / TPS, etid = etx % TPS;
   // KS_TAIL_B: the correction tile of (inst, K, I), where the output word goes as well; K = 0's tile is requested before
   // the fold, whose operand loads it then travels with (`lin` is free: the last digit's reads of it are waited for)
   u64 *tail_row = nullptr; // (block-uniform: K = 0's tile)
@@ -411,7 +445,7 @@ ks_inner_kernel(DevCtx cx, const u64 *__restrict__ target_b, size_t target_bs, c
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // reads of `lin` issued so far have returned
 #pragma unroll
     for (int it = 0; it < NPAIR; it++)
-      __builtin_amdgcn_global_load_lds(tail_row + (size_t)K * tail_ps + 2 * (threadIdx.x + it * T), lin + 2 * it * T, 16, 0, 0);
+      __builtin_amdgcn_global_load_lds(tail_row + (size_t)K * tail_ps + 2 * (etx + it * T), lin + 2 * it * T, 16, 0, 0);
   };
   if constexpr (TAIL == KS_TAIL_B) {
     tail_ps = tail.dst_ps;
@@ -426,7 +460,7 @@ ks_inner_kernel(DevCtx cx, const u64 *__restrict__ target_b, size_t target_bs, c
       const size_t off = (size_t)(Irow < l ? Irow : l - 1) * N + gbase;
 #pragma unroll
       for (int it = 0; it < NPAIR; it++) {
-        const size_t o = off + 2 * (threadIdx.x + it * T);
+        const size_t o = off + 2 * (etx + it * T);
         if constexpr (MODE == KS_FOLDMUL) {
           const ulonglong2 a0 = *reinterpret_cast<const ulonglong2 *>(msrc.a + o);
           const ulonglong2 a1 = *reinterpret_cast<const ulonglong2 *>(msrc.a + msrc.sa + o);
@@ -466,19 +500,19 @@ ks_inner_kernel(DevCtx cx, const u64 *__restrict__ target_b, size_t target_bs, c
         __syncthreads(); // the tile in LDS has been consumed
 #pragma unroll
         for (int it = 0; it < NPAIR; it++) {
-          const int idx = 2 * (threadIdx.x + it * T);
+          const int idx = 2 * (etx + it * T);
           const int sb = idx >> P, e = idx & (S - 1);
           lds[sb * SP + lds_pad<P>(e)] = barrett128(K ? acc1[2 * it] : acc0[2 * it], pm);
           lds[sb * SP + lds_pad<P>(e + 1)] = barrett128(K ? acc1[2 * it + 1] : acc0[2 * it + 1], pm);
         }
         __syncthreads();
         // as ntt_pass_kernel<P, LR, contiguous, inverse>: global twiddle heap of the row's prime
-        RoundSeq<P, LR, 0, true, false, true>::run(lds + sub * SP, tid, sub0 + sub, pre, twi, pm);
+        RoundSeq<P, LR, 0, true, false, true>::run(lds + esub * SP, etid, sub0 + esub, pre, twi, pm);
         __syncthreads();
         u64 *r = r_out + ((size_t)2 * inst + K) * N + gbase;
 #pragma unroll
         for (int it = 0; it < NPAIR; it++) {
-          const int idx = 2 * (threadIdx.x + it * T);
+          const int idx = 2 * (etx + it * T);
           const int sb = idx >> P, e = idx & (S - 1);
           ulonglong2 v;
           v.x = lds[sb * SP + lds_pad<P>(e)];
@@ -494,7 +528,7 @@ ks_inner_kernel(DevCtx cx, const u64 *__restrict__ target_b, size_t target_bs, c
     const ulonglong2 *twi = cx.tw_inv + (size_t)kap * cx.N;
     const ulonglong2 pinv = cx.invq[(size_t)(cx.k - 1) * cx.k + kap]; // P^-1 mod q_last ((0, 0) on the special row: not used)
     __syncthreads(); // the forward heaps have been consumed: the same nodes of the inverse table take their place
-    for (int idx = threadIdx.x; idx < (C << P); idx += T) {
+    for (int idx = etx; idx < (C << P); idx += T) {
       const int sb = idx >> P, n = idx & (S - 1);
       if (n) {
         const int d = 31 - __clz(n);
@@ -506,7 +540,7 @@ ks_inner_kernel(DevCtx cx, const u64 *__restrict__ target_b, size_t target_bs, c
       __syncthreads(); // the tile in LDS has been consumed
 #pragma unroll
       for (int it = 0; it < NPAIR; it++) {
-        const int idx = 2 * (threadIdx.x + it * T);
+        const int idx = 2 * (etx + it * T);
         const int sb = idx >> P, e = idx & (S - 1);
         const u128_t ax = K ? acc1[2 * it] : acc0[2 * it], ay = K ? acc1[2 * it + 1] : acc0[2 * it + 1];
         u64 vx, vy;
@@ -522,12 +556,12 @@ ks_inner_kernel(DevCtx cx, const u64 *__restrict__ target_b, size_t target_bs, c
       }
       __syncthreads();
       // as ntt_loop_kernel's inverse pass: local heaps, N^-1 left to the strided pass (ntt_tail_kernel)
-      RoundSeq<P, LR, 0, true, true, true, false>::run(lds + sub * SP, tid, 0, 0, twl + (sub << P), pm);
+      RoundSeq<P, LR, 0, true, true, true, false>::run(lds + esub * SP, etid, 0, 0, twl + (esub << P), pm);
       __syncthreads();
       u64 *r = (special ? r_out : tail.t) + ((size_t)2 * inst + K) * N + gbase;
 #pragma unroll
       for (int it = 0; it < NPAIR; it++) {
-        const int idx = 2 * (threadIdx.x + it * T);
+        const int idx = 2 * (etx + it * T);
         const int sb = idx >> P, e = idx & (S - 1);
         ulonglong2 v;
         v.x = lds[sb * SP + lds_pad<P>(e)];
@@ -554,18 +588,18 @@ ks_inner_kernel(DevCtx cx, const u64 *__restrict__ target_b, size_t target_bs, c
       __builtin_amdgcn_wave_barrier();
       // the digits' rounds: first round from `lin` into the padded tile, K = 1's tile requested behind its reads
       auto next_tile = [&]() { if (K == 0) dma_corr(1); };
-      ntt_round<P, LR, RS::bits(0), RS::lo(0), false, true, true, true, true>(lds + sub * SP, tid, 0, 0, twl + (sub << P), pm,
-                                                                            lin + sub * S, next_tile);
+      ntt_round<P, LR, RS::bits(0), RS::lo(0), false, true, true, true, true, decltype(next_tile), KsUT>(
+          lds + esub * SP, etid, 0, 0, twl + (esub << P), pm, lin + esub * S, next_tile, ut);
       if constexpr (RS::NR > 1) {
         __builtin_amdgcn_wave_barrier();
-        RoundSeq<P, LR, 1, false, true, true, true, true, true>::run(lds + sub * SP, tid, 0, 0, twl + (sub << P), pm);
+        RoundSeq<P, LR, 1, false, true, true, true, true, true>::run(lds + esub * SP, etid, 0, 0, twl + (esub << P), pm, ut);
       }
       __builtin_amdgcn_wave_barrier();
       // (one descriptor per tile and the lane offset the key loads use: no 64-bit address per store)
       const __amdgpu_buffer_rsrc_t out = __builtin_amdgcn_make_buffer_rsrc(tail_row + (size_t)K * tail_ps, 0, 0x7fffffff, 0x00020000);
 #pragma unroll
       for (int it = 0; it < NPAIR; it++) {
-        const int idx = 2 * (threadIdx.x + it * T);
+        const int idx = 2 * (etx + it * T);
         const int sb = idx >> P, e = idx & (S - 1);
         const u64 wx = lds[sb * SP + lds_pad<P>(e)], wy = lds[sb * SP + lds_pad<P>(e + 1)];
         ulonglong2 v;
@@ -577,7 +611,7 @@ ks_inner_kernel(DevCtx cx, const u64 *__restrict__ target_b, size_t target_bs, c
         w.y = (uint32_t)(v.x >> 32);
         w.z = (uint32_t)v.y;
         w.w = (uint32_t)(v.y >> 32);
-        __builtin_amdgcn_raw_buffer_store_b128(w, out, 16u * threadIdx.x + 16u * (uint32_t)(it * T), 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(w, out, 16u * etx + 16u * (uint32_t)(it * T), 0, 0);
       }
     }
     return;
@@ -588,7 +622,7 @@ ks_inner_kernel(DevCtx cx, const u64 *__restrict__ target_b, size_t target_bs, c
   if (lazy_out && I != l) { // block-uniform
 #pragma unroll
     for (int it = 0; it < NPAIR; it++) {
-      const int idx = 2 * (threadIdx.x + it * T);
+      const int idx = 2 * (etx + it * T);
       ulonglong2 r0, r1;
       r0.x = reduce128_lazy(acc0[2 * it], pm);
       r0.y = reduce128_lazy(acc0[2 * it + 1], pm);
@@ -601,7 +635,7 @@ ks_inner_kernel(DevCtx cx, const u64 *__restrict__ target_b, size_t target_bs, c
   }
 #pragma unroll
   for (int it = 0; it < NPAIR; it++) {
-    const int idx = 2 * (threadIdx.x + it * T);
+    const int idx = 2 * (etx + it * T);
     ulonglong2 r0, r1;
     r0.x = barrett128(acc0[2 * it], pm);
     r0.y = barrett128(acc0[2 * it + 1], pm);
